@@ -2,7 +2,7 @@
 """Headline benchmark: fwd+bwd samples/s of TransformerEncoder d_model=1024, 8 heads, seq=512,
 batch 256 per GPU (BASELINE.json configs[4]; U = 4096 hidden units, pre-norm).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N = 1 runs in this process.  For N > 1 every rank is its own process on its own GPU: either an
 external launcher starts them (the driver: ``python -m torch.distributed.run --nproc-per-node N
@@ -13,9 +13,15 @@ per-GPU batch, weak scaling; the parameter gradients are all-reduced over xGMI i
 ``backward``); the 128-byte RCCL id travels through a file -- the product imports no torch.
 
 A step = forward + backward + the SGD update of every parameter, on synthetic fp32 tensors
-already resident in HBM.  Rank 0 prints ONE JSON line (contract in the task description) with
-two extra objects: ``roofline`` (the fp32-MFMA GEMM family, algorithmic FLOPs / HIP-event time
-measured over the timed region) and ``cpu_baseline`` (the NumPy oracle on a bounded sample).
+already resident in HBM.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the
+K steps and prints the headline (``value``, ``ms_per_step``, per-step device times).  ``--full``
+adds everything else, as in earlier rounds: ``roofline`` (the fp32-MFMA GEMM family, algorithmic
+FLOPs / HIP-event time measured over the timed region), the ``alt_math`` regions, the other
+BASELINE configs and ``cpu_baseline`` (the NumPy oracle on a bounded sample).
+
+``--dump-outputs DIR`` writes what the last timed step computed -- the encoder output, the input
+gradient and the parameters after the SGD update -- as DIR/<name>.npy (float32; a fixed seeded
+sample of the larger arrays), so that two builds can be compared output for output.
 """
 
 from __future__ import annotations
@@ -40,6 +46,10 @@ MATH_NOTE = {     # what a non-default --math does to the matrix products (inclu
     'bf16x3_fast': 'products as six v_mfma_f32_32x32x16_bf16 of three-way bf16-split operands, one accumulator',
     'f16x2': 'products as three v_mfma_f32_32x32x16_f16 of row-scaled two-way fp16-split operands (the bf16 split for batched products)',
 }
+# SGD step of the workload.  The gradients are sums over batch * seq rows and dy is the same every step, so the updates
+# push the parameters one way: at 1e-4 they reach NaN within 25 steps at the default shape.  1e-8 keeps them finite
+# (400 steps moved the largest d2_w element from 0.01564 to 0.01575) while each update still changes the weights.
+LEARNING_RATE = 1e-8
 MFMA_BOUND = ('sgemm_', 'mha_core_')    # kernel-timer names of the MFMA-bound family: GEMMs and the fused attention core
 
 
@@ -67,19 +77,35 @@ def make_params(rng, feat, heads, hidden):
         d1_w=init([feat, hidden], s_f), d1_b=init([hidden]), d2_w=init([hidden, feat], s_h), d2_b=init([feat]))
 
 
+def parameters(enc):
+    """The encoder's parameters under make_params' names: the layers' own device arrays."""
+    att = enc._self_attention
+    out = {'att_' + n: getattr(att, '_' + n) for n in ('wq', 'wk', 'wv', 'wo', 'bq', 'bk', 'bv', 'bo')}
+    out.update(n1_gamma=enc._norm1._gamma, n1_beta=enc._norm1._beta, n2_gamma=enc._norm2._gamma, n2_beta=enc._norm2._beta,
+               d1_w=enc._dense1._linear._w, d1_b=enc._dense1._linear._b, d2_w=enc._dense2._w, d2_b=enc._dense2._b)
+    return out
+
+
 def bind(enc, p):
     """Overwrite the lazily initialised parameters IN PLACE (same device storage, same layout)."""
-    att = enc._self_attention
-    for n in ('wq', 'wk', 'wv', 'wo', 'bq', 'bk', 'bv', 'bo'):
-        getattr(att, '_' + n).set(p['att_' + n])
-    enc._norm1._gamma.set(p['n1_gamma'])
-    enc._norm1._beta.set(p['n1_beta'])
-    enc._norm2._gamma.set(p['n2_gamma'])
-    enc._norm2._beta.set(p['n2_beta'])
-    enc._dense1._linear._w.set(p['d1_w'])
-    enc._dense1._linear._b.set(p['d1_b'])
-    enc._dense2._w.set(p['d2_w'])
-    enc._dense2._b.set(p['d2_b'])
+    for name, arr in parameters(enc).items():
+        arr.set(p[name])
+
+
+DUMP_SAMPLE = 1 << 20      # elements kept of a larger array: ~32 MB for the whole dump at the default shape
+
+
+def host_outputs(y, dx, enc):
+    """What the last timed step handed its caller (output, input gradient) and left in the parameters, on the host as
+    float32: arrays above DUMP_SAMPLE elements as the same seeded sample of flat indices in every run."""
+    arrays = {'y': y, 'dx': dx, **{'param_' + k: v for k, v in parameters(enc).items()}}
+    out = {}
+    for name, arr in arrays.items():
+        host = np.asarray(arr, dtype=np.float32)
+        if host.size > DUMP_SAMPLE:
+            host = host.reshape(-1)[np.sort(np.random.default_rng(0).choice(host.size, DUMP_SAMPLE, replace=False))]
+        out[name] = host
+    return out
 
 
 def cpu_baseline(args, params):
@@ -96,7 +122,7 @@ def cpu_baseline(args, params):
         _, cache = O.encoder_fwd(p, qkv, True)
         _, grads = O.encoder_bwd(p, cache, dy, True)
         for k in p:
-            p[k] = O.sgd_step(p[k], grads[k], 1e-4)
+            p[k] = O.sgd_step(p[k], grads[k], LEARNING_RATE)
         times.append(time.perf_counter() - t0)
     best = min(times)
     out = dict(value=b / best, unit='samples/s', cores=os.cpu_count(), kind='port',
@@ -115,7 +141,7 @@ def cpu_baseline(args, params):
         _, cache = O.encoder_fwd(params, qv, True, verbatim=True)
         _, grads = O.encoder_bwd(params, cache, dv, True, verbatim=True)
         for k in params:
-            O.sgd_step(params[k], grads[k], 1e-4)
+            O.sgd_step(params[k], grads[k], LEARNING_RATE)
         tv = time.perf_counter() - t0
         out['reference_verbatim'] = dict(
             value=sv / tv / args.seq, unit='samples/s', tokens_per_s=sv / tv, cores=1, kind='port',
@@ -210,7 +236,14 @@ def main():
                     help="arithmetic of the matrix products for the headline measurement (include/npm_hip.h npm_set_math)")
     ap.add_argument('--no-alt-math', action='store_true',
                     help="skip the second timed region that repeats the K steps with --math bf16x3 ('alt_math' in the JSON)")
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline, measure the roofline (kernel timer over the timed region), the alt_math regions, '
+                         'the other BASELINE configs and the CPU baseline; the --no-* options above select among these')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="write the last timed step's output, input gradient and updated parameters as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'RANK' not in os.environ:
         # Plain `python bench.py --gpus N`: this process becomes the launcher.  It has not touched the GPU (nothing
@@ -233,6 +266,9 @@ def main():
     qkv = D.from_host(data_rng.standard_normal(shape, dtype=np.float32))
     dy = D.from_host(data_rng.standard_normal(shape, dtype=np.float32) * np.float32(0.01))
 
+    # The lazy initialisation draws from NumPy's global generator, and the first warm-up backward runs on the activations
+    # of that forward: seeded, every run with the same arguments computes the same outputs.
+    np.random.seed(0)
     enc = npm.layers.TransformerEncoder(num_heads=args.heads, hidden_units=args.hidden, norm_first=True)
     # Lazy initialisation happens at the first forward (reference layer.py:33-35).  With warm-up
     # steps the first of them does it at full size, so that EVERY launch a profiler sees belongs to
@@ -242,11 +278,15 @@ def main():
     else:
         enc(D.from_host(np.zeros([1, 8, args.features], dtype=np.float32)))
     bind(enc, params)
-    sgd = npm.optimizer.SGDOptimizer(1e-4)
+    sgd = npm.optimizer.SGDOptimizer(LEARNING_RATE)
 
     def step():
         enc(qkv)
         enc(dy, backprop=True, optimizer_=sgd)
+
+    def kept_step():                                     # the same step, keeping what its caller receives
+        y = enc(qkv)
+        return y, enc(dy, backprop=True, optimizer_=sgd)
 
     for i in range(args.warmup):
         if i > 0:
@@ -260,14 +300,18 @@ def main():
     if rccl:
         comm.stats_enable(True)
         comm.stats()                                     # drop what the warm-up steps recorded
-    timer = None if args.no_kernel_timer else D.KernelTimer()
+    timer = D.KernelTimer() if args.full and not args.no_kernel_timer else None
     if timer is not None:
         timer.__enter__()
+    keep_last = args.dump_outputs is not None and rank == 0
     marks = [D.Event() for _ in range(args.steps + 1)]   # one HIP event per step boundary, on the compute stream
     marks[0].record()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step()
+        if keep_last and i == args.steps - 1:
+            last = kept_step()
+        else:
+            step()
         marks[i + 1].record()
     D.synchronize()
     local_elapsed = time.perf_counter() - t0             # this rank alone, before it waits for the others
@@ -276,6 +320,12 @@ def main():
     elapsed = time.perf_counter() - t0
     if timer is not None:
         timer.__exit__(None, None, None)
+    if keep_last:
+        # before any further region changes the parameters
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in host_outputs(*last, enc).items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), arr)
+        del last
     step_order = [marks[i].elapsed_ms(marks[i + 1]) for i in range(args.steps)]
     step_ms = sorted(step_order)
     exchange_stats = comm.stats() if rccl else None
@@ -302,7 +352,8 @@ def main():
         'step_ms_device': ({'median': step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2]),
                             'min': step_ms[0], 'max': step_ms[-1], 'mean': sum(step_ms) / len(step_ms),
                            'first': step_order[0], 'slowest_step': step_order.index(step_ms[-1]),
-                            'note': 'HIP events at step boundaries, rank 0; the kernel timer\'s own events are inside these intervals'}
+                            'note': 'HIP events at step boundaries, rank 0' + ('; the kernel timer\'s own events are inside these intervals'
+                                                                                if timer is not None else '')}
                            if step_ms else None),
         'dtype': 'f32' if args.math == 'f32' else f'f32 ({args.math}: {MATH_NOTE[args.math]}, fp32 accumulate)',
         'math': args.math, 'data': 'synthetic N(0,1) fp32 inputs resident in HBM; random-init '
@@ -408,7 +459,7 @@ def main():
                            'step_frac_of_fp32_mfma_peak': alt_value / world * fps / 1e12 / FP32_MFMA_PEAK_TFLOPS}
 
     result['parity'] = parity_note(args.math) if args.math in reported_math_modes() else None
-    if args.math == 'f32' and not args.no_alt_math and 'bf16x3' in reported_math_modes():
+    if args.full and args.math == 'f32' and not args.no_alt_math and 'bf16x3' in reported_math_modes():
         # the matrix products on the bf16 pipe (three-way operand split, fp32-class error -- DESIGN.md 4.1,
         # tests/test_gpu_gemm.py::test_split_math_error_statistics)
         alt_timer, obj = alt_region('bf16x3')
@@ -421,7 +472,7 @@ def main():
                     'Not the headline: value above is the exact-f32 MFMA path.'})
         obj['parity'] = parity_note('bf16x3')
         result['alt_math'] = obj
-    if args.math == 'f32' and not args.no_alt_math and 'f16x2' in reported_math_modes():
+    if args.full and args.math == 'f32' and not args.no_alt_math and 'f16x2' in reported_math_modes():
         # ... and on the f16 pipe: two-way fp16 split with row scaling, three MFMAs per product (csrc/npm_gemm_f16x2.hip)
         alt_timer, obj = alt_region('f16x2')
         obj.update({
@@ -434,7 +485,7 @@ def main():
                     'Not the headline: value above is the exact-f32 MFMA path.'})
         obj['parity'] = parity_note('f16x2')
         result['alt_math_f16x2'] = obj
-    if world == 1 and not args.no_configs and args.math == 'f32':
+    if args.full and world == 1 and not args.no_configs and args.math == 'f32':
         # The other single-GPU configurations of BASELINE.json at full size, same process, after the headline regions
         # (tools/config_bench.py: >= configs_min_seconds timed after half of that as warm-up, fwd+bwd+SGD, exact-f32).
         sys.path.insert(0, os.path.join(ROOT, 'tools'))
@@ -459,10 +510,10 @@ def main():
     D.synchronize()
     parallel.shutdown()                                  # all ranks leave the group HERE: no collective (and no busy-waiting
     #                                                      barrier kernel) is outstanding while rank 0 samples the CPU below
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result['cpu_baseline'] = cpu_baseline(args, params)      # rank 0's host cores, after every timed region; N = 1 only
     elif rank == 0:
-        result['cpu_baseline'] = None                            # (N > 1 runs stay short: the baseline is on the N = 1 line)
+        result['cpu_baseline'] = None                            # (N > 1 runs stay short: the baseline is on the N = 1 --full line)
     if rank == 0:
         print(json.dumps(result))
 

@@ -1,6 +1,9 @@
-"""TEST INFRASTRUCTURE (build container only): the reference's OWN, unchanged ``optimizer.py``, ``loss.py`` and
-``train.py`` driving the device layers after ``np_modeling_amd.install()`` -- the drop-in claim of
-BASELINE.json's north_star ("Trainer/optimizer/loss drop in unchanged"), on the host simulator of the C ABI.
+"""TEST INFRASTRUCTURE: ``optimizer``, ``loss`` and ``train`` modules under the reference's import names driving the
+device layers after ``np_modeling_amd.install()``, on the host simulator of the C ABI.  With NPM_REFERENCE naming a
+checkout of the reference, they are the reference's OWN, unchanged ``optimizer.py``, ``loss.py`` and ``train.py`` -- the
+drop-in claim of BASELINE.json's north_star ("Trainer/optimizer/loss drop in unchanged"); without it, this package's
+versions of the same contract (``np_modeling_amd.install(include_support_modules=True)``).  The expected values are the
+same either way: fixtures recorded from the reference, and the oracle.
 
 Run as a child process by tests/test_reference_dropin.py (a fresh interpreter: the reference's module names
 ``optimizer`` / ``loss`` / ``train`` must not already be bound to anything else).  Flows:
@@ -26,7 +29,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 sys.dont_write_bytecode = True
 
-REFERENCE = os.environ.get('NPM_REFERENCE', '/root/reference')
+REFERENCE = os.environ.get('NPM_REFERENCE', '')
 
 
 def main():
@@ -36,14 +39,22 @@ def main():
     from oracle import np_oracle as O
 
     hostsim.install()
-    npm.install()                               # `layers` now resolves to the device layers
-    sys.path.insert(0, REFERENCE)
-    import loss                                 # the reference's own modules
+    if REFERENCE:
+        assert os.path.isfile(os.path.join(REFERENCE, 'train.py')), f'NPM_REFERENCE={REFERENCE} is not a reference checkout'
+        npm.install()                           # `layers` now resolves to the device layers
+        sys.path.insert(0, REFERENCE)
+    else:
+        npm.install(include_support_modules=True)
+    import loss                                 # the reference's own modules, or this package's
     import optimizer
     import train
     from layers import conv, mlp, transformer   # ours, through the reference's import names
     for mod in (loss, optimizer, train):
-        assert os.path.realpath(mod.__file__).startswith(os.path.realpath(REFERENCE)), mod.__file__
+        if REFERENCE:
+            assert os.path.realpath(mod.__file__).startswith(os.path.realpath(REFERENCE)), mod.__file__
+        else:
+            assert mod is getattr(npm, mod.__name__.rsplit('.', 1)[-1]), mod.__name__
+    print('support modules:', REFERENCE or 'np_modeling_amd')
     assert mlp.Dense is npm.layers.Dense and conv.Conv2D is npm.layers.Conv2D
 
     def losses_of(text):
@@ -121,7 +132,7 @@ def main():
         return np.asarray(getattr(owner, '_' + attr))
 
     enc = fresh()
-    ref_sgd = optimizer.SGDOptimizer(lr)         # the REFERENCE's class, unchanged (optimizer.py:26-33)
+    ref_sgd = optimizer.SGDOptimizer(lr)         # the reference's class, unchanged (optimizer.py:26-33), or ours
     seen = []
     inner = ref_sgd.update_variable
     ref_sgd.update_variable = lambda identifier, variable, gradient: (seen.append(identifier), inner(identifier, variable, gradient))[1]

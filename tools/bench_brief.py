@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""stdin: bench.py's JSON line -> one short line (ms per step, GEMM / attention / LayerNorm figures)."""
+"""stdin: the JSON line of bench.py --full -> one short line (ms per step, GEMM / attention / LayerNorm figures)."""
 import json
 import sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])

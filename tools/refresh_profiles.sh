@@ -26,7 +26,7 @@ echo "== PMC traffic (two passes)"
   done ) || exit 1
 python3 profiles/summarize_pmc.py "$OUT"/pmc_FETCH_SIZE/*/*_counter_collection.csv "$OUT"/pmc_WRITE_SIZE/*/*_counter_collection.csv --session "${R}:$(date +%Y-%m-%dT%H:%M):$(hostname)" > "$OUT/pmc_traffic.json" || exit 1
 cp "$OUT/pmc_traffic.json" profiles/pmc_traffic.json
-echo "== bench (default command)"; timeout -k 10 500 python bench.py > "$OUT/${R}_bench.json" 2> "$OUT/bench.err" || exit 1
+echo "== bench (--full)"; timeout -k 10 500 python bench.py --full > "$OUT/${R}_bench.json" 2> "$OUT/bench.err" || exit 1
 python3 -c "import json; d=json.load(open('$OUT/${R}_bench.json')); t=json.load(open('$OUT/pmc_traffic.json')); assert d['roofline']['traffic'] == t['gemm_family_bytes_per_launch'], (d['roofline']['traffic'], d['roofline'].get('traffic_source')); print('roofline.traffic =', d['roofline']['traffic'], 'from', t['session'])" || exit 1
 [ "$PART" == pmc ] && { echo "== done (PMC traffic and the bench line only)"; exit 0; }
 echo "== clock / power during 60 steps"; tools/clock_sampler.sh "$OUT/clocks_f32.log" -- timeout -k 10 200 python bench.py --steps 60 --warmup 3 --no-cpu-baseline --no-alt-math --no-configs > "$OUT/bench_60.json" 2>/dev/null
