@@ -318,6 +318,14 @@ typedef struct npm_mha_core {
 int npm_mha_core_supported(int head_dim);          /* 1 when npm_mha_core_fwd/bwd take this head dimension */
 int npm_mha_core_fwd(const npm_mha_core *c);
 int npm_mha_core_bwd(const npm_mha_core *c);
+/* Grouped-query attention (the reference's gqa_fwd, layers/attentions_test.py:267-358): c->heads query heads share kv_heads
+ * key / value heads, and query head h reads K / V head h % kv_heads.  k, v, dk and dv are [B, Skv, kv_heads, D] with their own
+ * pitches (>= kv_heads * D; a packed [B, S, heads + 2 kv_heads, D] buffer works); everything per query head (q, ctx, lse, mask,
+ * tile summary, scores, neg_delta, dq) is laid out as in npm_mha_core_fwd / _bwd.  The backward writes one dK / dV partial per
+ * query head into pooled scratch and sums each group in a fixed order (bitwise reproducible, no atomics).  kv_heads < 1 or
+ * heads % kv_heads != 0: NPM_E_BAD_ARGUMENT; kv_heads == heads is the ungrouped call exactly. */
+int npm_mha_core_fwd_grouped(const npm_mha_core *c, int32_t kv_heads);
+int npm_mha_core_bwd_grouped(const npm_mha_core *c, int32_t kv_heads);
 /* A plane (b, h) with a query row that has no allowed key at all gets 0xFF in every "some position allowed" byte (see above).
  * summary[2][plane_b][plane_h][ceil(seq_q / 32)][ceil(seq_kv / 128)] (first the "some position allowed" bytes, then, in the
  * same order, the "every position inside the tensors allowed" bytes) of a byte mask laid out like npm_mha_core's (element
@@ -327,7 +335,8 @@ int npm_mha_core_bwd(const npm_mha_core *c);
 int npm_mha_mask_summary(const uint8_t *mask, int64_t stride_b, int64_t stride_h, int64_t stride_q, int32_t planes_b,
                          int32_t planes_h, int32_t seq_q, int32_t seq_kv, uint8_t *summary);
 /* Which kernel the most recent npm_mha_core_fwd / npm_mha_core_bwd call launched, as "<kernel> D=<head_dim> mask=<0|1>
- * scores=<0|1>" (e.g. "mha_bwd16_kernel D=128 mask=0 scores=1"); "" before the first call.  Tests use it to assert that
+ * scores=<0|1>" (e.g. "mha_bwd16_kernel D=128 mask=0 scores=1"), followed by " kv_heads=<n>" for a grouped call with fewer
+ * K / V heads than query heads; "" before the first call.  Tests use it to assert that
  * a comparison exercised the kernel it names. */
 const char *npm_last_attn_kernel(void);
 /* Diagnostics: when buf != NULL every block of the backward kernel writes 16 words of s_memtime stamps of ONE of its

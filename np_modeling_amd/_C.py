@@ -137,6 +137,8 @@ SIGNATURES = {
     'npm_mha_core_supported': [C.c_int],
     'npm_mha_core_fwd': [C.POINTER(npm_mha_core)],
     'npm_mha_core_bwd': [C.POINTER(npm_mha_core)],
+    'npm_mha_core_fwd_grouped': [C.POINTER(npm_mha_core), _I32],
+    'npm_mha_core_bwd_grouped': [C.POINTER(npm_mha_core), _I32],
     'npm_mha_mask_summary': [_P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _P],
     'npm_adam_step': [_P, _P, _P, _P, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int],
     'npm_fill_f64': [_P, C.c_double, _SZ],

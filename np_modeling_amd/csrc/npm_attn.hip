@@ -8,6 +8,9 @@
 //
 // Layout: q/k/v/ctx and their gradients stay [B, S, H, D] (row pitch given: H*D, or 3*H*D inside a packed qkv
 // buffer); a head is the column slice [h*D, (h+1)*D) of a row.  D in {16, 32, 64, 128}.
+// Grouped-query attention (npm_mha_core_*_grouped): k/v/dk/dv have kv_heads heads, query head h reads K / V head h % kv_heads
+// (the reference's gqa_fwd, layers/attentions_test.py:305-308); the backward writes per-query-head dK / dV partials and
+// mha_gqa_reduce_kernel sums each group in a fixed order.
 //
 // MFMA orientation (one f32 per lane per operand: lane l supplies A[i = l & 31][k = l >> 5], B[k = l >> 5][j = l & 31];
 // the result has its column j on the lane and rows (r & 3) + 8 (r >> 2) + 4 (l >> 5) in registers r = 0..15):
@@ -20,6 +23,7 @@
 // Operand tiles arrive by LDS-DMA (buffer_load_dwordx4 ... lds) with the bank swizzle applied on the SOURCE address.
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 #include "npm_mfma_tile.h"
 
@@ -56,6 +60,7 @@ struct MhaArgs {
     long mask_sb, mask_sh, mask_sq;
     float *scores;                    // optional [B, H, Sq, Skv]: raw (unscaled, masked) scores kept for the backward
     int batch, heads, seq_q, seq_kv;
+    int kv_heads;                     // K / V heads (grouped-query attention): query head h reads K / V head h % kv_heads
     float scale;
     int q_tiles;                      // forward: 128-query tiles per (b, h)
     int q_pair;                       // forward: 1 = a block takes the two tiles u and q_tiles - 1 - u (balanced work under a mask)
@@ -224,8 +229,8 @@ mha_fwd_kernel(const MhaArgs p) {
     const int qrow = qt * 128 + wave * 32 + l32;                             // this lane's query
     const bool qok = qrow < p.seq_q;
 
-    const auto descK = make_desc(p.k + (long)b * p.seq_kv * p.k_pitch + h * D, ((long)(p.seq_kv - 1) * p.k_pitch + D) * 4);
-    const auto descV = make_desc(p.v + (long)b * p.seq_kv * p.v_pitch + h * D, ((long)(p.seq_kv - 1) * p.v_pitch + D) * 4);
+    const auto descK = make_desc(p.k + (long)b * p.seq_kv * p.k_pitch + (h % p.kv_heads) * D, ((long)(p.seq_kv - 1) * p.k_pitch + D) * 4);
+    const auto descV = make_desc(p.v + (long)b * p.seq_kv * p.v_pitch + (h % p.kv_heads) * D, ((long)(p.seq_kv - 1) * p.v_pitch + D) * 4);
     const auto rsrcQ = make_rsrc(p.q + (long)b * p.seq_q * p.q_pitch + h * D, ((long)(p.seq_q - 1) * p.q_pitch + D) * 4);
 
     // Q fragment: element s of group g is Q[qrow][8 g + 4 half + s]
@@ -535,8 +540,8 @@ mha_fwd8_kernel(const MhaArgs p) {
     const int units = pairing ? (p.q_tiles + 1) / 2 : p.q_tiles;
     const int unit = logical % units, bh = logical / units;
     const int b = bh / p.heads, h = bh - b * p.heads;
-    const auto descK = make_desc(p.k + (long)b * p.seq_kv * p.k_pitch + h * D, ((long)(p.seq_kv - 1) * p.k_pitch + D) * 4);
-    const auto descV = make_desc(p.v + (long)b * p.seq_kv * p.v_pitch + h * D, ((long)(p.seq_kv - 1) * p.v_pitch + D) * 4);
+    const auto descK = make_desc(p.k + (long)b * p.seq_kv * p.k_pitch + (h % p.kv_heads) * D, ((long)(p.seq_kv - 1) * p.k_pitch + D) * 4);
+    const auto descV = make_desc(p.v + (long)b * p.seq_kv * p.v_pitch + (h % p.kv_heads) * D, ((long)(p.seq_kv - 1) * p.v_pitch + D) * 4);
     const auto rsrcQ = make_rsrc(p.q + (long)b * p.seq_q * p.q_pitch + h * D, ((long)(p.seq_q - 1) * p.q_pitch + D) * 4);
     const auto rsrcC = make_rsrc(p.ctx + (long)b * p.seq_q * p.ctx_pitch + h * D, ((long)(p.seq_q - 1) * p.ctx_pitch + D) * 4);
     const auto rsrcM = make_rsrc(MASK ? p.mask + b * p.mask_sb + h * p.mask_sh : nullptr, MASK ? (long)(p.seq_q - 1) * p.mask_sq + p.seq_kv : 0);
@@ -829,8 +834,8 @@ mha_bwd_kernel(const MhaArgs p) {
     const int b = bh / p.heads, h = bh - b * p.heads;
     float *xs = sRow + wave * 64;
 
-    const auto descK = make_desc(p.k + (long)b * p.seq_kv * p.k_pitch + h * D, ((long)(p.seq_kv - 1) * p.k_pitch + D) * 4);
-    const auto rsrcV = make_rsrc(p.v + (long)b * p.seq_kv * p.v_pitch + h * D, ((long)(p.seq_kv - 1) * p.v_pitch + D) * 4);
+    const auto descK = make_desc(p.k + (long)b * p.seq_kv * p.k_pitch + (h % p.kv_heads) * D, ((long)(p.seq_kv - 1) * p.k_pitch + D) * 4);
+    const auto rsrcV = make_rsrc(p.v + (long)b * p.seq_kv * p.v_pitch + (h % p.kv_heads) * D, ((long)(p.seq_kv - 1) * p.v_pitch + D) * 4);
     const auto descQ = make_desc(p.q + (long)b * p.seq_q * p.q_pitch + h * D, ((long)(p.seq_q - 1) * p.q_pitch + D) * 4);
     const auto descDO = make_desc(p.dctx + (long)b * p.seq_q * p.dctx_pitch + h * D, ((long)(p.seq_q - 1) * p.dctx_pitch + D) * 4);
     const auto rsrcDQ = make_rsrc(p.dq + (long)b * p.seq_q * p.dq_pitch + h * D, ((long)(p.seq_q - 1) * p.dq_pitch + D) * 4);
@@ -1192,8 +1197,8 @@ mha_bwd16_kernel(const MhaArgs p) {
     long long *const blk_tr = (TRACE && p.trace && tid == 0) ? p.trace + (long)blockIdx.x * 16 : nullptr;
     if (blk_tr) blk_tr[9] = __builtin_amdgcn_s_memtime();
 
-    const auto descK = make_desc(p.k + (long)b * p.seq_kv * p.k_pitch + h * D, ((long)(p.seq_kv - 1) * p.k_pitch + D) * 4);
-    const auto rsrcV = make_rsrc(p.v + (long)b * p.seq_kv * p.v_pitch + h * D, ((long)(p.seq_kv - 1) * p.v_pitch + D) * 4);
+    const auto descK = make_desc(p.k + (long)b * p.seq_kv * p.k_pitch + (h % p.kv_heads) * D, ((long)(p.seq_kv - 1) * p.k_pitch + D) * 4);
+    const auto rsrcV = make_rsrc(p.v + (long)b * p.seq_kv * p.v_pitch + (h % p.kv_heads) * D, ((long)(p.seq_kv - 1) * p.v_pitch + D) * 4);
     const auto descQ = make_desc(p.q + (long)b * p.seq_q * p.q_pitch + h * D, ((long)(p.seq_q - 1) * p.q_pitch + D) * 4);
     const auto descDO = make_desc(p.dctx + (long)b * p.seq_q * p.dctx_pitch + h * D, ((long)(p.seq_q - 1) * p.dctx_pitch + D) * 4);
     const auto rsrcDQ = make_rsrc(p.dq + (long)b * p.seq_q * p.dq_pitch + h * D, ((long)(p.seq_q - 1) * p.dq_pitch + D) * 4);
@@ -1528,8 +1533,8 @@ mha_bwd8_kernel(const MhaArgs p) {
     const int bh = blockIdx.x;
     const int b = bh / p.heads, h = bh - b * p.heads;
 
-    const auto descK = make_desc(p.k + (long)b * p.seq_kv * p.k_pitch + h * D, ((long)(p.seq_kv - 1) * p.k_pitch + D) * 4);
-    const auto rsrcV = make_rsrc(p.v + (long)b * p.seq_kv * p.v_pitch + h * D, ((long)(p.seq_kv - 1) * p.v_pitch + D) * 4);
+    const auto descK = make_desc(p.k + (long)b * p.seq_kv * p.k_pitch + (h % p.kv_heads) * D, ((long)(p.seq_kv - 1) * p.k_pitch + D) * 4);
+    const auto rsrcV = make_rsrc(p.v + (long)b * p.seq_kv * p.v_pitch + (h % p.kv_heads) * D, ((long)(p.seq_kv - 1) * p.v_pitch + D) * 4);
     const auto descQ = make_desc(p.q + (long)b * p.seq_q * p.q_pitch + h * D, ((long)(p.seq_q - 1) * p.q_pitch + D) * 4);
     const auto descDO = make_desc(p.dctx + (long)b * p.seq_q * p.dctx_pitch + h * D, ((long)(p.seq_q - 1) * p.dctx_pitch + D) * 4);
     const auto rsrcDQ = make_rsrc(p.dq + (long)b * p.seq_q * p.dq_pitch + h * D, ((long)(p.seq_q - 1) * p.dq_pitch + D) * 4);
@@ -2098,6 +2103,59 @@ mha_lse2_kernel(const float *__restrict__ lse, float *__restrict__ lse2, long pl
     lse2[i] = s_ < seq ? lse[bh * seq + s_] * LOG2E : 0.f;
 }
 
+// dK / dV of grouped-query attention from the per-query-head partials the backward kernels wrote ([rows = B * Skv, heads * D]
+// each, row pitch heads * D): out[b, j, c, :] = sum over g = 0 .. G-1, in that order, of part[b, j, g * kv_heads + c, :]
+// (G = heads / kv_heads; query head g * kv_heads + c reads K / V head c) -- no atomics, so the sums are bitwise reproducible.
+// dK and dV in one launch: one thread per 16-byte piece of an output row (the first rows * width4 pieces are dK's), grid-strided.
+// A streaming kernel: G reads and one write per piece; GS = G (2, 4, 8) issues the G loads back to back, GS = 0 loops.
+template <int GS>
+__global__ void __launch_bounds__(256)
+mha_gqa_reduce_kernel(const float *__restrict__ part_k, const float *__restrict__ part_v, float *__restrict__ dk, long dk_pitch,
+                      float *__restrict__ dv, long dv_pitch, long rows, int heads, int kv_heads, int dim) {
+    const int groups = GS ? GS : heads / kv_heads;
+    const long width4 = (long)kv_heads * dim / 4;
+    const long per = rows * width4, total = 2 * per;
+    const long part_pitch = (long)heads * dim, group_stride = (long)kv_heads * dim;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const bool second = i >= per;
+        const long r = second ? i - per : i;
+        const long row = r / width4, col = (r - row * width4) * 4;
+        const float *src = (second ? part_v : part_k) + row * part_pitch + col;
+        float4 acc;
+        if (GS) {
+            float4 x[GS ? GS : 1];
+#pragma unroll
+            for (int g = 0; g < GS; ++g) x[g] = ld4(src + g * group_stride);
+            acc = x[0];
+#pragma unroll
+            for (int g = 1; g < GS; ++g) { acc.x += x[g].x; acc.y += x[g].y; acc.z += x[g].z; acc.w += x[g].w; }
+        } else {
+            acc = ld4(src);
+            for (int g = 1; g < groups; ++g) {
+                const float4 x = ld4(src + g * group_stride);
+                acc.x += x.x; acc.y += x.y; acc.z += x.z; acc.w += x.w;
+            }
+        }
+        float *dst = second ? dv + row * dv_pitch + col : dk + row * dk_pitch + col;
+        *reinterpret_cast<float4 *>(dst) = acc;
+    }
+}
+
+int launch_gqa_reduce(const float *part_k, const float *part_v, float *dk, long dk_pitch, float *dv, long dv_pitch, long rows,
+                      int heads, int kv_heads, int dim, hipStream_t s) {
+    const long total = 2 * rows * ((long)kv_heads * dim / 4);
+    const int grid = (int)std::min<long>((total + 255) / 256, 2048);      // memory-bound: at most 8 blocks per CU, grid-strided
+    if (grid == 0) return NPM_OK;
+    switch (heads / kv_heads) {
+        case 2: hipLaunchKernelGGL(mha_gqa_reduce_kernel<2>, dim3(grid), dim3(256), 0, s, part_k, part_v, dk, dk_pitch, dv, dv_pitch, rows, heads, kv_heads, dim); break;
+        case 4: hipLaunchKernelGGL(mha_gqa_reduce_kernel<4>, dim3(grid), dim3(256), 0, s, part_k, part_v, dk, dk_pitch, dv, dv_pitch, rows, heads, kv_heads, dim); break;
+        case 8: hipLaunchKernelGGL(mha_gqa_reduce_kernel<8>, dim3(grid), dim3(256), 0, s, part_k, part_v, dk, dk_pitch, dv, dv_pitch, rows, heads, kv_heads, dim); break;
+        default: hipLaunchKernelGGL(mha_gqa_reduce_kernel<0>, dim3(grid), dim3(256), 0, s, part_k, part_v, dk, dk_pitch, dv, dv_pitch, rows, heads, kv_heads, dim); break;
+    }
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
+}
+
 // Tile summary of a mask: byte (qt, kb) of plane (b, h) has bit w set when some position of queries 32 qt .. 32 qt + 31 x keys
 // 128 kb + 16 w .. + 15 is allowed; a second array of the same shape behind it (`total` bytes later) has the bit set when EVERY
 // position of the sub-tile that lies inside the tensors is.  One block per (plane, qt, kb): thread = (query row, 16-key group).
@@ -2229,16 +2287,20 @@ int launch_bwd(const MhaArgs &a, hipStream_t s) {
 
 inline bool al16(const void *ptr) { return ((uintptr_t)ptr & 15) == 0; }
 
-int fill_args(const npm_mha_core *c, bool backward, MhaArgs &a) {
+// kv_heads: K / V heads (0: c->heads, the ungrouped call); k / v / dk / dv rows hold kv_heads heads
+int fill_args(const npm_mha_core *c, bool backward, int kv_heads, MhaArgs &a) {
     NPM_ARG(c != nullptr);
     NPM_ARG(c->batch >= 0 && c->heads >= 1 && c->seq_q >= 0 && c->seq_kv >= 1);
+    if (kv_heads == 0) kv_heads = c->heads;
+    NPM_ARG(kv_heads >= 1 && c->heads % kv_heads == 0);
     const int d = c->head_dim;
     if (!(d == 16 || d == 32 || d == 64 || d == 128))
         return npm::fail(NPM_E_UNSUPPORTED, "npm_mha_core: head_dim %d is not one of 16, 32, 64, 128 (use the GEMM composition)", d);
     NPM_ARG(c->scale > 0.f);
     NPM_ARG(c->q && c->k && c->v && c->ctx && c->lse);
     auto pitch_ok = [&](int64_t pitch) { return pitch >= (int64_t)c->heads * d && pitch % 4 == 0; };
-    NPM_ARG(pitch_ok(c->q_pitch) && pitch_ok(c->k_pitch) && pitch_ok(c->v_pitch) && pitch_ok(c->ctx_pitch));
+    auto kv_pitch_ok = [&](int64_t pitch) { return pitch >= (int64_t)kv_heads * d && pitch % 4 == 0; };
+    NPM_ARG(pitch_ok(c->q_pitch) && kv_pitch_ok(c->k_pitch) && kv_pitch_ok(c->v_pitch) && pitch_ok(c->ctx_pitch));
     NPM_ARG(al16(c->q) && al16(c->k) && al16(c->v) && al16(c->ctx));
     auto span_ok = [&](int64_t rows, int64_t pitch) { return (rows + 128) * pitch * 4 < (1LL << 31); };   // per (batch) extent below 2^31 bytes
     NPM_ARG(span_ok(c->seq_q, c->q_pitch) && span_ok(c->seq_kv, c->k_pitch) && span_ok(c->seq_kv, c->v_pitch) && span_ok(c->seq_q, c->ctx_pitch));
@@ -2264,6 +2326,7 @@ int fill_args(const npm_mha_core *c, bool backward, MhaArgs &a) {
     NPM_ARG(!c->scores || ((int64_t)c->seq_q + 32) * c->seq_kv * 4 < (1LL << 31));      // one (b, h) score matrix behind one descriptor
     NPM_ARG(!c->mask || (c->mask_stride_q >= 0 && ((int64_t)c->seq_q + 32) * c->mask_stride_q + c->seq_kv < (1LL << 31)));
     a.batch = c->batch; a.heads = c->heads; a.seq_q = c->seq_q; a.seq_kv = c->seq_kv;
+    a.kv_heads = kv_heads;
     a.scale = c->scale;
     a.q_tiles = (c->seq_q + 127) / 128;
     a.q_pair = a.skip != nullptr && a.q_tiles >= 2 && g_attn_pair;
@@ -2271,7 +2334,7 @@ int fill_args(const npm_mha_core *c, bool backward, MhaArgs &a) {
     a.stagger = g_attn_stagger;
     if (backward) {
         NPM_ARG(c->dctx && c->dq && c->dk && c->dv);
-        NPM_ARG(pitch_ok(c->dctx_pitch) && pitch_ok(c->dq_pitch) && pitch_ok(c->dk_pitch) && pitch_ok(c->dv_pitch));
+        NPM_ARG(pitch_ok(c->dctx_pitch) && pitch_ok(c->dq_pitch) && kv_pitch_ok(c->dk_pitch) && kv_pitch_ok(c->dv_pitch));
         NPM_ARG(al16(c->dctx) && al16(c->dq) && al16(c->dk) && al16(c->dv));
         NPM_ARG(span_ok(c->seq_q, c->dctx_pitch) && span_ok(c->seq_q, c->dq_pitch) && span_ok(c->seq_kv, c->dk_pitch) && span_ok(c->seq_kv, c->dv_pitch));
         a.dctx = c->dctx; a.dctx_pitch = c->dctx_pitch;
@@ -2314,36 +2377,36 @@ extern "C" int npm_mha_mask_summary(const uint8_t *mask, int64_t stride_b, int64
 
 extern "C" int npm_mha_core_supported(int head_dim) { return head_dim == 16 || head_dim == 32 || head_dim == 64 || head_dim == 128; }
 
-extern "C" int npm_mha_core_fwd(const npm_mha_core *c) {
-    NPM_REQUIRE_INIT();
+namespace {
+
+// grouped calls with more than one query head per K / V head say so in npm_last_attn_kernel
+void note_grouped(const MhaArgs &a) {
+    if (a.kv_heads == a.heads) return;
+    const size_t n = strlen(g_attn_last);
+    snprintf(g_attn_last + n, sizeof g_attn_last - n, " kv_heads=%d", a.kv_heads);
+}
+
+int core_fwd(const npm_mha_core *c, int kv_heads) {
     MhaArgs a;
-    int rc = fill_args(c, false, a);
+    int rc = fill_args(c, false, kv_heads, a);
     if (rc) return rc;
     if ((long)a.batch * a.heads * a.q_tiles == 0) return NPM_OK;
     NPM_ARG((long)a.batch * a.heads * a.q_tiles < (1L << 31));
     hipStream_t s = npm::ctx().stream;
     npm::note_math(NPM_MATH_F32);
     switch (c->head_dim) {
-        case 16: return launch_fwd<16>(a, s);
-        case 32: return launch_fwd<32>(a, s);
-        case 64: return launch_fwd<64>(a, s);
-        default: return launch_fwd<128>(a, s);
+        case 16: rc = launch_fwd<16>(a, s); break;
+        case 32: rc = launch_fwd<32>(a, s); break;
+        case 64: rc = launch_fwd<64>(a, s); break;
+        default: rc = launch_fwd<128>(a, s); break;
     }
+    if (rc == NPM_OK) note_grouped(a);
+    return rc;
 }
 
-extern "C" int npm_mha_core_bwd(const npm_mha_core *c) {
-    NPM_REQUIRE_INIT();
-    MhaArgs a;
-    int rc = fill_args(c, true, a);
-    if (rc) return rc;
-    if ((long)a.batch * a.heads == 0) return NPM_OK;
-    hipStream_t s = npm::ctx().stream;
-    if (a.seq_q == 0) {                                  // no queries: nothing flows back to the keys and values
-        const size_t width = sizeof(float) * (size_t)a.heads * c->head_dim, rows = (size_t)a.batch * a.seq_kv;
-        NPM_HIP(hipMemset2DAsync(a.dk, sizeof(float) * a.dk_pitch, 0, width, rows, s));
-        NPM_HIP(hipMemset2DAsync(a.dv, sizeof(float) * a.dv_pitch, 0, width, rows, s));
-        return NPM_OK;
-    }
+// the backward kernels for the arguments in `a` (row terms, then the kernel NPM_TUNE_ATTN_BWD16 selects)
+int run_bwd(MhaArgs &a, const npm_mha_core *c, hipStream_t s) {
+    int rc;
     npm::Scratch ws;                                  // stream-ordered pool: safe to release when this call returns
     const bool wide128 = c->head_dim == 128 && a.scores != nullptr && a.skip == nullptr;      // the case mha_bwd16_kernel was built for
     const bool use8 = (g_attn_bwd16 == 3 || (g_attn_bwd16 == 2 && !wide128)) && !a.trace;
@@ -2405,4 +2468,62 @@ extern "C" int npm_mha_core_bwd(const npm_mha_core *c) {
         case 64: return launch_bwd<64>(a, s);
         default: return launch_bwd<128>(a, s);
     }
+}
+
+int core_bwd(const npm_mha_core *c, int kv_heads) {
+    MhaArgs a;
+    int rc = fill_args(c, true, kv_heads, a);
+    if (rc) return rc;
+    if ((long)a.batch * a.heads == 0) return NPM_OK;
+    hipStream_t s = npm::ctx().stream;
+    if (a.seq_q == 0) {                                  // no queries: nothing flows back to the keys and values
+        const size_t width = sizeof(float) * (size_t)a.kv_heads * c->head_dim, rows = (size_t)a.batch * a.seq_kv;
+        NPM_HIP(hipMemset2DAsync(a.dk, sizeof(float) * a.dk_pitch, 0, width, rows, s));
+        NPM_HIP(hipMemset2DAsync(a.dv, sizeof(float) * a.dv_pitch, 0, width, rows, s));
+        return NPM_OK;
+    }
+    if (a.kv_heads == a.heads) return run_bwd(a, c, s);
+    // Grouped: every (b, h) block writes its query head's dK / dV into pooled partials [B, Skv, heads, D] (the store path of the
+    // ungrouped call at row pitch heads * D), then mha_gqa_reduce_kernel sums each group into the caller's dk / dv.
+    const int d = c->head_dim;
+    const long rows = (long)a.batch * a.seq_kv, part_pitch = (long)a.heads * d;
+    NPM_ARG(((int64_t)a.seq_kv + 128) * part_pitch * 4 < (1LL << 31));
+    npm::Scratch parts;                               // stream-ordered pool: safe to release when this call returns
+    const size_t n = (size_t)rows * part_pitch;
+    rc = parts.alloc(sizeof(float) * 2 * n);
+    if (rc) return rc;
+    float *dk = a.dk, *dv = a.dv;
+    const long dk_pitch = a.dk_pitch, dv_pitch = a.dv_pitch;
+    a.dk = (float *)parts.ptr; a.dv = a.dk + n;
+    a.dk_pitch = a.dv_pitch = part_pitch;
+    rc = run_bwd(a, c, s);
+    if (rc) return rc;
+    rc = launch_gqa_reduce(a.dk, a.dv, dk, dk_pitch, dv, dv_pitch, rows, a.heads, a.kv_heads, d, s);
+    if (rc) return rc;
+    note_grouped(a);
+    return NPM_OK;
+}
+
+}  // namespace
+
+extern "C" int npm_mha_core_fwd(const npm_mha_core *c) {
+    NPM_REQUIRE_INIT();
+    return core_fwd(c, 0);
+}
+
+extern "C" int npm_mha_core_bwd(const npm_mha_core *c) {
+    NPM_REQUIRE_INIT();
+    return core_bwd(c, 0);
+}
+
+extern "C" int npm_mha_core_fwd_grouped(const npm_mha_core *c, int32_t kv_heads) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(kv_heads >= 1);
+    return core_fwd(c, kv_heads);
+}
+
+extern "C" int npm_mha_core_bwd_grouped(const npm_mha_core *c, int32_t kv_heads) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(kv_heads >= 1);
+    return core_bwd(c, kv_heads);
 }

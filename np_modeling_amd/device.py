@@ -954,32 +954,43 @@ def _core_desc(q: Mat, k: Mat, v: Mat, ctx: Mat, lse: DeviceArray, dims, scale: 
 
 
 def mha_core_fwd(q: Mat, k: Mat, v: Mat, dims, scale: float, mask: Optional[AttnMask] = None,
-                 save_scores: bool = False):
+                 save_scores: bool = False, kv_heads: Optional[int] = None):
     """ctx[b, i, h, :] = softmax_j(scale q_i . k_j [masked]) v_j in one kernel (include/npm_hip.h npm_mha_core_fwd).
     ``q``/``k``/``v``: (array, row pitch) of [B, S, H, D] operands.  Returns (ctx [B, Sq, H, D], lse [B, H, Sq],
-    scores or None)."""
+    scores or None).  ``kv_heads`` (grouped-query attention, npm_mha_core_fwd_grouped): k / v are [B, Skv, kv_heads, D] and
+    query head h reads K / V head h % kv_heads; None is the ungrouped call."""
     b, h, sq, skv, d = dims
+    hkv = h if kv_heads is None else int(kv_heads)
     ctx, lse = empty([b, sq, h, d]), empty([b, h, sq])
     scores = empty([b, h, sq, skv]) if save_scores else None
     c = _core_desc(q, k, v, Mat(ctx, h * d), lse, dims, scale, mask, scores)
-    nbytes = 4.0 * b * h * d * (2 * sq + 2 * skv) + (4.0 * b * h * sq * skv if save_scores else 0.0)
+    nbytes = 4.0 * b * d * (2 * h * sq + 2 * hkv * skv) + (4.0 * b * h * sq * skv if save_scores else 0.0)
     with _timed('mha_core_fwd', flops=4.0 * b * h * sq * skv * d, nbytes=nbytes):
-        _C.check(_C.lib().npm_mha_core_fwd(C.byref(c)), 'npm_mha_core_fwd')
+        if kv_heads is None:
+            _C.check(_C.lib().npm_mha_core_fwd(C.byref(c)), 'npm_mha_core_fwd')
+        else:
+            _C.check(_C.lib().npm_mha_core_fwd_grouped(C.byref(c), hkv), 'npm_mha_core_fwd_grouped')
     return ctx, lse, scores
 
 
 def mha_core_bwd(q: Mat, k: Mat, v: Mat, ctx: DeviceArray, lse: DeviceArray, dctx: DeviceArray,
                  dq: Mat, dk: Mat, dv: Mat, dims, scale: float, mask: Optional[AttnMask] = None,
-                 scores: Optional[DeviceArray] = None, neg_delta: Optional[Tuple[DeviceArray, int, int]] = None) -> None:
+                 scores: Optional[DeviceArray] = None, neg_delta: Optional[Tuple[DeviceArray, int, int]] = None,
+                 kv_heads: Optional[int] = None) -> None:
     """dq, dk, dv of the attention core from q, k, v, the forward's ctx and lse, and dctx (npm_mha_core_bwd).
     Algorithmic work: the four products dP, dV, dK, dQ (the recomputed q.k is the kernel's own business).
-    ``neg_delta=(array, stride_b, stride_h)``: the row terms -scale * (dctx . ctx) already taken by the GEMM that produced dctx."""
+    ``neg_delta=(array, stride_b, stride_h)``: the row terms -scale * (dctx . ctx) already taken by the GEMM that produced dctx.
+    ``kv_heads``: grouped-query attention (npm_mha_core_bwd_grouped), k / v / dk / dv with kv_heads heads."""
     b, h, sq, skv, d = dims
+    hkv = h if kv_heads is None else int(kv_heads)
     c = _core_desc(q, k, v, Mat(ctx, h * d), lse, dims, scale, mask, scores)
     c.dctx, c.dctx_pitch = dctx.ptr, h * d
     c.dq, c.dq_pitch, c.dk, c.dk_pitch, c.dv, c.dv_pitch = dq.ptr, dq.ld, dk.ptr, dk.ld, dv.ptr, dv.ld
     if neg_delta is not None:
         c.neg_delta, c.neg_delta_stride_b, c.neg_delta_stride_h = neg_delta[0].ptr, int(neg_delta[1]), int(neg_delta[2])
-    nbytes = 4.0 * b * h * d * (4 * sq + 4 * skv) + (4.0 * b * h * sq * skv if scores is not None else 0.0)
+    nbytes = 4.0 * b * d * (4 * h * sq + 4 * hkv * skv) + (4.0 * b * h * sq * skv if scores is not None else 0.0)
     with _timed('mha_core_bwd', flops=8.0 * b * h * sq * skv * d, nbytes=nbytes):
-        _C.check(_C.lib().npm_mha_core_bwd(C.byref(c)), 'npm_mha_core_bwd')
+        if kv_heads is None:
+            _C.check(_C.lib().npm_mha_core_bwd(C.byref(c)), 'npm_mha_core_bwd')
+        else:
+            _C.check(_C.lib().npm_mha_core_bwd_grouped(C.byref(c), hkv), 'npm_mha_core_bwd_grouped')

@@ -29,6 +29,15 @@ position) then stay on the device between steps.
 
 Parameter layouts are the reference's: wq/wk [H, Dk, H*Dk], wv [H, Dv, H*Dv], wo [H*Dk, H, Dv],
 bq/bk [H, Dk], bv [H, Dv], bo [H*Dk] (attentions.py:46-65), drawn in that order.
+
+Grouped-query attention (``num_kv_heads=Hkv``, the reference's ``gqa_fwd``, layers/attentions_test.py:267-358): the
+Hq = ``num_heads`` query heads share Hkv key / value heads, so wk [Hkv, Dk, F], wv [Hkv, Dv, Fv], bk [Hkv, Dk] and
+bv [Hkv, Dv] (Dk = F / Hq, Dv = Fv / Hq as in MHA; same draw order).  Query head h = g * Hkv + c reads K / V head
+c = h % Hkv (the reference reshapes q to [B, Sq, Hq / Hkv, Hkv, Dk] and pairs its Hkv axis with k's heads).  The fused
+kernels take the grouping as an argument (``npm_mha_core_*_grouped``); the GEMM composition runs one batched GEMM over
+(B, Hkv) per group g -- query head g * Hkv + c is a column offset g * Hkv * D of the [B, S, Hq, D] tensors -- and sums
+the dK / dV of the groups in the residual epilogue, in the order g = 0, 1, ...  ``num_kv_heads=None`` (or ``num_heads``)
+is multi-head attention, run exactly as without the keyword.
 """
 
 from __future__ import annotations
@@ -46,10 +55,16 @@ from np_modeling_amd.layers import activations, layer
 _PARAMS = ('_wq', '_wk', '_wv', '_wo', '_bq', '_bk', '_bv', '_bo')
 
 
+def _from(x: D.DeviceArray, offset: int) -> D.DeviceArray:
+    """``x`` entered ``offset`` elements later (a head-slice operand of the grouped composition), spanning to its end."""
+    return x if offset == 0 else x.flat_view(offset, [x.size - offset])
+
+
 class MultiHeadAttention(layer.StatefulLayer):
-    def __init__(self, num_heads: int, *args, **kwargs):
+    def __init__(self, num_heads: int, *args, num_kv_heads: Optional[int] = None, **kwargs):
         super().__init__(*args, **kwargs)
         self._num_heads = num_heads
+        self._num_kv_heads = num_heads if num_kv_heads is None else num_kv_heads
         self._softmax = activations.Softmax()
 
     def initialize(self, query, key=None, value=None, *args, **kwargs) -> None:
@@ -64,25 +79,27 @@ class MultiHeadAttention(layer.StatefulLayer):
         assert key.shape[1] == value.shape[1]
         self._seq_len_q = query.shape[1]
         self._seq_len_kv = key.shape[1]
-        h = self._num_heads
+        h, hkv = self._num_heads, self._num_kv_heads
+        assert hkv >= 1 and h % hkv == 0, f'num_heads {h} is not a multiple of num_kv_heads {hkv}'
         assert key.shape[2] % h == 0
         self._key_dim = dk = key.shape[2] // h
         assert value.shape[2] % h == 0
         self._value_dim = dv = value.shape[2] // h
         # Draw order wq, wk, wv, wo, bq, bk, bv, bo (attentions.py:46-65).  When the three in-projections
-        # have one shape they are stored back to back (views of one [3, H, D, F] buffer), so that
+        # have one head size they are stored back to back (views of one [H + 2 Hkv, D, F] buffer), so that
         # self-attention can run them as ONE GEMM; rebinding any of them (weight binders do) just
         # falls back to three GEMMs.
-        draws = [self._initializer([h, dk, h * dk]), self._initializer([h, dk, h * dk]),
-                 self._initializer([h, dv, h * dv])]
+        draws = [self._initializer([h, dk, h * dk]), self._initializer([hkv, dk, h * dk]),
+                 self._initializer([hkv, dv, h * dv])]
         wo = self._initializer([h * dk, h, dv])
-        bias_draws = [self._initializer([h, dk]), self._initializer([h, dk]), self._initializer([h, dv])]
+        bias_draws = [self._initializer([h, dk]), self._initializer([hkv, dk]), self._initializer([hkv, dv])]
         bo = self._initializer([h * dk])
         if dk == dv:
-            packed_w, packed_b = D.empty([3, h, dk, h * dk]), D.empty([3, h, dk])
+            packed_w, packed_b = D.empty([h + 2 * hkv, dk, h * dk]), D.empty([h + 2 * hkv, dk])
             for i, (name, bname) in enumerate((('_wq', '_bq'), ('_wk', '_bk'), ('_wv', '_bv'))):
-                setattr(self, name, packed_w.flat_view(i * h * dk * h * dk, [h, dk, h * dk]).set(draws[i]))
-                setattr(self, bname, packed_b.flat_view(i * h * dk, [h, dk]).set(bias_draws[i]))
+                first, heads = (0, h) if i == 0 else (h + (i - 1) * hkv, hkv)       # head rows of the packed buffer
+                setattr(self, name, packed_w.flat_view(first * dk * h * dk, [heads, dk, h * dk]).set(draws[i]))
+                setattr(self, bname, packed_b.flat_view(first * dk, [heads, dk]).set(bias_draws[i]))
         else:
             self._wq, self._wk, self._wv = (D.as_device(a) for a in draws)
             self._bq, self._bk, self._bv = (D.as_device(a) for a in bias_draws)
@@ -96,7 +113,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         rebound between a forward and its backward (weight binders, tests)."""
         w = [self._param(p) for p in ('_wq', '_wk', '_wv')]
         b = [self._param(p) for p in ('_bq', '_bk', '_bv')]
-        return (w[0].shape == w[1].shape == w[2].shape and
+        return (w[0].shape[1:] == w[1].shape[1:] and w[1].shape == w[2].shape and
                 w[1].ptr == w[0].ptr + w[0].nbytes and w[2].ptr == w[1].ptr + w[1].nbytes and
                 b[1].ptr == b[0].ptr + b[0].nbytes and b[2].ptr == b[1].ptr + b[1].nbytes)
 
@@ -123,6 +140,8 @@ class MultiHeadAttention(layer.StatefulLayer):
 
     def _forward_impl(self, query, key, value, residual: Optional[D.DeviceArray] = None, mask=None):
         h, dk, dv = self._num_heads, self._key_dim, self._value_dim
+        hkv = self._num_kv_heads
+        grouped = hkv != h
         b, sq, f = query.shape
         skv = key.shape[1]
         fv = value.shape[2]
@@ -143,25 +162,28 @@ class MultiHeadAttention(layer.StatefulLayer):
         self._core = core
 
         # in-projections: [rows, F] x w[H*D, F]^T + b.  q/k/v are [B, S, H, D] head slices addressed through
-        # (array, element offset, row pitch): separate tensors, or thirds of one packed [B, S, 3, H, D].
+        # (array, element offset, row pitch): separate tensors, or parts of one packed [B, S, H + 2 Hkv, D].
         packed = self._packed_qkv(query, key, value)
         self._packed = packed
+        fkv, fvkv = hkv * dk, hkv * dv                                   # row widths of k and v
         if packed:
-            qkv = D.empty([b, sq, 3, h, dk])
-            D.gemm(b * sq, 3 * f, f, Mat(query, f), Mat(wq, f), Mat(qkv, 3 * f), trans_b=True, bias=bq)
-            pitch = 3 * f
-            # k and v are the same buffer entered f and 2f elements later (row pitch 3f); the views span to the end
-            q, k, v = qkv, qkv.flat_view(f, [qkv.size - f]), qkv.flat_view(2 * f, [qkv.size - 2 * f])
+            width = f + 2 * fkv
+            qkv = D.empty([b, sq, h + 2 * hkv, dk])
+            D.gemm(b * sq, width, f, Mat(query, f), Mat(wq, f), Mat(qkv, width), trans_b=True, bias=bq)
+            pitch = width
+            # k and v are the same buffer entered f and f + Hkv*Dk elements later (row pitch H*Dk + 2 Hkv*Dk); the views
+            # span to the end
+            q, k, v = qkv, qkv.flat_view(f, [qkv.size - f]), qkv.flat_view(f + fkv, [qkv.size - f - fkv])
         else:
             pitch = None
             q = D.empty([b, sq, h, dk])
-            k = D.empty([b, skv, h, dk])
-            v = D.empty([b, skv, h, dv])
+            k = D.empty([b, skv, hkv, dk])
+            v = D.empty([b, skv, hkv, dv])
             D.gemm(b * sq, h * dk, f, Mat(query, f), Mat(wq, f), Mat(q, h * dk), trans_b=True, bias=bq)
-            D.gemm(b * skv, h * dk, f, Mat(key, f), Mat(wk, f), Mat(k, h * dk), trans_b=True, bias=bk)
-            D.gemm(b * skv, h * dv, fv, Mat(value, fv), Mat(wv, fv), Mat(v, h * dv), trans_b=True, bias=bv)
+            D.gemm(b * skv, fkv, f, Mat(key, f), Mat(wk, f), Mat(k, fkv), trans_b=True, bias=bk)
+            D.gemm(b * skv, fvkv, fv, Mat(value, fv), Mat(wv, fv), Mat(v, fvkv), trans_b=True, bias=bv)
         self._q, self._k, self._v = q, k, v
-        pq, pk, pv = pitch or h * dk, pitch or h * dk, pitch or h * dv       # row pitches of q, k, v
+        pq, pk, pv = pitch or h * dk, pitch or fkv, pitch or fvkv       # row pitches of q, k, v
         self._pitches = (pq, pk, pv)
 
         self._scale = 1.0 / math.sqrt(dk)
@@ -169,20 +191,23 @@ class MultiHeadAttention(layer.StatefulLayer):
             # scores, softmax and context in one kernel; what the backward needs is the log-sum-exp per row
             ctx, self._lse, self._raw_scores = D.mha_core_fwd(
                 Mat(q, pq), Mat(k, pk), Mat(v, pv), (b, h, sq, skv, dk), self._scale, self._mask,
-                save_scores=D.attn_save_scores(dk))
+                save_scores=D.attn_save_scores(dk), kv_heads=hkv if grouped else None)
             self._softmax._y = self._attention_scores = None
         else:
-            # attention[b, h] = q_h k_h^T ; scores = softmax(attention / sqrt(dk))
+            # attention[b, h] = q_h k_h^T ; scores = softmax(attention / sqrt(dk)).  One GEMM batched over (B, Hkv) per
+            # group g: query heads g Hkv .. g Hkv + Hkv - 1 with K / V heads 0 .. Hkv - 1 (one group when not grouped)
             scores = D.empty([b, h, sq, skv])
-            D.gemm(sq, skv, dk, Mat(q, pq, sq * pq, dk), Mat(k, pk, skv * pk, dk),
-                   Mat(scores, skv, h * sq * skv, sq * skv), trans_b=True, batch=(b, h))
+            for g in range(h // hkv):
+                D.gemm(sq, skv, dk, Mat(_from(q, g * fkv), pq, sq * pq, dk), Mat(k, pk, skv * pk, dk),
+                       Mat(_from(scores, g * hkv * sq * skv), skv, h * sq * skv, sq * skv), trans_b=True, batch=(b, hkv))
             D.softmax_fwd(scores, self._scale, out=scores)
             self._softmax._y = scores
             self._attention_scores = scores
             # context[b, :, h, :] = scores[b, h] v_h      -> [B, Sq, H, Dv]
             ctx = D.empty([b, sq, h, dv])
-            D.gemm(sq, dv, skv, Mat(scores, skv, h * sq * skv, sq * skv), Mat(v, pv, skv * pv, dv),
-                   Mat(ctx, h * dv, sq * h * dv, dv), batch=(b, h))
+            for g in range(h // hkv):
+                D.gemm(sq, dv, skv, Mat(_from(scores, g * hkv * sq * skv), skv, h * sq * skv, sq * skv), Mat(v, pv, skv * pv, dv),
+                       Mat(_from(ctx, g * fvkv), h * dv, sq * h * dv, dv), batch=(b, hkv))
         self._context = ctx
 
         # output projection: [B*Sq, H*Dv] x wo[F, H*Dv]^T + bo (+ skip connection)
@@ -204,6 +229,8 @@ class MultiHeadAttention(layer.StatefulLayer):
         (cross-attention over one kv tensor): returns (dquery (+ residual), dkey + dvalue), the second
         accumulated in its GEMMs' epilogues (transformer.py:186)."""
         h, dk, dv = self._num_heads, self._key_dim, self._value_dim
+        hkv = self._num_kv_heads
+        grouped, fkv, fvkv = hkv != h, hkv * dk, hkv * dv
         query, key, value = self._query, self._key, self._value
         q, k, v, scores, ctx = self._q, self._k, self._v, self._attention_scores, self._context
         b, sq, f = dy.shape
@@ -237,22 +264,27 @@ class MultiHeadAttention(layer.StatefulLayer):
         pq, pk, pv = self._pitches
         # dbq/dbk/dbv = sum over (batch, position) of dq/dk/dv (attentions.py:186-188): taken from the dq/dk/dv
         # tiles of the in-projection weight-gradient GEMMs below
+        width = f + 2 * fkv                 # packed: row width of [B, S, H + 2 Hkv, D]
         if packed:      # gradients of the packed parameters and of q/k/v live in packed buffers too
-            dw_all, db_all = scope.take([3, h, dk, f], owner=(self, '_wq')), scope.take([3, h, dk], owner=(self, '_bq'))
-            dwq, dwk, dwv = (dw_all.flat_view(i * h * dk * f, [h, dk, f]) for i in range(3))
-            dbq, dbk, dbv = (db_all.flat_view(i * h * dk, [h, dk]) for i in range(3))
-            dqkv = D.empty([b, sq, 3, h, dk])
-            dq, dk_, dv_ = dqkv, dqkv.flat_view(f, [dqkv.size - f]), dqkv.flat_view(2 * f, [dqkv.size - 2 * f])
-            gq = gk = gv = 3 * f
+            dw_all = scope.take([h + 2 * hkv, dk, f], owner=(self, '_wq'))
+            db_all = scope.take([h + 2 * hkv, dk], owner=(self, '_bq'))
+            dwq, dwk, dwv = (dw_all.flat_view(first * dk * f, [heads, dk, f]) for first, heads in ((0, h), (h, hkv), (h + hkv, hkv)))
+            dbq, dbk, dbv = (db_all.flat_view(first * dk, [heads, dk]) for first, heads in ((0, h), (h, hkv), (h + hkv, hkv)))
+            dqkv = D.empty([b, sq, h + 2 * hkv, dk])
+            dq, dk_, dv_ = dqkv, dqkv.flat_view(f, [dqkv.size - f]), dqkv.flat_view(f + fkv, [dqkv.size - f - fkv])
+            gq = gk = gv = width
         else:
             dwq, dwk, dwv = (scope.take(w_.shape, owner=(self, a_)) for w_, a_ in ((wq, '_wq'), (wk, '_wk'), (wv, '_wv')))
-            dbq, dbk, dbv = (scope.take([h, d_], owner=(self, a_)) for d_, a_ in ((dk, '_bq'), (dk, '_bk'), (dv, '_bv')))
-            dq, dk_, dv_ = D.empty([b, sq, h, dk]), D.empty([b, skv, h, dk]), D.empty([b, skv, h, dv])
-            gq, gk, gv = h * dk, h * dk, h * dv
+            dbq, dbk, dbv = (scope.take([n_, d_], owner=(self, a_)) for n_, d_, a_ in ((h, dk, '_bq'), (hkv, dk, '_bk'), (hkv, dv, '_bv')))
+            dq, dk_, dv_ = D.empty([b, sq, h, dk]), D.empty([b, skv, hkv, dk]), D.empty([b, skv, hkv, dv])
+            gq, gk, gv = h * dk, fkv, fvkv
         if self._core:
             # attentions.py:146-162 in one kernel: P is recomputed from the saved log-sum-exp, tile by tile
             D.mha_core_bwd(Mat(q, pq), Mat(k, pk), Mat(v, pv), ctx, self._lse, dctx, Mat(dq, gq), Mat(dk_, gk),
-                           Mat(dv_, gv), (b, h, sq, skv, dk), self._scale, self._mask, self._raw_scores, neg_delta=neg_delta)
+                           Mat(dv_, gv), (b, h, sq, skv, dk), self._scale, self._mask, self._raw_scores, neg_delta=neg_delta,
+                           kv_heads=hkv if grouped else None)
+        elif grouped:
+            self._grouped_composition_bwd(dctx, dq, dk_, dv_, (gq, gk, gv))
         else:
             # softmax @ V (attentions.py:146-148)
             # dP = dctx_h v_h^T followed by the softmax backward and the 1/sqrt(dk) of attentions.py:150-155.
@@ -279,11 +311,11 @@ class MultiHeadAttention(layer.StatefulLayer):
 
         # in-projections (attentions.py:167-188): dw = dproj^T x ; dx = dproj w
         if packed:
-            D.gemm(3 * f, f, m_q, Mat(dqkv, 3 * f), Mat(query, f), Mat(dw_all, f), trans_a=True, asum_out=db_all)
+            D.gemm(width, f, m_q, Mat(dqkv, width), Mat(query, f), Mat(dw_all, f), trans_a=True, asum_out=db_all)
         else:
             D.gemm(h * dk, f, m_q, Mat(dq, gq), Mat(query, f), Mat(dwq, f), trans_a=True, asum_out=dbq)
-            D.gemm(h * dk, f, m_kv, Mat(dk_, gk), Mat(key, f), Mat(dwk, f), trans_a=True, asum_out=dbk)
-            D.gemm(h * dv, fv, m_kv, Mat(dv_, gv), Mat(value, fv), Mat(dwv, fv), trans_a=True, asum_out=dbv)
+            D.gemm(fkv, f, m_kv, Mat(dk_, gk), Mat(key, f), Mat(dwk, f), trans_a=True, asum_out=dbk)
+            D.gemm(fvkv, fv, m_kv, Mat(dv_, gv), Mat(value, fv), Mat(dwv, fv), trans_a=True, asum_out=dbv)
         # every parameter gradient of this layer now exists: start exchanging them (data parallel) under
         # the remaining input-gradient GEMMs
         scope.flush()
@@ -291,28 +323,28 @@ class MultiHeadAttention(layer.StatefulLayer):
             assert query is key and key is value
             total = D.empty([b, sq, f])
             res = None if residual is None else Mat(residual, f)
-            if packed and self._params_adjacent():      # dq wq + dk wk + dv wv: one contraction over the packed 3F axis
-                D.gemm(m_q, f, 3 * f, Mat(dqkv, 3 * f), Mat(wq, f), Mat(total, f), residual=res)
+            if packed and self._params_adjacent():      # dq wq + dk wk + dv wv: one contraction over the packed (H + 2 Hkv) D axis
+                D.gemm(m_q, f, width, Mat(dqkv, width), Mat(wq, f), Mat(total, f), residual=res)
             else:
                 D.gemm(m_q, f, h * dk, Mat(dq, gq), Mat(wq, f), Mat(total, f), residual=res)
-                D.gemm(m_kv, f, h * dk, Mat(dk_, gk), Mat(wk, f), Mat(total, f), residual=Mat(total, f))
-                D.gemm(m_kv, fv, h * dv, Mat(dv_, gv), Mat(wv, fv), Mat(total, fv), residual=Mat(total, fv))
+                D.gemm(m_kv, f, fkv, Mat(dk_, gk), Mat(wk, f), Mat(total, f), residual=Mat(total, f))
+                D.gemm(m_kv, fv, fvkv, Mat(dv_, gv), Mat(wv, fv), Mat(total, fv), residual=Mat(total, fv))
             result = total
         elif sum_kv:
             assert key is value and fv == f
             dquery, dkv = D.empty([b, sq, f]), D.empty([b, skv, f])
             D.gemm(m_q, f, h * dk, Mat(dq, gq), Mat(wq, f), Mat(dquery, f),
                    residual=None if residual is None else Mat(residual, f))
-            D.gemm(m_kv, f, h * dk, Mat(dk_, gk), Mat(wk, f), Mat(dkv, f))
-            D.gemm(m_kv, f, h * dv, Mat(dv_, gv), Mat(wv, f), Mat(dkv, f), residual=Mat(dkv, f))
+            D.gemm(m_kv, f, fkv, Mat(dk_, gk), Mat(wk, f), Mat(dkv, f))
+            D.gemm(m_kv, f, fvkv, Mat(dv_, gv), Mat(wv, f), Mat(dkv, f), residual=Mat(dkv, f))
             result = (dquery, dkv)
         else:
             assert residual is None
             dquery, dkey, dvalue = D.empty([b, sq, f]), D.empty([b, skv, f]), D.empty([b, skv, fv])
             D.gemm(m_q, f, h * dk, Mat(dq, gq), Mat(wq, f), Mat(dquery, f))
-            D.gemm(m_kv, f, h * dk, Mat(dk_, gk), Mat(wk, f), Mat(dkey, f))
+            D.gemm(m_kv, f, fkv, Mat(dk_, gk), Mat(wk, f), Mat(dkey, f))
             assert value.shape == (b, skv, h * dv)
-            D.gemm(m_kv, fv, h * dv, Mat(dv_, gv), Mat(wv, fv), Mat(dvalue, fv))
+            D.gemm(m_kv, fv, fvkv, Mat(dv_, gv), Mat(wv, fv), Mat(dvalue, fv))
             result = (dquery, dkey, dvalue)
 
         # update order of attentions.py:190-197
@@ -320,3 +352,31 @@ class MultiHeadAttention(layer.StatefulLayer):
                                 ('_bq', dbq), ('_bk', dbk), ('_bv', dbv), ('_bo', dbo)):
             scope.defer(optimizer_, self, attribute, grad)
         return result
+
+    def _grouped_composition_bwd(self, dctx, dq, dk_, dv_, pitches) -> None:
+        """attentions.py:146-162 for grouped-query attention from GEMMs: per group g one product batched over (B, Hkv) for each of
+        dP, dV, dQ, dK (query heads g Hkv + c, K / V heads c); dV and dK sum the groups in the residual epilogue aliased to C, in
+        the order g = 0, 1, ..., so the result does not depend on scheduling."""
+        h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
+        q, k, v, scores = self._q, self._k, self._v, self._attention_scores
+        pq, pk, pv = self._pitches
+        gq, gk, gv = pitches
+        b, sq = dctx.shape[:2]
+        skv = self._key.shape[1]
+        plane = sq * skv
+        datt = D.empty([b, h, sq, skv])
+        for g in range(h // hkv):                 # dP = dctx_h v_c^T
+            D.gemm(sq, skv, dv, Mat(_from(dctx, g * hkv * dv), h * dv, sq * h * dv, dv), Mat(v, pv, skv * pv, dv),
+                   Mat(_from(datt, g * hkv * plane), skv, h * plane, plane), trans_b=True, batch=(b, hkv))
+        D.softmax_bwd(scores, datt, self._scale, out=datt)
+        for g in range(h // hkv):
+            s_g = Mat(_from(scores, g * hkv * plane), skv, h * plane, plane)
+            a_g = Mat(_from(datt, g * hkv * plane), skv, h * plane, plane)
+            acc_v = None if g == 0 else Mat(dv_, gv, skv * gv, dv)
+            acc_k = None if g == 0 else Mat(dk_, gk, skv * gk, dk)
+            D.gemm(skv, dv, sq, s_g, Mat(_from(dctx, g * hkv * dv), h * dv, sq * h * dv, dv),
+                   Mat(dv_, gv, skv * gv, dv), trans_a=True, batch=(b, hkv), residual=acc_v)          # (+)= P_h^T dctx_h
+            D.gemm(sq, dk, skv, a_g, Mat(k, pk, skv * pk, dk),
+                   Mat(_from(dq, g * hkv * dk), gq, sq * gq, dk), batch=(b, hkv))                      # datt_h k_c
+            D.gemm(skv, dk, sq, a_g, Mat(_from(q, g * hkv * dk), pq, sq * pq, dk),
+                   Mat(dk_, gk, skv * gk, dk), trans_a=True, batch=(b, hkv), residual=acc_k)          # (+)= datt_h^T q_h

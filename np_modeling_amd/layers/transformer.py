@@ -9,9 +9,14 @@ into the epilogue of ``dense2``'s dx GEMM, so no standalone elementwise pass run
 All parameter updates are deferred to the end of ``backward`` (every dx is computed from
 pre-update weights in the reference too), which lets the data-parallel gradient all-reduce
 overlap the rest of the backward pass.
+
+``num_kv_heads`` (default None: multi-head attention) makes every attention layer grouped-query attention with that many
+key / value heads (attentions.py); nothing else changes.
 """
 
 from __future__ import annotations
+
+from typing import Optional
 
 from np_modeling_amd import device as D
 from np_modeling_amd import parallel
@@ -67,9 +72,9 @@ def _block_backward(dy, norm, dropout, norm_first: bool, body_backward, optimize
 
 class TransformerEncoder(layer.Layer):
     def __init__(self, num_heads: int, hidden_units: int, norm_first: bool, drop_rate: float = 0.0,
-                 *args, **kwargs):
+                 *args, num_kv_heads: Optional[int] = None, **kwargs):
         super().__init__(*args, **kwargs)
-        self._self_attention = attentions.MultiHeadAttention(num_heads)
+        self._self_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)
         self._dense1 = mlp.Dense(units=hidden_units)
         self._norm1 = normalizations.LayerNormalization()
         self._norm2 = normalizations.LayerNormalization()
@@ -207,10 +212,10 @@ class TransformerDecoder(layer.Layer):
     ``dkv = dkey + dvalue`` of the cross-attention (transformer.py:186)."""
 
     def __init__(self, num_heads: int, hidden_units: int, norm_first: bool, drop_rate: float = 0.0,
-                 *args, **kwargs):
+                 *args, num_kv_heads: Optional[int] = None, **kwargs):
         super().__init__(*args, **kwargs)
-        self._self_attention = attentions.MultiHeadAttention(num_heads)
-        self._cross_attention = attentions.MultiHeadAttention(num_heads)
+        self._self_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)
+        self._cross_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)
         self._dense1 = mlp.Dense(units=hidden_units)
         self._norm1 = normalizations.LayerNormalization()
         self._norm2 = normalizations.LayerNormalization()
