@@ -1038,11 +1038,17 @@ mha_bwd_kernel(const MhaArgs p) {
                 for (int r = 0; r < 16; ++r)
                     mk[r] = __builtin_amdgcn_raw_buffer_load_b8(rsrcM, mvoff, (q0 + (r & 3) + 8 * (r >> 2)) * (int)p.mask_sq, 0);
             }
+            // A key beyond the end reads 0 (score 0): its P = 2^(-log2(e) LSE) overflows to inf for a row with LSE < -88, and inf
+            // times the zero K row is NaN in dQ.  The ragged last key block gives such keys the score -inf (P = 0) instead.
+            if (kb * 128 + 128 > p.seq_kv && !kvok) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) S[r] = -INFINITY;
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 // an excluded position has the score -inf (np.where(mask, scaled, -inf)): P = 0 -- except in a row with NO allowed
                 // key, whose LSE is -inf too: P = NaN there, as NumPy's softmax of a row of -inf, and as the saved scores (which
-                // carry the -inf) give it.  (a key or query beyond the end reads 0 too: its P is never used)
+                // carry the -inf) give it.  (a query beyond the end reads 0 too: its P is never used)
                 const float pr = fast_exp2(fmaf((MASK && mk[r] == 0) ? -INFINITY : S[r], c, -Lr[r]));
                 P[r] = pr;
                 dS[r] = pr * (dP[r] - Dr[r]);                 // dP and delta carry the 1 / sqrt(Dk) already
@@ -1342,6 +1348,13 @@ mha_bwd16_kernel(const MhaArgs p) {
             }
             STAMP(2);
             // ---- P = exp(scale S - LSE); dS = P (dP - delta) (both carry the 1 / sqrt(Dk) already), also into LDS
+            //      (keys beyond the end: score -inf, see mha_bwd_kernel)
+            if (kb * 128 + 128 > p.seq_kv && !kvok) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) S[t][r] = -INFINITY;
+            }
             f32x4 P[2], dS[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t)
@@ -1865,8 +1878,12 @@ mha_bwd8_kernel(const MhaArgs p) {
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        // (an excluded position: score -inf, so P = 0 -- and NaN in a row without any allowed key, see mha_bwd_kernel)
-                        const float pr = fast_exp2(fmaf((masked_sub[kg] && mk[kg][t][r] == 0) ? -INFINITY : S[kg][t][r], c, -Lr[t][r]));
+                        // (an excluded position: score -inf, so P = 0 -- and NaN in a row without any allowed key, see mha_bwd_kernel;
+                        //  a key beyond the end: score -inf too, see there.  The masked instances rely on its mask byte, which reads 0, so
+                        //  a sub-tile whose summary "all" bit is set still gives such a key score 0.  A select, not a branch: a branch
+                        //  here moves the blocks that tools/waitcnt_pins.json pins)
+                        const bool out = (masked_sub[kg] && mk[kg][t][r] == 0) || (!MASK && kvoob[kg] != 0);
+                        const float pr = fast_exp2(fmaf(out ? -INFINITY : S[kg][t][r], c, -Lr[t][r]));
                         P[t][r] = pr;
                         dS[kg][t][r] = pr * dP[t][r];
                         tDS[wsS[r] + t * SROWS16 + 128 * kg] = dS[kg][t][r];
