@@ -145,6 +145,8 @@ enum {
     NPM_TUNE_GEMM_SPLIT_GENS = 18,   /* split-K of tall-K products (weight gradients): 1 (default) for A-heavy products that also sum A's columns, a K range longer than 768 K tiles is cut further when that makes whole generations of resident blocks (3 x 4 per CU: the packed q/k/v weight gradient 6.00 -> 5.71 ms); 0 one generation of three blocks per CU always (round 3) */
     NPM_TUNE_STREAM_NT = 12,         /* 1 (default): the HBM-bound kernels move tensors of >= 32 MB with the nontemporal cache hint; 0: default policy */
     NPM_TUNE_LN_NT_SPLIT = 19,       /* LayerNorm at d in (512, 1024]: backward mode + 4 * forward mode; a mode: 0 nontemporal hint on loads and stores, 1 on the loads only, 2 on the stores only.  Default 5: loads only in both (dx and z are read at once by the GEMMs behind them; measured inside the encoder step, profiles/r05_ln_nt_split.log) */
+    NPM_TUNE_DECODE_SPLITS = 20,     /* npm_mha_decode_fwd: blocks the keys of one (batch, K / V head) are split over: 0 (default) automatic (npm_mha_decode_splits), n in 1 .. NPM_DECODE_MAX_SPLITS forced -- more splits than 16-key tiles leaves empty splits, which is allowed */
+    NPM_TUNE_DECODE_NT = 21,         /* npm_mha_decode_fwd, the cache hint of the K / V loads (each byte is read once): 0 (default) nontemporal when the valid part of K is at least 32 MB (NPM_TUNE_STREAM_NT's rule), 1 always, 2 never; measured in tools/decode_bench.py */
     NPM_TUNE_GEMM_ABLATE = 99
 };
 int npm_set_tuning(int knob, int value);
@@ -343,6 +345,46 @@ const char *npm_last_attn_kernel(void);
  * tiles (phase boundaries: tile start, after S, dP, dV, dK, the dS barrier, dQ, the dQ stores; word 8: next tile's start)
  * to buf[blockIdx * 16 ..]; NULL switches it off. */
 int npm_debug_attn_trace(long long *buf);
+
+/* ---- incremental decoding: attention over a key / value cache (inference; the reference has none: "# TODO: support cache",
+ * layers/transformer.py:120) ----
+ * T = new_tokens query tokens per sequence attend to the first L = kv_len rows of a cache [B, capacity, kv_heads, D]:
+ *   ctx[b, t, h, :] = sum_j softmax_j(scale * q[b, t, h, :] . k[b, j, h % kv_heads, :]) v[b, j, h % kv_heads, :]
+ *   j < L when causal == 0; j <= L - T + t when causal != 0 (the T new tokens are the LAST T keys of the cache, already appended).
+ * Rows L .. capacity - 1 of the cache are never part of a result, whatever they hold (NaN included); capacity itself is not an
+ * argument: the kernel reads no row at or past L.  One block serves the heads / kv_heads query heads that share a K / V head (so
+ * K and V are read once per group), the keys are split over several blocks whose partial results a second kernel merges in
+ * split order (no atomics: bitwise reproducible; the split count is npm_mha_decode_splits, a function of the shape and of
+ * NPM_TUNE_DECODE_SPLITS only).  fp32 in and out, exact-fp32 MFMA (npm_set_math does not apply).  head_dim in {16, 32, 64, 128} and
+ * group_rows = (heads / kv_heads) * new_tokens <= NPM_DECODE_MAX_ROWS, else NPM_E_UNSUPPORTED (callers then use npm_mha_core_fwd_grouped
+ * with a causal mask, or the GEMM composition).  NPM_E_BAD_ARGUMENT: kv_len < new_tokens, heads % kv_heads != 0, a pointer that
+ * is not 16-byte aligned, a pitch or batch stride that is not a multiple of 4 floats or is narrower than its row. */
+#define NPM_DECODE_MAX_ROWS 32
+#define NPM_DECODE_MAX_SPLITS 1024
+typedef struct npm_mha_decode {
+    int32_t batch, heads, kv_heads, new_tokens, kv_len, head_dim;   /* kv_len = L: valid cache rows, the new tokens included */
+    int32_t causal;                                /* 0: every row sees keys 0 .. L - 1; else row t sees keys 0 .. L - T + t */
+    float scale;                                   /* 1 / sqrt(Dk), > 0 */
+    const float *q; int64_t q_pitch;               /* [B, T, heads, D]; pitch = floats between consecutive (b, t) rows */
+    const float *k; int64_t k_pitch, k_stride_b;   /* cache [B, capacity, kv_heads, D]: floats between rows / between batch entries */
+    const float *v; int64_t v_pitch, v_stride_b;
+    float *ctx; int64_t ctx_pitch;                 /* out [B, T, heads, D] */
+    float *lse;                                    /* optional out [B, heads, T]: log sum_j exp(scale * q.k) over the visible keys */
+} npm_mha_decode;
+int npm_mha_decode_supported(int head_dim, int group_rows);      /* group_rows = (heads / kv_heads) * new_tokens */
+int npm_mha_decode_fwd(const npm_mha_decode *d);
+/* The number of key splits npm_mha_decode_fwd uses for this shape under the current NPM_TUNE_DECODE_SPLITS. */
+int npm_mha_decode_splits(int batch, int kv_heads, int kv_len);
+/* cache[b, at + t, 0 .. row_len - 1] = src[b * new_tokens + t, 0 .. row_len - 1] for every b < batch, t < new_tokens: the freshly
+ * projected K (or V) rows of T tokens per sequence into cache rows at .. at + T - 1.  src_pitch: floats between consecutive
+ * (b, t) rows of the source (a packed [B, T, heads + 2 kv_heads, D] projection is read in place); cache_pitch / cache_stride_b as
+ * k_pitch / k_stride_b above.  The caller checks at + new_tokens against the capacity.  16-byte accesses: row_len, pitches and
+ * the stride multiples of 4 floats, pointers 16-byte aligned, else NPM_E_BAD_ARGUMENT. */
+int npm_kv_append(const float *src, int64_t src_pitch, float *cache, int64_t cache_pitch, int64_t cache_stride_b,
+                  int32_t batch, int32_t new_tokens, int32_t row_len, int32_t at);
+/* What the most recent npm_mha_decode_fwd launched: "<kernel> D=<head_dim> rows=<group_rows> splits=<n> causal=<0|1>"; "" before
+ * the first call. */
+const char *npm_last_decode_kernel(void);
 
 /* ---- around the path ("next" rows of SURVEY.md section 8f): keeps a Trainer step on the device ---- */
 /* Adam with the reference's numerics (optimizer.py:53-67): fp64 moments m, v (device buffers of n doubles,

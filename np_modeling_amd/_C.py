@@ -78,6 +78,20 @@ class npm_mha_core(C.Structure):
     ]
 
 
+class npm_mha_decode(C.Structure):
+    _fields_ = [
+        ('batch', C.c_int32), ('heads', C.c_int32), ('kv_heads', C.c_int32), ('new_tokens', C.c_int32), ('kv_len', C.c_int32),
+        ('head_dim', C.c_int32),
+        ('causal', C.c_int32),
+        ('scale', C.c_float),
+        ('q', C.c_void_p), ('q_pitch', C.c_int64),
+        ('k', C.c_void_p), ('k_pitch', C.c_int64), ('k_stride_b', C.c_int64),
+        ('v', C.c_void_p), ('v_pitch', C.c_int64), ('v_stride_b', C.c_int64),
+        ('ctx', C.c_void_p), ('ctx_pitch', C.c_int64),
+        ('lse', C.c_void_p),
+    ]
+
+
 class npm_comm_exchange_stats(C.Structure):
     _fields_ = [('bytes', C.c_ulonglong), ('allreduce_calls', C.c_int), ('waits', C.c_int),
                 ('allreduce_ms', C.c_double), ('exposed_ms', C.c_double), ('last_allreduce_ms', C.c_double),
@@ -140,6 +154,10 @@ SIGNATURES = {
     'npm_mha_core_fwd_grouped': [C.POINTER(npm_mha_core), _I32],
     'npm_mha_core_bwd_grouped': [C.POINTER(npm_mha_core), _I32],
     'npm_mha_mask_summary': [_P, _I64, _I64, _I64, _I32, _I32, _I32, _I32, _P],
+    'npm_mha_decode_supported': [C.c_int, C.c_int],
+    'npm_mha_decode_fwd': [C.POINTER(npm_mha_decode)],
+    'npm_mha_decode_splits': [C.c_int, C.c_int, C.c_int],
+    'npm_kv_append': [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _I32],
     'npm_adam_step': [_P, _P, _P, _P, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int],
     'npm_fill_f64': [_P, C.c_double, _SZ],
     'npm_mse_fwd': [_P, _P, _SZ, C.POINTER(C.c_double)],
@@ -154,6 +172,7 @@ _SPECIAL = {
     'npm_last_error': (C.c_char_p, []),
     'npm_stream': (C.c_void_p, []),
     'npm_last_attn_kernel': (C.c_char_p, []),
+    'npm_last_decode_kernel': (C.c_char_p, []),
 }
 
 COMM_SIGNATURES = {
@@ -382,6 +401,14 @@ def last_math() -> str:
 def last_attn_kernel() -> str:
     """What the most recent fused attention call launched (include/npm_hip.h npm_last_attn_kernel)."""
     return lib().npm_last_attn_kernel().decode()
+
+
+def last_decode_kernel() -> str:
+    """What the most recent npm_mha_decode_fwd launched (include/npm_hip.h npm_last_decode_kernel)."""
+    return lib().npm_last_decode_kernel().decode()
+
+
+TUNE_DECODE_SPLITS, TUNE_DECODE_NT = 20, 21     # include/npm_hip.h NPM_TUNE_DECODE_*
 
 
 def comm_lib():

@@ -1,0 +1,450 @@
+// Incremental decoding: attention of T new query tokens over a key / value cache, and the append into that cache
+// (include/npm_hip.h: npm_mha_decode_fwd, npm_kv_append).  Inference only: nothing is saved for a backward.
+//
+//   ctx[b, t, h, :] = sum_j softmax_j(scale q[b, t, h, :] . K[b, j, h % Hkv, :]) V[b, j, h % Hkv, :]
+//   j < L (causal = 0)    j <= L - T + t (causal = 1: the T new tokens are the last T keys of the cache)
+//
+// The work is one pass over K and V, so the kernel is shaped around that stream:
+//   * ONE block serves a whole grouped-query group: the rows of its score tile are the R = (Hq / Hkv) T pairs (query head of the
+//     group, new token) that share K / V head c -- heads c, c + Hkv, c + 2 Hkv, ... (the project's h % Hkv mapping) -- so K and
+//     V of that head are read once per (batch, K / V head, key range), not once per query head.
+//   * the keys are SPLIT over gridDim.x blocks so that small B Hkv still fills the chip; each split leaves (m, l, acc[D]) per row
+//     (largest raw score, sum, unnormalised accumulator) in pooled scratch and mha_decode_combine_kernel merges the
+//     splits of a row in split order: no atomics, bitwise reproducible.  One split: the kernel writes ctx itself.
+//   * inside a block the four waves take the 16-key tiles of the split's range round robin and merge through LDS, wave 0 first.
+//
+// MFMA orientation (v_mfma_f32_16x16x4_f32: lane l supplies A[m = l & 15][k = l >> 4] and B[k = l >> 4][n = l & 15]; register w of
+// the result is row m = 4 (l >> 4) + w, column n = l & 15).  As in the training forward the QUERY ROW is on the lane:
+//   S^T[key, row] = K Q^T       A = K (key j = l & 15), B = Q (row i = l & 15).  The contraction index is permuted so that a
+//                               lane's K operand is one 16-byte load: step (u, e) contracts d = 16 u + 4 (l >> 4) + e.
+//   O^T[d, row] += V^T P^T      P^T is, register for register, the B operand: register w of S^T holds key 4 (l >> 4) + w, so step w
+//                               contracts keys {4 g + w}, and A = V[key 4 (l >> 4) + w][d]: lane c = l & 15 loads VW = min(4, D / 16)
+//                               consecutive floats at d = 16 VW dq + VW c; component e of that load feeds output block (dq, e),
+//                               whose row m is d = 16 VW dq + VW m + e.  (D = 16 / 32 have fewer than 64 floats per key, so there
+//                               V moves 4 / 8 bytes per lane; K always moves 16.)
+// Row statistics are lane-local but for one exchange across the four 16-lane groups; the running sum stays a per-lane partial
+// (every lane of a row applies the same rescale) and is reduced once at the end.
+//
+// Nothing past the valid length enters a result: a key at or past L, or one a causal row may not see, gets score -inf by
+// SELECTION (never by arithmetic on what was loaded); loads of such keys are redirected to key L - 1 (in bounds whatever the
+// capacity) and V of keys >= L is zeroed, which only the last tile of a call pays for; a row (or a whole split) without a
+// visible key has m = -inf, l = 0 and is given weight 0 by comparing, not by exp(-inf - -inf).
+//
+// The running maximum is kept as the RAW score s_max (before the scale): the reference point of the exponents is m = s_max c
+// (c = scale log2(e); rounding is monotone, so that is the largest scaled score), and lse = scale s_max + ln(2) log2(l) takes one
+// rounding of a large number instead of the three of ln(2) (s_max c + log2(l)).  Every exponent is fma(s, c, -m) with the ROUNDED
+// m = fl(s_max c) (so the sums l are relative to m exactly, and merging waves and splits, exp2(m_a - m_b), is consistent); the
+// rounding of m itself, delta = m - s_max c, is recovered exactly by one fma and added to log2(l).  Floating-point contraction
+// is off in these kernels: each fma is written out.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "npm_internal.h"
+
+namespace {
+
+constexpr float LOG2E = 1.44269504088896340736f;
+constexpr float LN2 = 0.69314718055994530942f;
+constexpr int WAVES = 4;          // per block
+constexpr int TILE = 16;          // keys per wave tile
+
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+
+#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+
+int g_splits = 0;                 // NPM_TUNE_DECODE_SPLITS: 0 automatic, n > 0 forced
+int g_nt = 0;                     // NPM_TUNE_DECODE_NT: 0 by size (npm::stream_nt_enabled of the valid K bytes), 1 always, 2 never
+char g_last[96] = "";
+
+struct DecodeArgs {
+    const float *q, *k, *v;
+    long q_pitch, k_pitch, k_sb, v_pitch, v_sb;
+    float *ctx;
+    long ctx_pitch;
+    float *lse;                   // optional [B, Hq, T]
+    float *part_ml;               // splits > 1: [B, Hkv, splits, RP, 2]: largest raw score, sum
+    float *part_acc;              //             [B, Hkv, splits, RP, D]
+    int heads, kv_heads, tokens, len, causal, rows, tiles_per_split;
+    float c, scale;               // scale * log2(e), scale
+};
+
+template <int VW> struct VecOf;
+template <> struct VecOf<4> { using type = f32x4v; };
+template <> struct VecOf<2> { using type = f32x2v; };
+template <> struct VecOf<1> { using type = float; };
+
+template <bool NT, typename V>
+__device__ __forceinline__ V ld_kv(const float *p) {
+    if (NT) return __builtin_nontemporal_load(reinterpret_cast<const V *>(p));
+    return *reinterpret_cast<const V *>(p);
+}
+
+template <int VW> __device__ __forceinline__ float comp(const typename VecOf<VW>::type &x, int e) { return x[e]; }
+template <> __device__ __forceinline__ float comp<1>(const float &x, int) { return x; }
+
+// D: head size; RB: 16-row blocks of the score tile (rows = (Hq / Hkv) T <= 16 RB); NT: nontemporal K / V loads.
+template <int D, int RB, bool NT>
+__global__ void __launch_bounds__(WAVES * 64)
+mha_decode_kernel(const DecodeArgs a) {
+#pragma clang fp contract(off)
+    constexpr int KU = D / 16;                    // 16-byte K loads per lane and tile
+    constexpr int VW = D >= 64 ? 4 : D / 16;      // floats per V load
+    constexpr int DQ = D / (16 * VW);             // V loads per lane and key
+    constexpr int NS = KU >= 4 ? 4 : KU;          // score accumulation chains
+    using VVec = typename VecOf<VW>::type;
+    __shared__ __attribute__((aligned(16))) float s_acc[WAVES][16][D + 4];
+    __shared__ float s_m[WAVES][16], s_l[WAVES][16];
+
+    const int split = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = lane & 15, g = lane >> 4;
+    const int L = a.len, T = a.tokens, R = a.rows;
+
+    // this lane's query rows (one per row block): head c + (r / T) Hkv, token r % T; padding rows are zeros and never stored
+    f32x4v q[RB][KU];
+    int limit[RB];                                // keys this row may see: j < limit
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) {
+        const int r = rb * 16 + n;
+        const int t = r % T, h = c + (r / T) * a.kv_heads;
+        limit[rb] = r < R ? (a.causal ? L - T + t + 1 : L) : 0;
+        const float *src = a.q + ((long)b * T + t) * a.q_pitch + (long)h * D + 4 * g;
+#pragma unroll
+        for (int u = 0; u < KU; ++u) q[rb][u] = r < R ? *reinterpret_cast<const f32x4v *>(src + 16 * u) : f32x4v{0.f, 0.f, 0.f, 0.f};
+    }
+
+    f32x4v acc[RB][DQ][VW];
+    float m[RB], l[RB];
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) {
+        m[rb] = -INFINITY;
+        l[rb] = 0.f;
+#pragma unroll
+        for (int dq = 0; dq < DQ; ++dq)
+#pragma unroll
+            for (int e = 0; e < VW; ++e) acc[rb][dq][e] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    }
+
+    const int tiles = (L + TILE - 1) / TILE;
+    const int t_begin = split * a.tiles_per_split;
+    const int t_end = min(tiles, t_begin + a.tiles_per_split);
+    const float *kbase = a.k + (long)b * a.k_sb + (long)c * D + 4 * g;
+    const float *vbase = a.v + (long)b * a.v_sb + (long)c * D + VW * n;
+
+    f32x4v kr[KU];
+    VVec vr[4][DQ];
+    auto load_tile = [&](int tile) {
+        const int key0 = tile * TILE;
+        const float *kp = kbase + (long)min(key0 + n, L - 1) * a.k_pitch;
+#pragma unroll
+        for (int u = 0; u < KU; ++u) kr[u] = ld_kv<NT, f32x4v>(kp + 16 * u);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float *vp = vbase + (long)min(key0 + 4 * g + w, L - 1) * a.v_pitch;
+#pragma unroll
+            for (int dq = 0; dq < DQ; ++dq) vr[w][dq] = ld_kv<NT, VVec>(vp + 16 * VW * dq);
+        }
+    };
+
+    int tile = t_begin + wave;
+    if (tile < t_end) load_tile(tile);
+    for (; tile < t_end; tile += WAVES) {
+        const int key0 = tile * TILE;
+        // S^T = K Q^T
+        // NS independent accumulation chains (16-byte load u feeds chain u % NS), summed pairwise: shorter dependent MFMA chains,
+        // and a score that is the sum of like-signed terms (a key aligned with the query) loses half the bits a single chain of
+        // D / 4 steps loses
+        f32x4v sp[RB][NS], s[RB];
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb)
+#pragma unroll
+            for (int i = 0; i < NS; ++i) sp[rb][i] = f32x4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < KU; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int rb = 0; rb < RB; ++rb) sp[rb][u % NS] = MFMA16(kr[u][e], q[rb][u][e], sp[rb][u % NS]);
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) s[rb] = NS == 4 ? (sp[rb][0] + sp[rb][1]) + (sp[rb][2] + sp[rb][3]) : NS == 2 ? sp[rb][0] + sp[rb][1] : sp[rb][0];
+        // V of this tile into the A operands (keys >= L zeroed: the last tile of the cache only), then the next tile's loads
+        VVec va[4][DQ];
+        const bool ragged = key0 + TILE > L;      // wave-uniform
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+#pragma unroll
+            for (int dq = 0; dq < DQ; ++dq) {
+                va[w][dq] = vr[w][dq];
+                if (ragged && key0 + 4 * g + w >= L) va[w][dq] = VVec(0.f);
+            }
+        if (tile + WAVES < t_end) load_tile(tile + WAVES);
+
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) {
+            // -inf by selection for keys the row does not see; then log2 units
+            float x[4], tmax = -INFINITY;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const bool seen = key0 + 4 * g + w < limit[rb];
+                x[w] = seen ? s[rb][w] : -INFINITY;
+                tmax = fmaxf(tmax, x[w]);
+            }
+            tmax = fmaxf(tmax, __shfl_xor(tmax, 16));
+            tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+            const float m_new = fmaxf(m[rb], tmax);                   // raw
+            const float ref = m_new == -INFINITY ? 0.f : m_new * a.c; // a row with nothing visible yet: exponents stay -inf, not NaN
+            const float alpha = __builtin_amdgcn_exp2f(m[rb] * a.c - ref);   // -inf * c = -inf: 0
+            m[rb] = m_new;
+            float psum = 0.f;
+            f32x4v p;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                p[w] = __builtin_amdgcn_exp2f(fmaf(x[w], a.c, -ref));
+                psum += p[w];
+            }
+            l[rb] = l[rb] * alpha + psum;
+#pragma unroll
+            for (int dq = 0; dq < DQ; ++dq)
+#pragma unroll
+                for (int e = 0; e < VW; ++e) {
+                    f32x4v o = acc[rb][dq][e] * alpha;
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) o = MFMA16(comp<VW>(va[w][dq], e), p[w], o);
+                    acc[rb][dq][e] = o;
+                }
+        }
+    }
+
+    // merge the four waves in wave order, one row block at a time, and store
+    const long slot = ((long)b * a.kv_heads + c) * gridDim.x + split;
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb) {
+        float lsum = l[rb];
+        lsum += __shfl_xor(lsum, 16);
+        lsum += __shfl_xor(lsum, 32);
+        if (rb) __syncthreads();
+        if (g == 0) { s_m[wave][n] = m[rb]; s_l[wave][n] = lsum; }
+        __syncthreads();
+        float m_tot = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) m_tot = fmaxf(m_tot, s_m[w][n]);
+        const float ref = m_tot == -INFINITY ? 0.f : m_tot * a.c;
+        const float weight = __builtin_amdgcn_exp2f(m[rb] * a.c - ref);   // 0 for a wave that saw nothing of this row
+#pragma unroll
+        for (int dq = 0; dq < DQ; ++dq)
+#pragma unroll
+            for (int e = 0; e < VW; ++e)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) s_acc[wave][n][16 * VW * dq + VW * (4 * g + w) + e] = acc[rb][dq][e][w] * weight;
+        __syncthreads();
+        for (int i = threadIdx.x; i < 16 * (D / 4); i += WAVES * 64) {
+            const int row = i / (D / 4), d = (i % (D / 4)) * 4;
+            const int r = rb * 16 + row;
+            float mt = -INFINITY;
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) mt = fmaxf(mt, s_m[w][row]);
+            const float rf = mt == -INFINITY ? 0.f : mt * a.c;
+            float lt = 0.f;
+            f32x4v o{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) {
+                lt += s_l[w][row] * __builtin_amdgcn_exp2f(s_m[w][row] * a.c - rf);
+                o += *reinterpret_cast<const f32x4v *>(&s_acc[w][row][d]);
+            }
+            if (a.part_acc) {                      // this split's (m, l, acc) of the row, padding rows included (finite: q = 0)
+                const long prow = slot * (RB * 16) + r;
+                *reinterpret_cast<f32x4v *>(a.part_acc + prow * D + d) = o;
+                if (d == 0) { a.part_ml[2 * prow] = mt; a.part_ml[2 * prow + 1] = lt; }
+            } else if (r < R) {
+                const int t = r % T, h = c + (r / T) * a.kv_heads;
+                *reinterpret_cast<f32x4v *>(a.ctx + ((long)b * T + t) * a.ctx_pitch + (long)h * D + d) = o / lt;
+                if (d == 0 && a.lse)
+                    a.lse[((long)b * a.heads + h) * T + t] = fmaf(a.scale, mt, (__builtin_amdgcn_logf(lt) + fmaf(-mt, a.c, rf)) * LN2);
+            }
+        }
+    }
+}
+
+// One thread per (batch, K / V head, row, four columns): the splits of the row merged in split order.
+template <int D>
+__global__ void __launch_bounds__(256)
+mha_decode_combine_kernel(const float *__restrict__ part_ml, const float *__restrict__ part_acc, float *__restrict__ ctx,
+                          long ctx_pitch, float *__restrict__ lse, int batch, int heads, int kv_heads, int tokens, int rows,
+                          int rows_pad, int splits, float c2, float scale) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long total = (long)batch * kv_heads * rows * (D / 4);
+    if (i >= total) return;
+    const int d = (int)(i % (D / 4)) * 4;
+    const int r = (int)((i / (D / 4)) % rows);
+    const long plane = i / ((long)(D / 4) * rows);                    // b * kv_heads + c
+    const int c = (int)(plane % kv_heads);
+    const long b = plane / kv_heads;
+    const long first = plane * splits * rows_pad + r;
+    float mt = -INFINITY;
+    for (int s = 0; s < splits; ++s) mt = fmaxf(mt, part_ml[2 * (first + (long)s * rows_pad)]);
+    float lt = 0.f;
+    f32x4v o{0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < splits; ++s) {
+        const long prow = first + (long)s * rows_pad;
+        const float ms = part_ml[2 * prow];
+        if (ms == -INFINITY) continue;                                // a split without a visible key: weight 0, its acc is not read
+        const float w = __builtin_amdgcn_exp2f(ms * c2 - mt * c2);
+        lt += part_ml[2 * prow + 1] * w;
+        o += *reinterpret_cast<const f32x4v *>(part_acc + prow * D + d) * w;
+    }
+    const int t = r % tokens, h = c + (r / tokens) * kv_heads;
+    *reinterpret_cast<f32x4v *>(ctx + (b * tokens + t) * ctx_pitch + (long)h * D + d) = o / lt;
+    if (d == 0 && lse) lse[(b * heads + h) * tokens + t] = fmaf(scale, mt, (__builtin_amdgcn_logf(lt) + fmaf(-mt, c2, mt * c2)) * LN2);
+}
+
+// cache[b, at + t, :row_len] = src[b * T + t, :row_len], 16 bytes per thread and step
+__global__ void __launch_bounds__(256)
+kv_append_kernel(const float *__restrict__ src, long src_pitch, float *__restrict__ cache, long cache_pitch, long cache_sb,
+                 int tokens, int row4, int at, long total) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int col = (int)(i % row4) * 4;
+        const long row = i / row4;
+        const long b = row / tokens;
+        const int t = (int)(row - b * tokens);
+        *reinterpret_cast<f32x4v *>(cache + b * cache_sb + (long)(at + t) * cache_pitch + col) =
+            *reinterpret_cast<const f32x4v *>(src + row * src_pitch + col);
+    }
+}
+
+template <int D, int RB>
+void launch_decode(const DecodeArgs &a, dim3 grid, bool nt, hipStream_t s) {
+    if (nt) hipLaunchKernelGGL((mha_decode_kernel<D, RB, true>), grid, dim3(WAVES * 64), 0, s, a);
+    else hipLaunchKernelGGL((mha_decode_kernel<D, RB, false>), grid, dim3(WAVES * 64), 0, s, a);
+}
+
+template <int D>
+void launch_decode_rb(const DecodeArgs &a, dim3 grid, int rb, bool nt, hipStream_t s) {
+    if (rb == 1) launch_decode<D, 1>(a, grid, nt, s);
+    else launch_decode<D, 2>(a, grid, nt, s);
+}
+
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+extern "C" int npm_decode_set_splits(int value) {
+    if (value < 0 || value > NPM_DECODE_MAX_SPLITS)
+        return npm::fail(NPM_E_BAD_ARGUMENT, "npm_set_tuning: NPM_TUNE_DECODE_SPLITS takes 0 .. %d", NPM_DECODE_MAX_SPLITS);
+    g_splits = value;
+    return NPM_OK;
+}
+
+extern "C" int npm_decode_set_nt(int value) {
+    if (value < 0 || value > 2) return npm::fail(NPM_E_BAD_ARGUMENT, "npm_set_tuning: NPM_TUNE_DECODE_NT takes 0, 1 or 2");
+    g_nt = value;
+    return NPM_OK;
+}
+
+extern "C" int npm_mha_decode_supported(int head_dim, int group_rows) {
+    const bool dim_ok = head_dim == 16 || head_dim == 32 || head_dim == 64 || head_dim == 128;
+    return dim_ok && group_rows >= 1 && group_rows <= NPM_DECODE_MAX_ROWS;
+}
+
+extern "C" int npm_mha_decode_splits(int batch, int kv_heads, int kv_len) {
+    if (batch < 1 || kv_heads < 1 || kv_len < 1) return 1;
+    if (g_splits > 0) return g_splits;
+    // Fill the chip: about two blocks per compute unit of the 256, but never fewer than 256 keys (16 tiles, four per wave) per
+    // split -- below that the partials and the second launch cost more than the idle units.  Shape arguments only.
+    const long planes = (long)batch * kv_heads;
+    const long want = (512 + planes - 1) / planes;
+    const long by_len = std::max<long>(1, kv_len / 256);
+    return (int)std::max<long>(1, std::min<long>(std::min(want, by_len), NPM_DECODE_MAX_SPLITS));
+}
+
+extern "C" const char *npm_last_decode_kernel(void) { return g_last; }
+
+extern "C" int npm_mha_decode_fwd(const npm_mha_decode *d) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(d != nullptr);
+    NPM_ARG(d->batch >= 1 && d->heads >= 1 && d->kv_heads >= 1 && d->new_tokens >= 1 && d->head_dim >= 1);
+    NPM_ARG(d->heads % d->kv_heads == 0);
+    NPM_ARG(d->kv_len >= d->new_tokens);
+    NPM_ARG(d->scale > 0.f);
+    NPM_ARG(d->q != nullptr && d->k != nullptr && d->v != nullptr && d->ctx != nullptr);
+    const int D = d->head_dim, rows = d->heads / d->kv_heads * d->new_tokens;
+    if (!npm_mha_decode_supported(D, rows))
+        return npm::fail(NPM_E_UNSUPPORTED, "npm_mha_decode_fwd: head_dim %d with %d rows per K / V head is not supported "
+                         "(head_dim in {16, 32, 64, 128}, rows <= %d)", D, rows, NPM_DECODE_MAX_ROWS);
+    NPM_ARG(aligned16(d->q) && aligned16(d->k) && aligned16(d->v) && aligned16(d->ctx));
+    NPM_ARG(d->q_pitch % 4 == 0 && d->k_pitch % 4 == 0 && d->v_pitch % 4 == 0 && d->ctx_pitch % 4 == 0);
+    NPM_ARG(d->k_stride_b % 4 == 0 && d->v_stride_b % 4 == 0);
+    NPM_ARG(d->q_pitch >= (int64_t)d->heads * D && d->ctx_pitch >= (int64_t)d->heads * D);
+    NPM_ARG(d->k_pitch >= (int64_t)d->kv_heads * D && d->v_pitch >= (int64_t)d->kv_heads * D);
+    NPM_ARG(d->batch <= 65535 && d->kv_heads <= 65535);
+
+    const int tiles = (d->kv_len + TILE - 1) / TILE;
+    const int splits = npm_mha_decode_splits(d->batch, d->kv_heads, d->kv_len);
+    const int rb = rows > 16 ? 2 : 1;
+    DecodeArgs a{};
+    a.q = d->q; a.k = d->k; a.v = d->v;
+    a.q_pitch = d->q_pitch; a.k_pitch = d->k_pitch; a.k_sb = d->k_stride_b; a.v_pitch = d->v_pitch; a.v_sb = d->v_stride_b;
+    a.ctx = d->ctx; a.ctx_pitch = d->ctx_pitch; a.lse = d->lse;
+    a.heads = d->heads; a.kv_heads = d->kv_heads; a.tokens = d->new_tokens; a.len = d->kv_len; a.causal = d->causal != 0;
+    a.rows = rows;
+    a.tiles_per_split = (tiles + splits - 1) / splits;
+    a.c = d->scale * LOG2E;
+    a.scale = d->scale;
+
+    hipStream_t s = npm::ctx().stream;
+    npm::Scratch ml, acc;
+    const long prow = (long)d->batch * d->kv_heads * splits * rb * 16;
+    if (splits > 1) {
+        if (int rc = ml.alloc(sizeof(float) * 2 * prow)) return rc;
+        if (int rc = acc.alloc(sizeof(float) * prow * D)) return rc;
+        a.part_ml = static_cast<float *>(ml.ptr);
+        a.part_acc = static_cast<float *>(acc.ptr);
+    }
+    const dim3 grid(splits, d->kv_heads, d->batch);
+    // Each K / V byte is read once by one block.  Measured (tools/decode_bench.py, profiles/r08_decode_bench.log): from 64 MB of
+    // K + V up the nontemporal hint is 3 - 13 % faster (the stream does not displace itself in the L2s and the Infinity Cache);
+    // below that plain loads are 0 - 3 % faster.  The project's rule for streaming tensors (32 MB each) draws the same line.
+    const bool nt = g_nt == 1 || (g_nt == 0 && npm::stream_nt_enabled(sizeof(float) * (size_t)d->batch * d->kv_len * d->kv_heads * D));
+    switch (D) {
+        case 16: launch_decode_rb<16>(a, grid, rb, nt, s); break;
+        case 32: launch_decode_rb<32>(a, grid, rb, nt, s); break;
+        case 64: launch_decode_rb<64>(a, grid, rb, nt, s); break;
+        default: launch_decode_rb<128>(a, grid, rb, nt, s); break;
+    }
+    NPM_CHECK_LAUNCH();
+    if (splits > 1) {
+        const long total = (long)d->batch * d->kv_heads * rows * (D / 4);
+        const dim3 cgrid((unsigned)((total + 255) / 256));
+#define NPM_COMBINE(DD) hipLaunchKernelGGL(mha_decode_combine_kernel<DD>, cgrid, dim3(256), 0, s, a.part_ml, a.part_acc, a.ctx, \
+                                           a.ctx_pitch, a.lse, d->batch, d->heads, d->kv_heads, d->new_tokens, rows, rb * 16, splits, a.c, a.scale)
+        switch (D) {
+            case 16: NPM_COMBINE(16); break;
+            case 32: NPM_COMBINE(32); break;
+            case 64: NPM_COMBINE(64); break;
+            default: NPM_COMBINE(128); break;
+        }
+#undef NPM_COMBINE
+        NPM_CHECK_LAUNCH();
+    }
+    snprintf(g_last, sizeof g_last, "mha_decode_kernel D=%d rows=%d splits=%d causal=%d", D, rows, splits, a.causal);
+    return NPM_OK;
+}
+
+extern "C" int npm_kv_append(const float *src, int64_t src_pitch, float *cache, int64_t cache_pitch, int64_t cache_stride_b,
+                             int32_t batch, int32_t new_tokens, int32_t row_len, int32_t at) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(batch >= 0 && new_tokens >= 0 && row_len >= 0 && at >= 0);
+    if (batch == 0 || new_tokens == 0 || row_len == 0) return NPM_OK;
+    NPM_ARG(src != nullptr && cache != nullptr);
+    NPM_ARG(aligned16(src) && aligned16(cache));
+    NPM_ARG(row_len % 4 == 0 && src_pitch % 4 == 0 && cache_pitch % 4 == 0 && cache_stride_b % 4 == 0);
+    NPM_ARG(src_pitch >= row_len && cache_pitch >= row_len);
+    const long total = (long)batch * new_tokens * (row_len / 4);
+    const int grid = (int)std::min<long>((total + 255) / 256, 2048);
+    hipLaunchKernelGGL(kv_append_kernel, dim3(grid), dim3(256), 0, npm::ctx().stream, src, (long)src_pitch, cache, (long)cache_pitch,
+                       (long)cache_stride_b, new_tokens, row_len / 4, at, total);
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
+}

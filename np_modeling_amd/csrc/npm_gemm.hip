@@ -444,6 +444,8 @@ extern "C" int npm_conv_set_wgrad_fused(int mode);
 extern "C" int npm_attn_set_bwd16(int on);
 extern "C" int npm_attn_set_fwd8(int mode);
 extern "C" int npm_attn_set_stagger(int units);
+extern "C" int npm_decode_set_splits(int value);
+extern "C" int npm_decode_set_nt(int value);
 
 extern "C" int npm_set_math(int mode) { return npm_set_tuning(NPM_TUNE_GEMM_MATH, mode); }
 extern "C" int npm_get_math(void) { return g_math; }
@@ -474,6 +476,8 @@ extern "C" int npm_set_tuning(int knob, int value) {
         case NPM_TUNE_CONV_KORDER: return npm_conv_set_korder(value);
         case NPM_TUNE_STREAM_NT: npm::set_stream_nt(value); return NPM_OK;
         case NPM_TUNE_GEMM_SPLIT_GENS: g_split_gens = value != 0; return NPM_OK;
+        case NPM_TUNE_DECODE_SPLITS: return npm_decode_set_splits(value);
+        case NPM_TUNE_DECODE_NT: return npm_decode_set_nt(value);
         default: return npm::fail(NPM_E_BAD_ARGUMENT, "npm_set_tuning: unknown knob %d", knob);
     }
 }

@@ -994,3 +994,95 @@ def mha_core_bwd(q: Mat, k: Mat, v: Mat, ctx: DeviceArray, lse: DeviceArray, dct
             _C.check(_C.lib().npm_mha_core_bwd(C.byref(c)), 'npm_mha_core_bwd')
         else:
             _C.check(_C.lib().npm_mha_core_bwd_grouped(C.byref(c), hkv), 'npm_mha_core_bwd_grouped')
+
+
+# ---- incremental decoding: key / value cache ----------------------------------------------------------------------------
+def mha_decode_supported(head_dim: int, group_rows: int, value_dim: Optional[int] = None) -> bool:
+    """Whether ``npm_mha_decode_fwd`` takes this head size with ``group_rows`` = (Hq / Hkv) * T score rows per K / V head.  The
+    kernel runs the exact-fp32 MFMA only, so under a split math mode the layers fall back to compositions that honour it."""
+    if not ATTN_CORE or (value_dim is not None and value_dim != head_dim) or _C.current_math() != 'f32':
+        return False
+    return bool(_C.lib().npm_mha_decode_supported(int(head_dim), int(group_rows)))
+
+
+def kv_append(src: Mat, cache: DeviceArray, batch: int, tokens: int, at: int) -> None:
+    """cache[b, at + t] = src[b * tokens + t] for a cache [B, capacity, Hkv, D]; ``src``: (array, row pitch) of [B, T, Hkv * D]
+    rows, e.g. the K part of a packed projection (include/npm_hip.h npm_kv_append).  Raises ValueError before anything is
+    launched when the rows do not fit."""
+    b, capacity, hkv, d = cache.shape
+    if batch != b or at < 0 or at + tokens > capacity:
+        raise ValueError(f'appending {tokens} rows at {at} to a cache of batch {b}, capacity {capacity} (batch {batch})')
+    with _timed('kv_append', nbytes=8.0 * batch * tokens * hkv * d):
+        _C.check(_C.lib().npm_kv_append(src.ptr, src.ld, cache.ptr, hkv * d, capacity * hkv * d, batch, tokens, hkv * d, at),
+                 'npm_kv_append')
+
+
+def mha_decode(q: Mat, k: DeviceArray, v: DeviceArray, heads: int, tokens: int, kv_len: int, scale: float, causal: bool,
+               want_lse: bool = False):
+    """ctx [B, T, Hq, D] (and lse [B, Hq, T] or None) of ``tokens`` query rows per sequence over the first ``kv_len`` rows of
+    the caches ``k`` / ``v`` [B, capacity, Hkv, D] (include/npm_hip.h npm_mha_decode_fwd).  ``q``: (array, row pitch)."""
+    b, capacity, hkv, d = k.shape
+    assert v.shape == k.shape and tokens <= kv_len <= capacity
+    ctx = empty([b, tokens, heads, d])
+    lse = empty([b, heads, tokens]) if want_lse else None
+    c = _C.npm_mha_decode()
+    c.batch, c.heads, c.kv_heads, c.new_tokens, c.kv_len, c.head_dim = b, int(heads), hkv, int(tokens), int(kv_len), d
+    c.causal, c.scale = int(bool(causal)), float(scale)
+    c.q, c.q_pitch = q.ptr, q.ld
+    c.k, c.k_pitch, c.k_stride_b = k.ptr, hkv * d, capacity * hkv * d
+    c.v, c.v_pitch, c.v_stride_b = v.ptr, hkv * d, capacity * hkv * d
+    c.ctx, c.ctx_pitch = ctx.ptr, heads * d
+    c.lse = None if lse is None else lse.ptr
+    with _timed('mha_decode', flops=4.0 * b * heads * tokens * kv_len * d, nbytes=4.0 * b * d * (2 * heads * tokens + 2 * hkv * kv_len)):
+        _C.check(_C.lib().npm_mha_decode_fwd(C.byref(c)), 'npm_mha_decode_fwd')
+    return ctx, lse
+
+
+def kv_gather(cache: DeviceArray, out: DeviceArray, length: int) -> None:
+    """out[b, :length] = cache[b, :length] for a cache [B, capacity, Hkv, D] and ``out`` [B, length, Hkv, D]: the valid rows made
+    contiguous for a kernel that addresses K / V without a batch stride (one device copy per sequence; a fallback path)."""
+    b, capacity, hkv, d = cache.shape
+    assert out.shape == (b, length, hkv, d) and length <= capacity
+    for i in range(b):
+        _C.check(_C.lib().npm_d2d(out.ptr + 4 * i * length * hkv * d, cache.ptr + 4 * i * capacity * hkv * d, 4 * length * hkv * d),
+                 'npm_d2d')
+
+
+class KVCache:
+    """Keys and values of the tokens seen so far: ``k`` [B, capacity, Hkv, Dk] and ``v`` [B, capacity, Hkv, Dv] on the device,
+    of which the first ``length`` rows are valid.  Rows at and past ``length`` hold whatever was there; nothing reads them.
+    ``frozen`` marks a cross-attention cache (filled once, attended to as a whole, never appended to by ``forward``)."""
+
+    def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None):
+        value_dim = key_dim if value_dim is None else value_dim
+        if min(batch, capacity, kv_heads, key_dim, value_dim) < 1:
+            raise ValueError('KVCache: batch, capacity, kv_heads and the head sizes must be positive')
+        self.batch, self.capacity, self.kv_heads = int(batch), int(capacity), int(kv_heads)
+        self.key_dim, self.value_dim = int(key_dim), int(value_dim)
+        self.k = empty([batch, capacity, kv_heads, key_dim])
+        self.v = empty([batch, capacity, kv_heads, value_dim])
+        self.length = 0
+        self.frozen = False
+
+    def reset(self) -> None:
+        self.length = 0
+        self.frozen = False
+
+    def room(self, tokens: int) -> None:
+        """ValueError when ``tokens`` more rows do not fit -- checked before anything is launched."""
+        if tokens < 0 or self.length + tokens > self.capacity:
+            raise ValueError(f'KVCache: {tokens} new rows after {self.length} do not fit the capacity {self.capacity}')
+
+    def append(self, k: Mat, v: Mat, tokens: int) -> None:
+        """``tokens`` freshly projected rows per sequence ([B, T, Hkv * D] with a row pitch each) behind the valid ones."""
+        self.room(tokens)
+        if self.frozen:
+            raise ValueError('KVCache: this cache was filled for cross-attention and is frozen; reset() it first')
+        kv_append(k, self.k, self.batch, tokens, self.length)
+        kv_append(v, self.v, self.batch, tokens, self.length)
+        self.length += tokens
+
+    def attend(self, q: Mat, heads: int, tokens: int, scale: float, causal: bool, want_lse: bool = False):
+        """``mha_decode`` of ``tokens`` query rows per sequence over the valid rows."""
+        assert self.key_dim == self.value_dim
+        return mha_decode(q, self.k, self.v, heads, tokens, self.length, scale, causal, want_lse)

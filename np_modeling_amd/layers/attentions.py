@@ -38,6 +38,15 @@ kernels take the grouping as an argument (``npm_mha_core_*_grouped``); the GEMM 
 (B, Hkv) per group g -- query head g * Hkv + c is a column offset g * Hkv * D of the [B, S, Hq, D] tensors -- and sums
 the dK / dV of the groups in the residual epilogue, in the order g = 0, 1, ...  ``num_kv_heads=None`` (or ``num_heads``)
 is multi-head attention, run exactly as without the keyword.
+
+Incremental decoding (inference; the reference has none: ``# TODO: support cache``, layers/transformer.py:120).
+``make_cache(batch, capacity)`` returns a ``device.KVCache`` with Hkv heads; ``forward(x, cache=cache)`` projects the T new
+tokens (one packed GEMM where the parameters allow), appends their K / V rows behind the ``cache.length`` valid ones and attends
+causally over all of them -- T is the whole prompt or 1.  Cross-attention projects K / V once with ``fill_cache(cache, key,
+value)`` and then ``forward(x, cache=cache)`` attends to the whole frozen cache.  The attention itself is ``npm_mha_decode_fwd``
+(csrc/npm_decode.hip: one block per K / V head serves its whole group of query heads, keys split over blocks) where it takes the
+shape; otherwise the fused forward with a causal ``AttnMask`` over the valid rows (a long prefill), or the GEMM composition on the
+valid rows (other head sizes, split math modes): ``_cached_path`` names which ran.  Nothing is saved for a backward.
 """
 
 from __future__ import annotations
@@ -66,6 +75,8 @@ class MultiHeadAttention(layer.StatefulLayer):
         self._num_heads = num_heads
         self._num_kv_heads = num_heads if num_kv_heads is None else num_kv_heads
         self._softmax = activations.Softmax()
+        self._cached_forward = False    # the last forward ran with a cache: it saved nothing a backward could use
+        self._cached_path = None        # 'decode' | 'fused_masked' | 'gemm': how the last cached forward attended
 
     def initialize(self, query, key=None, value=None, *args, **kwargs) -> None:
         # query [B, Sq, H*Dk]; key [B, Skv, H*Dk]; value [B, Skv, H*Dv]
@@ -132,8 +143,13 @@ class MultiHeadAttention(layer.StatefulLayer):
                 [(self, '_bq'), (self, '_bk'), (self, '_bv')]]
 
     # -- forward -------------------------------------------------------------------------
-    def forward(self, query, key=None, value=None, mask=None):
+    def forward(self, query, key=None, value=None, mask=None, cache=None):
         query = D.as_device(query)
+        if cache is not None:
+            if key is not None or value is not None or mask is not None:
+                raise ValueError('with a cache, forward takes the new query tokens only: cross-attention keys and values go '
+                                 'through fill_cache(cache, key, value), and the causal rule is implied')
+            return self._forward_cached(query, cache)
         key = query if key is None else D.as_device(key)
         value = key if value is None else D.as_device(value)
         return self._forward_impl(query, key, value, mask=mask)
@@ -149,6 +165,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         wq, wk, wv, wo = (self._param(p) for p in ('_wq', '_wk', '_wv', '_wo'))
         bq, bk, bv, bo = (self._param(p) for p in ('_bq', '_bk', '_bv', '_bo'))
         self._query, self._key, self._value = query, key, value
+        self._cached_forward = False
         if mask is not None and not isinstance(mask, D.AttnMask) and np.ndim(mask) == 0 and not mask:   # `if mask:` false (attentions.py:84,106)
             mask = None
         if isinstance(mask, D.AttnMask):                               # made once by the caller (its bytes and tile summary stay
@@ -216,8 +233,126 @@ class MultiHeadAttention(layer.StatefulLayer):
                residual=None if residual is None else Mat(residual, f))
         return out
 
+    # -- incremental decoding ------------------------------------------------------------------
+    def make_cache(self, batch: int, capacity: int) -> D.KVCache:
+        """An empty key / value cache for ``batch`` sequences of up to ``capacity`` tokens (Hkv heads: grouped-query attention
+        keeps its smaller cache).  The layer must have its parameters (one forward, or a weight binder)."""
+        if not self._initialized:
+            raise RuntimeError('make_cache: the layer has no parameters yet (run one forward, or bind weights, first)')
+        return D.KVCache(batch, capacity, self._num_kv_heads, self._key_dim, self._value_dim)
+
+    def fill_cache(self, cache: D.KVCache, key, value=None) -> D.KVCache:
+        """Cross-attention: project ``key`` / ``value`` [B, Skv, F] once into ``cache`` and freeze it; ``forward(x, cache=cache)``
+        then attends to all of it, not causally, and appends nothing."""
+        key = D.as_device(key)
+        value = key if value is None else D.as_device(value)
+        h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
+        b, skv, f = key.shape
+        fv = value.shape[2]
+        assert f == h * dk and value.shape[:2] == (b, skv) and fv == h * dv
+        cache.reset()
+        cache.room(skv)                                                  # ValueError before anything is launched
+        k, v = D.empty([b, skv, hkv, dk]), D.empty([b, skv, hkv, dv])
+        D.gemm(b * skv, hkv * dk, f, Mat(key, f), Mat(self._param('_wk'), f), Mat(k, hkv * dk), trans_b=True, bias=self._param('_bk'))
+        D.gemm(b * skv, hkv * dv, fv, Mat(value, fv), Mat(self._param('_wv'), fv), Mat(v, hkv * dv), trans_b=True, bias=self._param('_bv'))
+        cache.append(Mat(k, hkv * dk), Mat(v, hkv * dv), skv)
+        cache.frozen = True
+        return cache
+
+    def _forward_cached(self, query: D.DeviceArray, cache: D.KVCache, residual: Optional[D.DeviceArray] = None):
+        """``forward(query, cache=cache)``: self-attention over a growing cache (causal), or cross-attention over a frozen one."""
+        h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
+        b, t, f = query.shape
+        assert f == h * dk and (cache.batch, cache.kv_heads, cache.key_dim, cache.value_dim) == (b, hkv, dk, dv), \
+            f'cache made for {(cache.batch, cache.kv_heads, cache.key_dim, cache.value_dim)}, used with {(b, hkv, dk, dv)}'
+        cross = cache.frozen
+        if not cross:
+            cache.room(t)                                                # ValueError before anything is launched
+        elif cache.length == 0:
+            raise ValueError('the frozen cache is empty: fill_cache(cache, key, value) first')
+        self._cached_forward = True
+        wq, wk, wv, wo = (self._param(p) for p in ('_wq', '_wk', '_wv', '_wo'))
+        bq, bk, bv, bo = (self._param(p) for p in ('_bq', '_bk', '_bv', '_bo'))
+        fkv, fvkv = hkv * dk, hkv * dv
+        fresh = None                                                     # the new tokens' own (k, v) Mats, self-attention only
+        if cross:
+            q = D.empty([b, t, h, dk])
+            D.gemm(b * t, f, f, Mat(query, f), Mat(wq, f), Mat(q, f), trans_b=True, bias=bq)
+            q = Mat(q, f)
+        else:
+            # ONE GEMM over M = B T rows makes q, k and v where the parameters are adjacent; K and V rows then go into the cache
+            # straight out of the packed buffer (npm_kv_append reads with its row pitch)
+            if dk == dv and D.PACK_QKV and self._params_adjacent():
+                width = f + 2 * fkv
+                qkv = D.empty([b, t, h + 2 * hkv, dk])
+                D.gemm(b * t, width, f, Mat(query, f), Mat(wq, f), Mat(qkv, width), trans_b=True, bias=bq)
+                q = Mat(qkv, width)
+                fresh = (Mat(qkv.flat_view(f, [qkv.size - f]), width), Mat(qkv.flat_view(f + fkv, [qkv.size - f - fkv]), width))
+            else:
+                qa, ka, va = D.empty([b, t, h, dk]), D.empty([b, t, hkv, dk]), D.empty([b, t, hkv, dv])
+                D.gemm(b * t, f, f, Mat(query, f), Mat(wq, f), Mat(qa, f), trans_b=True, bias=bq)
+                D.gemm(b * t, fkv, f, Mat(query, f), Mat(wk, f), Mat(ka, fkv), trans_b=True, bias=bk)
+                D.gemm(b * t, fvkv, f, Mat(query, f), Mat(wv, f), Mat(va, fvkv), trans_b=True, bias=bv)
+                q, fresh = Mat(qa, f), (Mat(ka, fkv), Mat(va, fvkv))
+            cache.append(fresh[0], fresh[1], t)
+        ctx = self._attend_cached(q, cache, t, causal=not cross, fresh=fresh)
+        out = D.empty([b, t, f])
+        D.gemm(b * t, f, h * dv, Mat(ctx, h * dv), Mat(wo, h * dv), Mat(out, f), trans_b=True, bias=bo,
+               residual=None if residual is None else Mat(residual, f))
+        return out
+
+    def _attend_cached(self, q: Mat, cache: D.KVCache, t: int, causal: bool, fresh) -> D.DeviceArray:
+        """ctx [B, T, Hq, Dv] of the T query rows ``q`` over the valid rows of ``cache``; sets ``_cached_path``."""
+        h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
+        b, length, scale = cache.batch, cache.length, 1.0 / math.sqrt(self._key_dim)
+        if t <= length and D.mha_decode_supported(dk, h // hkv * t, dv):     # (the kernel's contract: L >= T, causal or not)
+            self._cached_path = 'decode'
+            return cache.attend(q, h, t, scale, causal)[0]
+        if D.mha_core_supported(dk, dv, any_math=True):
+            # more rows than the decode kernel takes (a long prefill), or a split math mode: the fused training forward, with the
+            # causal rule as a mask over the valid rows.  It addresses K / V as [B, L, Hkv, D]: the new tokens' own projection
+            # when they are the whole cache (prefill from empty), the cache itself when it is full, else a copy of the valid rows.
+            self._cached_path = 'fused_masked'
+            if fresh is not None and length == t:
+                k, v = fresh
+            elif length == cache.capacity or b == 1:
+                k, v = Mat(cache.k, hkv * dk), Mat(cache.v, hkv * dv)
+            else:
+                k, v = (Mat(self._valid_rows(x, length), hkv * dk) for x in (cache.k, cache.v))
+            mask = D.AttnMask(np.arange(length)[None, :] <= (length - t + np.arange(t))[:, None], b, h, t, length) if causal and t > 1 else None
+            return D.mha_core_fwd(q, k, v, (b, h, t, length, dk), scale, mask, kv_heads=hkv if hkv != h else None)[0]
+        # other head sizes: the GEMM composition on the valid rows, batched over (B, Hkv) per group as in _forward_impl.  It has
+        # no masked softmax, so a causal chunk runs one query row at a time, each over the keys it sees.
+        self._cached_path = 'gemm'
+        ctx = D.empty([b, t, h, dv])
+        pk, pv, cap = hkv * dk, hkv * dv, cache.capacity
+        for first, rows, keys in ([(i, 1, length - t + i + 1) for i in range(t)] if causal and t > 1 else [(0, t, length)]):
+            scores = D.empty([b, h, rows, keys])
+            for g in range(h // hkv):
+                D.gemm(rows, keys, dk, Mat(q.ptr + 4 * (first * q.ld + g * pk), q.ld, t * q.ld, dk), Mat(cache.k, pk, cap * pk, dk),
+                       Mat(_from(scores, g * hkv * rows * keys), keys, h * rows * keys, rows * keys), trans_b=True, batch=(b, hkv))
+            D.softmax_fwd(scores, scale, out=scores)
+            for g in range(h // hkv):
+                D.gemm(rows, dv, keys, Mat(_from(scores, g * hkv * rows * keys), keys, h * rows * keys, rows * keys),
+                       Mat(cache.v, pv, cap * pv, dv),
+                       Mat(ctx.ptr + 4 * (first * h * dv + g * pv), h * dv, t * h * dv, dv), batch=(b, hkv))
+        return ctx
+
+    @staticmethod
+    def _valid_rows(x: D.DeviceArray, length: int) -> D.DeviceArray:
+        """The first ``length`` rows of every batch entry of a cache tensor [B, capacity, Hkv, D], contiguous."""
+        b, cap, hkv, d = x.shape
+        out = D.empty([b, length, hkv, d])
+        D.kv_gather(x, out, length)
+        return out
+
     # -- backward --------------------------------------------------------------------------
+    _NO_BACKWARD = ('backward after a forward with a cache: incremental decoding is inference only and saves none of the '
+                    'activations a backward needs -- run forward without a cache first')
+
     def backward(self, dy, optimizer_):
+        if self._cached_forward:
+            raise RuntimeError(self._NO_BACKWARD)
         with parallel.grad_scope(self._numel(), self._arena) as scope:
             return self._backward_impl(D.as_device(dy), optimizer_, scope)
 
@@ -228,6 +363,8 @@ class MultiHeadAttention(layer.StatefulLayer):
         epilogues when ``sum_inputs`` is set (reference layers/transformer.py:84-85).  ``sum_kv``
         (cross-attention over one kv tensor): returns (dquery (+ residual), dkey + dvalue), the second
         accumulated in its GEMMs' epilogues (transformer.py:186)."""
+        if self._cached_forward:
+            raise RuntimeError(self._NO_BACKWARD)
         h, dk, dv = self._num_heads, self._key_dim, self._value_dim
         hkv = self._num_kv_heads
         grouped, fkv, fvkv = hkv != h, hkv * dk, hkv * dv

@@ -12,11 +12,18 @@ overlap the rest of the backward pass.
 
 ``num_kv_heads`` (default None: multi-head attention) makes every attention layer grouped-query attention with that many
 key / value heads (attentions.py); nothing else changes.
+
+``TransformerDecoder(causal=True)`` gives the self-attention a lower-triangular mask (the decoder everybody means by the word;
+the reference's passes none, transformer.py:127), and ``start_decoding`` / ``decode`` run it incrementally over key / value
+caches (inference; the reference marks the gap: ``# TODO: support cache``, transformer.py:120).  With ``causal=True`` and no
+dropout, feeding a sequence to ``decode`` in chunks of any sizes gives, row for row, what ``forward`` gives for all of it.
 """
 
 from __future__ import annotations
 
 from typing import Optional
+
+import numpy as np
 
 from np_modeling_amd import device as D
 from np_modeling_amd import parallel
@@ -212,8 +219,12 @@ class TransformerDecoder(layer.Layer):
     ``dkv = dkey + dvalue`` of the cross-attention (transformer.py:186)."""
 
     def __init__(self, num_heads: int, hidden_units: int, norm_first: bool, drop_rate: float = 0.0,
-                 *args, num_kv_heads: Optional[int] = None, **kwargs):
+                 *args, num_kv_heads: Optional[int] = None, causal: bool = False, **kwargs):
         super().__init__(*args, **kwargs)
+        self._num_heads = num_heads
+        self._causal = bool(causal)
+        self._causal_masks = {}         # (B, Sq) -> device.AttnMask: bytes and tile summary stay on the device between steps
+        self._decoded = False           # decode() ran since the last forward: the saved activations are not that forward's
         self._self_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)
         self._cross_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)
         self._dense1 = mlp.Dense(units=hidden_units)
@@ -262,11 +273,22 @@ class TransformerDecoder(layer.Layer):
             self._pack_parameters(_block_segments(self._norm3, ffn, pre) + _block_segments(self._norm2, ca, pre)
                                   + _block_segments(self._norm1, sa, pre))
 
+    def _self_mask(self, batch: int, seq: int):
+        """None, or (``causal=True``) the lower-triangular mask of the self-attention, made once per (B, Sq): its tile summary
+        lets the fused kernels skip the upper triangle."""
+        if not self._causal:
+            return None
+        key = (int(batch), int(seq))
+        if key not in self._causal_masks:
+            self._causal_masks[key] = D.AttnMask(np.tril(np.ones([seq, seq], dtype=bool)), batch, self._num_heads, seq, seq)
+        return self._causal_masks[key]
+
     def forward(self, q, kv):
         """Three residual blocks: self-attention, cross-attention over ``kv``, feed-forward (transformer.py:120-157).
         The residual additions ride the producing GEMMs' epilogues and the dropouts the LayerNorm kernels, as in the encoder."""
         q, kv = D.as_device(q), D.as_device(kv)
         batch, seq_len_q, features = q.shape
+        self._decoded = False
         self._fused = self._fusable(features)
         if not self._fused:
             return self._forward_unfused(q, kv)
@@ -277,7 +299,7 @@ class TransformerDecoder(layer.Layer):
         # 149-150,154-155) and is applied inside that norm's kernels
         h = self._norm1._forward_impl(q, self._dropout1) if pre else q
         self._ensure(sa, h)
-        out = sa._forward_impl(h, h, h, residual=q)                       # ... + skip (transformer.py:130)
+        out = sa._forward_impl(h, h, h, residual=q, mask=self._self_mask(batch, seq_len_q))   # ... + skip (transformer.py:130)
         if not pre:
             out = self._norm1._forward_impl(out, self._dropout1)
         skip = out
@@ -297,9 +319,49 @@ class TransformerDecoder(layer.Layer):
         self._pack()
         return out.reshape(batch, seq_len_q, features)
 
+    # -- incremental decoding (inference) ------------------------------------------------------------------------------
+    def start_decoding(self, kv, capacity: int) -> 'DecodeState':
+        """Caches for ``decode``: an empty self-attention cache of ``capacity`` tokens per sequence and the cross-attention's
+        keys / values, projected from ``kv`` [B, Skv, F] once.  The layer must have its parameters (one forward, or bound weights)."""
+        if not (self._initialized and self._self_attention._initialized and self._cross_attention._initialized):
+            raise RuntimeError('start_decoding: the decoder has no parameters yet (run one forward, or bind weights, first)')
+        kv = D.as_device(kv)
+        batch, seq_kv, _ = kv.shape
+        cross = self._cross_attention.fill_cache(self._cross_attention.make_cache(batch, seq_kv), kv)
+        return DecodeState(self._self_attention.make_cache(batch, capacity), cross)
+
+    def decode(self, q_new, state: 'DecodeState'):
+        """One incremental step: the T new tokens ``q_new`` [B, T, F] through cached causal self-attention, cross-attention over
+        the frozen cache, feed-forward and the three norms -> [B, T, F].  Dropout is the identity (inference: the reference's
+        ``DropOut.forward(training=False)``).  T may be a whole prompt or 1; the self-attention cache grows by T."""
+        q = D.as_device(q_new)
+        batch, tokens, features = q.shape
+        state.self_cache.room(tokens)                                     # ValueError before anything is launched
+        self._decoded = True
+        pre = self._norm_first
+        sa, ca = self._self_attention, self._cross_attention
+        h = self._norm1._forward_impl(q) if pre else q
+        out = sa._forward_cached(h, state.self_cache, residual=q)
+        if not pre:
+            out = self._norm1._forward_impl(out)
+        skip = out
+        h = self._norm2._forward_impl(out) if pre else out
+        out = ca._forward_cached(h, state.cross_cache, residual=skip)
+        if not pre:
+            out = self._norm2._forward_impl(out)
+        out = out.reshape(-1, features)
+        skip = out
+        h = self._norm3._forward_impl(out) if pre else out
+        out = self._dense2._forward_impl(self._dense1(h), residual=skip)
+        if not pre:
+            out = self._norm3._forward_impl(out)
+        return out.reshape(batch, tokens, features)
+
     def _forward_unfused(self, q, kv):
         batch, seq_len_q, features = q.shape
-        out = _block_forward(q, self._norm1, self._dropout1, self._norm_first, self._self_attention)
+        mask = self._self_mask(batch, seq_len_q)
+        out = _block_forward(q, self._norm1, self._dropout1, self._norm_first,
+                             self._self_attention if mask is None else lambda x: self._self_attention(x, mask=mask))
         out = _block_forward(out, self._norm2, self._dropout2, self._norm_first,
                              lambda x: self._cross_attention(x, kv))
         out = _block_forward(out.reshape(-1, features), self._norm3, self._dropout3, self._norm_first,
@@ -309,6 +371,9 @@ class TransformerDecoder(layer.Layer):
 
     def backward(self, dy, optimizer_):
         """Returns ``(dq, dkv)``; ``dkv`` is the cross-attention's dkey + dvalue (transformer.py:159-203)."""
+        if self._decoded:
+            raise RuntimeError('backward after decode(): incremental decoding is inference only and overwrote what the last '
+                               'forward saved -- run forward again first')
         dy = D.as_device(dy)
         with parallel.grad_scope(self._numel(), self._arena) as scope:
             if self._fused and self._dense1._fused_relu():           # the composition the forward ran
@@ -376,3 +441,17 @@ class TransformerDecoder(layer.Layer):
         dy = _block_backward(dy, self._norm1, self._dropout1, self._norm_first, self_attention_backward,
                              optimizer_, scope)
         return dy, kv_grad[0]
+
+
+class DecodeState:
+    """What ``TransformerDecoder.decode`` carries from step to step: the self-attention's growing key / value cache and the
+    cross-attention's frozen one (``device.KVCache``).  ``position``: tokens decoded so far."""
+
+    __slots__ = ('self_cache', 'cross_cache')
+
+    def __init__(self, self_cache: D.KVCache, cross_cache: D.KVCache):
+        self.self_cache, self.cross_cache = self_cache, cross_cache
+
+    @property
+    def position(self) -> int:
+        return self.self_cache.length
