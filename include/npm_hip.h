@@ -383,8 +383,33 @@ int npm_mha_decode_splits(int batch, int kv_heads, int kv_len);
 int npm_kv_append(const float *src, int64_t src_pitch, float *cache, int64_t cache_pitch, int64_t cache_stride_b,
                   int32_t batch, int32_t new_tokens, int32_t row_len, int32_t at);
 /* What the most recent npm_mha_decode_fwd launched: "<kernel> D=<head_dim> rows=<group_rows> splits=<n> causal=<0|1>"; "" before
- * the first call. */
+ * the first call.  After npm_mha_decode_fwd_varlen: the same string followed by " varlen=1". */
 const char *npm_last_decode_kernel(void);
+
+/* ---- ragged batches: one length per sequence (device arrays of batch int32 each; they are read by the kernels, never on the host) ----
+ * npm_mha_decode_fwd with L_b = kv_lens[b] valid cache rows for sequence b (this call's new tokens included) and n_b = new_lens[b]
+ * new tokens (NULL: all d->new_tokens); x is padded on the right to T = d->new_tokens rows.  Row t of sequence b sees keys
+ *   j < (t < n_b ? (causal ? L_b - n_b + t + 1 : L_b) : 0).
+ * A row that sees no key (a padded token t >= n_b, or L_b = 0) gets ctx = 0 and lse = -inf by selection, never 0 / 0; nothing at or
+ * past row L_b of the cache enters a result, whatever it holds.  d->kv_len is an upper bound of kv_lens known to the host: it sizes
+ * the grid, the split count (npm_mha_decode_splits(batch, kv_heads, d->kv_len)) and the key range of every split, so with all
+ * kv_lens[b] == d->kv_len and all new_lens[b] == d->new_tokens the result is bitwise that of npm_mha_decode_fwd.  A block whose key
+ * range starts at or past L_b returns before it loads any key: the cost follows the sum of the lengths, not batch * d->kv_len.
+ * The caller guarantees 0 <= new_lens[b] <= d->new_tokens, 0 <= kv_lens[b] <= d->kv_len and, when causal, new_lens[b] <= kv_lens[b]
+ * (the new tokens are among the valid rows; a frozen cross-attention cache may be shorter than the query).  NPM_E_BAD_ARGUMENT for
+ * kv_lens == NULL; otherwise the argument checks of npm_mha_decode_fwd except kv_len >= new_tokens (kv_len >= 0 here). */
+int npm_mha_decode_fwd_varlen(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens);
+/* npm_kv_append per sequence: cache[b, at_lens[b] + t, 0 .. row_len - 1] = src[b * new_tokens + t, 0 .. row_len - 1] for
+ * t < new_lens[b] (NULL: every t < new_tokens); no other cache row is written.  The caller checks at_lens[b] + new_lens[b] against
+ * the capacity on the host.  Alignment rules as npm_kv_append. */
+int npm_kv_append_varlen(const float *src, int64_t src_pitch, float *cache, int64_t cache_pitch, int64_t cache_stride_b,
+                         int32_t batch, int32_t new_tokens, int32_t row_len, const int32_t *at_lens, const int32_t *new_lens);
+/* out[b, j, 0 .. row_len - 1] = j < lens[b] ? cache[b, j, 0 .. row_len - 1] : 0 for every b < batch, j < rows; out is
+ * [batch, rows, row_len], contiguous: the valid rows of a ragged cache for a kernel that addresses K / V without a batch stride,
+ * with ZEROS behind them (the fused forward multiplies P = 0 by whatever V holds there).  Cache rows at and past lens[b] are not
+ * read.  One launch.  Alignment rules as npm_kv_append. */
+int npm_kv_gather_varlen(const float *cache, int64_t cache_pitch, int64_t cache_stride_b, float *out, int32_t batch, int32_t rows,
+                         int32_t row_len, const int32_t *lens);
 
 /* ---- around the path ("next" rows of SURVEY.md section 8f): keeps a Trainer step on the device ---- */
 /* Adam with the reference's numerics (optimizer.py:53-67): fp64 moments m, v (device buffers of n doubles,

@@ -1,5 +1,6 @@
 // Incremental decoding: attention of T new query tokens over a key / value cache, and the append into that cache
-// (include/npm_hip.h: npm_mha_decode_fwd, npm_kv_append).  Inference only: nothing is saved for a backward.
+// (include/npm_hip.h: npm_mha_decode_fwd, npm_kv_append), and their forms with one length per sequence for ragged batches
+// (npm_mha_decode_fwd_varlen, npm_kv_append_varlen, npm_kv_gather_varlen).  Inference only: nothing is saved for a backward.
 //
 //   ctx[b, t, h, :] = sum_j softmax_j(scale q[b, t, h, :] . K[b, j, h % Hkv, :]) V[b, j, h % Hkv, :]
 //   j < L (causal = 0)    j <= L - T + t (causal = 1: the T new tokens are the last T keys of the cache)
@@ -85,9 +86,13 @@ template <int VW> __device__ __forceinline__ float comp(const typename VecOf<VW>
 template <> __device__ __forceinline__ float comp<1>(const float &x, int) { return x; }
 
 // D: head size; RB: 16-row blocks of the score tile (rows = (Hq / Hkv) T <= 16 RB); NT: nontemporal K / V loads.
-template <int D, int RB, bool NT>
+// VL (npm_mha_decode_fwd_varlen): the sequence has L = kv_lens[b] <= a.len valid keys and nb = new_lens[b] <= a.tokens new tokens.
+// The tile partition stays that of a.len, so a sequence with L == a.len and nb == a.tokens computes, operation for operation, what
+// the VL = false instance computes; a block whose key range starts at or past L leaves an empty partial and returns before it
+// loads anything; a row without a visible key (a padded token, L = 0) is stored as ctx = 0, lse = -inf by selection.
+template <int D, int RB, bool NT, bool VL>
 __global__ void __launch_bounds__(WAVES * 64)
-mha_decode_kernel(const DecodeArgs a) {
+mha_decode_kernel(const DecodeArgs a, const int *__restrict__ kv_lens, const int *__restrict__ new_lens) {
 #pragma clang fp contract(off)
     constexpr int KU = D / 16;                    // 16-byte K loads per lane and tile
     constexpr int VW = D >= 64 ? 4 : D / 16;      // floats per V load
@@ -100,19 +105,33 @@ mha_decode_kernel(const DecodeArgs a) {
     const int split = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = lane & 15, g = lane >> 4;
-    const int L = a.len, T = a.tokens, R = a.rows;
+    const int T = a.tokens, R = a.rows;
+    // VL: block-uniform loads of the sequence's own lengths (scalar loads; nothing is stored through the scalar unit)
+    const int L = VL ? kv_lens[b] : a.len;
+    const int nb = VL ? (new_lens ? new_lens[b] : T) : T;
+    if (VL && a.part_acc && split * a.tiles_per_split * TILE >= L) {
+        // nothing of this sequence lies in the split's key range: the empty partial (its acc is never read), before any load
+        if (threadIdx.x < RB * 16) {
+            const long prow = (((long)b * a.kv_heads + c) * gridDim.x + split) * (RB * 16) + threadIdx.x;
+            a.part_ml[2 * prow] = -INFINITY;
+            a.part_ml[2 * prow + 1] = 0.f;
+        }
+        return;
+    }
 
     // this lane's query rows (one per row block): head c + (r / T) Hkv, token r % T; padding rows are zeros and never stored
+    // (VL: so are the rows of tokens at and past nb, which are stored as ctx = 0, lse = -inf)
     f32x4v q[RB][KU];
     int limit[RB];                                // keys this row may see: j < limit
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
         const int r = rb * 16 + n;
         const int t = r % T, h = c + (r / T) * a.kv_heads;
-        limit[rb] = r < R ? (a.causal ? L - T + t + 1 : L) : 0;
+        const bool live = VL ? r < R && t < nb : r < R;
+        limit[rb] = live ? (a.causal ? L - nb + t + 1 : L) : 0;
         const float *src = a.q + ((long)b * T + t) * a.q_pitch + (long)h * D + 4 * g;
 #pragma unroll
-        for (int u = 0; u < KU; ++u) q[rb][u] = r < R ? *reinterpret_cast<const f32x4v *>(src + 16 * u) : f32x4v{0.f, 0.f, 0.f, 0.f};
+        for (int u = 0; u < KU; ++u) q[rb][u] = live ? *reinterpret_cast<const f32x4v *>(src + 16 * u) : f32x4v{0.f, 0.f, 0.f, 0.f};
     }
 
     f32x4v acc[RB][DQ][VW];
@@ -127,8 +146,8 @@ mha_decode_kernel(const DecodeArgs a) {
             for (int e = 0; e < VW; ++e) acc[rb][dq][e] = f32x4v{0.f, 0.f, 0.f, 0.f};
     }
 
-    const int tiles = (L + TILE - 1) / TILE;
-    const int t_begin = split * a.tiles_per_split;
+    const int tiles = (L + TILE - 1) / TILE;      // VL: the sequence's own tiles within the split ranges of a.len; every tile below
+    const int t_begin = split * a.tiles_per_split;  // holds a key < L, so L >= 1 wherever a load is redirected to key L - 1
     const int t_end = min(tiles, t_begin + a.tiles_per_split);
     const float *kbase = a.k + (long)b * a.k_sb + (long)c * D + 4 * g;
     const float *vbase = a.v + (long)b * a.v_sb + (long)c * D + VW * n;
@@ -259,16 +278,21 @@ mha_decode_kernel(const DecodeArgs a) {
                 if (d == 0) { a.part_ml[2 * prow] = mt; a.part_ml[2 * prow + 1] = lt; }
             } else if (r < R) {
                 const int t = r % T, h = c + (r / T) * a.kv_heads;
-                *reinterpret_cast<f32x4v *>(a.ctx + ((long)b * T + t) * a.ctx_pitch + (long)h * D + d) = o / lt;
+                const bool none = VL && mt == -INFINITY;       // no visible key: 0 and -inf by selection, not 0 / 0
+                *reinterpret_cast<f32x4v *>(a.ctx + ((long)b * T + t) * a.ctx_pitch + (long)h * D + d) =
+                    none ? f32x4v{0.f, 0.f, 0.f, 0.f} : o / lt;
                 if (d == 0 && a.lse)
-                    a.lse[((long)b * a.heads + h) * T + t] = fmaf(a.scale, mt, (__builtin_amdgcn_logf(lt) + fmaf(-mt, a.c, rf)) * LN2);
+                    a.lse[((long)b * a.heads + h) * T + t] =
+                        none ? -INFINITY : fmaf(a.scale, mt, (__builtin_amdgcn_logf(lt) + fmaf(-mt, a.c, rf)) * LN2);
             }
         }
     }
 }
 
+
 // One thread per (batch, K / V head, row, four columns): the splits of the row merged in split order.
-template <int D>
+// VL: a row none of whose splits saw a key (a padded token, a sequence without keys) is ctx = 0, lse = -inf by selection.
+template <int D, bool VL = false>
 __global__ void __launch_bounds__(256)
 mha_decode_combine_kernel(const float *__restrict__ part_ml, const float *__restrict__ part_acc, float *__restrict__ ctx,
                           long ctx_pitch, float *__restrict__ lse, int batch, int heads, int kv_heads, int tokens, int rows,
@@ -296,8 +320,10 @@ mha_decode_combine_kernel(const float *__restrict__ part_ml, const float *__rest
         o += *reinterpret_cast<const f32x4v *>(part_acc + prow * D + d) * w;
     }
     const int t = r % tokens, h = c + (r / tokens) * kv_heads;
-    *reinterpret_cast<f32x4v *>(ctx + (b * tokens + t) * ctx_pitch + (long)h * D + d) = o / lt;
-    if (d == 0 && lse) lse[(b * heads + h) * tokens + t] = fmaf(scale, mt, (__builtin_amdgcn_logf(lt) + fmaf(-mt, c2, mt * c2)) * LN2);
+    const bool none = VL && mt == -INFINITY;
+    *reinterpret_cast<f32x4v *>(ctx + (b * tokens + t) * ctx_pitch + (long)h * D + d) = none ? f32x4v{0.f, 0.f, 0.f, 0.f} : o / lt;
+    if (d == 0 && lse)
+        lse[(b * heads + h) * tokens + t] = none ? -INFINITY : fmaf(scale, mt, (__builtin_amdgcn_logf(lt) + fmaf(-mt, c2, mt * c2)) * LN2);
 }
 
 // cache[b, at + t, :row_len] = src[b * T + t, :row_len], 16 bytes per thread and step
@@ -314,16 +340,51 @@ kv_append_kernel(const float *__restrict__ src, long src_pitch, float *__restric
     }
 }
 
-template <int D, int RB>
-void launch_decode(const DecodeArgs &a, dim3 grid, bool nt, hipStream_t s) {
-    if (nt) hipLaunchKernelGGL((mha_decode_kernel<D, RB, true>), grid, dim3(WAVES * 64), 0, s, a);
-    else hipLaunchKernelGGL((mha_decode_kernel<D, RB, false>), grid, dim3(WAVES * 64), 0, s, a);
+// cache[b, at_lens[b] + t, :row_len] = src[b * T + t, :row_len] for t < new_lens[b] (NULL: every t); other rows are not touched
+__global__ void __launch_bounds__(256)
+kv_append_varlen_kernel(const float *__restrict__ src, long src_pitch, float *__restrict__ cache, long cache_pitch, long cache_sb,
+                        int tokens, int row4, const int *__restrict__ at_lens, const int *__restrict__ new_lens, long total) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int col = (int)(i % row4) * 4;
+        const long row = i / row4;
+        const long b = row / tokens;
+        const int t = (int)(row - b * tokens);
+        if (new_lens && t >= new_lens[b]) continue;
+        *reinterpret_cast<f32x4v *>(cache + b * cache_sb + (long)(at_lens[b] + t) * cache_pitch + col) =
+            *reinterpret_cast<const f32x4v *>(src + row * src_pitch + col);
+    }
+}
+
+// out[b, j, :row_len] = j < lens[b] ? cache[b, j, :row_len] : 0 for j < rows; out is [B, rows, row_len], contiguous.  Rows at and
+// past lens[b] are not read.
+__global__ void __launch_bounds__(256)
+kv_gather_varlen_kernel(const float *__restrict__ cache, long cache_pitch, long cache_sb, float *__restrict__ out, int rows,
+                        int row4, const int *__restrict__ lens, long total) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int col = (int)(i % row4) * 4;
+        const long row = i / row4;
+        const long b = row / rows;
+        const int j = (int)(row - b * rows);
+        f32x4v x{0.f, 0.f, 0.f, 0.f};
+        if (j < lens[b]) x = *reinterpret_cast<const f32x4v *>(cache + b * cache_sb + (long)j * cache_pitch + col);
+        *reinterpret_cast<f32x4v *>(out + row * (4L * row4) + col) = x;
+    }
+}
+
+// VL = false (npm_mha_decode_fwd): the instances that never look at the length arrays
+template <int D, int RB, bool VL>
+void launch_decode(const DecodeArgs &a, const int *kv_lens, const int *new_lens, dim3 grid, bool nt, hipStream_t s) {
+    if (nt) hipLaunchKernelGGL((mha_decode_kernel<D, RB, true, VL>), grid, dim3(WAVES * 64), 0, s, a, kv_lens, new_lens);
+    else hipLaunchKernelGGL((mha_decode_kernel<D, RB, false, VL>), grid, dim3(WAVES * 64), 0, s, a, kv_lens, new_lens);
 }
 
 template <int D>
-void launch_decode_rb(const DecodeArgs &a, dim3 grid, int rb, bool nt, hipStream_t s) {
-    if (rb == 1) launch_decode<D, 1>(a, grid, nt, s);
-    else launch_decode<D, 2>(a, grid, nt, s);
+void launch_decode_rb(const DecodeArgs &a, const int *kv_lens, const int *new_lens, dim3 grid, int rb, bool nt, hipStream_t s) {
+    if (kv_lens) {
+        if (rb == 1) launch_decode<D, 1, true>(a, kv_lens, new_lens, grid, nt, s);
+        else launch_decode<D, 2, true>(a, kv_lens, new_lens, grid, nt, s);
+    } else if (rb == 1) launch_decode<D, 1, false>(a, nullptr, nullptr, grid, nt, s);
+    else launch_decode<D, 2, false>(a, nullptr, nullptr, grid, nt, s);
 }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -361,18 +422,21 @@ extern "C" int npm_mha_decode_splits(int batch, int kv_heads, int kv_len) {
 
 extern "C" const char *npm_last_decode_kernel(void) { return g_last; }
 
-extern "C" int npm_mha_decode_fwd(const npm_mha_decode *d) {
+// npm_mha_decode_fwd (kv_lens == nullptr) and npm_mha_decode_fwd_varlen: one host path, so that the split count, the tile
+// partition and the load policy of a varlen call are those of the uniform call at d->kv_len.
+static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens) {
+    const bool varlen = kv_lens != nullptr;
     NPM_REQUIRE_INIT();
     NPM_ARG(d != nullptr);
     NPM_ARG(d->batch >= 1 && d->heads >= 1 && d->kv_heads >= 1 && d->new_tokens >= 1 && d->head_dim >= 1);
     NPM_ARG(d->heads % d->kv_heads == 0);
-    NPM_ARG(d->kv_len >= d->new_tokens);
+    NPM_ARG(varlen ? d->kv_len >= 0 : d->kv_len >= d->new_tokens);     // varlen: new_lens[b] <= kv_lens[b] <= kv_len is the caller's
     NPM_ARG(d->scale > 0.f);
     NPM_ARG(d->q != nullptr && d->k != nullptr && d->v != nullptr && d->ctx != nullptr);
     const int D = d->head_dim, rows = d->heads / d->kv_heads * d->new_tokens;
     if (!npm_mha_decode_supported(D, rows))
-        return npm::fail(NPM_E_UNSUPPORTED, "npm_mha_decode_fwd: head_dim %d with %d rows per K / V head is not supported "
-                         "(head_dim in {16, 32, 64, 128}, rows <= %d)", D, rows, NPM_DECODE_MAX_ROWS);
+        return npm::fail(NPM_E_UNSUPPORTED, "%s: head_dim %d with %d rows per K / V head is not supported "
+                         "(head_dim in {16, 32, 64, 128}, rows <= %d)", name, D, rows, NPM_DECODE_MAX_ROWS);
     NPM_ARG(aligned16(d->q) && aligned16(d->k) && aligned16(d->v) && aligned16(d->ctx));
     NPM_ARG(d->q_pitch % 4 == 0 && d->k_pitch % 4 == 0 && d->v_pitch % 4 == 0 && d->ctx_pitch % 4 == 0);
     NPM_ARG(d->k_stride_b % 4 == 0 && d->v_stride_b % 4 == 0);
@@ -408,17 +472,19 @@ extern "C" int npm_mha_decode_fwd(const npm_mha_decode *d) {
     // below that plain loads are 0 - 3 % faster.  The project's rule for streaming tensors (32 MB each) draws the same line.
     const bool nt = g_nt == 1 || (g_nt == 0 && npm::stream_nt_enabled(sizeof(float) * (size_t)d->batch * d->kv_len * d->kv_heads * D));
     switch (D) {
-        case 16: launch_decode_rb<16>(a, grid, rb, nt, s); break;
-        case 32: launch_decode_rb<32>(a, grid, rb, nt, s); break;
-        case 64: launch_decode_rb<64>(a, grid, rb, nt, s); break;
-        default: launch_decode_rb<128>(a, grid, rb, nt, s); break;
+        case 16: launch_decode_rb<16>(a, kv_lens, new_lens, grid, rb, nt, s); break;
+        case 32: launch_decode_rb<32>(a, kv_lens, new_lens, grid, rb, nt, s); break;
+        case 64: launch_decode_rb<64>(a, kv_lens, new_lens, grid, rb, nt, s); break;
+        default: launch_decode_rb<128>(a, kv_lens, new_lens, grid, rb, nt, s); break;
     }
     NPM_CHECK_LAUNCH();
     if (splits > 1) {
         const long total = (long)d->batch * d->kv_heads * rows * (D / 4);
         const dim3 cgrid((unsigned)((total + 255) / 256));
-#define NPM_COMBINE(DD) hipLaunchKernelGGL(mha_decode_combine_kernel<DD>, cgrid, dim3(256), 0, s, a.part_ml, a.part_acc, a.ctx, \
-                                           a.ctx_pitch, a.lse, d->batch, d->heads, d->kv_heads, d->new_tokens, rows, rb * 16, splits, a.c, a.scale)
+#define NPM_COMBINE_VL(DD, VL) hipLaunchKernelGGL((mha_decode_combine_kernel<DD, VL>), cgrid, dim3(256), 0, s, a.part_ml, a.part_acc, \
+                                                  a.ctx, a.ctx_pitch, a.lse, d->batch, d->heads, d->kv_heads, d->new_tokens, rows, rb * 16, \
+                                                  splits, a.c, a.scale)
+#define NPM_COMBINE(DD) do { if (varlen) NPM_COMBINE_VL(DD, true); else NPM_COMBINE_VL(DD, false); } while (0)
         switch (D) {
             case 16: NPM_COMBINE(16); break;
             case 32: NPM_COMBINE(32); break;
@@ -426,10 +492,19 @@ extern "C" int npm_mha_decode_fwd(const npm_mha_decode *d) {
             default: NPM_COMBINE(128); break;
         }
 #undef NPM_COMBINE
+#undef NPM_COMBINE_VL
         NPM_CHECK_LAUNCH();
     }
-    snprintf(g_last, sizeof g_last, "mha_decode_kernel D=%d rows=%d splits=%d causal=%d", D, rows, splits, a.causal);
+    snprintf(g_last, sizeof g_last, "mha_decode_kernel D=%d rows=%d splits=%d causal=%d%s", D, rows, splits, a.causal,
+             varlen ? " varlen=1" : "");
     return NPM_OK;
+}
+
+extern "C" int npm_mha_decode_fwd(const npm_mha_decode *d) { return decode_fwd("npm_mha_decode_fwd", d, nullptr, nullptr); }
+
+extern "C" int npm_mha_decode_fwd_varlen(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens) {
+    if (kv_lens == nullptr) return npm::fail(NPM_E_BAD_ARGUMENT, "npm_mha_decode_fwd_varlen: kv_lens is NULL");
+    return decode_fwd("npm_mha_decode_fwd_varlen", d, kv_lens, new_lens);
 }
 
 extern "C" int npm_kv_append(const float *src, int64_t src_pitch, float *cache, int64_t cache_pitch, int64_t cache_stride_b,
@@ -445,6 +520,40 @@ extern "C" int npm_kv_append(const float *src, int64_t src_pitch, float *cache, 
     const int grid = (int)std::min<long>((total + 255) / 256, 2048);
     hipLaunchKernelGGL(kv_append_kernel, dim3(grid), dim3(256), 0, npm::ctx().stream, src, (long)src_pitch, cache, (long)cache_pitch,
                        (long)cache_stride_b, new_tokens, row_len / 4, at, total);
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
+}
+
+extern "C" int npm_kv_append_varlen(const float *src, int64_t src_pitch, float *cache, int64_t cache_pitch, int64_t cache_stride_b,
+                                    int32_t batch, int32_t new_tokens, int32_t row_len, const int32_t *at_lens,
+                                    const int32_t *new_lens) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(batch >= 0 && new_tokens >= 0 && row_len >= 0);
+    if (batch == 0 || new_tokens == 0 || row_len == 0) return NPM_OK;
+    NPM_ARG(src != nullptr && cache != nullptr && at_lens != nullptr);
+    NPM_ARG(aligned16(src) && aligned16(cache));
+    NPM_ARG(row_len % 4 == 0 && src_pitch % 4 == 0 && cache_pitch % 4 == 0 && cache_stride_b % 4 == 0);
+    NPM_ARG(src_pitch >= row_len && cache_pitch >= row_len);
+    const long total = (long)batch * new_tokens * (row_len / 4);
+    const int grid = (int)std::min<long>((total + 255) / 256, 2048);
+    hipLaunchKernelGGL(kv_append_varlen_kernel, dim3(grid), dim3(256), 0, npm::ctx().stream, src, (long)src_pitch, cache,
+                       (long)cache_pitch, (long)cache_stride_b, new_tokens, row_len / 4, at_lens, new_lens, total);
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
+}
+
+extern "C" int npm_kv_gather_varlen(const float *cache, int64_t cache_pitch, int64_t cache_stride_b, float *out, int32_t batch,
+                                    int32_t rows, int32_t row_len, const int32_t *lens) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(batch >= 0 && rows >= 0 && row_len >= 0);
+    if (batch == 0 || rows == 0 || row_len == 0) return NPM_OK;
+    NPM_ARG(cache != nullptr && out != nullptr && lens != nullptr);
+    NPM_ARG(aligned16(cache) && aligned16(out));
+    NPM_ARG(row_len % 4 == 0 && cache_pitch % 4 == 0 && cache_stride_b % 4 == 0 && cache_pitch >= row_len);
+    const long total = (long)batch * rows * (row_len / 4);
+    const int grid = (int)std::min<long>((total + 255) / 256, 2048);
+    hipLaunchKernelGGL(kv_gather_varlen_kernel, dim3(grid), dim3(256), 0, npm::ctx().stream, cache, (long)cache_pitch,
+                       (long)cache_stride_b, out, rows, row_len / 4, lens, total);
     NPM_CHECK_LAUNCH();
     return NPM_OK;
 }

@@ -1017,12 +1017,9 @@ def kv_append(src: Mat, cache: DeviceArray, batch: int, tokens: int, at: int) ->
                  'npm_kv_append')
 
 
-def mha_decode(q: Mat, k: DeviceArray, v: DeviceArray, heads: int, tokens: int, kv_len: int, scale: float, causal: bool,
-               want_lse: bool = False):
-    """ctx [B, T, Hq, D] (and lse [B, Hq, T] or None) of ``tokens`` query rows per sequence over the first ``kv_len`` rows of
-    the caches ``k`` / ``v`` [B, capacity, Hkv, D] (include/npm_hip.h npm_mha_decode_fwd).  ``q``: (array, row pitch)."""
+def _decode_desc(q: Mat, k: DeviceArray, v: DeviceArray, heads: int, tokens: int, kv_len: int, scale: float, causal: bool,
+                 want_lse: bool):
     b, capacity, hkv, d = k.shape
-    assert v.shape == k.shape and tokens <= kv_len <= capacity
     ctx = empty([b, tokens, heads, d])
     lse = empty([b, heads, tokens]) if want_lse else None
     c = _C.npm_mha_decode()
@@ -1033,9 +1030,55 @@ def mha_decode(q: Mat, k: DeviceArray, v: DeviceArray, heads: int, tokens: int, 
     c.v, c.v_pitch, c.v_stride_b = v.ptr, hkv * d, capacity * hkv * d
     c.ctx, c.ctx_pitch = ctx.ptr, heads * d
     c.lse = None if lse is None else lse.ptr
+    return c, ctx, lse
+
+
+def mha_decode(q: Mat, k: DeviceArray, v: DeviceArray, heads: int, tokens: int, kv_len: int, scale: float, causal: bool,
+               want_lse: bool = False):
+    """ctx [B, T, Hq, D] (and lse [B, Hq, T] or None) of ``tokens`` query rows per sequence over the first ``kv_len`` rows of
+    the caches ``k`` / ``v`` [B, capacity, Hkv, D] (include/npm_hip.h npm_mha_decode_fwd).  ``q``: (array, row pitch)."""
+    b, capacity, hkv, d = k.shape
+    assert v.shape == k.shape and tokens <= kv_len <= capacity
+    c, ctx, lse = _decode_desc(q, k, v, heads, tokens, kv_len, scale, causal, want_lse)
     with _timed('mha_decode', flops=4.0 * b * heads * tokens * kv_len * d, nbytes=4.0 * b * d * (2 * heads * tokens + 2 * hkv * kv_len)):
         _C.check(_C.lib().npm_mha_decode_fwd(C.byref(c)), 'npm_mha_decode_fwd')
     return ctx, lse
+
+
+def mha_decode_varlen(q: Mat, k: DeviceArray, v: DeviceArray, heads: int, tokens: int, kv_max: int, kv_lens: int,
+                      new_lens: Optional[int], scale: float, causal: bool, want_lse: bool = False, keys: Optional[int] = None):
+    """``mha_decode`` of a ragged batch (include/npm_hip.h npm_mha_decode_fwd_varlen): ``kv_lens`` / ``new_lens`` are DEVICE
+    addresses of [B] int32 (valid rows with the new tokens included; new tokens of the padded ``tokens``, or None for all),
+    ``kv_max`` the host's upper bound of ``kv_lens``.  Rows without a visible key come back as ctx 0, lse -inf.  ``keys``: the
+    sum of the lengths, for the timer's byte count."""
+    b, capacity, hkv, d = k.shape
+    assert v.shape == k.shape and 0 <= kv_max <= capacity
+    c, ctx, lse = _decode_desc(q, k, v, heads, tokens, kv_max, scale, causal, want_lse)
+    keys = b * kv_max if keys is None else int(keys)
+    with _timed('mha_decode', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + 2 * hkv * keys)):
+        _C.check(_C.lib().npm_mha_decode_fwd_varlen(C.byref(c), kv_lens, new_lens), 'npm_mha_decode_fwd_varlen')
+    return ctx, lse
+
+
+def kv_append_varlen(src: Mat, cache: DeviceArray, batch: int, tokens: int, at_lens: int, new_lens: Optional[int], rows: int) -> None:
+    """cache[b, at[b] + t] = src[b * tokens + t] for t < new[b] (include/npm_hip.h npm_kv_append_varlen); ``at_lens`` /
+    ``new_lens``: device addresses of [B] int32.  The caller has checked the capacity; ``rows``: the rows written, for the timer."""
+    b, capacity, hkv, d = cache.shape
+    assert batch == b
+    with _timed('kv_append', nbytes=8.0 * rows * hkv * d):
+        _C.check(_C.lib().npm_kv_append_varlen(src.ptr, src.ld, cache.ptr, hkv * d, capacity * hkv * d, batch, tokens, hkv * d,
+                                               at_lens, new_lens), 'npm_kv_append_varlen')
+
+
+def kv_gather_varlen(cache: DeviceArray, out: DeviceArray, lens: int) -> None:
+    """out[b, j] = cache[b, j] for j < lens[b], zeros behind, for ``out`` [B, rows, Hkv, D] (include/npm_hip.h
+    npm_kv_gather_varlen; one launch).  ``lens``: device address of [B] int32."""
+    b, capacity, hkv, d = cache.shape
+    rows = out.shape[1]
+    assert out.shape == (b, rows, hkv, d) and rows <= capacity
+    with _timed('kv_gather', nbytes=8.0 * b * rows * hkv * d):
+        _C.check(_C.lib().npm_kv_gather_varlen(cache.ptr, hkv * d, capacity * hkv * d, out.ptr, b, rows, hkv * d, lens),
+                 'npm_kv_gather_varlen')
 
 
 def kv_gather(cache: DeviceArray, out: DeviceArray, length: int) -> None:
@@ -1050,8 +1093,15 @@ def kv_gather(cache: DeviceArray, out: DeviceArray, length: int) -> None:
 
 class KVCache:
     """Keys and values of the tokens seen so far: ``k`` [B, capacity, Hkv, Dk] and ``v`` [B, capacity, Hkv, Dv] on the device,
-    of which the first ``length`` rows are valid.  Rows at and past ``length`` hold whatever was there; nothing reads them.
-    ``frozen`` marks a cross-attention cache (filled once, attended to as a whole, never appended to by ``forward``)."""
+    of which the first ``lengths[b]`` rows of sequence b are valid.  Rows at and past that hold whatever was there; nothing reads
+    them.  ``frozen`` marks a cross-attention cache (filled once, attended to as a whole, never appended to by ``forward``).
+
+    ``lengths`` (host int64 [B]) is authoritative: ``room`` and every check read it, nothing is read back from the device.  While
+    every sequence has the same number of rows the cache is *uniform*: ``length`` is that number and every call is the scalar
+    one (npm_kv_append / npm_mha_decode_fwd).  ``new_lengths`` (per-sequence counts n[b] <= tokens of a right-padded chunk) makes
+    it *ragged*: ``length`` then raises, ``max_length`` is the largest, and the kernels read the lengths from a device int32
+    mirror, uploaded once per ragged call ([3, B] int32 -- rows before, new rows, rows after -- shared by the append and the
+    attention that follows it)."""
 
     def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None):
         value_dim = key_dim if value_dim is None else value_dim
@@ -1061,28 +1111,108 @@ class KVCache:
         self.key_dim, self.value_dim = int(key_dim), int(value_dim)
         self.k = empty([batch, capacity, kv_heads, key_dim])
         self.v = empty([batch, capacity, kv_heads, value_dim])
-        self.length = 0
+        self.lengths = np.zeros([self.batch], dtype=np.int64)
+        self._mirror = None               # (host int32 [3, B]: before, new, after; ByteBuffer) of the last ragged call
         self.frozen = False
+
+    @property
+    def ragged(self) -> bool:
+        return bool((self.lengths != self.lengths[0]).any())
+
+    @property
+    def length(self) -> int:
+        """The number of valid rows while it is the same for every sequence."""
+        if self.ragged:
+            raise ValueError(f'KVCache.length: the sequences hold different numbers of rows {self.lengths.tolist()}; '
+                             'use lengths / max_length')
+        return int(self.lengths[0])
+
+    @length.setter
+    def length(self, value: int) -> None:
+        self.lengths = np.full([self.batch], int(value), dtype=np.int64)
+
+    @property
+    def max_length(self) -> int:
+        return int(self.lengths.max())
 
     def reset(self) -> None:
-        self.length = 0
+        self.lengths = np.zeros([self.batch], dtype=np.int64)
+        self._mirror = None
         self.frozen = False
 
-    def room(self, tokens: int) -> None:
-        """ValueError when ``tokens`` more rows do not fit -- checked before anything is launched."""
-        if tokens < 0 or self.length + tokens > self.capacity:
-            raise ValueError(f'KVCache: {tokens} new rows after {self.length} do not fit the capacity {self.capacity}')
+    def new_lengths(self, tokens: int, new_lengths) -> Optional[np.ndarray]:
+        """``new_lengths`` as int64 [B] with 0 <= n[b] <= tokens (ValueError otherwise); None when it is None or says what the
+        scalar call says (every n[b] == tokens)."""
+        if new_lengths is None:
+            return None
+        n = np.asarray(new_lengths)
+        if n.shape != (self.batch,) or not np.issubdtype(n.dtype, np.integer) or (n < 0).any() or (n > tokens).any():
+            raise ValueError(f'new_lengths must be {self.batch} integers in 0 .. {tokens}, got {np.asarray(new_lengths).tolist()}')
+        return None if (n == tokens).all() else n.astype(np.int64)
 
-    def append(self, k: Mat, v: Mat, tokens: int) -> None:
-        """``tokens`` freshly projected rows per sequence ([B, T, Hkv * D] with a row pitch each) behind the valid ones."""
-        self.room(tokens)
+    def room(self, tokens: int, new_lengths=None) -> None:
+        """ValueError when ``tokens`` (or ``new_lengths[b]``) more rows do not fit ANY sequence -- checked before anything is
+        launched."""
+        n = self.new_lengths(tokens, new_lengths)
+        if n is None:
+            n = np.full([self.batch], tokens, dtype=np.int64)
+        if tokens < 0 or (self.lengths + n > self.capacity).any():
+            raise ValueError(f'KVCache: {n.tolist() if new_lengths is not None else tokens} new rows after '
+                             f'{self.lengths.tolist() if self.ragged else int(self.lengths[0])} do not fit the capacity {self.capacity}')
+
+    def _device_lengths(self, before: np.ndarray, n: np.ndarray):
+        """Device addresses of (before, n, before + n) as int32 [B] each; one upload unless the last one holds the same numbers."""
+        host = np.stack([before, n, before + n]).astype(np.int32)
+        if self._mirror is None or not np.array_equal(self._mirror[0], host):
+            self._mirror = (host, bytes_from_host(host))
+        ptr = self._mirror[1].ptr
+        return ptr, ptr + 4 * self.batch, ptr + 8 * self.batch
+
+    def append(self, k: Mat, v: Mat, tokens: int, new_lengths=None) -> None:
+        """``tokens`` freshly projected rows per sequence ([B, T, Hkv * D] with a row pitch each) behind the valid ones; with
+        ``new_lengths`` only the first n[b] of them, behind sequence b's own ``lengths[b]`` rows."""
+        self.room(tokens, new_lengths)
         if self.frozen:
             raise ValueError('KVCache: this cache was filled for cross-attention and is frozen; reset() it first')
-        kv_append(k, self.k, self.batch, tokens, self.length)
-        kv_append(v, self.v, self.batch, tokens, self.length)
-        self.length += tokens
+        n = self.new_lengths(tokens, new_lengths)
+        if n is None and not self.ragged:
+            at = self.length
+            kv_append(k, self.k, self.batch, tokens, at)
+            kv_append(v, self.v, self.batch, tokens, at)
+            self.lengths = self.lengths + tokens
+            return
+        if n is None:
+            n = np.full([self.batch], tokens, dtype=np.int64)
+        at_ptr, new_ptr, _ = self._device_lengths(self.lengths, n)
+        kv_append_varlen(k, self.k, self.batch, tokens, at_ptr, new_ptr, int(n.sum()))
+        kv_append_varlen(v, self.v, self.batch, tokens, at_ptr, new_ptr, int(n.sum()))
+        self.lengths = self.lengths + n
 
-    def attend(self, q: Mat, heads: int, tokens: int, scale: float, causal: bool, want_lse: bool = False):
-        """``mha_decode`` of ``tokens`` query rows per sequence over the valid rows."""
+    def attend(self, q: Mat, heads: int, tokens: int, scale: float, causal: bool, want_lse: bool = False, new_lengths=None):
+        """``mha_decode`` of ``tokens`` query rows per sequence over the valid rows; with ``new_lengths`` (or a ragged cache)
+        ``mha_decode_varlen``: rows t >= n[b] are padding and come back as zeros.  ``causal``: the n[b] new tokens are the last
+        n[b] valid rows of sequence b (they were appended first)."""
         assert self.key_dim == self.value_dim
-        return mha_decode(q, self.k, self.v, heads, tokens, self.length, scale, causal, want_lse)
+        n = self.new_lengths(tokens, new_lengths)
+        if n is None and not self.ragged:
+            return mha_decode(q, self.k, self.v, heads, tokens, self.length, scale, causal, want_lse)
+        if n is None:
+            n = np.full([self.batch], tokens, dtype=np.int64)
+        if causal and (n > self.lengths).any():
+            raise ValueError(f'KVCache.attend: {n.tolist()} new tokens are not among the {self.lengths.tolist()} valid rows')
+        _, new_ptr, kv_ptr = self._device_lengths(self.lengths - n, n)
+        return mha_decode_varlen(q, self.k, self.v, heads, tokens, self.max_length, kv_ptr, new_ptr, scale, causal, want_lse,
+                                 keys=int(self.lengths.sum()))
+
+    def gather(self, rows: int):
+        """(k, v) [B, rows, Hkv, D]: the valid rows of every sequence, zeros behind them (``kv_gather_varlen``)."""
+        if self._mirror is not None and np.array_equal(self._mirror[0][2], self.lengths):      # this call's append uploaded them
+            kv_ptr = self._mirror[1].ptr + 8 * self.batch
+        else:
+            kv_ptr = self._device_lengths(self.lengths, np.zeros([self.batch], dtype=np.int64))[2]
+        out = []
+        for x in (self.k, self.v):
+            y = empty([self.batch, rows, self.kv_heads, x.shape[3]])
+            kv_gather_varlen(x, y, kv_ptr)
+            out.append(y)
+        return out

@@ -47,6 +47,14 @@ value)`` and then ``forward(x, cache=cache)`` attends to the whole frozen cache.
 (csrc/npm_decode.hip: one block per K / V head serves its whole group of query heads, keys split over blocks) where it takes the
 shape; otherwise the fused forward with a causal ``AttnMask`` over the valid rows (a long prefill), or the GEMM composition on the
 valid rows (other head sizes, split math modes): ``_cached_path`` names which ran.  Nothing is saved for a backward.
+
+Ragged batches.  ``forward(x, cache=cache, new_lengths=n)``: ``x`` [B, T, F] is padded on the right and sequence b brings n[b] <= T
+tokens (0: it rides along); their K / V go behind the sequence's own ``cache.lengths[b]`` rows and row t < n[b] sees keys
+j <= lengths[b] + t.  ``fill_cache(cache, key, value, lengths=...)`` does the same for a padded cross-attention memory.  Valid rows
+equal what the sequence gives alone at batch 1; padded rows are unspecified but finite; nothing at or past a sequence's length
+enters a result.  ``'decode'`` is then ``npm_mha_decode_fwd_varlen``, ``'fused_masked'`` (a ragged prefill) builds its mask from the
+lengths and takes K / V from the fresh projection or ``npm_kv_gather_varlen``; the GEMM composition has no masked softmax and
+raises NotImplementedError.  Lengths that are all equal take exactly the calls they took without the keyword.
 """
 
 from __future__ import annotations
@@ -143,13 +151,15 @@ class MultiHeadAttention(layer.StatefulLayer):
                 [(self, '_bq'), (self, '_bk'), (self, '_bv')]]
 
     # -- forward -------------------------------------------------------------------------
-    def forward(self, query, key=None, value=None, mask=None, cache=None):
+    def forward(self, query, key=None, value=None, mask=None, cache=None, new_lengths=None):
         query = D.as_device(query)
         if cache is not None:
             if key is not None or value is not None or mask is not None:
                 raise ValueError('with a cache, forward takes the new query tokens only: cross-attention keys and values go '
                                  'through fill_cache(cache, key, value), and the causal rule is implied')
-            return self._forward_cached(query, cache)
+            return self._forward_cached(query, cache, new_lengths=new_lengths)
+        if new_lengths is not None:
+            raise ValueError('new_lengths counts the tokens a ragged batch adds to a cache: it needs cache=')
         key = query if key is None else D.as_device(key)
         value = key if value is None else D.as_device(value)
         return self._forward_impl(query, key, value, mask=mask)
@@ -241,9 +251,10 @@ class MultiHeadAttention(layer.StatefulLayer):
             raise RuntimeError('make_cache: the layer has no parameters yet (run one forward, or bind weights, first)')
         return D.KVCache(batch, capacity, self._num_kv_heads, self._key_dim, self._value_dim)
 
-    def fill_cache(self, cache: D.KVCache, key, value=None) -> D.KVCache:
+    def fill_cache(self, cache: D.KVCache, key, value=None, lengths=None) -> D.KVCache:
         """Cross-attention: project ``key`` / ``value`` [B, Skv, F] once into ``cache`` and freeze it; ``forward(x, cache=cache)``
-        then attends to all of it, not causally, and appends nothing."""
+        then attends to all of it, not causally, and appends nothing.  ``lengths`` [B]: the memory is padded on the right and
+        sequence b has only ``lengths[b]`` rows; the rest is neither stored nor attended to."""
         key = D.as_device(key)
         value = key if value is None else D.as_device(value)
         h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
@@ -251,25 +262,34 @@ class MultiHeadAttention(layer.StatefulLayer):
         fv = value.shape[2]
         assert f == h * dk and value.shape[:2] == (b, skv) and fv == h * dv
         cache.reset()
-        cache.room(skv)                                                  # ValueError before anything is launched
+        cache.room(skv, lengths)                                         # ValueError before anything is launched
         k, v = D.empty([b, skv, hkv, dk]), D.empty([b, skv, hkv, dv])
         D.gemm(b * skv, hkv * dk, f, Mat(key, f), Mat(self._param('_wk'), f), Mat(k, hkv * dk), trans_b=True, bias=self._param('_bk'))
         D.gemm(b * skv, hkv * dv, fv, Mat(value, fv), Mat(self._param('_wv'), fv), Mat(v, hkv * dv), trans_b=True, bias=self._param('_bv'))
-        cache.append(Mat(k, hkv * dk), Mat(v, hkv * dv), skv)
+        cache.append(Mat(k, hkv * dk), Mat(v, hkv * dv), skv, lengths)
         cache.frozen = True
         return cache
 
-    def _forward_cached(self, query: D.DeviceArray, cache: D.KVCache, residual: Optional[D.DeviceArray] = None):
-        """``forward(query, cache=cache)``: self-attention over a growing cache (causal), or cross-attention over a frozen one."""
+    def _forward_cached(self, query: D.DeviceArray, cache: D.KVCache, residual: Optional[D.DeviceArray] = None, new_lengths=None):
+        """``forward(query, cache=cache)``: self-attention over a growing cache (causal), or cross-attention over a frozen one.
+        ``new_lengths`` [B]: ``query`` is padded on the right and sequence b brings n[b] <= T tokens.  The projections are
+        row-wise, so the padded rows (which must be finite) ride along; their K / V are not stored and their outputs are
+        unspecified but finite."""
         h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
         b, t, f = query.shape
         assert f == h * dk and (cache.batch, cache.kv_heads, cache.key_dim, cache.value_dim) == (b, hkv, dk, dv), \
             f'cache made for {(cache.batch, cache.kv_heads, cache.key_dim, cache.value_dim)}, used with {(b, hkv, dk, dv)}'
         cross = cache.frozen
+        new_lengths = cache.new_lengths(t, new_lengths)                  # None when it says what T says
+        ragged = new_lengths is not None or cache.ragged
+        if ragged and not (D.mha_decode_supported(dk, h // hkv * t, dv) or D.mha_core_supported(dk, dv, any_math=True)):
+            raise NotImplementedError('per-sequence lengths need head sizes Dk == Dv in {16, 32, 64, 128} (the decode kernel or '
+                                      'the fused masked forward); the GEMM composition has no masked softmax')
         if not cross:
-            cache.room(t)                                                # ValueError before anything is launched
-        elif cache.length == 0:
+            cache.room(t, new_lengths)                                   # ValueError before anything is launched
+        elif cache.max_length == 0:
             raise ValueError('the frozen cache is empty: fill_cache(cache, key, value) first')
+        before = cache.lengths.copy()
         self._cached_forward = True
         wq, wk, wv, wo = (self._param(p) for p in ('_wq', '_wk', '_wv', '_wo'))
         bq, bk, bv, bo = (self._param(p) for p in ('_bq', '_bk', '_bv', '_bo'))
@@ -294,8 +314,11 @@ class MultiHeadAttention(layer.StatefulLayer):
                 D.gemm(b * t, fkv, f, Mat(query, f), Mat(wk, f), Mat(ka, fkv), trans_b=True, bias=bk)
                 D.gemm(b * t, fvkv, f, Mat(query, f), Mat(wv, f), Mat(va, fvkv), trans_b=True, bias=bv)
                 q, fresh = Mat(qa, f), (Mat(ka, fkv), Mat(va, fvkv))
-            cache.append(fresh[0], fresh[1], t)
-        ctx = self._attend_cached(q, cache, t, causal=not cross, fresh=fresh)
+            cache.append(fresh[0], fresh[1], t, new_lengths)
+        if ragged:
+            ctx = self._attend_ragged(q, cache, t, not cross, fresh, before, new_lengths)
+        else:
+            ctx = self._attend_cached(q, cache, t, causal=not cross, fresh=fresh)
         out = D.empty([b, t, f])
         D.gemm(b * t, f, h * dv, Mat(ctx, h * dv), Mat(wo, h * dv), Mat(out, f), trans_b=True, bias=bo,
                residual=None if residual is None else Mat(residual, f))
@@ -337,6 +360,32 @@ class MultiHeadAttention(layer.StatefulLayer):
                        Mat(cache.v, pv, cap * pv, dv),
                        Mat(ctx.ptr + 4 * (first * h * dv + g * pv), h * dv, t * h * dv, dv), batch=(b, hkv))
         return ctx
+
+    def _attend_ragged(self, q: Mat, cache: D.KVCache, t: int, causal: bool, fresh, before: np.ndarray, new_lengths) -> D.DeviceArray:
+        """``_attend_cached`` when the sequences differ: ``before`` [B] rows were valid before this call, sequence b brings
+        ``new_lengths[b]`` (None: T) of the T padded query rows.  Row t < n[b] sees keys j <= before[b] + t (causal) or
+        j < lengths[b] (frozen cache)."""
+        h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
+        b, scale = cache.batch, 1.0 / math.sqrt(self._key_dim)
+        n = np.full([b], t, dtype=np.int64) if new_lengths is None else new_lengths
+        if D.mha_decode_supported(dk, h // hkv * t, dv):
+            self._cached_path = 'decode'
+            return cache.attend(q, h, t, scale, causal, new_lengths=n)[0]
+        # a ragged prefill, mostly: the fused training forward with the lengths as a mask [B, 1, T, keys], whose tile summary
+        # skips what lies past them.  K / V: the fresh projection when every sequence started empty (keys = T; the rows of padded
+        # tokens are masked), else the valid rows gathered with zeros behind them (P = 0 times stale memory could be NaN).
+        self._cached_path = 'fused_masked'
+        if fresh is not None and not before.any():
+            keys, (k, v) = t, fresh
+        else:
+            keys = cache.max_length
+            k, v = (Mat(x, hkv * dk) for x in cache.gather(keys))
+        limit = (before[:, None] + np.arange(t)[None, :] + 1) if causal else np.broadcast_to(cache.lengths[:, None], (b, t))
+        limit = np.where(np.arange(t)[None, :] < n[:, None], limit, 0)
+        visible = np.arange(keys)[None, None, :] < limit[:, :, None]                      # [B, T, keys]
+        visible[:, :, 0] |= ~visible.any(axis=2)                         # a row without a key is given key 0: finite, unspecified
+        mask = D.AttnMask(visible[:, None], b, h, t, keys)
+        return D.mha_core_fwd(q, k, v, (b, h, t, keys, dk), scale, mask, kv_heads=hkv if hkv != h else None)[0]
 
     @staticmethod
     def _valid_rows(x: D.DeviceArray, length: int) -> D.DeviceArray:

@@ -320,33 +320,40 @@ class TransformerDecoder(layer.Layer):
         return out.reshape(batch, seq_len_q, features)
 
     # -- incremental decoding (inference) ------------------------------------------------------------------------------
-    def start_decoding(self, kv, capacity: int) -> 'DecodeState':
+    def start_decoding(self, kv, capacity: int, kv_lengths=None) -> 'DecodeState':
         """Caches for ``decode``: an empty self-attention cache of ``capacity`` tokens per sequence and the cross-attention's
-        keys / values, projected from ``kv`` [B, Skv, F] once.  The layer must have its parameters (one forward, or bound weights)."""
+        keys / values, projected from ``kv`` [B, Skv, F] once.  ``kv_lengths`` [B]: ``kv`` is padded on the right and sequence b
+        has only that many memory rows.  The layer must have its parameters (one forward, or bound weights)."""
         if not (self._initialized and self._self_attention._initialized and self._cross_attention._initialized):
             raise RuntimeError('start_decoding: the decoder has no parameters yet (run one forward, or bind weights, first)')
         kv = D.as_device(kv)
         batch, seq_kv, _ = kv.shape
-        cross = self._cross_attention.fill_cache(self._cross_attention.make_cache(batch, seq_kv), kv)
+        cross = self._cross_attention.fill_cache(self._cross_attention.make_cache(batch, seq_kv), kv, lengths=kv_lengths)
         return DecodeState(self._self_attention.make_cache(batch, capacity), cross)
 
-    def decode(self, q_new, state: 'DecodeState'):
+    def decode(self, q_new, state: 'DecodeState', new_lengths=None):
         """One incremental step: the T new tokens ``q_new`` [B, T, F] through cached causal self-attention, cross-attention over
         the frozen cache, feed-forward and the three norms -> [B, T, F].  Dropout is the identity (inference: the reference's
-        ``DropOut.forward(training=False)``).  T may be a whole prompt or 1; the self-attention cache grows by T."""
+        ``DropOut.forward(training=False)``).  T may be a whole prompt or 1; the self-attention cache grows by T.
+
+        ``new_lengths`` [B] (a ragged batch): ``q_new`` is padded on the right (with finite values) and sequence b brings
+        n[b] <= T tokens, 0 for one that has finished; its cache grows by n[b].  Only the two attentions look across rows, and
+        they are told the lengths; LayerNorm, the dense layers and the residual additions work row by row, so a padded row
+        passes through them without touching a valid row or being touched by one.  Output rows t >= n[b] are unspecified but
+        finite; rows t < n[b] are what sequence b gives when decoded alone."""
         q = D.as_device(q_new)
         batch, tokens, features = q.shape
-        state.self_cache.room(tokens)                                     # ValueError before anything is launched
+        state.self_cache.room(tokens, new_lengths)                        # ValueError before anything is launched
         self._decoded = True
         pre = self._norm_first
         sa, ca = self._self_attention, self._cross_attention
         h = self._norm1._forward_impl(q) if pre else q
-        out = sa._forward_cached(h, state.self_cache, residual=q)
+        out = sa._forward_cached(h, state.self_cache, residual=q, new_lengths=new_lengths)
         if not pre:
             out = self._norm1._forward_impl(out)
         skip = out
         h = self._norm2._forward_impl(out) if pre else out
-        out = ca._forward_cached(h, state.cross_cache, residual=skip)
+        out = ca._forward_cached(h, state.cross_cache, residual=skip, new_lengths=new_lengths)
         if not pre:
             out = self._norm2._forward_impl(out)
         out = out.reshape(-1, features)
@@ -445,7 +452,8 @@ class TransformerDecoder(layer.Layer):
 
 class DecodeState:
     """What ``TransformerDecoder.decode`` carries from step to step: the self-attention's growing key / value cache and the
-    cross-attention's frozen one (``device.KVCache``).  ``position``: tokens decoded so far."""
+    cross-attention's frozen one (``device.KVCache``).  ``position``: tokens decoded so far while that is the same number for
+    every sequence (it raises once a ragged batch made them differ); ``positions``: the number per sequence."""
 
     __slots__ = ('self_cache', 'cross_cache')
 
@@ -455,3 +463,7 @@ class DecodeState:
     @property
     def position(self) -> int:
         return self.self_cache.length
+
+    @property
+    def positions(self) -> np.ndarray:
+        return self.self_cache.lengths.copy()
