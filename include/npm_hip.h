@@ -383,7 +383,8 @@ int npm_mha_decode_splits(int batch, int kv_heads, int kv_len);
 int npm_kv_append(const float *src, int64_t src_pitch, float *cache, int64_t cache_pitch, int64_t cache_stride_b,
                   int32_t batch, int32_t new_tokens, int32_t row_len, int32_t at);
 /* What the most recent npm_mha_decode_fwd launched: "<kernel> D=<head_dim> rows=<group_rows> splits=<n> causal=<0|1>"; "" before
- * the first call.  After npm_mha_decode_fwd_varlen: the same string followed by " varlen=1". */
+ * the first call.  After npm_mha_decode_fwd_varlen: the same string followed by " varlen=1"; after npm_mha_decode_fwd_paged: that
+ * followed by " paged=<page_rows>". */
 const char *npm_last_decode_kernel(void);
 
 /* ---- ragged batches: one length per sequence (device arrays of batch int32 each; they are read by the kernels, never on the host) ----
@@ -410,6 +411,32 @@ int npm_kv_append_varlen(const float *src, int64_t src_pitch, float *cache, int6
  * read.  One launch.  Alignment rules as npm_kv_append. */
 int npm_kv_gather_varlen(const float *cache, int64_t cache_pitch, int64_t cache_stride_b, float *out, int32_t batch, int32_t rows,
                          int32_t row_len, const int32_t *lens);
+
+/* ---- paged caches: K / V rows in a pool of pages, one block table per sequence ----
+ * npm_mha_decode_fwd_varlen over a paged cache.  d->k / d->v are page pools [pages, page_rows, kv_heads, D]: d->k_pitch / v_pitch the
+ * row pitch inside a page, d->k_stride_b / v_stride_b the PAGE stride (>= page_rows * pitch).  Key j of sequence b is row
+ * (j & (page_rows - 1)) of page block_table[b * table_pitch + (j >> log2 page_rows)]; block_table is a device array of
+ * batch * table_pitch int32 with table_pitch * page_rows >= d->kv_len.  page_rows is a power of two >= 16 (the kernel's key tile),
+ * so a tile never straddles a page and paging is one wave-uniform table lookup per tile in front of the varlen kernel's own
+ * arithmetic: split count, tile partition, load policy and every floating-point operation are those of npm_mha_decode_fwd_varlen
+ * with the same d->kv_len, and the result is BITWISE that call's on a contiguous cache holding the same rows.  Table entries at and
+ * past ceil(kv_lens[b] / page_rows) may hold anything: they are never read (the look-ahead index is clamped to the page of key
+ * kv_lens[b] - 1).  The caller guarantees that every entry before that names a page of the pool.  NPM_E_BAD_ARGUMENT for kv_lens or
+ * block_table == NULL and for a page_rows that is not a power of two >= 16; otherwise the checks of npm_mha_decode_fwd_varlen.
+ * npm_last_decode_kernel() afterwards: the varlen string followed by " paged=<page_rows>". */
+int npm_mha_decode_fwd_paged(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens, const int32_t *block_table,
+                             int32_t table_pitch, int32_t page_rows);
+/* npm_kv_append_varlen into a page pool: row at_lens[b] + t of sequence b, addressed through the block table as above, =
+ * src[b * new_tokens + t] for t < new_lens[b] (NULL: every t).  The caller has put a page into the table for every row written.
+ * row_pitch / page_stride: floats between rows of a page / between pages.  Alignment rules as npm_kv_append; at_lens or block_table
+ * == NULL or a bad page_rows: NPM_E_BAD_ARGUMENT. */
+int npm_kv_append_paged(const float *src, int64_t src_pitch, float *pool, int64_t row_pitch, int64_t page_stride, int32_t batch,
+                        int32_t new_tokens, int32_t row_len, const int32_t *at_lens, const int32_t *new_lens,
+                        const int32_t *block_table, int32_t table_pitch, int32_t page_rows);
+/* npm_kv_gather_varlen out of a page pool: out[b, j] = j < lens[b] ? row j of sequence b : 0 for j < rows; out is
+ * [batch, rows, row_len], contiguous.  Neither a row at or past lens[b] nor its table entry is read. */
+int npm_kv_gather_paged(const float *pool, int64_t row_pitch, int64_t page_stride, float *out, int32_t batch, int32_t rows,
+                        int32_t row_len, const int32_t *lens, const int32_t *block_table, int32_t table_pitch, int32_t page_rows);
 
 /* ---- around the path ("next" rows of SURVEY.md section 8f): keeps a Trainer step on the device ---- */
 /* Adam with the reference's numerics (optimizer.py:53-67): fp64 moments m, v (device buffers of n doubles,

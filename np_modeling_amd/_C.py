@@ -161,6 +161,9 @@ SIGNATURES = {
     'npm_mha_decode_fwd_varlen': [C.POINTER(npm_mha_decode), _P, _P],
     'npm_kv_append_varlen': [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _P, _P],
     'npm_kv_gather_varlen': [_P, _I64, _I64, _P, _I32, _I32, _I32, _P],
+    'npm_mha_decode_fwd_paged': [C.POINTER(npm_mha_decode), _P, _P, _P, _I32, _I32],
+    'npm_kv_append_paged': [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _I32, _I32],
+    'npm_kv_gather_paged': [_P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P, _I32, _I32],
     'npm_adam_step': [_P, _P, _P, _P, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int],
     'npm_fill_f64': [_P, C.c_double, _SZ],
     'npm_mse_fwd': [_P, _P, _SZ, C.POINTER(C.c_double)],

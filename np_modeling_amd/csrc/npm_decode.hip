@@ -1,6 +1,8 @@
 // Incremental decoding: attention of T new query tokens over a key / value cache, and the append into that cache
 // (include/npm_hip.h: npm_mha_decode_fwd, npm_kv_append), and their forms with one length per sequence for ragged batches
-// (npm_mha_decode_fwd_varlen, npm_kv_append_varlen, npm_kv_gather_varlen).  Inference only: nothing is saved for a backward.
+// (npm_mha_decode_fwd_varlen, npm_kv_append_varlen, npm_kv_gather_varlen), and the forms of those over a PAGED cache
+// (npm_mha_decode_fwd_paged, npm_kv_append_paged, npm_kv_gather_paged): K / V rows live in a pool of pages of page_rows rows each
+// and a per-sequence block table names the page of every page_rows logical rows.  Inference only: nothing is saved for a backward.
 //
 //   ctx[b, t, h, :] = sum_j softmax_j(scale q[b, t, h, :] . K[b, j, h % Hkv, :]) V[b, j, h % Hkv, :]
 //   j < L (causal = 0)    j <= L - T + t (causal = 1: the T new tokens are the last T keys of the cache)
@@ -37,6 +39,14 @@
 // m = fl(s_max c) (so the sums l are relative to m exactly, and merging waves and splits, exp2(m_a - m_b), is consistent); the
 // rounding of m itself, delta = m - s_max c, is recovered exactly by one fma and added to log2(l).  Floating-point contraction
 // is off in these kernels: each fma is written out.
+//
+// Paged (PG): page_rows is a power of two >= TILE, so a 16-key tile never straddles a page and the redirect to key L - 1 stays in
+// the tile's own page (a loaded tile holds a key < L: key0 <= L - 1 < key0 + 16).  Paging is then ONE wave-uniform table lookup per
+// tile (a scalar load) in front of the same address arithmetic; the source asks for a tile's page one loop step before the loads
+// that need it (the compiler schedules the scalar load next to those loads all the same: DESIGN.md 4.5b has the measured cost).
+// The table index is clamped to the page of key L - 1: entries past a sequence's
+// last page are not even read.  Split partition, online softmax, wave merge and the combine kernel do not know about pages, so a
+// paged call is bitwise the varlen call on a contiguous cache of the same rows.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -71,6 +81,12 @@ struct DecodeArgs {
     float c, scale;               // scale * log2(e), scale
 };
 
+// npm_*_paged: row j of sequence b is row (j & (rows - 1)) of page table[b * pitch + (j >> shift)]; rows = 1 << shift
+struct PageArgs {
+    const int *table;
+    int pitch, shift;
+};
+
 template <int VW> struct VecOf;
 template <> struct VecOf<4> { using type = f32x4v; };
 template <> struct VecOf<2> { using type = f32x2v; };
@@ -90,10 +106,12 @@ template <> __device__ __forceinline__ float comp<1>(const float &x, int) { retu
 // The tile partition stays that of a.len, so a sequence with L == a.len and nb == a.tokens computes, operation for operation, what
 // the VL = false instance computes; a block whose key range starts at or past L leaves an empty partial and returns before it
 // loads anything; a row without a visible key (a padded token, L = 0) is stored as ctx = 0, lse = -inf by selection.
-template <int D, int RB, bool NT, bool VL>
+// PG (npm_mha_decode_fwd_paged, implies VL): a.k / a.v are page pools, a.k_sb / a.v_sb the page strides, pg the block table.
+template <int D, int RB, bool NT, bool VL, bool PG>
 __global__ void __launch_bounds__(WAVES * 64)
-mha_decode_kernel(const DecodeArgs a, const int *__restrict__ kv_lens, const int *__restrict__ new_lens) {
+mha_decode_kernel(const DecodeArgs a, const int *__restrict__ kv_lens, const int *__restrict__ new_lens, const PageArgs pg) {
 #pragma clang fp contract(off)
+    static_assert(VL || !PG, "a paged cache has per-sequence lengths");
     constexpr int KU = D / 16;                    // 16-byte K loads per lane and tile
     constexpr int VW = D >= 64 ? 4 : D / 16;      // floats per V load
     constexpr int DQ = D / (16 * VW);             // V loads per lane and key
@@ -149,26 +167,37 @@ mha_decode_kernel(const DecodeArgs a, const int *__restrict__ kv_lens, const int
     const int tiles = (L + TILE - 1) / TILE;      // VL: the sequence's own tiles within the split ranges of a.len; every tile below
     const int t_begin = split * a.tiles_per_split;  // holds a key < L, so L >= 1 wherever a load is redirected to key L - 1
     const int t_end = min(tiles, t_begin + a.tiles_per_split);
-    const float *kbase = a.k + (long)b * a.k_sb + (long)c * D + 4 * g;
-    const float *vbase = a.v + (long)b * a.v_sb + (long)c * D + VW * n;
+    const float *kbase = a.k + (PG ? 0L : (long)b * a.k_sb) + (long)c * D + 4 * g;
+    const float *vbase = a.v + (PG ? 0L : (long)b * a.v_sb) + (long)c * D + VW * n;
 
     f32x4v kr[KU];
     VVec vr[4][DQ];
-    auto load_tile = [&](int tile) {
+    // PG: the page of a tile, a function of b, the tile index and kernel arguments only -- wave-uniform, a scalar load.  The index
+    // is clamped to the page of key L - 1 (callers have L >= 1), so a look-ahead past the sequence's last tile reads a page in use.
+    auto page_of = [&](int tile) -> int {
+        const int idx = __builtin_amdgcn_readfirstlane(min(tile * TILE, L - 1) >> pg.shift);
+        return pg.table[(long)b * pg.pitch + idx];
+    };
+    auto load_tile = [&](int tile, int page) {
         const int key0 = tile * TILE;
-        const float *kp = kbase + (long)min(key0 + n, L - 1) * a.k_pitch;
+        const int in_page = PG ? (1 << pg.shift) - 1 : ~0;                // PG: the row within the page
+        const float *kp = kbase + (PG ? (long)page * a.k_sb : 0L) + (long)(min(key0 + n, L - 1) & in_page) * a.k_pitch;
 #pragma unroll
         for (int u = 0; u < KU; ++u) kr[u] = ld_kv<NT, f32x4v>(kp + 16 * u);
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
-            const float *vp = vbase + (long)min(key0 + 4 * g + w, L - 1) * a.v_pitch;
+            const float *vp = vbase + (PG ? (long)page * a.v_sb : 0L) + (long)(min(key0 + 4 * g + w, L - 1) & in_page) * a.v_pitch;
 #pragma unroll
             for (int dq = 0; dq < DQ; ++dq) vr[w][dq] = ld_kv<NT, VVec>(vp + 16 * VW * dq);
         }
     };
 
     int tile = t_begin + wave;
-    if (tile < t_end) load_tile(tile);
+    int page_next = 0;                            // PG: the page of tile + WAVES, looked up one step before its loads
+    if (tile < t_end) {
+        load_tile(tile, PG ? page_of(tile) : 0);
+        if (PG) page_next = page_of(tile + WAVES);
+    }
     for (; tile < t_end; tile += WAVES) {
         const int key0 = tile * TILE;
         // S^T = K Q^T
@@ -198,7 +227,8 @@ mha_decode_kernel(const DecodeArgs a, const int *__restrict__ kv_lens, const int
                 va[w][dq] = vr[w][dq];
                 if (ragged && key0 + 4 * g + w >= L) va[w][dq] = VVec(0.f);
             }
-        if (tile + WAVES < t_end) load_tile(tile + WAVES);
+        if (tile + WAVES < t_end) load_tile(tile + WAVES, page_next);
+        if (PG) page_next = page_of(tile + 2 * WAVES);
 
 #pragma unroll
         for (int rb = 0; rb < RB; ++rb) {
@@ -371,20 +401,66 @@ kv_gather_varlen_kernel(const float *__restrict__ cache, long cache_pitch, long 
     }
 }
 
-// VL = false (npm_mha_decode_fwd): the instances that never look at the length arrays
-template <int D, int RB, bool VL>
-void launch_decode(const DecodeArgs &a, const int *kv_lens, const int *new_lens, dim3 grid, bool nt, hipStream_t s) {
-    if (nt) hipLaunchKernelGGL((mha_decode_kernel<D, RB, true, VL>), grid, dim3(WAVES * 64), 0, s, a, kv_lens, new_lens);
-    else hipLaunchKernelGGL((mha_decode_kernel<D, RB, false, VL>), grid, dim3(WAVES * 64), 0, s, a, kv_lens, new_lens);
+// kv_append_varlen_kernel into a page pool: row at_lens[b] + t of sequence b through the block table
+__global__ void __launch_bounds__(256)
+kv_append_paged_kernel(const float *__restrict__ src, long src_pitch, float *__restrict__ pool, long row_pitch, long page_stride,
+                       int tokens, int row4, const int *__restrict__ at_lens, const int *__restrict__ new_lens,
+                       const int *__restrict__ table, int table_pitch, int shift, long total) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int col = (int)(i % row4) * 4;
+        const long row = i / row4;
+        const long b = row / tokens;
+        const int t = (int)(row - b * tokens);
+        if (new_lens && t >= new_lens[b]) continue;
+        const int j = at_lens[b] + t;
+        const long page = table[b * table_pitch + (j >> shift)];
+        *reinterpret_cast<f32x4v *>(pool + page * page_stride + (long)(j & ((1 << shift) - 1)) * row_pitch + col) =
+            *reinterpret_cast<const f32x4v *>(src + row * src_pitch + col);
+    }
+}
+
+// kv_gather_varlen_kernel out of a page pool.  Neither a row at or past lens[b] nor its table entry is read.
+__global__ void __launch_bounds__(256)
+kv_gather_paged_kernel(const float *__restrict__ pool, long row_pitch, long page_stride, float *__restrict__ out, int rows, int row4,
+                       const int *__restrict__ lens, const int *__restrict__ table, int table_pitch, int shift, long total) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int col = (int)(i % row4) * 4;
+        const long row = i / row4;
+        const long b = row / rows;
+        const int j = (int)(row - b * rows);
+        f32x4v x{0.f, 0.f, 0.f, 0.f};
+        if (j < lens[b]) {
+            const long page = table[b * table_pitch + (j >> shift)];
+            x = *reinterpret_cast<const f32x4v *>(pool + page * page_stride + (long)(j & ((1 << shift) - 1)) * row_pitch + col);
+        }
+        *reinterpret_cast<f32x4v *>(out + row * (4L * row4) + col) = x;
+    }
+}
+
+// VL = false (npm_mha_decode_fwd): the instances that never look at the length arrays; PG: the ones that read through a block table
+template <int D, int RB, bool VL, bool PG>
+void launch_decode(const DecodeArgs &a, const int *kv_lens, const int *new_lens, const PageArgs &pg, dim3 grid, bool nt, hipStream_t s) {
+    if (nt) hipLaunchKernelGGL((mha_decode_kernel<D, RB, true, VL, PG>), grid, dim3(WAVES * 64), 0, s, a, kv_lens, new_lens, pg);
+    else hipLaunchKernelGGL((mha_decode_kernel<D, RB, false, VL, PG>), grid, dim3(WAVES * 64), 0, s, a, kv_lens, new_lens, pg);
 }
 
 template <int D>
-void launch_decode_rb(const DecodeArgs &a, const int *kv_lens, const int *new_lens, dim3 grid, int rb, bool nt, hipStream_t s) {
-    if (kv_lens) {
-        if (rb == 1) launch_decode<D, 1, true>(a, kv_lens, new_lens, grid, nt, s);
-        else launch_decode<D, 2, true>(a, kv_lens, new_lens, grid, nt, s);
-    } else if (rb == 1) launch_decode<D, 1, false>(a, nullptr, nullptr, grid, nt, s);
-    else launch_decode<D, 2, false>(a, nullptr, nullptr, grid, nt, s);
+void launch_decode_rb(const DecodeArgs &a, const int *kv_lens, const int *new_lens, const PageArgs &pg, dim3 grid, int rb, bool nt,
+                      hipStream_t s) {
+    if (pg.table) {
+        if (rb == 1) launch_decode<D, 1, true, true>(a, kv_lens, new_lens, pg, grid, nt, s);
+        else launch_decode<D, 2, true, true>(a, kv_lens, new_lens, pg, grid, nt, s);
+    } else if (kv_lens) {
+        if (rb == 1) launch_decode<D, 1, true, false>(a, kv_lens, new_lens, pg, grid, nt, s);
+        else launch_decode<D, 2, true, false>(a, kv_lens, new_lens, pg, grid, nt, s);
+    } else if (rb == 1) launch_decode<D, 1, false, false>(a, nullptr, nullptr, pg, grid, nt, s);
+    else launch_decode<D, 2, false, false>(a, nullptr, nullptr, pg, grid, nt, s);
+}
+
+// page_rows -> log2, or -1 unless it is a power of two >= TILE
+int page_shift(int page_rows) {
+    if (page_rows < TILE || (page_rows & (page_rows - 1))) return -1;
+    return __builtin_ctz((unsigned)page_rows);
 }
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -422,12 +498,21 @@ extern "C" int npm_mha_decode_splits(int batch, int kv_heads, int kv_len) {
 
 extern "C" const char *npm_last_decode_kernel(void) { return g_last; }
 
-// npm_mha_decode_fwd (kv_lens == nullptr) and npm_mha_decode_fwd_varlen: one host path, so that the split count, the tile
-// partition and the load policy of a varlen call are those of the uniform call at d->kv_len.
-static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens) {
-    const bool varlen = kv_lens != nullptr;
+// npm_mha_decode_fwd (kv_lens == nullptr), npm_mha_decode_fwd_varlen and npm_mha_decode_fwd_paged (block_table != nullptr): one
+// host path, so that the split count, the tile partition and the load policy of a varlen or paged call are those of the uniform
+// call at d->kv_len.
+static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens,
+                      const int32_t *block_table = nullptr, int32_t table_pitch = 0, int32_t page_rows = 0) {
+    const bool varlen = kv_lens != nullptr, paged = block_table != nullptr;
     NPM_REQUIRE_INIT();
     NPM_ARG(d != nullptr);
+    PageArgs pg{};
+    if (paged) {
+        NPM_ARG(varlen && page_shift(page_rows) >= 0);
+        NPM_ARG(d->kv_len >= 0 && (int64_t)table_pitch * page_rows >= d->kv_len);       // a table row names every page of kv_len rows
+        NPM_ARG(d->k_stride_b >= (int64_t)page_rows * d->k_pitch && d->v_stride_b >= (int64_t)page_rows * d->v_pitch);
+        pg.table = block_table; pg.pitch = table_pitch; pg.shift = page_shift(page_rows);
+    }
     NPM_ARG(d->batch >= 1 && d->heads >= 1 && d->kv_heads >= 1 && d->new_tokens >= 1 && d->head_dim >= 1);
     NPM_ARG(d->heads % d->kv_heads == 0);
     NPM_ARG(varlen ? d->kv_len >= 0 : d->kv_len >= d->new_tokens);     // varlen: new_lens[b] <= kv_lens[b] <= kv_len is the caller's
@@ -472,10 +557,10 @@ static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *
     // below that plain loads are 0 - 3 % faster.  The project's rule for streaming tensors (32 MB each) draws the same line.
     const bool nt = g_nt == 1 || (g_nt == 0 && npm::stream_nt_enabled(sizeof(float) * (size_t)d->batch * d->kv_len * d->kv_heads * D));
     switch (D) {
-        case 16: launch_decode_rb<16>(a, kv_lens, new_lens, grid, rb, nt, s); break;
-        case 32: launch_decode_rb<32>(a, kv_lens, new_lens, grid, rb, nt, s); break;
-        case 64: launch_decode_rb<64>(a, kv_lens, new_lens, grid, rb, nt, s); break;
-        default: launch_decode_rb<128>(a, kv_lens, new_lens, grid, rb, nt, s); break;
+        case 16: launch_decode_rb<16>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+        case 32: launch_decode_rb<32>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+        case 64: launch_decode_rb<64>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+        default: launch_decode_rb<128>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
     }
     NPM_CHECK_LAUNCH();
     if (splits > 1) {
@@ -495,8 +580,9 @@ static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *
 #undef NPM_COMBINE_VL
         NPM_CHECK_LAUNCH();
     }
-    snprintf(g_last, sizeof g_last, "mha_decode_kernel D=%d rows=%d splits=%d causal=%d%s", D, rows, splits, a.causal,
-             varlen ? " varlen=1" : "");
+    int at = snprintf(g_last, sizeof g_last, "mha_decode_kernel D=%d rows=%d splits=%d causal=%d%s", D, rows, splits, a.causal,
+                      varlen ? " varlen=1" : "");
+    if (paged) snprintf(g_last + at, sizeof g_last - at, " paged=%d", page_rows);
     return NPM_OK;
 }
 
@@ -505,6 +591,15 @@ extern "C" int npm_mha_decode_fwd(const npm_mha_decode *d) { return decode_fwd("
 extern "C" int npm_mha_decode_fwd_varlen(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens) {
     if (kv_lens == nullptr) return npm::fail(NPM_E_BAD_ARGUMENT, "npm_mha_decode_fwd_varlen: kv_lens is NULL");
     return decode_fwd("npm_mha_decode_fwd_varlen", d, kv_lens, new_lens);
+}
+
+extern "C" int npm_mha_decode_fwd_paged(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens,
+                                        const int32_t *block_table, int32_t table_pitch, int32_t page_rows) {
+    if (kv_lens == nullptr) return npm::fail(NPM_E_BAD_ARGUMENT, "npm_mha_decode_fwd_paged: kv_lens is NULL");
+    if (block_table == nullptr) return npm::fail(NPM_E_BAD_ARGUMENT, "npm_mha_decode_fwd_paged: block_table is NULL");
+    if (page_shift(page_rows) < 0)
+        return npm::fail(NPM_E_BAD_ARGUMENT, "npm_mha_decode_fwd_paged: page_rows %d is not a power of two >= %d", page_rows, TILE);
+    return decode_fwd("npm_mha_decode_fwd_paged", d, kv_lens, new_lens, block_table, table_pitch, page_rows);
 }
 
 extern "C" int npm_kv_append(const float *src, int64_t src_pitch, float *cache, int64_t cache_pitch, int64_t cache_stride_b,
@@ -554,6 +649,45 @@ extern "C" int npm_kv_gather_varlen(const float *cache, int64_t cache_pitch, int
     const int grid = (int)std::min<long>((total + 255) / 256, 2048);
     hipLaunchKernelGGL(kv_gather_varlen_kernel, dim3(grid), dim3(256), 0, npm::ctx().stream, cache, (long)cache_pitch,
                        (long)cache_stride_b, out, rows, row_len / 4, lens, total);
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
+}
+
+extern "C" int npm_kv_append_paged(const float *src, int64_t src_pitch, float *pool, int64_t row_pitch, int64_t page_stride,
+                                   int32_t batch, int32_t new_tokens, int32_t row_len, const int32_t *at_lens,
+                                   const int32_t *new_lens, const int32_t *block_table, int32_t table_pitch, int32_t page_rows) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(batch >= 0 && new_tokens >= 0 && row_len >= 0);
+    NPM_ARG(at_lens != nullptr && block_table != nullptr && table_pitch >= 0 && page_shift(page_rows) >= 0);
+    if (batch == 0 || new_tokens == 0 || row_len == 0) return NPM_OK;
+    NPM_ARG(src != nullptr && pool != nullptr);
+    NPM_ARG(aligned16(src) && aligned16(pool));
+    NPM_ARG(row_len % 4 == 0 && src_pitch % 4 == 0 && row_pitch % 4 == 0 && page_stride % 4 == 0);
+    NPM_ARG(src_pitch >= row_len && row_pitch >= row_len && page_stride >= (int64_t)page_rows * row_pitch);
+    const long total = (long)batch * new_tokens * (row_len / 4);
+    const int grid = (int)std::min<long>((total + 255) / 256, 2048);
+    hipLaunchKernelGGL(kv_append_paged_kernel, dim3(grid), dim3(256), 0, npm::ctx().stream, src, (long)src_pitch, pool,
+                       (long)row_pitch, (long)page_stride, new_tokens, row_len / 4, at_lens, new_lens, block_table, table_pitch,
+                       page_shift(page_rows), total);
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
+}
+
+extern "C" int npm_kv_gather_paged(const float *pool, int64_t row_pitch, int64_t page_stride, float *out, int32_t batch, int32_t rows,
+                                   int32_t row_len, const int32_t *lens, const int32_t *block_table, int32_t table_pitch,
+                                   int32_t page_rows) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(batch >= 0 && rows >= 0 && row_len >= 0);
+    NPM_ARG(lens != nullptr && block_table != nullptr && table_pitch >= 0 && page_shift(page_rows) >= 0);
+    if (batch == 0 || rows == 0 || row_len == 0) return NPM_OK;
+    NPM_ARG(pool != nullptr && out != nullptr);
+    NPM_ARG(aligned16(pool) && aligned16(out));
+    NPM_ARG(row_len % 4 == 0 && row_pitch % 4 == 0 && page_stride % 4 == 0 && row_pitch >= row_len);
+    NPM_ARG(page_stride >= (int64_t)page_rows * row_pitch);
+    const long total = (long)batch * rows * (row_len / 4);
+    const int grid = (int)std::min<long>((total + 255) / 256, 2048);
+    hipLaunchKernelGGL(kv_gather_paged_kernel, dim3(grid), dim3(256), 0, npm::ctx().stream, pool, (long)row_pitch, (long)page_stride,
+                       out, rows, row_len / 4, lens, block_table, table_pitch, page_shift(page_rows), total);
     NPM_CHECK_LAUNCH();
     return NPM_OK;
 }

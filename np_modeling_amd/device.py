@@ -18,6 +18,7 @@ Anything that is not on the hot path (losses, Adam's fp64 moment math) works thr
 from __future__ import annotations
 
 import ctypes as C
+import heapq
 import math
 import numbers
 import os
@@ -1216,3 +1217,198 @@ class KVCache:
             kv_gather_varlen(x, y, kv_ptr)
             out.append(y)
         return out
+
+
+# ---- paged key / value cache ---------------------------------------------------------------------------------------------------
+def mha_decode_paged(q: Mat, k: DeviceArray, v: DeviceArray, batch: int, heads: int, tokens: int, kv_max: int, kv_lens: int,
+                     new_lens: Optional[int], table: int, table_pitch: int, scale: float, causal: bool, want_lse: bool = False,
+                     keys: Optional[int] = None):
+    """``mha_decode_varlen`` over page pools ``k`` / ``v`` [pages, page_rows, Hkv, D] (include/npm_hip.h npm_mha_decode_fwd_paged):
+    ``table`` is the DEVICE address of the block table, int32 [batch, table_pitch]; key j of sequence b is row j % page_rows of
+    page table[b, j // page_rows].  Bitwise ``mha_decode_varlen`` on a contiguous cache holding the same rows."""
+    pages, page_rows, hkv, d = k.shape
+    assert v.shape == k.shape and 0 <= kv_max <= table_pitch * page_rows
+    ctx = empty([batch, tokens, heads, d])
+    lse = empty([batch, heads, tokens]) if want_lse else None
+    c = _C.npm_mha_decode()
+    c.batch, c.heads, c.kv_heads, c.new_tokens, c.kv_len, c.head_dim = int(batch), int(heads), hkv, int(tokens), int(kv_max), d
+    c.causal, c.scale = int(bool(causal)), float(scale)
+    c.q, c.q_pitch = q.ptr, q.ld
+    c.k, c.k_pitch, c.k_stride_b = k.ptr, hkv * d, page_rows * hkv * d
+    c.v, c.v_pitch, c.v_stride_b = v.ptr, hkv * d, page_rows * hkv * d
+    c.ctx, c.ctx_pitch = ctx.ptr, heads * d
+    c.lse = None if lse is None else lse.ptr
+    keys = batch * kv_max if keys is None else int(keys)
+    with _timed('mha_decode', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * batch * heads * tokens + 2 * hkv * keys)):
+        _C.check(_C.lib().npm_mha_decode_fwd_paged(C.byref(c), kv_lens, new_lens, table, int(table_pitch), page_rows),
+                 'npm_mha_decode_fwd_paged')
+    return ctx, lse
+
+
+def kv_append_paged(src: Mat, pool: DeviceArray, batch: int, tokens: int, at_lens: int, new_lens: Optional[int], table: int,
+                    table_pitch: int, rows: int) -> None:
+    """Row at[b] + t of sequence b, through the block table, = src[b * tokens + t] for t < new[b] (include/npm_hip.h
+    npm_kv_append_paged).  The caller has allocated the pages; ``rows``: the rows written, for the timer."""
+    pages, page_rows, hkv, d = pool.shape
+    with _timed('kv_append', nbytes=8.0 * rows * hkv * d):
+        _C.check(_C.lib().npm_kv_append_paged(src.ptr, src.ld, pool.ptr, hkv * d, page_rows * hkv * d, batch, tokens, hkv * d,
+                                              at_lens, new_lens, table, int(table_pitch), page_rows), 'npm_kv_append_paged')
+
+
+def kv_gather_paged(pool: DeviceArray, out: DeviceArray, lens: int, table: int, table_pitch: int) -> None:
+    """out[b, j] = row j of sequence b for j < lens[b], zeros behind, for ``out`` [B, rows, Hkv, D] (include/npm_hip.h
+    npm_kv_gather_paged; one launch)."""
+    pages, page_rows, hkv, d = pool.shape
+    b, rows = out.shape[:2]
+    assert out.shape == (b, rows, hkv, d) and rows <= table_pitch * page_rows
+    with _timed('kv_gather', nbytes=8.0 * b * rows * hkv * d):
+        _C.check(_C.lib().npm_kv_gather_paged(pool.ptr, hkv * d, page_rows * hkv * d, out.ptr, b, rows, hkv * d, lens, table,
+                                              int(table_pitch), page_rows), 'npm_kv_gather_paged')
+
+
+class PagedKVCache(KVCache):
+    """``KVCache`` whose rows live in a pool of pages: ``k`` [pages, page_size, Hkv, Dk] and ``v`` [pages, page_size, Hkv, Dv] on
+    the device, and ``block_table`` (host int32 [B, ceil(capacity / page_size)], -1 = none) naming the page of every
+    ``page_size`` logical rows of a sequence.  Pages are handed out as sequences grow (lowest-numbered free page first, so two
+    runs build the same table) and come back with ``release(b)``; the released slot then takes a new sequence through the
+    ordinary ragged call while the others keep decoding.  The pool, not ``batch * capacity``, is what the cache costs.
+
+    ``capacity`` is the most rows ONE sequence may reach; ``pages`` the pool size (None: ``batch * ceil(capacity / page_size)``,
+    which cannot run out).  ``page_size``: a power of two >= 16 (the decode kernel's key tile: a tile never straddles a page).
+    Host state is authoritative, as ``lengths`` is; the device mirror of the table is uploaded only when the table changed
+    (``table_uploads`` counts them).  Every call is the paged one (npm_kv_append_paged / npm_mha_decode_fwd_paged /
+    npm_kv_gather_paged), uniform lengths included: it is bitwise the uniform entry point."""
+
+    def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None, *, page_size: int,
+                 pages: Optional[int] = None):
+        value_dim = key_dim if value_dim is None else value_dim
+        if min(batch, capacity, kv_heads, key_dim, value_dim) < 1:
+            raise ValueError('PagedKVCache: batch, capacity, kv_heads and the head sizes must be positive')
+        page_size = int(page_size)
+        if page_size < 16 or page_size & (page_size - 1):
+            raise ValueError(f'PagedKVCache: page_size must be a power of two >= 16, got {page_size}')
+        self.batch, self.capacity, self.kv_heads = int(batch), int(capacity), int(kv_heads)
+        self.key_dim, self.value_dim = int(key_dim), int(value_dim)
+        self.page_size = page_size
+        self.pages_per_sequence = -(-self.capacity // page_size)
+        self.pages = self.batch * self.pages_per_sequence if pages is None else int(pages)
+        if self.pages < 1:
+            raise ValueError(f'PagedKVCache: pages must be positive, got {pages}')
+        self.k = empty([self.pages, page_size, kv_heads, key_dim])
+        self.v = empty([self.pages, page_size, kv_heads, value_dim])
+        self.table_uploads = 0
+        self.frozen = False
+        self._release_all()
+
+    def _release_all(self) -> None:
+        self.lengths = np.zeros([self.batch], dtype=np.int64)
+        self.block_table = np.full([self.batch, self.pages_per_sequence], -1, dtype=np.int32)
+        self._free = list(range(self.pages))          # a heap: the lowest-numbered free page first
+        self._mirror = None
+        self._table_dev = None                        # ByteBuffer of the table as the device last saw it
+        self._table_dirty = True
+
+    @property
+    def pages_free(self) -> int:
+        return len(self._free)
+
+    @property
+    def pages_in_use(self) -> int:
+        return self.pages - len(self._free)
+
+    @property
+    def length(self) -> int:
+        return KVCache.length.fget(self)
+
+    @length.setter
+    def length(self, value: int) -> None:
+        raise ValueError('PagedKVCache.length cannot be assigned: rows need pages (append), and release(b) returns them')
+
+    def reset(self) -> None:
+        self._release_all()
+        self.frozen = False
+
+    def _pages_needed(self, n: np.ndarray) -> np.ndarray:
+        """Pages every sequence lacks for n[b] more rows."""
+        size = self.page_size
+        return -(-(self.lengths + n) // size) - -(-self.lengths // size)
+
+    def room(self, tokens: int, new_lengths=None) -> None:
+        """``KVCache.room``, and ValueError when the new rows need more pages than are free -- before anything is launched, with
+        lengths, table and free list as they were."""
+        KVCache.room(self, tokens, new_lengths)
+        n = self.new_lengths(tokens, new_lengths)
+        if n is None:
+            n = np.full([self.batch], tokens, dtype=np.int64)
+        need = int(self._pages_needed(n).sum())
+        if need > self.pages_free:
+            raise ValueError(f'PagedKVCache: {n.tolist()} new rows after {self.lengths.tolist()} need {need} more pages of '
+                             f'{self.page_size} rows, {self.pages_free} of {self.pages} are free; release() a sequence first')
+
+    def _allocate(self, n: np.ndarray) -> None:
+        need = self._pages_needed(n)
+        have = -(-self.lengths // self.page_size)
+        for b in np.nonzero(need)[0]:
+            for slot in range(int(have[b]), int(have[b] + need[b])):
+                self.block_table[b, slot] = heapq.heappop(self._free)
+            self._table_dirty = True
+
+    def _device_table(self) -> int:
+        """Device address of the block table, int32 [B, pages_per_sequence]; uploaded only when it changed.  Slots without a page
+        go up as page 0: no kernel forms an address from them, and the entry stays inside the pool whatever happens."""
+        if self._table_dirty or self._table_dev is None:
+            self._table_dev = bytes_from_host(np.maximum(self.block_table, 0))
+            self._table_dirty = False
+            self.table_uploads += 1
+        return self._table_dev.ptr
+
+    def release(self, b) -> None:
+        """Sequence ``b`` (an index or several) ends: its pages go back to the free list and ``lengths[b] = 0``.  Nothing is
+        launched and nothing is cleared -- no kernel reads past a length."""
+        for i in np.unique(np.atleast_1d(np.asarray(b, dtype=np.int64))):
+            if not 0 <= i < self.batch:
+                raise IndexError(f'PagedKVCache.release: no sequence {i} in a batch of {self.batch}')
+            for page in self.block_table[i][self.block_table[i] >= 0]:
+                heapq.heappush(self._free, int(page))
+            self.block_table[i] = -1
+            self.lengths[i] = 0
+            self._table_dirty = True
+
+    def append(self, k: Mat, v: Mat, tokens: int, new_lengths=None) -> None:
+        self.room(tokens, new_lengths)
+        if self.frozen:
+            raise ValueError('KVCache: this cache was filled for cross-attention and is frozen; reset() it first')
+        n = self.new_lengths(tokens, new_lengths)
+        if n is None:
+            n = np.full([self.batch], tokens, dtype=np.int64)
+        self._allocate(n)
+        at_ptr, new_ptr, _ = self._device_lengths(self.lengths, n)
+        table = self._device_table()
+        for src, pool in ((k, self.k), (v, self.v)):
+            kv_append_paged(src, pool, self.batch, tokens, at_ptr, new_ptr, table, self.pages_per_sequence, int(n.sum()))
+        self.lengths = self.lengths + n
+
+    def attend(self, q: Mat, heads: int, tokens: int, scale: float, causal: bool, want_lse: bool = False, new_lengths=None):
+        assert self.key_dim == self.value_dim
+        n = self.new_lengths(tokens, new_lengths)
+        if n is None:
+            n = np.full([self.batch], tokens, dtype=np.int64)
+        if causal and (n > self.lengths).any():
+            raise ValueError(f'KVCache.attend: {n.tolist()} new tokens are not among the {self.lengths.tolist()} valid rows')
+        _, new_ptr, kv_ptr = self._device_lengths(self.lengths - n, n)
+        return mha_decode_paged(q, self.k, self.v, self.batch, heads, tokens, self.max_length, kv_ptr, new_ptr, self._device_table(),
+                                self.pages_per_sequence, scale, causal, want_lse, keys=int(self.lengths.sum()))
+
+    def gather(self, rows: int):
+        """(k, v) [B, rows, Hkv, D]: the valid rows of every sequence made contiguous, zeros behind them (``kv_gather_paged``)."""
+        if self._mirror is not None and np.array_equal(self._mirror[0][2], self.lengths):      # this call's append uploaded them
+            kv_ptr = self._mirror[1].ptr + 8 * self.batch
+        else:
+            kv_ptr = self._device_lengths(self.lengths, np.zeros([self.batch], dtype=np.int64))[2]
+        out = []
+        for x in (self.k, self.v):
+            y = empty([self.batch, rows, self.kv_heads, x.shape[3]])
+            kv_gather_paged(x, y, kv_ptr, self._device_table(), self.pages_per_sequence)
+            out.append(y)
+        return out
+

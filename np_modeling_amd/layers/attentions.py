@@ -244,12 +244,23 @@ class MultiHeadAttention(layer.StatefulLayer):
         return out
 
     # -- incremental decoding ------------------------------------------------------------------
-    def make_cache(self, batch: int, capacity: int) -> D.KVCache:
+    def make_cache(self, batch: int, capacity: int, page_size: Optional[int] = None, pages: Optional[int] = None) -> D.KVCache:
         """An empty key / value cache for ``batch`` sequences of up to ``capacity`` tokens (Hkv heads: grouped-query attention
-        keeps its smaller cache).  The layer must have its parameters (one forward, or a weight binder)."""
+        keeps its smaller cache).  The layer must have its parameters (one forward, or a weight binder).
+
+        ``page_size`` (a power of two >= 16): a ``device.PagedKVCache`` -- rows live in a pool of ``pages`` pages (None: enough
+        for every sequence to reach ``capacity``) that sequences take as they grow and give back with ``cache.release(b)``."""
         if not self._initialized:
             raise RuntimeError('make_cache: the layer has no parameters yet (run one forward, or bind weights, first)')
-        return D.KVCache(batch, capacity, self._num_kv_heads, self._key_dim, self._value_dim)
+        if page_size is None:
+            if pages is not None:
+                raise ValueError('make_cache: pages= sizes the pool of a paged cache: it needs page_size=')
+            return D.KVCache(batch, capacity, self._num_kv_heads, self._key_dim, self._value_dim)
+        dk, dv = self._key_dim, self._value_dim
+        if not (D.mha_decode_supported(dk, self._num_heads // self._num_kv_heads, dv) or D.mha_core_supported(dk, dv, any_math=True)):
+            raise NotImplementedError('a paged cache needs head sizes Dk == Dv in {16, 32, 64, 128} (the decode kernel or '
+                                      'the fused masked forward); the GEMM composition has no masked softmax')
+        return D.PagedKVCache(batch, capacity, self._num_kv_heads, dk, dv, page_size=page_size, pages=pages)
 
     def fill_cache(self, cache: D.KVCache, key, value=None, lengths=None) -> D.KVCache:
         """Cross-attention: project ``key`` / ``value`` [B, Skv, F] once into ``cache`` and freeze it; ``forward(x, cache=cache)``
@@ -281,7 +292,9 @@ class MultiHeadAttention(layer.StatefulLayer):
             f'cache made for {(cache.batch, cache.kv_heads, cache.key_dim, cache.value_dim)}, used with {(b, hkv, dk, dv)}'
         cross = cache.frozen
         new_lengths = cache.new_lengths(t, new_lengths)                  # None when it says what T says
-        ragged = new_lengths is not None or cache.ragged
+        # a paged cache has no [B, capacity, Hkv, D] tensor to hand to the uniform paths: it always takes the per-sequence route,
+        # whose kernels read through the block table (uniform lengths are bitwise the uniform entry point there)
+        ragged = new_lengths is not None or cache.ragged or isinstance(cache, D.PagedKVCache)
         if ragged and not (D.mha_decode_supported(dk, h // hkv * t, dv) or D.mha_core_supported(dk, dv, any_math=True)):
             raise NotImplementedError('per-sequence lengths need head sizes Dk == Dv in {16, 32, 64, 128} (the decode kernel or '
                                       'the fused masked forward); the GEMM composition has no masked softmax')

@@ -320,16 +320,53 @@ class TransformerDecoder(layer.Layer):
         return out.reshape(batch, seq_len_q, features)
 
     # -- incremental decoding (inference) ------------------------------------------------------------------------------
-    def start_decoding(self, kv, capacity: int, kv_lengths=None) -> 'DecodeState':
+    def start_decoding(self, kv, capacity: int, kv_lengths=None, *, page_size: Optional[int] = None, pages: Optional[int] = None,
+                       memory_capacity: Optional[int] = None) -> 'DecodeState':
         """Caches for ``decode``: an empty self-attention cache of ``capacity`` tokens per sequence and the cross-attention's
         keys / values, projected from ``kv`` [B, Skv, F] once.  ``kv_lengths`` [B]: ``kv`` is padded on the right and sequence b
-        has only that many memory rows.  The layer must have its parameters (one forward, or bound weights)."""
+        has only that many memory rows.  The layer must have its parameters (one forward, or bound weights).
+
+        ``page_size`` (and ``pages``): the self-attention cache is a ``device.PagedKVCache`` -- ``DecodeState.release(b)`` returns
+        a finished sequence's pages and ``admit`` puts a new sequence into its slot.  The cross-attention cache stays contiguous
+        (the memory fixes its size); ``memory_capacity`` (default Skv) is its row count, so that a sequence admitted later may
+        bring a longer memory than the first batch had."""
         if not (self._initialized and self._self_attention._initialized and self._cross_attention._initialized):
             raise RuntimeError('start_decoding: the decoder has no parameters yet (run one forward, or bind weights, first)')
         kv = D.as_device(kv)
         batch, seq_kv, _ = kv.shape
-        cross = self._cross_attention.fill_cache(self._cross_attention.make_cache(batch, seq_kv), kv, lengths=kv_lengths)
-        return DecodeState(self._self_attention.make_cache(batch, capacity), cross)
+        rows = seq_kv if memory_capacity is None else int(memory_capacity)
+        if rows < seq_kv:
+            raise ValueError(f'start_decoding: memory_capacity {rows} is less than the {seq_kv} memory rows given')
+        cross = self._cross_attention.fill_cache(self._cross_attention.make_cache(batch, rows), kv, lengths=kv_lengths)
+        if page_size is None and pages is None:
+            return DecodeState(self._self_attention.make_cache(batch, capacity), cross)
+        return DecodeState(self._self_attention.make_cache(batch, capacity, page_size=page_size, pages=pages), cross)
+
+    def admit(self, state: 'DecodeState', b: int, kv_b, kv_length: Optional[int] = None) -> None:
+        """A new sequence into slot ``b`` of a running batch (``state.release(b)`` emptied it): its memory ``kv_b`` [1, Skv, F]
+        (``kv_length`` valid rows, default all) is projected with the cross-attention's K / V weights into slot b of the cross
+        cache.  The next ``decode(q_new, state, new_lengths=n)`` carries the sequence's prompt in row b of the padded chunk."""
+        b = int(b)
+        cross, ca = state.cross_cache, self._cross_attention
+        if not 0 <= b < cross.batch:
+            raise IndexError(f'admit: no slot {b} in a batch of {cross.batch}')
+        if state.self_cache.lengths[b] != 0:
+            raise ValueError(f'admit: slot {b} still holds {int(state.self_cache.lengths[b])} rows; release({b}) it first')
+        kv_b = D.as_device(kv_b)
+        one, skv, f = kv_b.shape
+        rows = skv if kv_length is None else int(kv_length)
+        if one != 1 or not 1 <= rows <= skv:
+            raise ValueError(f'admit: the memory is [1, Skv, F] with 1 <= kv_length <= Skv, got {kv_b.shape} and {kv_length}')
+        if rows > cross.capacity:
+            raise ValueError(f'admit: {rows} memory rows do not fit the cross-attention cache of {cross.capacity} rows '
+                             '(start_decoding(..., memory_capacity=))')
+        hkv, dk, dv = cross.kv_heads, cross.key_dim, cross.value_dim
+        for w, bias, dim, pool in (('_wk', '_bk', dk, cross.k), ('_wv', '_bv', dv, cross.v)):
+            proj = D.empty([1, rows, hkv, dim])
+            D.gemm(rows, hkv * dim, f, D.Mat(kv_b, f), D.Mat(ca._param(w), f), D.Mat(proj, hkv * dim), trans_b=True, bias=ca._param(bias))
+            slot = pool.flat_view(b * cross.capacity * hkv * dim, [1, cross.capacity, hkv, dim])
+            D.kv_append(D.Mat(proj, hkv * dim), slot, 1, rows, 0)
+        cross.lengths[b] = rows
 
     def decode(self, q_new, state: 'DecodeState', new_lengths=None):
         """One incremental step: the T new tokens ``q_new`` [B, T, F] through cached causal self-attention, cross-attention over
@@ -459,6 +496,14 @@ class DecodeState:
 
     def __init__(self, self_cache: D.KVCache, cross_cache: D.KVCache):
         self.self_cache, self.cross_cache = self_cache, cross_cache
+
+    def release(self, b) -> None:
+        """Sequence ``b`` (an index or several) has finished: its self-attention pages go back to the pool and both caches hold
+        0 rows of it.  It then rides along with ``new_lengths[b] = 0`` until ``TransformerDecoder.admit`` fills the slot."""
+        if not isinstance(self.self_cache, D.PagedKVCache):
+            raise ValueError('DecodeState.release: the self-attention cache is not paged (start_decoding(..., page_size=))')
+        self.self_cache.release(b)
+        self.cross_cache.lengths[np.unique(np.atleast_1d(np.asarray(b, dtype=np.int64)))] = 0
 
     @property
     def position(self) -> int:
