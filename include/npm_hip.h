@@ -147,6 +147,8 @@ enum {
     NPM_TUNE_LN_NT_SPLIT = 19,       /* LayerNorm at d in (512, 1024]: backward mode + 4 * forward mode; a mode: 0 nontemporal hint on loads and stores, 1 on the loads only, 2 on the stores only.  Default 5: loads only in both (dx and z are read at once by the GEMMs behind them; measured inside the encoder step, profiles/r05_ln_nt_split.log) */
     NPM_TUNE_DECODE_SPLITS = 20,     /* npm_mha_decode_fwd: blocks the keys of one (batch, K / V head) are split over: 0 (default) automatic (npm_mha_decode_splits), n in 1 .. NPM_DECODE_MAX_SPLITS forced -- more splits than 16-key tiles leaves empty splits, which is allowed */
     NPM_TUNE_DECODE_NT = 21,         /* npm_mha_decode_fwd, the cache hint of the K / V loads (each byte is read once): 0 (default) nontemporal when the valid part of K is at least 32 MB (NPM_TUNE_STREAM_NT's rule), 1 always, 2 never; measured in tools/decode_bench.py */
+    NPM_TUNE_SKINNY_SPLITS = 22,     /* npm_sgemm_skinny: blocks the K range of one 64-column strip is split over: 0 (default) automatic (npm_sgemm_skinny_splits), n in 1 .. NPM_SKINNY_MAX_SPLITS forced -- more splits than 16-k chunks leaves empty splits, which is allowed */
+    NPM_TUNE_SKINNY_NT = 23,         /* npm_sgemm_skinny, the cache hint of the weight loads (each byte is read once): 0 (default) nontemporal when the weights are at least 32 MB (NPM_TUNE_STREAM_NT's rule), 1 always, 2 never; measured in tools/skinny_gemm_bench.py */
     NPM_TUNE_GEMM_ABLATE = 99
 };
 int npm_set_tuning(int knob, int value);
@@ -437,6 +439,33 @@ int npm_kv_append_paged(const float *src, int64_t src_pitch, float *pool, int64_
  * [batch, rows, row_len], contiguous.  Neither a row at or past lens[b] nor its table entry is read. */
 int npm_kv_gather_paged(const float *pool, int64_t row_pitch, int64_t page_stride, float *out, int32_t batch, int32_t rows,
                         int32_t row_len, const int32_t *lens, const int32_t *block_table, int32_t table_pitch, int32_t page_rows);
+
+/* ---- skinny-M GEMM: the matrix products of a decode step (inference) ----
+ * C[M, N] = epilogue(alpha * A[M, K] op(B)) for 1 <= M <= NPM_SKINNY_MAX_M rows, described by the same npm_gemm as npm_sgemm.  These
+ * are the products np.matmul / np.einsum make at M = B T rows of new tokens: the q / k / v and output projections of
+ * layers/attentions.py:88-100,114-117 (B stored [N, K]: trans_b = 1) and x @ w + b of layers/mlp.py:23-24 with the ReLU of
+ * activations.py:14-15 and the residual additions of transformer.py:39,53 (B stored [K, N]: trans_b = 0).  npm_sgemm runs them on
+ * its 128-row tiles with ceil(N / 128) blocks that each walk all of K; here the weights are the stream: every weight element is
+ * loaded once, by one wave, straight into registers; a block owns 64 columns and a range of K, and the ranges of a column strip are
+ * merged in a fixed order by a second kernel (no atomics: bitwise reproducible).  The split count and the order in which the k
+ * terms of an output element are added depend on (N, K, trans_b) and NPM_TUNE_SKINNY_SPLITS only, never on M or on the row's
+ * position: row r of an M-row call is bitwise the M = 1 call on that row.  Rows >= M of A's buffer, rows >= N of a [N, K] B and
+ * columns >= N of a [K, N] B are never read.
+ * Exact-fp32 MFMA (v_mfma_f32_16x16x4_f32) whatever npm_set_math says; npm_last_math() is left alone.
+ * Supported: trans_a = 0, batch0 = batch1 = 1, n and k multiples of 16 (>= 16), a / b / c (and bias / residual / aux when used) 16-byte
+ * aligned, lda / ldb / ldc / ldr / ldaux multiples of 4 floats and at least the row widths, epilogue any of NPM_EPI_BIAS,
+ * NPM_EPI_RESIDUAL and one of NPM_EPI_RELU / NPM_EPI_RELU_SAVE, colsum = bsum = asum = rowdot = NULL, split_k = 0.  Everything else is
+ * NPM_E_UNSUPPORTED before anything is launched or written (callers then use npm_sgemm). */
+#define NPM_SKINNY_MAX_M 64
+#define NPM_SKINNY_MAX_SPLITS 64
+int npm_sgemm_skinny(const npm_gemm *g);
+/* 1 when npm_sgemm_skinny takes this call, else 0; never sets an error. */
+int npm_sgemm_skinny_supported(const npm_gemm *g);
+/* The number of K splits npm_sgemm_skinny uses for this shape under the current NPM_TUNE_SKINNY_SPLITS: shape arguments only. */
+int npm_sgemm_skinny_splits(int n, int k, int trans_b);
+/* What the most recent npm_sgemm_skinny launched: "sgemm_skinny_kernel <NT|NN> M=<m> N=<n> K=<k> rb=<16-row blocks> splits=<n>
+ * nt=<0|1>" (nt: nontemporal weight loads); "" before the first call. */
+const char *npm_last_skinny_kernel(void);
 
 /* ---- around the path ("next" rows of SURVEY.md section 8f): keeps a Trainer step on the device ---- */
 /* Adam with the reference's numerics (optimizer.py:53-67): fp64 moments m, v (device buffers of n doubles,

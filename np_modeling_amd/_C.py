@@ -164,6 +164,9 @@ SIGNATURES = {
     'npm_mha_decode_fwd_paged': [C.POINTER(npm_mha_decode), _P, _P, _P, _I32, _I32],
     'npm_kv_append_paged': [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _I32, _I32],
     'npm_kv_gather_paged': [_P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P, _I32, _I32],
+    'npm_sgemm_skinny': [C.POINTER(npm_gemm)],
+    'npm_sgemm_skinny_supported': [C.POINTER(npm_gemm)],
+    'npm_sgemm_skinny_splits': [C.c_int, C.c_int, C.c_int],
     'npm_adam_step': [_P, _P, _P, _P, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int],
     'npm_fill_f64': [_P, C.c_double, _SZ],
     'npm_mse_fwd': [_P, _P, _SZ, C.POINTER(C.c_double)],
@@ -179,6 +182,7 @@ _SPECIAL = {
     'npm_stream': (C.c_void_p, []),
     'npm_last_attn_kernel': (C.c_char_p, []),
     'npm_last_decode_kernel': (C.c_char_p, []),
+    'npm_last_skinny_kernel': (C.c_char_p, []),
 }
 
 COMM_SIGNATURES = {
@@ -415,6 +419,13 @@ def last_decode_kernel() -> str:
 
 
 TUNE_DECODE_SPLITS, TUNE_DECODE_NT = 20, 21     # include/npm_hip.h NPM_TUNE_DECODE_*
+TUNE_SKINNY_SPLITS, TUNE_SKINNY_NT = 22, 23     # include/npm_hip.h NPM_TUNE_SKINNY_*
+SKINNY_MAX_M, SKINNY_MAX_SPLITS = 64, 64        # include/npm_hip.h NPM_SKINNY_MAX_*
+
+
+def last_skinny_kernel() -> str:
+    """What the most recent npm_sgemm_skinny launched (include/npm_hip.h npm_last_skinny_kernel)."""
+    return lib().npm_last_skinny_kernel().decode()
 
 
 def comm_lib():

@@ -446,6 +446,8 @@ extern "C" int npm_attn_set_fwd8(int mode);
 extern "C" int npm_attn_set_stagger(int units);
 extern "C" int npm_decode_set_splits(int value);
 extern "C" int npm_decode_set_nt(int value);
+extern "C" int npm_skinny_set_splits(int value);
+extern "C" int npm_skinny_set_nt(int value);
 
 extern "C" int npm_set_math(int mode) { return npm_set_tuning(NPM_TUNE_GEMM_MATH, mode); }
 extern "C" int npm_get_math(void) { return g_math; }
@@ -478,6 +480,8 @@ extern "C" int npm_set_tuning(int knob, int value) {
         case NPM_TUNE_GEMM_SPLIT_GENS: g_split_gens = value != 0; return NPM_OK;
         case NPM_TUNE_DECODE_SPLITS: return npm_decode_set_splits(value);
         case NPM_TUNE_DECODE_NT: return npm_decode_set_nt(value);
+        case NPM_TUNE_SKINNY_SPLITS: return npm_skinny_set_splits(value);
+        case NPM_TUNE_SKINNY_NT: return npm_skinny_set_nt(value);
         default: return npm::fail(NPM_E_BAD_ARGUMENT, "npm_set_tuning: unknown knob %d", knob);
     }
 }

@@ -640,6 +640,22 @@ ATTN_TILE_SKIP = os.environ.get('NPM_ATTN_TILE_SKIP', '1') != '0'
 # head size 128: the attention backward's row terms (dctx . ctx per query and head) come out of the epilogue of the GEMM that
 # produces dctx (NPM_EPI_ROWDOT) instead of a pass over dctx and ctx in front of the attention kernel (NPM_ATTN_ROWDOT=0: that pass)
 ATTN_ROWDOT = os.environ.get('NPM_ATTN_ROWDOT', '1') != '0'
+# decode steps: the projections and feed-forward products at M = B T <= SKINNY_MAX_M rows run on npm_sgemm_skinny (the weights
+# streamed once over the whole chip) instead of the 128-row training tiles (NPM_SKINNY_GEMM=0: npm_sgemm as before).  The
+# threshold is the largest M up to which the skinny kernel measured faster on all six decode shapes, warm and cold
+# (tools/skinny_gemm_bench.py, profiles/r11_skinny_gemm_bench.log).
+SKINNY_GEMM = os.environ.get('NPM_SKINNY_GEMM', '1') != '0'
+SKINNY_MAX_M = 64
+_SKINNY_LIB = (None, False)         # (library handle, whether it has the entry points)
+
+
+def _skinny_entry_points(lib) -> bool:
+    """Whether the loaded library handle has npm_sgemm_skinny (a host simulator of an earlier ABI does not)."""
+    global _SKINNY_LIB
+    if _SKINNY_LIB[0] is not lib:
+        _SKINNY_LIB = (lib, hasattr(lib, 'npm_sgemm_skinny') and hasattr(lib, 'npm_sgemm_skinny_supported'))
+    return _SKINNY_LIB[1]
+
 
 class KernelTimer:
     """Brackets every kernel-wrapper call with HIP events on the compute stream and books its
@@ -706,8 +722,13 @@ def gemm(m: int, n: int, k: int, a: Mat, b: Mat, c: Mat, *, trans_a: bool = Fals
          split_k: int = 0, colsum_out: Optional[DeviceArray] = None,
          softmax_bwd: Optional[Tuple[Mat, DeviceArray]] = None,
          bsum_out: Optional[DeviceArray] = None, asum_out: Optional[DeviceArray] = None,
-         rowdot: Optional[Tuple[Mat, DeviceArray, float]] = None) -> None:
+         rowdot: Optional[Tuple[Mat, DeviceArray, float]] = None,
+         skinny_ok: bool = False, save_optional: bool = False) -> None:
     """C = epilogue(alpha * op(A) @ op(B)); see include/npm_hip.h ``npm_sgemm``.
+    ``skinny_ok`` (the decode path sets it): the call may run on ``npm_sgemm_skinny`` when SKINNY_GEMM is on, m <= SKINNY_MAX_M,
+    the math mode is f32, the loaded library has the entry point and ``npm_sgemm_skinny_supported`` takes the call; otherwise it
+    is the ``npm_sgemm`` call it always was.  ``save_optional``: nobody reads ``relu_save``'s pre-activation (inference), so the
+    skinny route applies the ReLU without storing it.
     ``rowdot=(X, out, scale)``: besides C = A @ B, out[n // 128, m] (zeros on entry) += scale * sum over each block of 128
     columns of C * X -- the attention backward's row term dctx . ctx per head of size 128, taken where dctx is produced.
     ``colsum_out`` ([batch1, n]) receives the column sums of the stored C (a bias gradient
@@ -758,6 +779,17 @@ def gemm(m: int, n: int, k: int, a: Mat, b: Mat, c: Mat, *, trans_a: bool = Fals
     nb = batch[0] * batch[1]
     unique = 4.0 * nb * (m * k + k * n + m * n * (1 + (residual is not None) + (relu_save is not None) +
                                                   (relu_mask is not None) + (softmax_bwd is not None) + (rowdot is not None)))
+    if skinny_ok and SKINNY_GEMM and 0 < m <= SKINNY_MAX_M:
+        lib = _C.lib()
+        if _skinny_entry_points(lib) and _C.current_math() == 'f32':
+            gs = g
+            if save_optional and epi & _C.EPI_RELU_SAVE:
+                gs = _C.npm_gemm.from_buffer_copy(g)
+                gs.epilogue, gs.aux, gs.ldaux = (epi & ~_C.EPI_RELU_SAVE) | _C.EPI_RELU, None, 0
+            if lib.npm_sgemm_skinny_supported(C.byref(gs)):
+                with _timed('sgemm_skinny_' + layout, flops=2.0 * m * n * k, nbytes=unique):
+                    _C.check(lib.npm_sgemm_skinny(C.byref(gs)), 'npm_sgemm_skinny')
+                return
     with _timed('sgemm_' + layout, flops=2.0 * m * n * k * nb, nbytes=unique):
         _C.check(_C.lib().npm_sgemm(C.byref(g)), 'npm_sgemm')
     if bsum_out is not None and not fuse_b:      # A/B switch: separate pass over B

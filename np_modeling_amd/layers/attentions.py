@@ -310,7 +310,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         fresh = None                                                     # the new tokens' own (k, v) Mats, self-attention only
         if cross:
             q = D.empty([b, t, h, dk])
-            D.gemm(b * t, f, f, Mat(query, f), Mat(wq, f), Mat(q, f), trans_b=True, bias=bq)
+            D.gemm(b * t, f, f, Mat(query, f), Mat(wq, f), Mat(q, f), trans_b=True, bias=bq, skinny_ok=True)
             q = Mat(q, f)
         else:
             # ONE GEMM over M = B T rows makes q, k and v where the parameters are adjacent; K and V rows then go into the cache
@@ -318,14 +318,14 @@ class MultiHeadAttention(layer.StatefulLayer):
             if dk == dv and D.PACK_QKV and self._params_adjacent():
                 width = f + 2 * fkv
                 qkv = D.empty([b, t, h + 2 * hkv, dk])
-                D.gemm(b * t, width, f, Mat(query, f), Mat(wq, f), Mat(qkv, width), trans_b=True, bias=bq)
+                D.gemm(b * t, width, f, Mat(query, f), Mat(wq, f), Mat(qkv, width), trans_b=True, bias=bq, skinny_ok=True)
                 q = Mat(qkv, width)
                 fresh = (Mat(qkv.flat_view(f, [qkv.size - f]), width), Mat(qkv.flat_view(f + fkv, [qkv.size - f - fkv]), width))
             else:
                 qa, ka, va = D.empty([b, t, h, dk]), D.empty([b, t, hkv, dk]), D.empty([b, t, hkv, dv])
-                D.gemm(b * t, f, f, Mat(query, f), Mat(wq, f), Mat(qa, f), trans_b=True, bias=bq)
-                D.gemm(b * t, fkv, f, Mat(query, f), Mat(wk, f), Mat(ka, fkv), trans_b=True, bias=bk)
-                D.gemm(b * t, fvkv, f, Mat(query, f), Mat(wv, f), Mat(va, fvkv), trans_b=True, bias=bv)
+                D.gemm(b * t, f, f, Mat(query, f), Mat(wq, f), Mat(qa, f), trans_b=True, bias=bq, skinny_ok=True)
+                D.gemm(b * t, fkv, f, Mat(query, f), Mat(wk, f), Mat(ka, fkv), trans_b=True, bias=bk, skinny_ok=True)
+                D.gemm(b * t, fvkv, f, Mat(query, f), Mat(wv, f), Mat(va, fvkv), trans_b=True, bias=bv, skinny_ok=True)
                 q, fresh = Mat(qa, f), (Mat(ka, fkv), Mat(va, fvkv))
             cache.append(fresh[0], fresh[1], t, new_lengths)
         if ragged:
@@ -334,7 +334,7 @@ class MultiHeadAttention(layer.StatefulLayer):
             ctx = self._attend_cached(q, cache, t, causal=not cross, fresh=fresh)
         out = D.empty([b, t, f])
         D.gemm(b * t, f, h * dv, Mat(ctx, h * dv), Mat(wo, h * dv), Mat(out, f), trans_b=True, bias=bo,
-               residual=None if residual is None else Mat(residual, f))
+               residual=None if residual is None else Mat(residual, f), skinny_ok=True)
         return out
 
     def _attend_cached(self, q: Mat, cache: D.KVCache, t: int, causal: bool, fresh) -> D.DeviceArray:

@@ -396,7 +396,8 @@ class TransformerDecoder(layer.Layer):
         out = out.reshape(-1, features)
         skip = out
         h = self._norm3._forward_impl(out) if pre else out
-        out = self._dense2._forward_impl(self._dense1(h), residual=skip)
+        self._ensure(self._dense1, h)
+        out = self._dense2._forward_impl(self._dense1.forward(h, decode=True), residual=skip, decode=True)
         if not pre:
             out = self._norm3._forward_impl(out)
         return out.reshape(batch, tokens, features)
