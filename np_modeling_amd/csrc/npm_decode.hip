@@ -47,6 +47,15 @@
 // The table index is clamped to the page of key L - 1: entries past a sequence's
 // last page are not even read.  Split partition, online softmax, wave merge and the combine kernel do not know about pages, so a
 // paged call is bitwise the varlen call on a contiguous cache of the same rows.
+//
+// Row copies (the appends into a cache, the gathers out of one): two kernel templates, kv_append_kernel<VL, PG> and
+// kv_gather_kernel<PG>, over ONE description of where the rows of a cache live (RowLayout, by value) and one device helper,
+// row_of<PG>(layout, b, j), that turns (sequence, logical row) into an address -- base + b * stride + j * pitch, or through the
+// block table pool + table[b * table_pitch + (j >> shift)] * page_stride + (j & mask) * pitch.  The flags keep the five entry
+// points' code apart: the uniform append reads the scalar `at` and loads no length, the ragged and paged ones read at_lens[b] and
+// skip t >= new_lens[b], a gather writes zeros for j >= lens[b] and reads neither that row nor its table entry.  One host
+// function, row_copy, holds what the entry points share (checks, grid, launch); each entry point is its own preconditions -- the
+// paged ones refuse a NULL length array or table even when there is nothing to copy -- and one call.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -356,83 +365,52 @@ mha_decode_combine_kernel(const float *__restrict__ part_ml, const float *__rest
         lse[(b * heads + h) * tokens + t] = none ? -INFINITY : fmaf(scale, mt, (__builtin_amdgcn_logf(lt) + fmaf(-mt, c2, mt * c2)) * LN2);
 }
 
-// cache[b, at + t, :row_len] = src[b * T + t, :row_len], 16 bytes per thread and step
+// ---- row copies: the appends into a cache and the gathers out of one ------------------------------------------------------------
+// Where the rows of a cache live.  Contiguous (table == nullptr): row j of sequence b is base + b * stride + j * pitch.  Paged:
+// base is the page pool, stride the page stride and the row is row j & (page_rows - 1) of page table[b * table_pitch + (j >> shift)].
+struct RowLayout {
+    float *base;
+    long pitch, stride;
+    const int *table;
+    int table_pitch, shift;
+};
+
+template <bool PG>
+__device__ __forceinline__ float *row_of(const RowLayout &c, long b, int j) {
+    if (PG) return c.base + (long)c.table[b * c.table_pitch + (j >> c.shift)] * c.stride + (long)(j & ((1 << c.shift) - 1)) * c.pitch;
+    return c.base + b * c.stride + (long)j * c.pitch;
+}
+
+// row (at + t) of sequence b = src[b * T + t, :row_len], 16 bytes per thread and step.  VL = false (npm_kv_append): at is the scalar
+// and no length is loaded.  VL: at = at_lens[b], and only t < new_lens[b] (NULL: every t) is written; other rows are not touched.
+template <bool VL, bool PG>
 __global__ void __launch_bounds__(256)
-kv_append_kernel(const float *__restrict__ src, long src_pitch, float *__restrict__ cache, long cache_pitch, long cache_sb,
-                 int tokens, int row4, int at, long total) {
+kv_append_kernel(const float *__restrict__ src, long src_pitch, const RowLayout dst, int tokens, int row4, int at,
+                 const int *__restrict__ at_lens, const int *__restrict__ new_lens, long total) {
+    static_assert(VL || !PG, "a paged cache has per-sequence lengths");
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int col = (int)(i % row4) * 4;
         const long row = i / row4;
         const long b = row / tokens;
         const int t = (int)(row - b * tokens);
-        *reinterpret_cast<f32x4v *>(cache + b * cache_sb + (long)(at + t) * cache_pitch + col) =
+        if (VL && new_lens && t >= new_lens[b]) continue;
+        *reinterpret_cast<f32x4v *>(row_of<PG>(dst, b, (VL ? at_lens[b] : at) + t) + col) =
             *reinterpret_cast<const f32x4v *>(src + row * src_pitch + col);
     }
 }
 
-// cache[b, at_lens[b] + t, :row_len] = src[b * T + t, :row_len] for t < new_lens[b] (NULL: every t); other rows are not touched
+// out[b, j, :row_len] = j < lens[b] ? row j of sequence b : 0 for j < rows; out is [B, rows, row_len], contiguous.  Neither a row at
+// or past lens[b] nor its table entry is read.
+template <bool PG>
 __global__ void __launch_bounds__(256)
-kv_append_varlen_kernel(const float *__restrict__ src, long src_pitch, float *__restrict__ cache, long cache_pitch, long cache_sb,
-                        int tokens, int row4, const int *__restrict__ at_lens, const int *__restrict__ new_lens, long total) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int col = (int)(i % row4) * 4;
-        const long row = i / row4;
-        const long b = row / tokens;
-        const int t = (int)(row - b * tokens);
-        if (new_lens && t >= new_lens[b]) continue;
-        *reinterpret_cast<f32x4v *>(cache + b * cache_sb + (long)(at_lens[b] + t) * cache_pitch + col) =
-            *reinterpret_cast<const f32x4v *>(src + row * src_pitch + col);
-    }
-}
-
-// out[b, j, :row_len] = j < lens[b] ? cache[b, j, :row_len] : 0 for j < rows; out is [B, rows, row_len], contiguous.  Rows at and
-// past lens[b] are not read.
-__global__ void __launch_bounds__(256)
-kv_gather_varlen_kernel(const float *__restrict__ cache, long cache_pitch, long cache_sb, float *__restrict__ out, int rows,
-                        int row4, const int *__restrict__ lens, long total) {
+kv_gather_kernel(const RowLayout src, float *__restrict__ out, int rows, int row4, const int *__restrict__ lens, long total) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int col = (int)(i % row4) * 4;
         const long row = i / row4;
         const long b = row / rows;
         const int j = (int)(row - b * rows);
         f32x4v x{0.f, 0.f, 0.f, 0.f};
-        if (j < lens[b]) x = *reinterpret_cast<const f32x4v *>(cache + b * cache_sb + (long)j * cache_pitch + col);
-        *reinterpret_cast<f32x4v *>(out + row * (4L * row4) + col) = x;
-    }
-}
-
-// kv_append_varlen_kernel into a page pool: row at_lens[b] + t of sequence b through the block table
-__global__ void __launch_bounds__(256)
-kv_append_paged_kernel(const float *__restrict__ src, long src_pitch, float *__restrict__ pool, long row_pitch, long page_stride,
-                       int tokens, int row4, const int *__restrict__ at_lens, const int *__restrict__ new_lens,
-                       const int *__restrict__ table, int table_pitch, int shift, long total) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int col = (int)(i % row4) * 4;
-        const long row = i / row4;
-        const long b = row / tokens;
-        const int t = (int)(row - b * tokens);
-        if (new_lens && t >= new_lens[b]) continue;
-        const int j = at_lens[b] + t;
-        const long page = table[b * table_pitch + (j >> shift)];
-        *reinterpret_cast<f32x4v *>(pool + page * page_stride + (long)(j & ((1 << shift) - 1)) * row_pitch + col) =
-            *reinterpret_cast<const f32x4v *>(src + row * src_pitch + col);
-    }
-}
-
-// kv_gather_varlen_kernel out of a page pool.  Neither a row at or past lens[b] nor its table entry is read.
-__global__ void __launch_bounds__(256)
-kv_gather_paged_kernel(const float *__restrict__ pool, long row_pitch, long page_stride, float *__restrict__ out, int rows, int row4,
-                       const int *__restrict__ lens, const int *__restrict__ table, int table_pitch, int shift, long total) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int col = (int)(i % row4) * 4;
-        const long row = i / row4;
-        const long b = row / rows;
-        const int j = (int)(row - b * rows);
-        f32x4v x{0.f, 0.f, 0.f, 0.f};
-        if (j < lens[b]) {
-            const long page = table[b * table_pitch + (j >> shift)];
-            x = *reinterpret_cast<const f32x4v *>(pool + page * page_stride + (long)(j & ((1 << shift) - 1)) * row_pitch + col);
-        }
+        if (j < lens[b]) x = *reinterpret_cast<const f32x4v *>(row_of<PG>(src, b, j) + col);
         *reinterpret_cast<f32x4v *>(out + row * (4L * row4) + col) = x;
     }
 }
@@ -602,92 +580,89 @@ extern "C" int npm_mha_decode_fwd_paged(const npm_mha_decode *d, const int32_t *
     return decode_fwd("npm_mha_decode_fwd_paged", d, kv_lens, new_lens, block_table, table_pitch, page_rows);
 }
 
+// What the five row-copy entry points share, after NPM_REQUIRE_INIT and the preconditions that hold even for an empty call: the
+// checks, the grid and the launch.  ``rows`` [batch * count, row_len] with pitch rows_pitch is the source of an append (gather =
+// false) or the contiguous destination of a gather; ``lens``: at_lens of a ragged append (NULL: the uniform one at ``at``) or the
+// lengths of a gather; page_rows > 0: ``cache`` is paged.  An empty call is NPM_OK whatever the pointers are.
+static int row_copy(const char *name, bool gather, const float *rows, int64_t rows_pitch, const RowLayout &cache, int32_t page_rows,
+                    int32_t batch, int32_t count, int32_t row_len, bool ragged, int32_t at, const int32_t *lens,
+                    const int32_t *new_lens) {
+#define ROW_ARG(cond)                                                                                           \
+    do {                                                                                                        \
+        if (!(cond)) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: bad argument: %s", name, #cond);                \
+    } while (0)
+    ROW_ARG(batch >= 0 && count >= 0 && row_len >= 0 && at >= 0);
+    if (batch == 0 || count == 0 || row_len == 0) return NPM_OK;
+    ROW_ARG(rows != nullptr && cache.base != nullptr && (lens != nullptr || !ragged));
+    ROW_ARG(aligned16(rows) && aligned16(cache.base));
+    ROW_ARG(row_len % 4 == 0 && rows_pitch % 4 == 0 && cache.pitch % 4 == 0 && cache.stride % 4 == 0);
+    ROW_ARG(rows_pitch >= row_len && cache.pitch >= row_len && (!page_rows || cache.stride >= (int64_t)page_rows * cache.pitch));
+#undef ROW_ARG
+    const long total = (long)batch * count * (row_len / 4);
+    const dim3 grid((unsigned)std::min<long>((total + 255) / 256, 2048)), block(256);
+    hipStream_t s = npm::ctx().stream;
+    const int row4 = row_len / 4;
+    if (gather) {
+        float *out = const_cast<float *>(rows);                       // the entry point's own float *out
+        if (page_rows) hipLaunchKernelGGL(kv_gather_kernel<true>, grid, block, 0, s, cache, out, count, row4, lens, total);
+        else hipLaunchKernelGGL(kv_gather_kernel<false>, grid, block, 0, s, cache, out, count, row4, lens, total);
+    } else if (page_rows) {
+        hipLaunchKernelGGL((kv_append_kernel<true, true>), grid, block, 0, s, rows, (long)rows_pitch, cache, count, row4, at, lens, new_lens, total);
+    } else if (ragged) {
+        hipLaunchKernelGGL((kv_append_kernel<true, false>), grid, block, 0, s, rows, (long)rows_pitch, cache, count, row4, at, lens, new_lens, total);
+    } else {
+        hipLaunchKernelGGL((kv_append_kernel<false, false>), grid, block, 0, s, rows, (long)rows_pitch, cache, count, row4, at, lens, new_lens, total);
+    }
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
+}
+
+static RowLayout contiguous(const float *cache, int64_t pitch, int64_t stride_b) {
+    return RowLayout{const_cast<float *>(cache), (long)pitch, (long)stride_b, nullptr, 0, 0};
+}
+
+static RowLayout paged(const float *pool, int64_t row_pitch, int64_t page_stride, const int32_t *table, int32_t table_pitch,
+                       int32_t page_rows) {
+    return RowLayout{const_cast<float *>(pool), (long)row_pitch, (long)page_stride, table, table_pitch, page_shift(page_rows)};
+}
+
 extern "C" int npm_kv_append(const float *src, int64_t src_pitch, float *cache, int64_t cache_pitch, int64_t cache_stride_b,
                              int32_t batch, int32_t new_tokens, int32_t row_len, int32_t at) {
     NPM_REQUIRE_INIT();
-    NPM_ARG(batch >= 0 && new_tokens >= 0 && row_len >= 0 && at >= 0);
-    if (batch == 0 || new_tokens == 0 || row_len == 0) return NPM_OK;
-    NPM_ARG(src != nullptr && cache != nullptr);
-    NPM_ARG(aligned16(src) && aligned16(cache));
-    NPM_ARG(row_len % 4 == 0 && src_pitch % 4 == 0 && cache_pitch % 4 == 0 && cache_stride_b % 4 == 0);
-    NPM_ARG(src_pitch >= row_len && cache_pitch >= row_len);
-    const long total = (long)batch * new_tokens * (row_len / 4);
-    const int grid = (int)std::min<long>((total + 255) / 256, 2048);
-    hipLaunchKernelGGL(kv_append_kernel, dim3(grid), dim3(256), 0, npm::ctx().stream, src, (long)src_pitch, cache, (long)cache_pitch,
-                       (long)cache_stride_b, new_tokens, row_len / 4, at, total);
-    NPM_CHECK_LAUNCH();
-    return NPM_OK;
+    return row_copy("npm_kv_append", false, src, src_pitch, contiguous(cache, cache_pitch, cache_stride_b), 0, batch, new_tokens, row_len,
+                    false, at, nullptr, nullptr);
 }
 
 extern "C" int npm_kv_append_varlen(const float *src, int64_t src_pitch, float *cache, int64_t cache_pitch, int64_t cache_stride_b,
                                     int32_t batch, int32_t new_tokens, int32_t row_len, const int32_t *at_lens,
                                     const int32_t *new_lens) {
     NPM_REQUIRE_INIT();
-    NPM_ARG(batch >= 0 && new_tokens >= 0 && row_len >= 0);
-    if (batch == 0 || new_tokens == 0 || row_len == 0) return NPM_OK;
-    NPM_ARG(src != nullptr && cache != nullptr && at_lens != nullptr);
-    NPM_ARG(aligned16(src) && aligned16(cache));
-    NPM_ARG(row_len % 4 == 0 && src_pitch % 4 == 0 && cache_pitch % 4 == 0 && cache_stride_b % 4 == 0);
-    NPM_ARG(src_pitch >= row_len && cache_pitch >= row_len);
-    const long total = (long)batch * new_tokens * (row_len / 4);
-    const int grid = (int)std::min<long>((total + 255) / 256, 2048);
-    hipLaunchKernelGGL(kv_append_varlen_kernel, dim3(grid), dim3(256), 0, npm::ctx().stream, src, (long)src_pitch, cache,
-                       (long)cache_pitch, (long)cache_stride_b, new_tokens, row_len / 4, at_lens, new_lens, total);
-    NPM_CHECK_LAUNCH();
-    return NPM_OK;
+    return row_copy("npm_kv_append_varlen", false, src, src_pitch, contiguous(cache, cache_pitch, cache_stride_b), 0, batch, new_tokens,
+                    row_len, true, 0, at_lens, new_lens);
 }
 
 extern "C" int npm_kv_gather_varlen(const float *cache, int64_t cache_pitch, int64_t cache_stride_b, float *out, int32_t batch,
                                     int32_t rows, int32_t row_len, const int32_t *lens) {
     NPM_REQUIRE_INIT();
-    NPM_ARG(batch >= 0 && rows >= 0 && row_len >= 0);
-    if (batch == 0 || rows == 0 || row_len == 0) return NPM_OK;
-    NPM_ARG(cache != nullptr && out != nullptr && lens != nullptr);
-    NPM_ARG(aligned16(cache) && aligned16(out));
-    NPM_ARG(row_len % 4 == 0 && cache_pitch % 4 == 0 && cache_stride_b % 4 == 0 && cache_pitch >= row_len);
-    const long total = (long)batch * rows * (row_len / 4);
-    const int grid = (int)std::min<long>((total + 255) / 256, 2048);
-    hipLaunchKernelGGL(kv_gather_varlen_kernel, dim3(grid), dim3(256), 0, npm::ctx().stream, cache, (long)cache_pitch,
-                       (long)cache_stride_b, out, rows, row_len / 4, lens, total);
-    NPM_CHECK_LAUNCH();
-    return NPM_OK;
+    return row_copy("npm_kv_gather_varlen", true, out, row_len, contiguous(cache, cache_pitch, cache_stride_b), 0, batch, rows, row_len,
+                    true, 0, lens, nullptr);
 }
 
+// The paged forms refuse a NULL length array or table and a bad page size even when there is nothing to copy.
 extern "C" int npm_kv_append_paged(const float *src, int64_t src_pitch, float *pool, int64_t row_pitch, int64_t page_stride,
                                    int32_t batch, int32_t new_tokens, int32_t row_len, const int32_t *at_lens,
                                    const int32_t *new_lens, const int32_t *block_table, int32_t table_pitch, int32_t page_rows) {
     NPM_REQUIRE_INIT();
-    NPM_ARG(batch >= 0 && new_tokens >= 0 && row_len >= 0);
     NPM_ARG(at_lens != nullptr && block_table != nullptr && table_pitch >= 0 && page_shift(page_rows) >= 0);
-    if (batch == 0 || new_tokens == 0 || row_len == 0) return NPM_OK;
-    NPM_ARG(src != nullptr && pool != nullptr);
-    NPM_ARG(aligned16(src) && aligned16(pool));
-    NPM_ARG(row_len % 4 == 0 && src_pitch % 4 == 0 && row_pitch % 4 == 0 && page_stride % 4 == 0);
-    NPM_ARG(src_pitch >= row_len && row_pitch >= row_len && page_stride >= (int64_t)page_rows * row_pitch);
-    const long total = (long)batch * new_tokens * (row_len / 4);
-    const int grid = (int)std::min<long>((total + 255) / 256, 2048);
-    hipLaunchKernelGGL(kv_append_paged_kernel, dim3(grid), dim3(256), 0, npm::ctx().stream, src, (long)src_pitch, pool,
-                       (long)row_pitch, (long)page_stride, new_tokens, row_len / 4, at_lens, new_lens, block_table, table_pitch,
-                       page_shift(page_rows), total);
-    NPM_CHECK_LAUNCH();
-    return NPM_OK;
+    return row_copy("npm_kv_append_paged", false, src, src_pitch, paged(pool, row_pitch, page_stride, block_table, table_pitch, page_rows),
+                    page_rows, batch, new_tokens, row_len, true, 0, at_lens, new_lens);
 }
 
 extern "C" int npm_kv_gather_paged(const float *pool, int64_t row_pitch, int64_t page_stride, float *out, int32_t batch, int32_t rows,
                                    int32_t row_len, const int32_t *lens, const int32_t *block_table, int32_t table_pitch,
                                    int32_t page_rows) {
     NPM_REQUIRE_INIT();
-    NPM_ARG(batch >= 0 && rows >= 0 && row_len >= 0);
     NPM_ARG(lens != nullptr && block_table != nullptr && table_pitch >= 0 && page_shift(page_rows) >= 0);
-    if (batch == 0 || rows == 0 || row_len == 0) return NPM_OK;
-    NPM_ARG(pool != nullptr && out != nullptr);
-    NPM_ARG(aligned16(pool) && aligned16(out));
-    NPM_ARG(row_len % 4 == 0 && row_pitch % 4 == 0 && page_stride % 4 == 0 && row_pitch >= row_len);
-    NPM_ARG(page_stride >= (int64_t)page_rows * row_pitch);
-    const long total = (long)batch * rows * (row_len / 4);
-    const int grid = (int)std::min<long>((total + 255) / 256, 2048);
-    hipLaunchKernelGGL(kv_gather_paged_kernel, dim3(grid), dim3(256), 0, npm::ctx().stream, pool, (long)row_pitch, (long)page_stride,
-                       out, rows, row_len / 4, lens, block_table, table_pitch, page_shift(page_rows), total);
-    NPM_CHECK_LAUNCH();
-    return NPM_OK;
+    return row_copy("npm_kv_gather_paged", true, out, row_len, paged(pool, row_pitch, page_stride, block_table, table_pitch, page_rows),
+                    page_rows, batch, rows, row_len, true, 0, lens, nullptr);
 }

@@ -22,7 +22,7 @@ import heapq
 import math
 import numbers
 import os
-from typing import Optional, Sequence, Tuple, Union
+from typing import NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -1038,80 +1038,47 @@ def mha_decode_supported(head_dim: int, group_rows: int, value_dim: Optional[int
     return bool(_C.lib().npm_mha_decode_supported(int(head_dim), int(group_rows)))
 
 
-def kv_append(src: Mat, cache: DeviceArray, batch: int, tokens: int, at: int) -> None:
-    """cache[b, at + t] = src[b * tokens + t] for a cache [B, capacity, Hkv, D]; ``src``: (array, row pitch) of [B, T, Hkv * D]
-    rows, e.g. the K part of a packed projection (include/npm_hip.h npm_kv_append).  Raises ValueError before anything is
-    launched when the rows do not fit."""
-    b, capacity, hkv, d = cache.shape
-    if batch != b or at < 0 or at + tokens > capacity:
-        raise ValueError(f'appending {tokens} rows at {at} to a cache of batch {b}, capacity {capacity} (batch {batch})')
-    with _timed('kv_append', nbytes=8.0 * batch * tokens * hkv * d):
-        _C.check(_C.lib().npm_kv_append(src.ptr, src.ld, cache.ptr, hkv * d, capacity * hkv * d, batch, tokens, hkv * d, at),
-                 'npm_kv_append')
+class KVLayout(NamedTuple):
+    """Where the rows of one cache tensor live, as the entry points of include/npm_hip.h take it.  Contiguous: row j of sequence b
+    is ``pitch`` floats long at ``b * stride + j * pitch``.  Paged (``table``: the DEVICE address of the block table, int32
+    [B, table_pitch]): ``stride`` is that of a page and the row is row ``j % page_rows`` of page ``table[b, j // page_rows]``."""
+    pitch: int
+    stride: int
+    table: Optional[int] = None
+    table_pitch: int = 0
+    page_rows: int = 0
 
 
-def _decode_desc(q: Mat, k: DeviceArray, v: DeviceArray, heads: int, tokens: int, kv_len: int, scale: float, causal: bool,
-                 want_lse: bool):
-    b, capacity, hkv, d = k.shape
-    ctx = empty([b, tokens, heads, d])
-    lse = empty([b, heads, tokens]) if want_lse else None
-    c = _C.npm_mha_decode()
-    c.batch, c.heads, c.kv_heads, c.new_tokens, c.kv_len, c.head_dim = b, int(heads), hkv, int(tokens), int(kv_len), d
-    c.causal, c.scale = int(bool(causal)), float(scale)
-    c.q, c.q_pitch = q.ptr, q.ld
-    c.k, c.k_pitch, c.k_stride_b = k.ptr, hkv * d, capacity * hkv * d
-    c.v, c.v_pitch, c.v_stride_b = v.ptr, hkv * d, capacity * hkv * d
-    c.ctx, c.ctx_pitch = ctx.ptr, heads * d
-    c.lse = None if lse is None else lse.ptr
-    return c, ctx, lse
+def kv_append(src: Mat, dst: int, layout: KVLayout, batch: int, tokens: int, at: int, lens, rows: int) -> None:
+    """Row ``at + t`` of sequence b of the cache tensor at address ``dst`` = src[b * tokens + t]; ``src``: (array, row pitch) of
+    [B, T, Hkv * D] rows, e.g. the K part of a packed projection (include/npm_hip.h npm_kv_append).  ``lens`` = (at_lens,
+    new_lens), device addresses of [B] int32: sequence b starts at at_lens[b] and takes only t < new_lens[b]
+    (npm_kv_append_varlen; through the block table of a paged ``layout`` npm_kv_append_paged, which always has ``lens``).  The
+    caller has checked that the rows fit; ``rows``: the rows written, for the timer."""
+    row = layout.pitch
+    with _timed('kv_append', nbytes=8.0 * rows * row):
+        if layout.table is not None:
+            _C.check(_C.lib().npm_kv_append_paged(src.ptr, src.ld, dst, row, layout.stride, batch, tokens, row, lens[0], lens[1],
+                                                  layout.table, layout.table_pitch, layout.page_rows), 'npm_kv_append_paged')
+        elif lens is not None:
+            _C.check(_C.lib().npm_kv_append_varlen(src.ptr, src.ld, dst, row, layout.stride, batch, tokens, row, lens[0], lens[1]),
+                     'npm_kv_append_varlen')
+        else:
+            _C.check(_C.lib().npm_kv_append(src.ptr, src.ld, dst, row, layout.stride, batch, tokens, row, at), 'npm_kv_append')
 
 
-def mha_decode(q: Mat, k: DeviceArray, v: DeviceArray, heads: int, tokens: int, kv_len: int, scale: float, causal: bool,
-               want_lse: bool = False):
-    """ctx [B, T, Hq, D] (and lse [B, Hq, T] or None) of ``tokens`` query rows per sequence over the first ``kv_len`` rows of
-    the caches ``k`` / ``v`` [B, capacity, Hkv, D] (include/npm_hip.h npm_mha_decode_fwd).  ``q``: (array, row pitch)."""
-    b, capacity, hkv, d = k.shape
-    assert v.shape == k.shape and tokens <= kv_len <= capacity
-    c, ctx, lse = _decode_desc(q, k, v, heads, tokens, kv_len, scale, causal, want_lse)
-    with _timed('mha_decode', flops=4.0 * b * heads * tokens * kv_len * d, nbytes=4.0 * b * d * (2 * heads * tokens + 2 * hkv * kv_len)):
-        _C.check(_C.lib().npm_mha_decode_fwd(C.byref(c)), 'npm_mha_decode_fwd')
-    return ctx, lse
-
-
-def mha_decode_varlen(q: Mat, k: DeviceArray, v: DeviceArray, heads: int, tokens: int, kv_max: int, kv_lens: int,
-                      new_lens: Optional[int], scale: float, causal: bool, want_lse: bool = False, keys: Optional[int] = None):
-    """``mha_decode`` of a ragged batch (include/npm_hip.h npm_mha_decode_fwd_varlen): ``kv_lens`` / ``new_lens`` are DEVICE
-    addresses of [B] int32 (valid rows with the new tokens included; new tokens of the padded ``tokens``, or None for all),
-    ``kv_max`` the host's upper bound of ``kv_lens``.  Rows without a visible key come back as ctx 0, lse -inf.  ``keys``: the
-    sum of the lengths, for the timer's byte count."""
-    b, capacity, hkv, d = k.shape
-    assert v.shape == k.shape and 0 <= kv_max <= capacity
-    c, ctx, lse = _decode_desc(q, k, v, heads, tokens, kv_max, scale, causal, want_lse)
-    keys = b * kv_max if keys is None else int(keys)
-    with _timed('mha_decode', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + 2 * hkv * keys)):
-        _C.check(_C.lib().npm_mha_decode_fwd_varlen(C.byref(c), kv_lens, new_lens), 'npm_mha_decode_fwd_varlen')
-    return ctx, lse
-
-
-def kv_append_varlen(src: Mat, cache: DeviceArray, batch: int, tokens: int, at_lens: int, new_lens: Optional[int], rows: int) -> None:
-    """cache[b, at[b] + t] = src[b * tokens + t] for t < new[b] (include/npm_hip.h npm_kv_append_varlen); ``at_lens`` /
-    ``new_lens``: device addresses of [B] int32.  The caller has checked the capacity; ``rows``: the rows written, for the timer."""
-    b, capacity, hkv, d = cache.shape
-    assert batch == b
-    with _timed('kv_append', nbytes=8.0 * rows * hkv * d):
-        _C.check(_C.lib().npm_kv_append_varlen(src.ptr, src.ld, cache.ptr, hkv * d, capacity * hkv * d, batch, tokens, hkv * d,
-                                               at_lens, new_lens), 'npm_kv_append_varlen')
-
-
-def kv_gather_varlen(cache: DeviceArray, out: DeviceArray, lens: int) -> None:
-    """out[b, j] = cache[b, j] for j < lens[b], zeros behind, for ``out`` [B, rows, Hkv, D] (include/npm_hip.h
-    npm_kv_gather_varlen; one launch).  ``lens``: device address of [B] int32."""
-    b, capacity, hkv, d = cache.shape
-    rows = out.shape[1]
-    assert out.shape == (b, rows, hkv, d) and rows <= capacity
-    with _timed('kv_gather', nbytes=8.0 * b * rows * hkv * d):
-        _C.check(_C.lib().npm_kv_gather_varlen(cache.ptr, hkv * d, capacity * hkv * d, out.ptr, b, rows, hkv * d, lens),
-                 'npm_kv_gather_varlen')
+def kv_gather_rows(src: int, layout: KVLayout, out: DeviceArray, lens: int) -> None:
+    """out[b, j] = row j of sequence b of the cache tensor at ``src`` for j < lens[b], zeros behind, for ``out`` [B, rows, Hkv, D]
+    (include/npm_hip.h npm_kv_gather_varlen, or npm_kv_gather_paged for a paged ``layout``; one launch).  ``lens``: device address
+    of [B] int32."""
+    b, rows, row = out.shape[0], out.shape[1], layout.pitch
+    assert out.size == b * rows * row
+    with _timed('kv_gather', nbytes=8.0 * b * rows * row):
+        if layout.table is not None:
+            _C.check(_C.lib().npm_kv_gather_paged(src, row, layout.stride, out.ptr, b, rows, row, lens, layout.table, layout.table_pitch,
+                                                  layout.page_rows), 'npm_kv_gather_paged')
+        else:
+            _C.check(_C.lib().npm_kv_gather_varlen(src, row, layout.stride, out.ptr, b, rows, row, lens), 'npm_kv_gather_varlen')
 
 
 def kv_gather(cache: DeviceArray, out: DeviceArray, length: int) -> None:
@@ -1124,6 +1091,48 @@ def kv_gather(cache: DeviceArray, out: DeviceArray, length: int) -> None:
                  'npm_d2d')
 
 
+def _decode_desc(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, scale: float, causal: bool, want_lse: bool):
+    """The ``npm_mha_decode`` of ``tokens`` query rows per sequence over ``cache`` -- the only place that fills one -- with fresh
+    ctx [B, T, Hq, D] and lse [B, Hq, T] (or None), and the layout of ``cache.k`` (its table is that of ``cache.v`` too)."""
+    b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
+    kl, vl = cache.layout(cache.k), cache.layout(cache.v)
+    ctx = empty([b, tokens, heads, d])
+    lse = empty([b, heads, tokens]) if want_lse else None
+    c = _C.npm_mha_decode()
+    c.batch, c.heads, c.kv_heads, c.new_tokens, c.kv_len, c.head_dim = b, int(heads), hkv, int(tokens), int(kv_len), d
+    c.causal, c.scale = int(bool(causal)), float(scale)
+    c.q, c.q_pitch = q.ptr, q.ld
+    c.k, c.k_pitch, c.k_stride_b = cache.k.ptr, kl.pitch, kl.stride
+    c.v, c.v_pitch, c.v_stride_b = cache.v.ptr, vl.pitch, vl.stride
+    c.ctx, c.ctx_pitch = ctx.ptr, heads * d
+    c.lse = None if lse is None else lse.ptr
+    return c, ctx, lse, kl
+
+
+def mha_decode(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, scale: float, causal: bool, want_lse: bool = False,
+               lens=None, keys: Optional[int] = None):
+    """ctx [B, T, Hq, D] (and lse [B, Hq, T] or None) of ``tokens`` query rows per sequence over the first ``kv_len`` rows of
+    ``cache`` (include/npm_hip.h npm_mha_decode_fwd).  ``q``: (array, row pitch).
+
+    ``lens`` = (kv_lens, new_lens), DEVICE addresses of [B] int32 -- valid rows with the new tokens included; new tokens of the
+    padded ``tokens``, or None for all -- makes it the call of a ragged batch (npm_mha_decode_fwd_varlen; through the block table
+    of a paged cache npm_mha_decode_fwd_paged, bitwise the same on the same rows): ``kv_len`` is then the host's upper bound of
+    ``kv_lens`` and rows without a visible key come back as ctx 0, lse -inf.  ``keys``: the sum of the lengths, for the timer."""
+    assert cache.key_dim == cache.value_dim and 0 <= kv_len <= cache.capacity and (lens is not None or tokens <= kv_len)
+    c, ctx, lse, layout = _decode_desc(q, cache, heads, tokens, kv_len, scale, causal, want_lse)
+    b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
+    keys = b * kv_len if keys is None else int(keys)
+    with _timed('mha_decode', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + 2 * hkv * keys)):
+        if layout.table is not None:
+            _C.check(_C.lib().npm_mha_decode_fwd_paged(C.byref(c), lens[0], lens[1], layout.table, layout.table_pitch, layout.page_rows),
+                     'npm_mha_decode_fwd_paged')
+        elif lens is not None:
+            _C.check(_C.lib().npm_mha_decode_fwd_varlen(C.byref(c), lens[0], lens[1]), 'npm_mha_decode_fwd_varlen')
+        else:
+            _C.check(_C.lib().npm_mha_decode_fwd(C.byref(c)), 'npm_mha_decode_fwd')
+    return ctx, lse
+
+
 class KVCache:
     """Keys and values of the tokens seen so far: ``k`` [B, capacity, Hkv, Dk] and ``v`` [B, capacity, Hkv, Dv] on the device,
     of which the first ``lengths[b]`` rows of sequence b are valid.  Rows at and past that hold whatever was there; nothing reads
@@ -1134,7 +1143,12 @@ class KVCache:
     one (npm_kv_append / npm_mha_decode_fwd).  ``new_lengths`` (per-sequence counts n[b] <= tokens of a right-padded chunk) makes
     it *ragged*: ``length`` then raises, ``max_length`` is the largest, and the kernels read the lengths from a device int32
     mirror, uploaded once per ragged call ([3, B] int32 -- rows before, new rows, rows after -- shared by the append and the
-    attention that follows it)."""
+    attention that follows it).
+
+    ``append``, ``attend`` and ``gather`` are written once, here: where the rows live is ``layout(x)``, which the wrappers above
+    turn into the entry point.  ``paged``: whether that is a page pool (``PagedKVCache``)."""
+
+    paged = False
 
     def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None):
         value_dim = key_dim if value_dim is None else value_dim
@@ -1147,6 +1161,11 @@ class KVCache:
         self.lengths = np.zeros([self.batch], dtype=np.int64)
         self._mirror = None               # (host int32 [3, B]: before, new, after; ByteBuffer) of the last ragged call
         self.frozen = False
+
+    def layout(self, x: DeviceArray) -> KVLayout:
+        """Where the rows of ``x`` (``k`` or ``v``) live."""
+        row = self.kv_heads * x.shape[3]
+        return KVLayout(row, self.capacity * row)
 
     @property
     def ragged(self) -> bool:
@@ -1183,15 +1202,24 @@ class KVCache:
             raise ValueError(f'new_lengths must be {self.batch} integers in 0 .. {tokens}, got {np.asarray(new_lengths).tolist()}')
         return None if (n == tokens).all() else n.astype(np.int64)
 
+    def _counts(self, tokens: int, n: Optional[np.ndarray]) -> np.ndarray:
+        """The rows every sequence brings, int64 [B]: ``n`` as ``new_lengths()`` returned it, with its None spelled out."""
+        return np.full([self.batch], tokens, dtype=np.int64) if n is None else n
+
+    def _scalar_call(self, n: Optional[np.ndarray]) -> bool:
+        """Whether a call bringing ``n`` (of ``new_lengths()``) is the scalar one: a contiguous cache, uniform before and after."""
+        return n is None and not (self.paged or self.ragged)
+
     def room(self, tokens: int, new_lengths=None) -> None:
         """ValueError when ``tokens`` (or ``new_lengths[b]``) more rows do not fit ANY sequence -- checked before anything is
         launched."""
         n = self.new_lengths(tokens, new_lengths)
-        if n is None:
-            n = np.full([self.batch], tokens, dtype=np.int64)
-        if tokens < 0 or (self.lengths + n > self.capacity).any():
-            raise ValueError(f'KVCache: {n.tolist() if new_lengths is not None else tokens} new rows after '
+        if tokens < 0 or (self.lengths + (tokens if n is None else n) > self.capacity).any():
+            raise ValueError(f'KVCache: {self._counts(tokens, n).tolist() if new_lengths is not None else tokens} new rows after '
                              f'{self.lengths.tolist() if self.ragged else int(self.lengths[0])} do not fit the capacity {self.capacity}')
+
+    def _allocate(self, n: np.ndarray) -> None:
+        """What a ragged ``append`` does between its checks and its launches so that n[b] more rows have a place: nothing here."""
 
     def _device_lengths(self, before: np.ndarray, n: np.ndarray):
         """Device addresses of (before, n, before + n) as int32 [B] each; one upload unless the last one holds the same numbers."""
@@ -1201,6 +1229,13 @@ class KVCache:
         ptr = self._mirror[1].ptr
         return ptr, ptr + 4 * self.batch, ptr + 8 * self.batch
 
+    def _current_lengths(self) -> int:
+        """Device address of ``lengths`` as int32 [B]: the last row of the mirror when the last ragged call left them there (an
+        append of this forward did), else one upload."""
+        if self._mirror is None or not np.array_equal(self._mirror[0][2], self.lengths):
+            self._device_lengths(self.lengths, np.zeros([self.batch], dtype=np.int64))
+        return self._mirror[1].ptr + 8 * self.batch
+
     def append(self, k: Mat, v: Mat, tokens: int, new_lengths=None) -> None:
         """``tokens`` freshly projected rows per sequence ([B, T, Hkv * D] with a row pitch each) behind the valid ones; with
         ``new_lengths`` only the first n[b] of them, behind sequence b's own ``lengths[b]`` rows."""
@@ -1208,96 +1243,58 @@ class KVCache:
         if self.frozen:
             raise ValueError('KVCache: this cache was filled for cross-attention and is frozen; reset() it first')
         n = self.new_lengths(tokens, new_lengths)
-        if n is None and not self.ragged:
-            at = self.length
-            kv_append(k, self.k, self.batch, tokens, at)
-            kv_append(v, self.v, self.batch, tokens, at)
-            self.lengths = self.lengths + tokens
-            return
-        if n is None:
-            n = np.full([self.batch], tokens, dtype=np.int64)
-        at_ptr, new_ptr, _ = self._device_lengths(self.lengths, n)
-        kv_append_varlen(k, self.k, self.batch, tokens, at_ptr, new_ptr, int(n.sum()))
-        kv_append_varlen(v, self.v, self.batch, tokens, at_ptr, new_ptr, int(n.sum()))
+        if self._scalar_call(n):
+            n, at, lens, rows = tokens, int(self.lengths[0]), None, self.batch * tokens
+        else:
+            n = self._counts(tokens, n)
+            self._allocate(n)
+            at, lens, rows = 0, self._device_lengths(self.lengths, n)[:2], int(n.sum())
+        for src, dst in ((k, self.k), (v, self.v)):
+            kv_append(src, dst.ptr, self.layout(dst), self.batch, tokens, at, lens, rows)
         self.lengths = self.lengths + n
 
+    def write_slot(self, b: int, k: Optional[Mat], v: Optional[Mat], rows: int) -> None:
+        """Sequence ``b`` is replaced: its rows 0 .. rows - 1 are the ``rows`` rows of ``k`` / ``v`` ([rows, Hkv * D] with a row
+        pitch each) and ``lengths[b] = rows``; the other sequences are not touched (npm_kv_append on slot b alone).  ``k`` or ``v``
+        None: that tensor is written by another call (``TransformerDecoder.admit`` projects and writes one after the other)."""
+        b, rows = int(b), int(rows)
+        if not 0 <= b < self.batch:
+            raise IndexError(f'KVCache.write_slot: no sequence {b} in a batch of {self.batch}')
+        if not 0 <= rows <= self.capacity:
+            raise ValueError(f'KVCache.write_slot: {rows} rows do not fit the capacity {self.capacity}')
+        for src, dst in ((k, self.k), (v, self.v)):
+            if src is not None:
+                layout = self.layout(dst)
+                kv_append(src, dst.ptr + 4 * b * layout.stride, layout, 1, rows, 0, None, rows)
+        self.lengths[b] = rows
+
     def attend(self, q: Mat, heads: int, tokens: int, scale: float, causal: bool, want_lse: bool = False, new_lengths=None):
-        """``mha_decode`` of ``tokens`` query rows per sequence over the valid rows; with ``new_lengths`` (or a ragged cache)
-        ``mha_decode_varlen``: rows t >= n[b] are padding and come back as zeros.  ``causal``: the n[b] new tokens are the last
+        """``mha_decode`` of ``tokens`` query rows per sequence over the valid rows; with ``new_lengths`` (or a ragged or paged
+        cache) its ragged call: rows t >= n[b] are padding and come back as zeros.  ``causal``: the n[b] new tokens are the last
         n[b] valid rows of sequence b (they were appended first)."""
-        assert self.key_dim == self.value_dim
         n = self.new_lengths(tokens, new_lengths)
-        if n is None and not self.ragged:
-            return mha_decode(q, self.k, self.v, heads, tokens, self.length, scale, causal, want_lse)
-        if n is None:
-            n = np.full([self.batch], tokens, dtype=np.int64)
+        if self._scalar_call(n):
+            return mha_decode(q, self, heads, tokens, int(self.lengths[0]), scale, causal, want_lse)
+        n = self._counts(tokens, n)
         if causal and (n > self.lengths).any():
             raise ValueError(f'KVCache.attend: {n.tolist()} new tokens are not among the {self.lengths.tolist()} valid rows')
         _, new_ptr, kv_ptr = self._device_lengths(self.lengths - n, n)
-        return mha_decode_varlen(q, self.k, self.v, heads, tokens, self.max_length, kv_ptr, new_ptr, scale, causal, want_lse,
-                                 keys=int(self.lengths.sum()))
+        return mha_decode(q, self, heads, tokens, self.max_length, scale, causal, want_lse, lens=(kv_ptr, new_ptr),
+                          keys=int(self.lengths.sum()))
 
     def gather(self, rows: int):
-        """(k, v) [B, rows, Hkv, D]: the valid rows of every sequence, zeros behind them (``kv_gather_varlen``)."""
-        if self._mirror is not None and np.array_equal(self._mirror[0][2], self.lengths):      # this call's append uploaded them
-            kv_ptr = self._mirror[1].ptr + 8 * self.batch
-        else:
-            kv_ptr = self._device_lengths(self.lengths, np.zeros([self.batch], dtype=np.int64))[2]
+        """(k, v) [B, rows, Hkv, D]: the valid rows of every sequence made contiguous, zeros behind them (``kv_gather_rows``)."""
+        assert rows <= self.capacity
+        lens = self._current_lengths()
         out = []
         for x in (self.k, self.v):
             y = empty([self.batch, rows, self.kv_heads, x.shape[3]])
-            kv_gather_varlen(x, y, kv_ptr)
+            kv_gather_rows(x.ptr, self.layout(x), y, lens)
             out.append(y)
         return out
 
 
 # ---- paged key / value cache ---------------------------------------------------------------------------------------------------
-def mha_decode_paged(q: Mat, k: DeviceArray, v: DeviceArray, batch: int, heads: int, tokens: int, kv_max: int, kv_lens: int,
-                     new_lens: Optional[int], table: int, table_pitch: int, scale: float, causal: bool, want_lse: bool = False,
-                     keys: Optional[int] = None):
-    """``mha_decode_varlen`` over page pools ``k`` / ``v`` [pages, page_rows, Hkv, D] (include/npm_hip.h npm_mha_decode_fwd_paged):
-    ``table`` is the DEVICE address of the block table, int32 [batch, table_pitch]; key j of sequence b is row j % page_rows of
-    page table[b, j // page_rows].  Bitwise ``mha_decode_varlen`` on a contiguous cache holding the same rows."""
-    pages, page_rows, hkv, d = k.shape
-    assert v.shape == k.shape and 0 <= kv_max <= table_pitch * page_rows
-    ctx = empty([batch, tokens, heads, d])
-    lse = empty([batch, heads, tokens]) if want_lse else None
-    c = _C.npm_mha_decode()
-    c.batch, c.heads, c.kv_heads, c.new_tokens, c.kv_len, c.head_dim = int(batch), int(heads), hkv, int(tokens), int(kv_max), d
-    c.causal, c.scale = int(bool(causal)), float(scale)
-    c.q, c.q_pitch = q.ptr, q.ld
-    c.k, c.k_pitch, c.k_stride_b = k.ptr, hkv * d, page_rows * hkv * d
-    c.v, c.v_pitch, c.v_stride_b = v.ptr, hkv * d, page_rows * hkv * d
-    c.ctx, c.ctx_pitch = ctx.ptr, heads * d
-    c.lse = None if lse is None else lse.ptr
-    keys = batch * kv_max if keys is None else int(keys)
-    with _timed('mha_decode', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * batch * heads * tokens + 2 * hkv * keys)):
-        _C.check(_C.lib().npm_mha_decode_fwd_paged(C.byref(c), kv_lens, new_lens, table, int(table_pitch), page_rows),
-                 'npm_mha_decode_fwd_paged')
-    return ctx, lse
-
-
-def kv_append_paged(src: Mat, pool: DeviceArray, batch: int, tokens: int, at_lens: int, new_lens: Optional[int], table: int,
-                    table_pitch: int, rows: int) -> None:
-    """Row at[b] + t of sequence b, through the block table, = src[b * tokens + t] for t < new[b] (include/npm_hip.h
-    npm_kv_append_paged).  The caller has allocated the pages; ``rows``: the rows written, for the timer."""
-    pages, page_rows, hkv, d = pool.shape
-    with _timed('kv_append', nbytes=8.0 * rows * hkv * d):
-        _C.check(_C.lib().npm_kv_append_paged(src.ptr, src.ld, pool.ptr, hkv * d, page_rows * hkv * d, batch, tokens, hkv * d,
-                                              at_lens, new_lens, table, int(table_pitch), page_rows), 'npm_kv_append_paged')
-
-
-def kv_gather_paged(pool: DeviceArray, out: DeviceArray, lens: int, table: int, table_pitch: int) -> None:
-    """out[b, j] = row j of sequence b for j < lens[b], zeros behind, for ``out`` [B, rows, Hkv, D] (include/npm_hip.h
-    npm_kv_gather_paged; one launch)."""
-    pages, page_rows, hkv, d = pool.shape
-    b, rows = out.shape[:2]
-    assert out.shape == (b, rows, hkv, d) and rows <= table_pitch * page_rows
-    with _timed('kv_gather', nbytes=8.0 * b * rows * hkv * d):
-        _C.check(_C.lib().npm_kv_gather_paged(pool.ptr, hkv * d, page_rows * hkv * d, out.ptr, b, rows, hkv * d, lens, table,
-                                              int(table_pitch), page_rows), 'npm_kv_gather_paged')
-
-
 class PagedKVCache(KVCache):
     """``KVCache`` whose rows live in a pool of pages: ``k`` [pages, page_size, Hkv, Dk] and ``v`` [pages, page_size, Hkv, Dv] on
     the device, and ``block_table`` (host int32 [B, ceil(capacity / page_size)], -1 = none) naming the page of every
@@ -1309,7 +1306,12 @@ class PagedKVCache(KVCache):
     which cannot run out).  ``page_size``: a power of two >= 16 (the decode kernel's key tile: a tile never straddles a page).
     Host state is authoritative, as ``lengths`` is; the device mirror of the table is uploaded only when the table changed
     (``table_uploads`` counts them).  Every call is the paged one (npm_kv_append_paged / npm_mha_decode_fwd_paged /
-    npm_kv_gather_paged), uniform lengths included: it is bitwise the uniform entry point."""
+    npm_kv_gather_paged), uniform lengths included: it is bitwise the uniform entry point.
+
+    Its own: the pool and the table (``layout``), the page accounting ``append`` calls on (``room``, ``_allocate``) and
+    ``release``; ``append``, ``attend`` and ``gather`` are ``KVCache``'s."""
+
+    paged = True
 
     def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None, *, page_size: int,
                  pages: Optional[int] = None):
@@ -1329,14 +1331,16 @@ class PagedKVCache(KVCache):
         self.k = empty([self.pages, page_size, kv_heads, key_dim])
         self.v = empty([self.pages, page_size, kv_heads, value_dim])
         self.table_uploads = 0
-        self.frozen = False
-        self._release_all()
+        self.reset()
 
-    def _release_all(self) -> None:
-        self.lengths = np.zeros([self.batch], dtype=np.int64)
+    def layout(self, x: DeviceArray) -> KVLayout:
+        row = self.kv_heads * x.shape[3]
+        return KVLayout(row, self.page_size * row, self._device_table(), self.pages_per_sequence, self.page_size)
+
+    def reset(self) -> None:
+        KVCache.reset(self)
         self.block_table = np.full([self.batch, self.pages_per_sequence], -1, dtype=np.int32)
         self._free = list(range(self.pages))          # a heap: the lowest-numbered free page first
-        self._mirror = None
         self._table_dev = None                        # ByteBuffer of the table as the device last saw it
         self._table_dirty = True
 
@@ -1356,10 +1360,6 @@ class PagedKVCache(KVCache):
     def length(self, value: int) -> None:
         raise ValueError('PagedKVCache.length cannot be assigned: rows need pages (append), and release(b) returns them')
 
-    def reset(self) -> None:
-        self._release_all()
-        self.frozen = False
-
     def _pages_needed(self, n: np.ndarray) -> np.ndarray:
         """Pages every sequence lacks for n[b] more rows."""
         size = self.page_size
@@ -1369,9 +1369,7 @@ class PagedKVCache(KVCache):
         """``KVCache.room``, and ValueError when the new rows need more pages than are free -- before anything is launched, with
         lengths, table and free list as they were."""
         KVCache.room(self, tokens, new_lengths)
-        n = self.new_lengths(tokens, new_lengths)
-        if n is None:
-            n = np.full([self.batch], tokens, dtype=np.int64)
+        n = self._counts(tokens, self.new_lengths(tokens, new_lengths))
         need = int(self._pages_needed(n).sum())
         if need > self.pages_free:
             raise ValueError(f'PagedKVCache: {n.tolist()} new rows after {self.lengths.tolist()} need {need} more pages of '
@@ -1406,41 +1404,5 @@ class PagedKVCache(KVCache):
             self.lengths[i] = 0
             self._table_dirty = True
 
-    def append(self, k: Mat, v: Mat, tokens: int, new_lengths=None) -> None:
-        self.room(tokens, new_lengths)
-        if self.frozen:
-            raise ValueError('KVCache: this cache was filled for cross-attention and is frozen; reset() it first')
-        n = self.new_lengths(tokens, new_lengths)
-        if n is None:
-            n = np.full([self.batch], tokens, dtype=np.int64)
-        self._allocate(n)
-        at_ptr, new_ptr, _ = self._device_lengths(self.lengths, n)
-        table = self._device_table()
-        for src, pool in ((k, self.k), (v, self.v)):
-            kv_append_paged(src, pool, self.batch, tokens, at_ptr, new_ptr, table, self.pages_per_sequence, int(n.sum()))
-        self.lengths = self.lengths + n
-
-    def attend(self, q: Mat, heads: int, tokens: int, scale: float, causal: bool, want_lse: bool = False, new_lengths=None):
-        assert self.key_dim == self.value_dim
-        n = self.new_lengths(tokens, new_lengths)
-        if n is None:
-            n = np.full([self.batch], tokens, dtype=np.int64)
-        if causal and (n > self.lengths).any():
-            raise ValueError(f'KVCache.attend: {n.tolist()} new tokens are not among the {self.lengths.tolist()} valid rows')
-        _, new_ptr, kv_ptr = self._device_lengths(self.lengths - n, n)
-        return mha_decode_paged(q, self.k, self.v, self.batch, heads, tokens, self.max_length, kv_ptr, new_ptr, self._device_table(),
-                                self.pages_per_sequence, scale, causal, want_lse, keys=int(self.lengths.sum()))
-
-    def gather(self, rows: int):
-        """(k, v) [B, rows, Hkv, D]: the valid rows of every sequence made contiguous, zeros behind them (``kv_gather_paged``)."""
-        if self._mirror is not None and np.array_equal(self._mirror[0][2], self.lengths):      # this call's append uploaded them
-            kv_ptr = self._mirror[1].ptr + 8 * self.batch
-        else:
-            kv_ptr = self._device_lengths(self.lengths, np.zeros([self.batch], dtype=np.int64))[2]
-        out = []
-        for x in (self.k, self.v):
-            y = empty([self.batch, rows, self.kv_heads, x.shape[3]])
-            kv_gather_paged(x, y, kv_ptr, self._device_table(), self.pages_per_sequence)
-            out.append(y)
-        return out
-
+    def write_slot(self, b: int, k: Optional[Mat], v: Optional[Mat], rows: int) -> None:
+        raise NotImplementedError('PagedKVCache.write_slot: a released slot is filled by the ragged append, which hands out its pages')

@@ -294,7 +294,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         new_lengths = cache.new_lengths(t, new_lengths)                  # None when it says what T says
         # a paged cache has no [B, capacity, Hkv, D] tensor to hand to the uniform paths: it always takes the per-sequence route,
         # whose kernels read through the block table (uniform lengths are bitwise the uniform entry point there)
-        ragged = new_lengths is not None or cache.ragged or isinstance(cache, D.PagedKVCache)
+        ragged = new_lengths is not None or cache.ragged or cache.paged
         if ragged and not (D.mha_decode_supported(dk, h // hkv * t, dv) or D.mha_core_supported(dk, dv, any_math=True)):
             raise NotImplementedError('per-sequence lengths need head sizes Dk == Dv in {16, 32, 64, 128} (the decode kernel or '
                                       'the fused masked forward); the GEMM composition has no masked softmax')

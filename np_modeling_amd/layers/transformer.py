@@ -360,13 +360,15 @@ class TransformerDecoder(layer.Layer):
         if rows > cross.capacity:
             raise ValueError(f'admit: {rows} memory rows do not fit the cross-attention cache of {cross.capacity} rows '
                              '(start_decoding(..., memory_capacity=))')
-        hkv, dk, dv = cross.kv_heads, cross.key_dim, cross.value_dim
-        for w, bias, dim, pool in (('_wk', '_bk', dk, cross.k), ('_wv', '_bv', dv, cross.v)):
+        hkv = cross.kv_heads
+
+        def project(w, bias, dim):
             proj = D.empty([1, rows, hkv, dim])
             D.gemm(rows, hkv * dim, f, D.Mat(kv_b, f), D.Mat(ca._param(w), f), D.Mat(proj, hkv * dim), trans_b=True, bias=ca._param(bias))
-            slot = pool.flat_view(b * cross.capacity * hkv * dim, [1, cross.capacity, hkv, dim])
-            D.kv_append(D.Mat(proj, hkv * dim), slot, 1, rows, 0)
-        cross.lengths[b] = rows
+            return D.Mat(proj, hkv * dim)
+
+        cross.write_slot(b, project('_wk', '_bk', cross.key_dim), None, rows)     # K is projected and written, then V
+        cross.write_slot(b, None, project('_wv', '_bv', cross.value_dim), rows)
 
     def decode(self, q_new, state: 'DecodeState', new_lengths=None):
         """One incremental step: the T new tokens ``q_new`` [B, T, F] through cached causal self-attention, cross-attention over
@@ -501,7 +503,7 @@ class DecodeState:
     def release(self, b) -> None:
         """Sequence ``b`` (an index or several) has finished: its self-attention pages go back to the pool and both caches hold
         0 rows of it.  It then rides along with ``new_lengths[b] = 0`` until ``TransformerDecoder.admit`` fills the slot."""
-        if not isinstance(self.self_cache, D.PagedKVCache):
+        if not self.self_cache.paged:
             raise ValueError('DecodeState.release: the self-attention cache is not paged (start_decoding(..., page_size=))')
         self.self_cache.release(b)
         self.cross_cache.lengths[np.unique(np.atleast_1d(np.asarray(b, dtype=np.int64)))] = 0

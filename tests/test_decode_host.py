@@ -163,6 +163,39 @@ def test_cache_bookkeeping_overflow_and_reset(npm):
         D.KVCache(2, 0, 3, 16)
 
 
+def test_write_slot_replaces_one_sequence(npm):
+    D = npm.device
+    b, cap, hkv, d, length = 3, 8, 2, 16, 6
+    row = hkv * d
+    rng = np.random.default_rng(0)
+    cache = D.KVCache(b, cap, hkv, d)
+    for x in (cache.k, cache.v):                                          # rows past the lengths included: they must stay too
+        x.set(rng.standard_normal([b, cap, hkv, d]).astype(np.float32))
+    filled = D.from_host(rng.standard_normal([b, length, row]).astype(np.float32))
+    cache.append(D.Mat(filled, row), D.Mat(filled, row), length)
+    before_k, before_v = np.asarray(cache.k).copy(), np.asarray(cache.v).copy()
+    new_k, new_v = (rng.standard_normal([5, row + 4]).astype(np.float32) for _ in range(2))   # a row pitch larger than the row
+    calls = len(npm.sim.calls)
+    cache.write_slot(1, D.Mat(D.from_host(new_k), row + 4), D.Mat(D.from_host(new_v), row + 4), 5)
+    assert npm.sim.calls[calls:] == ['npm_kv_append', 'npm_kv_append']
+    assert cache.lengths.tolist() == [length, 5, length] and cache.ragged
+    got_k, got_v = np.asarray(cache.k), np.asarray(cache.v)
+    assert np.array_equal(got_k[1, :5].reshape(5, row), new_k[:, :row]) and np.array_equal(got_v[1, :5].reshape(5, row), new_v[:, :row])
+    for i in (0, 2):
+        assert np.array_equal(got_k[i].view(np.uint32), before_k[i].view(np.uint32))
+        assert np.array_equal(got_v[i].view(np.uint32), before_v[i].view(np.uint32))
+    assert np.array_equal(got_k[1, 5:].view(np.uint32), before_k[1, 5:].view(np.uint32))    # nor a row behind the new ones
+    calls = len(npm.sim.calls)
+    too_many = D.Mat(D.from_host(np.zeros([cap + 1, row], dtype=np.float32)), row)
+    with pytest.raises(ValueError):
+        cache.write_slot(1, too_many, too_many, cap + 1)
+    with pytest.raises(IndexError):
+        cache.write_slot(3, too_many, too_many, 1)
+    assert len(npm.sim.calls) == calls and cache.lengths.tolist() == [length, 5, length]
+    with pytest.raises(NotImplementedError):
+        D.PagedKVCache(b, cap, hkv, d, page_size=16).write_slot(1, too_many, too_many, 1)
+
+
 @pytest.mark.parametrize('heads,kv_heads,f', [(4, 4, 64), (8, 2, 128), (4, 1, 64)])
 def test_layer_with_cache_equals_the_full_causal_forward(npm, heads, kv_heads, f):
     att, p = DC.make_mha(npm, f, heads, kv_heads, seed=heads)

@@ -19,15 +19,15 @@ import numpy as np
 import pytest
 
 import attn_range_data as R
+import decode_gpu
 import decode_reference as DR
 import gqa_reference as G
+from decode_gpu import GUARD, NT_KNOB, SENTINEL, SPLITS_KNOB
+from decode_gpu import guarded as _guarded, layer_close as _layer_close
 from oracle import np_oracle as O
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
-SENTINEL = 777.0
-SPLITS_KNOB, NT_KNOB = 20, 21
 HEAD_DIMS = (16, 32, 64, 128)
 HEADS = ((8, 8), (8, 4), (8, 2), (8, 1), (6, 3), (1, 1))
 TOKENS = (1, 2, 5, 16)
@@ -47,9 +47,7 @@ def npm():
 @pytest.fixture(autouse=True)
 def _defaults_afterwards(npm):
     yield
-    from np_modeling_amd import _C
-    for knob in (SPLITS_KNOB, NT_KNOB):
-        _C.check(_C.lib().npm_set_tuning(knob, 0), 'npm_set_tuning')
+    decode_gpu.reset_knobs()
 
 
 def _set_splits(mode, length):
@@ -59,11 +57,6 @@ def _set_splits(mode, length):
     value = {'one': 1, 'auto': 0, 'many': min(tiles + 3, 1024)}.get(mode, mode)
     _C.check(_C.lib().npm_set_tuning(SPLITS_KNOB, int(value)), 'npm_set_tuning')
     return int(value) or None
-
-
-def _guarded(arr, n):
-    np.testing.assert_array_equal(arr.flat_view(n, [arr.size - n]).numpy(), SENTINEL)
-    return arr.flat_view(0, [n]).numpy()
 
 
 def _run(q, k, v, length, scale, causal, packed=False, want_lse=True, expect=0):
@@ -286,14 +279,6 @@ def test_kv_append_rejects_misaligned_arguments(npm):
 # the bound tests/test_gpu_gqa.py and tests/test_gpu_attn.py hold the layer's forward to.  Comparing two float32 evaluations
 # (the cached path and the fused forward on the whole sequence) allows the sum of the two.
 LAYER_TOL = 1e-5
-
-
-def _layer_close(got, want, tol, what):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape and np.isfinite(got).all(), what
-    frac = float((np.abs(got - want) / (tol * (np.abs(want) + max(np.abs(want).max(), 1.0)))).max())
-    print(f'{what}: {frac:.3f} of {tol:.1e} (|ref| + max |ref|)')
-    assert frac <= 1.0, f'{what}: {frac:.3g} of the bound {tol:.3g}'
 
 
 @pytest.mark.parametrize('heads,kv_heads,f', [(8, 8, 1024), (8, 2, 1024), (8, 1, 512), (4, 4, 64), (6, 3, 192), (4, 2, 48)])

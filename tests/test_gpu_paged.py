@@ -17,21 +17,19 @@ a fault -- every table entry is in range.  Guard regions keep their sentinel.
 Every test names an entry point, class or keyword that does not exist without this feature.
 """
 
-import ctypes as C
-
 import numpy as np
 import pytest
 
-import attn_range_data as R
 import decode_cases as DC
+import decode_gpu
 import paged_cases as PC
 import varlen_reference as VR
+from decode_gpu import GUARD, NT_KNOB, SENTINEL
+from decode_gpu import check as _check, data as _data, guarded as _guarded, ints as _ints, layer_close as _layer_close
+from decode_gpu import poison as _poison, run as _run, set_splits as _set_splits
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
-SENTINEL = 777.0
-SPLITS_KNOB, NT_KNOB = 20, 21
 LAYER_TOL = 1e-5
 BAD = 10002
 
@@ -45,122 +43,7 @@ def npm():
 @pytest.fixture(autouse=True)
 def _defaults_afterwards(npm):
     yield
-    from np_modeling_amd import _C
-    for knob in (SPLITS_KNOB, NT_KNOB):
-        _C.check(_C.lib().npm_set_tuning(knob, 0), 'npm_set_tuning')
-
-
-def _set_splits(mode, lmax):
-    from np_modeling_amd import _C
-    tiles = (lmax + 15) // 16
-    value = {'one': 1, 'auto': 0, 'many': min(tiles + 3, 1024)}.get(mode, mode)
-    _C.check(_C.lib().npm_set_tuning(SPLITS_KNOB, int(value)), 'npm_set_tuning')
-    return int(value) or None
-
-
-def _guarded(arr, n):
-    np.testing.assert_array_equal(arr.flat_view(n, [arr.size - n]).numpy(), SENTINEL)
-    return arr.flat_view(0, [n]).numpy()
-
-
-def _ints(values):
-    from np_modeling_amd import device as D
-    return D.bytes_from_host(np.ascontiguousarray(np.asarray(values, dtype=np.int32)))
-
-
-def _pad_rows(x, packed):
-    """[..., rows, Hkv, D] -> [..., rows, Hkv * D (+ 4 floats of NaN padding)], and the row pitch."""
-    hkv, d = x.shape[-2:]
-    flat = x.reshape(x.shape[:-2] + (hkv * d,))
-    if not packed:
-        return np.ascontiguousarray(flat), hkv * d
-    out = np.full(flat.shape[:-1] + (hkv * d + 4,), np.nan, dtype=np.float32)
-    out[..., :hkv * d] = flat
-    return out, hkv * d + 4
-
-
-def _run(q, k, v, lmax, scale, causal, kv_lens=None, new_lens=None, packed=False, paged=None, expect=0, null_lens=False,
-         null_table=False):
-    """q [B, T, Hq, D]; k / v [B, capacity, Hkv, D] (contiguous) or, with ``paged = (table [B, P], page_rows)``, page pools
-    [pages, page_rows, Hkv, D] -> ctx, lse, kernel string.  ``kv_lens`` None: npm_mha_decode_fwd at kv_len = lmax; else the varlen or
-    the paged entry point with d->kv_len = lmax.  ``packed``: q sits in a [B, T, Hq + 2 Hkv, D] buffer and the cache rows carry 4
-    floats of padding (NaN in both)."""
-    from np_modeling_amd import _C, device as D
-    b, t, hq, d = q.shape
-    rows, hkv = k.shape[1], k.shape[2]
-    if packed:
-        qp = hq * d + 2 * hkv * d
-        qbuf = np.full([b, t, qp], np.nan, dtype=np.float32)
-        qbuf[:, :, :hq * d] = q.reshape(b, t, hq * d)
-    else:
-        qp, qbuf = hq * d, q
-    kbuf, kp = _pad_rows(k, packed)
-    vbuf, _ = _pad_rows(v, packed)
-    qd, kd, vd = D.from_host(qbuf), D.from_host(kbuf), D.from_host(vbuf)
-    ctx = D.full([b * t * hq * d + GUARD], SENTINEL)
-    lse = D.full([b * hq * t + GUARD], SENTINEL)
-    c = _C.npm_mha_decode()
-    c.batch, c.heads, c.kv_heads, c.new_tokens, c.kv_len, c.head_dim = b, hq, hkv, t, lmax, d
-    c.causal, c.scale = int(causal), scale
-    c.q, c.q_pitch = qd.ptr, qp
-    c.k, c.k_pitch, c.k_stride_b = kd.ptr, kp, rows * kp
-    c.v, c.v_pitch, c.v_stride_b = vd.ptr, kp, rows * kp
-    c.ctx, c.ctx_pitch, c.lse = ctx.ptr, hq * d, lse.ptr
-    lens = None if null_lens or kv_lens is None else _ints(kv_lens)
-    new = None if new_lens is None else _ints(new_lens)
-    lens_ptr, new_ptr = (None if x is None else x.ptr for x in (lens, new))
-    if paged is not None:
-        table, page_rows = paged
-        assert table.min() >= 0 and table.max() < k.shape[0], 'every table entry must name a page of the pool'
-        table_dev = _ints(table)
-        rc = _C.lib().npm_mha_decode_fwd_paged(C.byref(c), lens_ptr, new_ptr, None if null_table else table_dev.ptr, table.shape[1],
-                                               page_rows)
-    elif kv_lens is None:
-        rc = _C.lib().npm_mha_decode_fwd(C.byref(c))
-    else:
-        rc = _C.lib().npm_mha_decode_fwd_varlen(C.byref(c), lens_ptr, new_ptr)
-    if expect:
-        assert rc == expect, (rc, _C.lib().npm_last_error())
-        np.testing.assert_array_equal(ctx.numpy(), SENTINEL)              # nothing was launched
-        return None
-    _C.check(rc, 'npm_mha_decode_fwd[_varlen|_paged]')
-    return _guarded(ctx, b * t * hq * d).reshape(b, t, hq, d), _guarded(lse, b * hq * t).reshape(b, hq, t), _C.last_decode_kernel()
-
-
-def _check(got_ctx, got_lse, q, k, v, kv_lens, new_lens, scale, causal, what):
-    """tests/test_gpu_varlen.py's check, restated: every valid element against float64 of its sequence alone at tol(X) of that
-    sequence; rows without a visible key are ctx == 0, lse == -inf."""
-    b, t = q.shape[:2]
-    want_ctx, want_lse = VR.decode_attention(q, k, v, kv_lens, new_lens, scale, causal)
-    seen = VR.valid_rows(t, kv_lens, new_lens)
-    assert (got_ctx[~seen] == 0).all(), f'{what}: ctx of a row without a visible key is not 0'
-    assert np.isneginf(got_lse.transpose(0, 2, 1)[~seen]).all(), f'{what}: lse of a row without a visible key is not -inf'
-    worst_ctx = worst_lse = 0.0
-    for i in np.nonzero(seen.any(axis=1))[0]:
-        rows = seen[i]
-        g_ctx, g_lse = got_ctx[i, rows].astype(np.float64), got_lse[i][:, rows].astype(np.float64)
-        assert np.isfinite(g_ctx).all() and np.isfinite(g_lse).all(), f'{what}: sequence {i} not finite'
-        x = R.exponent_magnitude(q[i:i + 1, rows], k[i:i + 1, :kv_lens[i]], scale, want_lse[i:i + 1, :, rows])
-        worst_ctx = max(worst_ctx, float((np.abs(g_ctx - want_ctx[i, rows]) / (R.exponent_tol(2e-6, x) * (1.0 + np.abs(want_ctx[i, rows])))).max()))
-        worst_lse = max(worst_lse, float(np.abs(g_lse - want_lse[i][:, rows]).max() / R.exponent_tol(3e-6, x)))
-    print(f'{what}: ctx {worst_ctx:.3f} of the bound, lse {worst_lse:.3f} of the bound')
-    assert worst_ctx <= 1.0, f'{what}: ctx {worst_ctx:.3g} of the bound'
-    assert worst_lse <= 1.0, f'{what}: lse {worst_lse:.3g} of the bound'
-
-
-def _data(seed, b, t, hq, hkv, d, cap):
-    rng = np.random.default_rng(seed)
-    return (rng.standard_normal([b, t, hq, d]).astype(np.float32), rng.standard_normal([b, cap, hkv, d]).astype(np.float32),
-            rng.standard_normal([b, cap, hkv, d]).astype(np.float32))
-
-
-def _poison(q, k, v, kv_lens, new_lens, fill=np.nan):
-    k, v, q = k.copy(), v.copy(), q.copy()
-    past = np.arange(k.shape[1])[None, :] >= np.asarray(kv_lens)[:, None]
-    k[past], v[past] = fill, fill
-    if new_lens is not None:
-        q[np.arange(q.shape[1])[None, :] >= np.asarray(new_lens)[:, None]] = fill
-    return q, k, v
+    decode_gpu.reset_knobs()
 
 
 def _bits_equal(a, b, what):
@@ -254,6 +137,53 @@ def test_paged_bad_arguments_launch_nothing(npm):
     np.testing.assert_array_equal(buf.numpy(), SENTINEL)
 
 
+def test_kv_entry_points_empty_and_null_order(npm):
+    """The return codes of the five row-copy entry points where no kernel is launched, row by row.  The contiguous three
+    (npm_kv_append, npm_kv_append_varlen, npm_kv_gather_varlen): a negative count is a bad argument, an empty call (batch, tokens /
+    rows or row_len 0) is NPM_OK even with every pointer NULL.  The paged two: a NULL length array or table, a negative table pitch
+    or a bad page size is a bad argument even on an empty call; with those valid an empty call is NPM_OK with NULL src / pool / out.
+    A call that has something to copy refuses each NULL pointer.  (NPM_E_NOT_INITIALIZED, which comes before all of it, cannot be
+    provoked in a process that has a device: tests/test_paged_host.py checks it where there is none.)"""
+    from np_modeling_amd import _C
+    lib, ok = _C.lib(), 0
+    buf = npm.device.full([64], SENTINEL)
+    lens = _ints([0, 0])
+    p, n = buf.ptr, lens.ptr
+    for batch, count, row in ((-1, 1, 4), (1, -1, 4), (1, 1, -4)):
+        assert lib.npm_kv_append(p, 4, p, 4, 16, batch, count, row, 0) == BAD
+        assert lib.npm_kv_append_varlen(p, 4, p, 4, 16, batch, count, row, n, None) == BAD
+        assert lib.npm_kv_gather_varlen(p, 4, 16, p, batch, count, row, n) == BAD
+        assert lib.npm_kv_append_paged(p, 4, p, 4, 64, batch, count, row, n, None, n, 1, 16) == BAD
+        assert lib.npm_kv_gather_paged(p, 4, 64, p, batch, count, row, n, n, 1, 16) == BAD
+    assert lib.npm_kv_append(p, 4, p, 4, 16, 1, 1, 4, -1) == BAD                                   # at < 0
+    assert lib.npm_kv_append(None, 4, None, 4, 16, 0, 1, 4, -1) == BAD                             # ... before the empty call
+    for batch, count, row in ((0, 1, 4), (1, 0, 4), (1, 1, 0), (0, 0, 0)):
+        assert lib.npm_kv_append(None, 4, None, 4, 16, batch, count, row, 0) == ok
+        assert lib.npm_kv_append_varlen(None, 4, None, 4, 16, batch, count, row, None, None) == ok
+        assert lib.npm_kv_gather_varlen(None, 4, 16, None, batch, count, row, None) == ok
+        for at_lens, table, pitch, page_rows in ((None, n, 1, 16), (n, None, 1, 16), (n, n, -1, 16), (n, n, 1, 0), (n, n, 1, 8),
+                                                 (n, n, 1, 24), (n, n, 1, -16)):
+            assert lib.npm_kv_append_paged(None, 4, None, 4, 64, batch, count, row, at_lens, None, table, pitch, page_rows) == BAD
+            assert lib.npm_kv_gather_paged(None, 4, 64, None, batch, count, row, at_lens, table, pitch, page_rows) == BAD
+        assert lib.npm_kv_append_paged(None, 4, None, 4, 64, batch, count, row, n, None, n, 1, 16) == ok
+        assert lib.npm_kv_gather_paged(None, 4, 64, None, batch, count, row, n, n, 1, 16) == ok
+        assert lib.npm_kv_append_paged(None, 4, None, 4, 64, batch, count, row, n, None, n, 0, 16) == ok      # table_pitch 0 is no error
+    for src, dst in ((None, p), (p, None)):                               # something to copy: every pointer is needed
+        assert lib.npm_kv_append(src, 4, dst, 4, 16, 1, 1, 4, 0) == BAD
+        assert lib.npm_kv_append_varlen(src, 4, dst, 4, 16, 1, 1, 4, n, None) == BAD
+        assert lib.npm_kv_gather_varlen(src, 4, 16, dst, 1, 1, 4, n) == BAD
+        assert lib.npm_kv_append_paged(src, 4, dst, 4, 64, 1, 1, 4, n, None, n, 1, 16) == BAD
+        assert lib.npm_kv_gather_paged(src, 4, 64, dst, 1, 1, 4, n, n, 1, 16) == BAD
+    assert lib.npm_kv_append_varlen(p, 4, p, 4, 16, 1, 1, 4, None, None) == BAD                    # at_lens
+    assert lib.npm_kv_gather_varlen(p, 4, 16, p, 1, 1, 4, None) == BAD                             # lens
+    assert lib.npm_kv_append(p, 4, p, 4, 16, 0, 1, 4, 0) == ok                                     # batch 0 on real memory: nothing copied
+    assert lib.npm_kv_append_varlen(p, 4, p, 4, 16, 0, 1, 4, n, None) == ok
+    assert lib.npm_kv_gather_varlen(p, 4, 16, p, 0, 1, 4, n) == ok
+    assert lib.npm_kv_append_paged(p, 4, p, 4, 64, 0, 1, 4, n, None, n, 1, 16) == ok
+    assert lib.npm_kv_gather_paged(p, 4, 64, p, 0, 1, 4, n, n, 1, 16) == ok
+    np.testing.assert_array_equal(buf.numpy(), SENTINEL)
+
+
 # ---- npm_kv_append_paged / npm_kv_gather_paged -------------------------------------------------------------------------------------
 @pytest.mark.parametrize('b,t,hkv,d,cap,at,n', [(3, 5, 2, 16, 40, (0, 35, 7), (5, 5, 0)), (1, 1, 8, 128, 9, (4,), (1,)),
                                                 (64, 7, 1, 32, 9, None, None), (2, 129, 3, 64, 300, (171, 0), (129, 1)),
@@ -312,14 +242,6 @@ def test_kv_append_paged_then_gather_paged_is_exact(npm, b, t, hkv, d, cap, at, 
 
 
 # ---- MultiHeadAttention: a paged cache against the contiguous one ------------------------------------------------------------------
-def _layer_close(got, want, tol, what):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape and np.isfinite(got).all(), what
-    frac = float((np.abs(got - want) / (tol * (np.abs(want) + max(np.abs(want).max(), 1.0)))).max())
-    print(f'{what}: {frac:.3f} of {tol:.1e} (|ref| + max |ref|)')
-    assert frac <= 1.0, f'{what}: {frac:.3g} of the bound {tol:.3g}'
-
-
 def _layer_run(att, x_rows, schedule, capacity, **paged):
     from np_modeling_amd import _C
     cache = att.make_cache(len(x_rows), capacity, **paged)

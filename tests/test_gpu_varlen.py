@@ -12,20 +12,18 @@ lse == -inf at the kernel level); guard regions keep their sentinel.
 Every test names an entry point or keyword that does not exist without this feature.
 """
 
-import ctypes as C
-
 import numpy as np
 import pytest
 
-import attn_range_data as R
 import decode_cases as DC
+import decode_gpu
 import varlen_reference as VR
+from decode_gpu import GUARD, NT_KNOB, SENTINEL
+from decode_gpu import check as _check, data as _data, guarded as _guarded, ints as _ints, layer_close as _layer_close
+from decode_gpu import poison as _poison, run as _run, set_splits as _set_splits
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
-SENTINEL = 777.0
-SPLITS_KNOB, NT_KNOB = 20, 21
 LAYER_TOL = 1e-5
 
 
@@ -38,103 +36,7 @@ def npm():
 @pytest.fixture(autouse=True)
 def _defaults_afterwards(npm):
     yield
-    from np_modeling_amd import _C
-    for knob in (SPLITS_KNOB, NT_KNOB):
-        _C.check(_C.lib().npm_set_tuning(knob, 0), 'npm_set_tuning')
-
-
-def _set_splits(mode, lmax):
-    from np_modeling_amd import _C
-    tiles = (lmax + 15) // 16
-    value = {'one': 1, 'auto': 0, 'many': min(tiles + 3, 1024)}.get(mode, mode)
-    _C.check(_C.lib().npm_set_tuning(SPLITS_KNOB, int(value)), 'npm_set_tuning')
-    return int(value) or None
-
-
-def _guarded(arr, n):
-    np.testing.assert_array_equal(arr.flat_view(n, [arr.size - n]).numpy(), SENTINEL)
-    return arr.flat_view(0, [n]).numpy()
-
-
-def _ints(values):
-    from np_modeling_amd import device as D
-    return D.bytes_from_host(np.ascontiguousarray(np.asarray(values, dtype=np.int32)))
-
-
-def _run(q, k, v, lmax, scale, causal, kv_lens=None, new_lens=None, packed=False, expect=0, null_lens=False):
-    """q [B, T, Hq, D], k / v [B, capacity, Hkv, D] host float32 -> ctx, lse, kernel string.  ``kv_lens`` None: the uniform entry
-    point npm_mha_decode_fwd at kv_len = lmax; else npm_mha_decode_fwd_varlen with d->kv_len = lmax.  ``packed``: q sits in a
-    [B, T, Hq + 2 Hkv, D] buffer and the cache rows carry 4 floats of padding (NaN in both)."""
-    from np_modeling_amd import _C, device as D
-    b, t, hq, d = q.shape
-    cap, hkv = k.shape[1], k.shape[2]
-    if packed:
-        qp = hq * d + 2 * hkv * d
-        qbuf = np.full([b, t, qp], np.nan, dtype=np.float32)
-        qbuf[:, :, :hq * d] = q.reshape(b, t, hq * d)
-        kp = hkv * d + 4
-        kbuf, vbuf = (np.full([b, cap, kp], np.nan, dtype=np.float32) for _ in range(2))
-        kbuf[:, :, :hkv * d], vbuf[:, :, :hkv * d] = k.reshape(b, cap, hkv * d), v.reshape(b, cap, hkv * d)
-    else:
-        qp, kp, qbuf, kbuf, vbuf = hq * d, hkv * d, q, k, v
-    qd, kd, vd = D.from_host(qbuf), D.from_host(kbuf), D.from_host(vbuf)
-    ctx = D.full([b * t * hq * d + GUARD], SENTINEL)
-    lse = D.full([b * hq * t + GUARD], SENTINEL)
-    c = _C.npm_mha_decode()
-    c.batch, c.heads, c.kv_heads, c.new_tokens, c.kv_len, c.head_dim = b, hq, hkv, t, lmax, d
-    c.causal, c.scale = int(causal), scale
-    c.q, c.q_pitch = qd.ptr, qp
-    c.k, c.k_pitch, c.k_stride_b = kd.ptr, kp, cap * kp
-    c.v, c.v_pitch, c.v_stride_b = vd.ptr, kp, cap * kp
-    c.ctx, c.ctx_pitch, c.lse = ctx.ptr, hq * d, lse.ptr
-    if kv_lens is None and not null_lens:
-        rc = _C.lib().npm_mha_decode_fwd(C.byref(c))
-    else:
-        lens = None if null_lens else _ints(kv_lens)
-        new = None if new_lens is None else _ints(new_lens)
-        rc = _C.lib().npm_mha_decode_fwd_varlen(C.byref(c), None if lens is None else lens.ptr, None if new is None else new.ptr)
-    if expect:
-        assert rc == expect, (rc, _C.lib().npm_last_error())
-        return None
-    _C.check(rc, 'npm_mha_decode_fwd[_varlen]')
-    return _guarded(ctx, b * t * hq * d).reshape(b, t, hq, d), _guarded(lse, b * hq * t).reshape(b, hq, t), _C.last_decode_kernel()
-
-
-def _check(got_ctx, got_lse, q, k, v, kv_lens, new_lens, scale, causal, what):
-    """Every valid element against float64 of its sequence alone at tol(X) of that sequence; rows without a visible key are
-    ctx == 0, lse == -inf.  Prints the largest fraction of the bound used."""
-    b, t = q.shape[:2]
-    want_ctx, want_lse = VR.decode_attention(q, k, v, kv_lens, new_lens, scale, causal)
-    seen = VR.valid_rows(t, kv_lens, new_lens)
-    assert (got_ctx[~seen] == 0).all(), f'{what}: ctx of a row without a visible key is not 0'
-    assert np.isneginf(got_lse.transpose(0, 2, 1)[~seen]).all(), f'{what}: lse of a row without a visible key is not -inf'
-    worst_ctx = worst_lse = 0.0
-    for i in np.nonzero(seen.any(axis=1))[0]:
-        rows = seen[i]
-        g_ctx, g_lse = got_ctx[i, rows].astype(np.float64), got_lse[i][:, rows].astype(np.float64)
-        assert np.isfinite(g_ctx).all() and np.isfinite(g_lse).all(), f'{what}: sequence {i} not finite'
-        x = R.exponent_magnitude(q[i:i + 1, rows], k[i:i + 1, :kv_lens[i]], scale, want_lse[i:i + 1, :, rows])
-        worst_ctx = max(worst_ctx, float((np.abs(g_ctx - want_ctx[i, rows]) / (R.exponent_tol(2e-6, x) * (1.0 + np.abs(want_ctx[i, rows])))).max()))
-        worst_lse = max(worst_lse, float(np.abs(g_lse - want_lse[i][:, rows]).max() / R.exponent_tol(3e-6, x)))
-    print(f'{what}: ctx {worst_ctx:.3f} of the bound, lse {worst_lse:.3f} of the bound')
-    assert worst_ctx <= 1.0, f'{what}: ctx {worst_ctx:.3g} of the bound'
-    assert worst_lse <= 1.0, f'{what}: lse {worst_lse:.3g} of the bound'
-
-
-def _data(seed, b, t, hq, hkv, d, cap):
-    rng = np.random.default_rng(seed)
-    return (rng.standard_normal([b, t, hq, d]).astype(np.float32), rng.standard_normal([b, cap, hkv, d]).astype(np.float32),
-            rng.standard_normal([b, cap, hkv, d]).astype(np.float32))
-
-
-def _poison(q, k, v, kv_lens, new_lens, fill=np.nan):
-    """Cache rows at and past each sequence's length, and the padded query rows, hold ``fill``."""
-    k, v, q = k.copy(), v.copy(), q.copy()
-    past = np.arange(k.shape[1])[None, :] >= np.asarray(kv_lens)[:, None]
-    k[past], v[past] = fill, fill
-    if new_lens is not None:
-        q[np.arange(q.shape[1])[None, :] >= np.asarray(new_lens)[:, None]] = fill
-    return q, k, v
+    decode_gpu.reset_knobs()
 
 
 # ---- npm_mha_decode_fwd_varlen ---------------------------------------------------------------------------------------------------
@@ -263,14 +165,6 @@ def test_kv_gather_varlen_is_exact_and_its_tail_is_zero(npm, b, hkv, d, cap, row
 
 
 # ---- MultiHeadAttention with a cache and per-sequence lengths ------------------------------------------------------------------
-def _layer_close(got, want, tol, what):
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    assert got.shape == want.shape and np.isfinite(got).all(), what
-    frac = float((np.abs(got - want) / (tol * (np.abs(want) + max(np.abs(want).max(), 1.0)))).max())
-    print(f'{what}: {frac:.3f} of {tol:.1e} (|ref| + max |ref|)')
-    assert frac <= 1.0, f'{what}: {frac:.3g} of the bound {tol:.3g}'
-
-
 def _poison_cache(cache):
     """NaN into every row at and past each sequence's length."""
     for arr in (cache.k, cache.v):
