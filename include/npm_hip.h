@@ -440,6 +440,32 @@ int npm_kv_append_paged(const float *src, int64_t src_pitch, float *pool, int64_
 int npm_kv_gather_paged(const float *pool, int64_t row_pitch, int64_t page_stride, float *out, int32_t batch, int32_t rows,
                         int32_t row_len, const int32_t *lens, const int32_t *block_table, int32_t table_pitch, int32_t page_rows);
 
+/* ---- prefill: any number of new tokens straight over the cache (a prompt, a chunk of one, a sequence admitted into a batch) ----
+ * The contract of npm_mha_decode_fwd / _varlen / _paged on the same descriptor, without the limit on (heads / kv_heads) * new_tokens:
+ *   kv_lens == NULL      every sequence has L = d->kv_len valid rows and brings T = d->new_tokens (needs kv_len >= new_tokens);
+ *   kv_lens != NULL      L_b = kv_lens[b], n_b = new_lens[b] (NULL: T) as in npm_mha_decode_fwd_varlen; d->kv_len is the host's
+ *                        upper bound and changes no result;
+ *   block_table == NULL  the cache is contiguous (d->k_stride_b the batch stride); otherwise d->k / d->v are page pools as in
+ *                        npm_mha_decode_fwd_paged (kv_lens is then required).
+ * Row t < n_b sees keys j <= L_b - n_b + t when causal and j < L_b otherwise; a row with no visible key (t >= n_b, L_b == 0) is
+ * stored as ctx = 0, lse = -inf by selection; lse is optional.  Nothing at or past row L_b of the cache enters a result, whatever it
+ * holds; table entries at and past ceil(L_b / page_rows) are not read.
+ * The kernel (csrc/npm_prefill.hip): a block covers 64 query rows -- (query head of the group, token) pairs -- of ONE K / V head,
+ * so K / V are read once per group; its four waves share every 16-key tile through LDS; it walks key tiles only up to the largest
+ * limit of its own rows (the causal upper triangle and everything past L_b are skipped), and a block whose tokens are all padding
+ * returns before it loads anything.  No mask, no gather, no [T, L] object: causality and lengths are arithmetic on (t, j, L_b, n_b)
+ * read on the device.  Keys are NOT split over blocks, so a valid row of sequence b depends only on that sequence's q, rows, L_b,
+ * n_b and d->new_tokens.  Hence, BITWISE: the paged result is the contiguous one on the same rows; kv_lens == NULL is the call
+ * with all lengths equal; sequence b in a batch is that sequence at batch 1 with the same new_tokens, whatever d->kv_len bounds.
+ * Exact fp32 MFMA (npm_set_math does not apply), no atomics.  head_dim in {16, 32, 64, 128}, else NPM_E_UNSUPPORTED.  Argument
+ * checks and error codes are those of the decode entry point of the same layout; a refused call launches nothing.
+ * npm_last_prefill_kernel(): "mha_prefill_kernel D=<head_dim> T=<new_tokens> rows=<query rows per block> causal=<0|1>", then
+ * " varlen=1" with kv_lens and " paged=<page_rows>" with a block table; "" before the first call. */
+int npm_mha_prefill_supported(int head_dim);
+int npm_mha_prefill_fwd(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens, const int32_t *block_table,
+                        int32_t table_pitch, int32_t page_rows);
+const char *npm_last_prefill_kernel(void);
+
 /* ---- skinny-M GEMM: the matrix products of a decode step (inference) ----
  * C[M, N] = epilogue(alpha * A[M, K] op(B)) for 1 <= M <= NPM_SKINNY_MAX_M rows, described by the same npm_gemm as npm_sgemm.  These
  * are the products np.matmul / np.einsum make at M = B T rows of new tokens: the q / k / v and output projections of

@@ -164,6 +164,8 @@ SIGNATURES = {
     'npm_mha_decode_fwd_paged': [C.POINTER(npm_mha_decode), _P, _P, _P, _I32, _I32],
     'npm_kv_append_paged': [_P, _I64, _P, _I64, _I64, _I32, _I32, _I32, _P, _P, _P, _I32, _I32],
     'npm_kv_gather_paged': [_P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P, _I32, _I32],
+    'npm_mha_prefill_supported': [C.c_int],
+    'npm_mha_prefill_fwd': [C.POINTER(npm_mha_decode), _P, _P, _P, _I32, _I32],
     'npm_sgemm_skinny': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_supported': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_splits': [C.c_int, C.c_int, C.c_int],
@@ -182,6 +184,7 @@ _SPECIAL = {
     'npm_stream': (C.c_void_p, []),
     'npm_last_attn_kernel': (C.c_char_p, []),
     'npm_last_decode_kernel': (C.c_char_p, []),
+    'npm_last_prefill_kernel': (C.c_char_p, []),
     'npm_last_skinny_kernel': (C.c_char_p, []),
 }
 
@@ -416,6 +419,11 @@ def last_attn_kernel() -> str:
 def last_decode_kernel() -> str:
     """What the most recent npm_mha_decode_fwd launched (include/npm_hip.h npm_last_decode_kernel)."""
     return lib().npm_last_decode_kernel().decode()
+
+
+def last_prefill_kernel() -> str:
+    """What the most recent npm_mha_prefill_fwd launched (include/npm_hip.h npm_last_prefill_kernel)."""
+    return lib().npm_last_prefill_kernel().decode()
 
 
 TUNE_DECODE_SPLITS, TUNE_DECODE_NT = 20, 21     # include/npm_hip.h NPM_TUNE_DECODE_*

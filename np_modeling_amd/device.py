@@ -1133,6 +1133,37 @@ def mha_decode(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, s
     return ctx, lse
 
 
+# prefill: cached forwards with more rows than the decode kernel takes (a prompt chunk on top of cached rows, a ragged or paged
+# prefill, a sequence admitted into a running batch, a long query over a frozen cross cache) run npm_mha_prefill_fwd straight
+# over the cache instead of the fused training forward on gathered K / V with a host-built mask.  Off by default: the gather /
+# mask path stays what every call sequence is until the switch is flipped (measured: tools/prefill_bench.py).
+PREFILL_KERNEL = os.environ.get('NPM_PREFILL_KERNEL', '0') != '0'
+
+
+def mha_prefill_supported(head_dim: int, value_dim: Optional[int] = None) -> bool:
+    """Whether ``npm_mha_prefill_fwd`` takes this head size (any number of rows).  Exact-fp32 MFMA only, like
+    ``mha_decode_supported``: false under a split math mode."""
+    if not ATTN_CORE or (value_dim is not None and value_dim != head_dim) or _C.current_math() != 'f32':
+        return False
+    return bool(_C.lib().npm_mha_prefill_supported(int(head_dim)))
+
+
+def mha_prefill(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, scale: float, causal: bool, want_lse: bool = False,
+                lens=None, keys: Optional[int] = None):
+    """``mha_decode`` without its limit on the rows (include/npm_hip.h npm_mha_prefill_fwd): ctx [B, T, Hq, D] (and lse
+    [B, Hq, T] or None) of ``tokens`` query rows per sequence over ``cache``, read in place -- through the block table of a paged
+    cache -- with ``lens`` = (kv_lens, new_lens) as there.  No mask and no gathered copy exist."""
+    assert cache.key_dim == cache.value_dim and 0 <= kv_len <= cache.capacity and (lens is not None or tokens <= kv_len)
+    c, ctx, lse, layout = _decode_desc(q, cache, heads, tokens, kv_len, scale, causal, want_lse)
+    b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
+    keys = b * kv_len if keys is None else int(keys)
+    kv_lens, new_lens = (None, None) if lens is None else lens
+    with _timed('mha_prefill', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + 2 * hkv * keys)):
+        _C.check(_C.lib().npm_mha_prefill_fwd(C.byref(c), kv_lens, new_lens, layout.table, layout.table_pitch, layout.page_rows),
+                 'npm_mha_prefill_fwd')
+    return ctx, lse
+
+
 class KVCache:
     """Keys and values of the tokens seen so far: ``k`` [B, capacity, Hkv, Dk] and ``v`` [B, capacity, Hkv, Dv] on the device,
     of which the first ``lengths[b]`` rows of sequence b are valid.  Rows at and past that hold whatever was there; nothing reads
@@ -1268,19 +1299,24 @@ class KVCache:
                 kv_append(src, dst.ptr + 4 * b * layout.stride, layout, 1, rows, 0, None, rows)
         self.lengths[b] = rows
 
-    def attend(self, q: Mat, heads: int, tokens: int, scale: float, causal: bool, want_lse: bool = False, new_lengths=None):
+    def attend(self, q: Mat, heads: int, tokens: int, scale: float, causal: bool, want_lse: bool = False, new_lengths=None,
+               kernel: str = 'decode'):
         """``mha_decode`` of ``tokens`` query rows per sequence over the valid rows; with ``new_lengths`` (or a ragged or paged
         cache) its ragged call: rows t >= n[b] are padding and come back as zeros.  ``causal``: the n[b] new tokens are the last
-        n[b] valid rows of sequence b (they were appended first)."""
+        n[b] valid rows of sequence b (they were appended first).  ``kernel='prefill'``: ``mha_prefill``, the same contract for any
+        number of rows (a uniform cache shorter than the query -- a frozen one -- takes its per-sequence call)."""
+        if kernel not in ('decode', 'prefill'):
+            raise ValueError(f"KVCache.attend: kernel must be 'decode' or 'prefill', got {kernel!r}")
+        attend = mha_prefill if kernel == 'prefill' else mha_decode
         n = self.new_lengths(tokens, new_lengths)
-        if self._scalar_call(n):
-            return mha_decode(q, self, heads, tokens, int(self.lengths[0]), scale, causal, want_lse)
+        if self._scalar_call(n) and (kernel == 'decode' or tokens <= int(self.lengths[0])):
+            return attend(q, self, heads, tokens, int(self.lengths[0]), scale, causal, want_lse)
         n = self._counts(tokens, n)
         if causal and (n > self.lengths).any():
             raise ValueError(f'KVCache.attend: {n.tolist()} new tokens are not among the {self.lengths.tolist()} valid rows')
         _, new_ptr, kv_ptr = self._device_lengths(self.lengths - n, n)
-        return mha_decode(q, self, heads, tokens, self.max_length, scale, causal, want_lse, lens=(kv_ptr, new_ptr),
-                          keys=int(self.lengths.sum()))
+        return attend(q, self, heads, tokens, self.max_length, scale, causal, want_lse, lens=(kv_ptr, new_ptr),
+                      keys=int(self.lengths.sum()))
 
     def gather(self, rows: int):
         """(k, v) [B, rows, Hkv, D]: the valid rows of every sequence made contiguous, zeros behind them (``kv_gather_rows``)."""

@@ -55,6 +55,13 @@ equal what the sequence gives alone at batch 1; padded rows are unspecified but 
 enters a result.  ``'decode'`` is then ``npm_mha_decode_fwd_varlen``, ``'fused_masked'`` (a ragged prefill) builds its mask from the
 lengths and takes K / V from the fresh projection or ``npm_kv_gather_varlen``; the GEMM composition has no masked softmax and
 raises NotImplementedError.  Lengths that are all equal take exactly the calls they took without the keyword.
+
+Prefill kernel (``device.PREFILL_KERNEL``, environment ``NPM_PREFILL_KERNEL=1``; off by default).  With the switch on, a cached
+forward that the decode kernel does not take runs ``npm_mha_prefill_fwd`` (csrc/npm_prefill.hip; ``_cached_path == 'prefill'``)
+straight over the cache under ``f32`` math and a supported head size: everything ``'fused_masked'`` served for ragged, paged and
+frozen caches, and the uniform contiguous cache with rows already in it or frozen -- no gathered K / V, no mask, no copy per
+sequence.  One case stays on ``'fused_masked'``: a uniform contiguous prefill from empty, where the fused forward reads the fresh
+projection in place.  With the switch off every call sequence is what it was.
 """
 
 from __future__ import annotations
@@ -84,7 +91,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         self._num_kv_heads = num_heads if num_kv_heads is None else num_kv_heads
         self._softmax = activations.Softmax()
         self._cached_forward = False    # the last forward ran with a cache: it saved nothing a backward could use
-        self._cached_path = None        # 'decode' | 'fused_masked' | 'gemm': how the last cached forward attended
+        self._cached_path = None        # 'decode' | 'prefill' | 'fused_masked' | 'gemm': how the last cached forward attended
 
     def initialize(self, query, key=None, value=None, *args, **kwargs) -> None:
         # query [B, Sq, H*Dk]; key [B, Skv, H*Dk]; value [B, Skv, H*Dv]
@@ -344,6 +351,12 @@ class MultiHeadAttention(layer.StatefulLayer):
         if t <= length and D.mha_decode_supported(dk, h // hkv * t, dv):     # (the kernel's contract: L >= T, causal or not)
             self._cached_path = 'decode'
             return cache.attend(q, h, t, scale, causal)[0]
+        if D.PREFILL_KERNEL and D.mha_prefill_supported(dk, dv) and not (fresh is not None and length == t):
+            # more rows than the decode kernel takes on top of cached rows, or over a frozen cache: the prefill kernel reads the
+            # cache in place (no copy of the valid rows, no mask).  A prefill from empty stays below: the fused forward reads
+            # the projection in place there.
+            self._cached_path = 'prefill'
+            return cache.attend(q, h, t, scale, causal, kernel='prefill')[0]
         if D.mha_core_supported(dk, dv, any_math=True):
             # more rows than the decode kernel takes (a long prefill), or a split math mode: the fused training forward, with the
             # causal rule as a mask over the valid rows.  It addresses K / V as [B, L, Hkv, D]: the new tokens' own projection
@@ -384,6 +397,11 @@ class MultiHeadAttention(layer.StatefulLayer):
         if D.mha_decode_supported(dk, h // hkv * t, dv):
             self._cached_path = 'decode'
             return cache.attend(q, h, t, scale, causal, new_lengths=n)[0]
+        if D.PREFILL_KERNEL and D.mha_prefill_supported(dk, dv):
+            # a ragged prefill, a chunk of one, a sequence admitted beside decoding ones, a paged or a frozen cache: the prefill
+            # kernel over the cache in place, through the block table -- lengths and causality are arithmetic on the device
+            self._cached_path = 'prefill'
+            return cache.attend(q, h, t, scale, causal, new_lengths=n, kernel='prefill')[0]
         # a ragged prefill, mostly: the fused training forward with the lengths as a mask [B, 1, T, keys], whose tile summary
         # skips what lies past them.  K / V: the fresh projection when every sequence started empty (keys = T; the rows of padded
         # tokens are masked), else the valid rows gathered with zeros behind them (P = 0 times stale memory could be NaN).
