@@ -16,6 +16,12 @@ an address from one reads NaN, never out of bounds).  Guard regions keep their s
 Layers: outputs against every sequence alone at tests/test_gpu_paged.py's bounds (1e-5 (|ref| + max |ref|) against float64, 2e-5
 between two float32 evaluations, 1e-4 for the decoder against float64) and against the switch-off result at the float32 bound.
 
+A second grid (``prefill_reference.group_cases``) holds the kernel to the same bound and identities where the 64-row tile is
+partly filled (Hq / Hkv of 3, 5, 7) and where a group needs a second, partly full head chunk (72, 65): ``q`` is N(0, 1) per (token,
+head), so a row stored in another row's slot misses the float64 bound by orders of magnitude.  ``range_cases`` moves every score
+of a row by up to +-200 and saturates the softmax (tests/attn_range_data.py) at B 2, L 300, T up to 70; ``repeat_cases`` runs one
+call three times and compares bits (the K / V tiles are double buffered in LDS behind one barrier per tile).
+
 Every test names npm_mha_prefill_*, ``PREFILL_KERNEL`` or the path 'prefill': none exists without this feature.
 """
 
@@ -141,6 +147,68 @@ def test_prefill_kernel_float64_bound_and_bitwise_identities(npm, case):
         _bits_equal((base[0][i:i + 1], base[1][i:i + 1]), alone, what + f' sequence {i} alone')
 
 
+@pytest.mark.parametrize('case', PR.group_cases(), ids=PR.case_id)
+def test_prefill_kernel_on_uneven_and_multi_chunk_groups(npm, case):
+    """The row mapping of a block where gb tb < 64 (rows of the tile that are no row of the call) and where blockIdx.x carries a
+    head chunk beside the token tile: the float64 bound, unchanged, is what catches a misplaced (token, head) row."""
+    d, hq, hkv, t, causal, lengths, n, packed, place = case
+    b, lmax = len(lengths), int(lengths.max())
+    q, k, v = PR.case_data(case)
+    qn, kn, vn = _poison(q, k, v, lengths, n)
+    scale = 1.0 / np.sqrt(d)
+    base = _run(qn, kn, vn, lmax, scale, causal, lengths, n, packed=packed)
+    name = f'mha_prefill_kernel D={d} T={t} rows={PR.ROWS} causal={causal} varlen=1'
+    assert base[2] == name
+    what = f'{name} H={hq}/{hkv} tile rows {PR.tile_rows(hq, hkv)} head chunks {PR.head_chunks(hq, hkv)[0]} L={lengths.tolist()} n={n.tolist()}'
+    _check(base[0], base[1], q, k, v, lengths, n, scale, causal, what)
+    for page_rows, order in ((16, 'random'), (64, 'identity')):          # the full cross is the first grid's
+        pk, pv, table = PC.build_pool(k, v, lengths, page_rows, order, seed=d + t + page_rows)
+        got = _run(qn, pk, pv, lmax, scale, causal, lengths, n, packed=packed, paged=(table, page_rows))
+        assert got[2] == name + f' paged={page_rows}'
+        _bits_equal(base, got, f'{got[2]} {order} L={lengths.tolist()}')
+    _bits_equal(base, _run(qn, kn, vn, lmax + 37, scale, causal, lengths, n, packed=packed), what + ' under a larger kv_len')
+    for i in range(b):
+        alone = _run(qn[i:i + 1], kn[i:i + 1], vn[i:i + 1], int(lengths[i]), scale, causal, lengths[i:i + 1], n[i:i + 1], packed=packed)
+        _bits_equal((base[0][i:i + 1], base[1][i:i + 1]), alone, what + f' sequence {i} alone')
+
+
+@pytest.mark.parametrize('d,hq,hkv,t', PR.RANGE_SHAPES)
+def test_prefill_shifted_and_saturated_scores(npm, d, hq, hkv, t):
+    """tests/test_gpu_decode.py's test of this name for npm_mha_prefill_fwd, at more rows than the decode kernel takes: every score
+    of a row moved by up to +-200; nearly one-hot rows whose largest scores sit in the last of 19 key tiles, at keys a causal row
+    cannot see.  The paged call on the same rows is bitwise the contiguous one."""
+    lengths = np.full(PR.RANGE_BATCH, PR.RANGE_LEN)
+    for kind in PR.RANGE_KINDS:
+        q, k, v, scale = PR.range_data(d, hq, hkv, t, kind)
+        pk, pv, table = PC.build_pool(k, v, lengths, 16, 'random', seed=d + t)
+        for causal in (0, 1):
+            ctx, lse, kernel = _run(q, k, v, PR.RANGE_LEN, scale, causal)
+            assert kernel == f'mha_prefill_kernel D={d} T={t} rows={PR.ROWS} causal={causal}'
+            _check(ctx, lse, q, k, v, lengths, None, scale, causal, f'{kind} H={hq}/{hkv} {kernel}')
+            got = _run(q, pk, pv, PR.RANGE_LEN, scale, causal, lengths, None, paged=(table, 16))
+            assert got[2] == kernel + ' varlen=1 paged=16'
+            _bits_equal((ctx, lse), got, f'{kind} {got[2]}')
+
+
+@pytest.mark.parametrize('case', PR.repeat_cases(), ids=PR.case_id)
+def test_prefill_same_call_repeated_is_bitwise_equal(npm, case):
+    """Three runs of one npm_mha_prefill_fwd call, contiguous and paged: a block that read a K / V tile from LDS before every
+    thread had stored it (or stored into the buffer others still read) would differ from run to run."""
+    d, hq, hkv, t, causal, lengths, n, packed, place = case
+    lmax = int(lengths.max())
+    q, k, v = PR.case_data(case)
+    qn, kn, vn = _poison(q, k, v, lengths, n)
+    scale = 1.0 / np.sqrt(d)
+    pk, pv, table = PC.build_pool(k, v, lengths, 16, 'random', seed=d + t)
+    first = _run(qn, kn, vn, lmax, scale, causal, lengths, n)
+    _check(first[0], first[1], q, k, v, lengths, n, scale, causal, f'{first[2]} H={hq}/{hkv} L={lengths.tolist()}')
+    for repeat in (1, 2):
+        _bits_equal(first, _run(qn, kn, vn, lmax, scale, causal, lengths, n), f'{first[2]} run {repeat} against run 0')
+    for repeat in (0, 1, 2):
+        got = _run(qn, pk, pv, lmax, scale, causal, lengths, n, paged=(table, 16))
+        _bits_equal(first, got, f'{got[2]} run {repeat} against the contiguous run 0')
+
+
 @pytest.mark.parametrize('d,hq,hkv,t,length,b,causal', [(128, 8, 2, 67, 300, 2, 1), (64, 8, 8, 64, 64, 3, 1), (16, 8, 1, 9, 129, 5, 0),
                                                         (32, 6, 3, 33, 33, 3, 1), (128, 8, 1, 19, 47, 2, 0), (64, 8, 8, 131, 700, 2, 1)])
 def test_prefill_without_lengths_is_bitwise_the_call_with_all_lengths_equal(npm, d, hq, hkv, t, length, b, causal):
@@ -223,7 +291,7 @@ def _layer_run(att, x_rows, schedule, capacity, **paged):
     return outs, paths, cache
 
 
-@pytest.mark.parametrize('heads,kv_heads,f', [(8, 8, 1024), (8, 2, 512), (8, 1, 128), (6, 3, 192)])
+@pytest.mark.parametrize('heads,kv_heads,f', [(8, 8, 1024), (8, 2, 512), (8, 1, 128), (6, 3, 192), (12, 4, 192), (5, 1, 160)])
 @pytest.mark.parametrize('page_size', [16, 64])
 def test_layer_ragged_prefill_and_second_chunk_into_a_paged_cache(npm, monkeypatch, heads, kv_heads, f, page_size):
     """A ragged prompt of 41 .. 70 tokens into an empty paged cache, single tokens, a second chunk on top, single tokens: with the
@@ -266,6 +334,49 @@ def test_layer_uniform_contiguous_cache_takes_the_kernel_only_on_top_of_rows(npm
     for i in range(2):
         _layer_close(got[i], want[i], LAYER_TOL, f'uniform chunk sequence {i} vs float64')
         _layer_close(got[i], off[i], 2 * LAYER_TOL, f'uniform chunk sequence {i} vs switch off')
+
+
+@pytest.mark.parametrize('heads,kv_heads,f,below,above', [(4, 4, 256, 32, 33), (4, 1, 512, 8, 9), (12, 4, 192, 10, 11)])
+def test_layer_hands_over_from_the_decode_kernel_to_the_prefill_kernel_past_32_rows(npm, monkeypatch, heads, kv_heads, f, below, above):
+    """On a contiguous cache that holds rows, with the switch on: (Hq / Hkv) T <= 32 is the decode kernel's chunk, one more row
+    is the prefill kernel's -- groups 1 and 4 at exactly 32 and 33 rows, group 3 at 30 and 33."""
+    from np_modeling_amd import _C, device as D
+    group = heads // kv_heads
+    assert group * below <= VR.MAX_ROWS < group * above and group * (below + 1) > VR.MAX_ROWS
+    att, p = DC.make_mha(npm, f, heads, kv_heads, seed=heads + below, batch=2)
+    sizes = [40, below, above]
+    x = np.random.default_rng(f + below).standard_normal([2, sum(sizes), f]).astype(np.float32)
+    monkeypatch.setattr(D, 'PREFILL_KERNEL', True)
+    got, paths = DC.run_mha_chunks(att, x, sizes, capacity=sum(sizes) + 3)
+    assert paths == ['fused_masked', 'decode', 'prefill']
+    assert _C.last_prefill_kernel() == f'mha_prefill_kernel D={f // heads} T={above} rows={PR.ROWS} causal=1'
+    want = VR.layer_alone(p, list(x), [np.array([s, s]) for s in sizes])
+    edges = np.cumsum([0] + sizes)
+    for i in range(2):
+        for name, lo, hi in (('decode', edges[1], edges[2]), ('prefill', edges[2], edges[3])):
+            _layer_close(got[i][lo:hi], want[i][lo:hi], LAYER_TOL, f'hand-over H{heads}/{kv_heads} {name} chunk of {hi - lo} sequence {i} vs float64')
+
+
+@pytest.mark.parametrize('page_size', [None, 16])
+def test_layer_uniform_frozen_cross_cache_shorter_than_the_query(npm, monkeypatch, page_size):
+    """kv_lengths=None, 5 memory rows under 40 query rows: the scalar npm_mha_prefill_fwd call needs kv_len >= new_tokens, so
+    KVCache.attend takes the per-sequence call."""
+    from np_modeling_amd import _C, device as D
+    att, p = DC.make_mha(npm, 256, 8, 2, seed=9, batch=3)
+    rng = np.random.default_rng(6)
+    kv = rng.standard_normal([3, 5, 256]).astype(np.float32)
+    x = rng.standard_normal([3, 40, 256]).astype(np.float32)
+    paged = {} if page_size is None else dict(page_size=page_size)
+    outs = []
+    for switch in (False, True):
+        monkeypatch.setattr(D, 'PREFILL_KERNEL', switch)
+        cache = att.fill_cache(att.make_cache(3, 5, **paged), kv)
+        outs.append(np.asarray(att(x, cache=cache)))
+        assert att._cached_path == ('prefill' if switch else 'fused_masked')
+    assert _C.last_prefill_kernel() == f'mha_prefill_kernel D=32 T=40 rows={PR.ROWS} causal=0 varlen=1' + (f' paged={page_size}' if page_size else '')
+    for i, want in enumerate(VR.cross_alone(p, list(x), kv, np.full(3, 5))):
+        _layer_close(outs[1][i], want, LAYER_TOL, f'short uniform cross sequence {i} vs float64')
+        _layer_close(outs[1][i], outs[0][i], 2 * LAYER_TOL, f'short uniform cross sequence {i} vs switch off')
 
 
 @pytest.mark.parametrize('page_size', [None, 16])

@@ -1,8 +1,9 @@
 """CPU: the prefill attention kernel without a GPU.
 
 * ``prefill_reference.tile_model`` -- float32 in the kernel's accumulation order (16-key tiles in order, online rescale) -- is held
-  to HALF of tests/decode_gpu.check's bound on exactly the case grid of tests/test_gpu_prefill.py, every sequence against float64
-  alone.  Float64 itself is the reference, so it stays inside the GPU bound with room to spare.
+  to HALF of tests/decode_gpu.check's bound on exactly the case grids of tests/test_gpu_prefill.py -- ``kernel_cases``, ``group_cases``
+  (partly filled tiles, a second head chunk) and the shifted and saturated scores of ``range_cases`` -- every sequence against
+  float64 alone.  Float64 itself is the reference, so it stays inside the GPU bound with room to spare.
 * the three entry points: header against bindings and exports.
 * dispatch on the simulator of tests/hostsim_prefill.py.  With ``device.PREFILL_KERNEL`` on, every cached forward the decode kernel
   does not take -- a ragged or paged prefill, a chunk on top of cached rows (uniform contiguous included), a frozen cross cache,
@@ -75,6 +76,76 @@ def test_case_grid_covers_what_the_kernel_can_get_wrong():
         assert seen == {'0', '1', 'T-1', 'T'}
     assert any({15, 16, 17} <= set(c[5].tolist()) for c in cases)
     assert all((c[6] <= c[5]).all() for c in cases if c[4])               # causal: the new tokens are among the valid rows
+
+
+def test_group_grid_covers_partly_filled_tiles_and_a_second_head_chunk():
+    """What ``kernel_cases`` cannot reach in mha_prefill_kernel's row mapping: its groupings all divide 64 and none exceeds it."""
+    assert all(PR.tile_rows(hq, hkv) == PR.ROWS and PR.head_chunks(hq, hkv) == (1, hq // hkv) for hq, hkv in PR.HEADS)
+    cases = PR.group_cases()
+    assert 80 <= len(cases) <= 100 and len({PR.case_id(c) for c in cases}) == len(cases)
+    assert not {PR.case_id(c) for c in cases} & {PR.case_id(c) for c in PR.kernel_cases()}
+    assert {(c[1], c[2]) for c in cases} == set(PR.GROUP_HEADS)
+    assert [PR.tile_rows(hq, hkv) for hq, hkv in PR.GROUP_HEADS] == [63, 60, 63, 64, 64]
+    assert [PR.head_chunks(hq, hkv) for hq, hkv in PR.GROUP_HEADS] == [(1, 3), (1, 5), (1, 7), (2, 8), (2, 1)]
+    partly = [c for c in cases if PR.tile_rows(c[1], c[2]) < PR.ROWS]
+    chunked = [c for c in cases if PR.head_chunks(c[1], c[2])[0] > 1]
+    assert {PR.tile_rows(c[1], c[2]) for c in partly} == {60, 63}
+    assert chunked and all(PR.head_chunks(c[1], c[2])[1] < PR.ROWS for c in chunked)          # the last chunk is partly full
+    assert any(c[2] > 1 for c in chunked) and any(c[2] > 1 for c in partly)                   # h = c + gi Hkv with Hkv > 1
+    for hq, hkv in PR.GROUP_HEADS:
+        r = PR.tokens_per_block(hq, hkv)
+        want = {1, r, r + 1, 2 * r + 3} | ({33} if hq // hkv >= PR.ROWS else set())
+        assert {c[3] for c in cases if (c[1], c[2]) == (hq, hkv)} == want
+    for kind in (partly, chunked):
+        assert {c[0] for c in kind} == {16, 32, 64, 128}
+        assert {c[4] for c in kind} == {0, 1} and {c[7] for c in kind} == {False, True} and {c[8] for c in kind} == {'top', 'clip'}
+        assert any(c[8] == 'clip' and c[5].tolist() == list(PR.EDGE_SET) for c in kind)      # the tile and page edges, and 700
+        assert any(c[3] > 2 and {0, 1, c[3] - 1, c[3]} <= set(c[6].tolist()) for c in kind)
+    assert PR.EDGE_SET == (15, 16, 17, 64, 65, 700)
+    assert all(c[5].max() <= 700 + c[3] for c in cases)
+    assert all((c[6] <= c[5]).all() for c in cases if c[4])
+
+
+def test_range_and_repeat_cases_are_what_the_gpu_tests_need():
+    cases = PR.range_cases()
+    assert {c[:4] for c in cases} == {(128, 8, 2, 67), (64, 8, 8, 70), (32, 6, 3, 40), (16, 8, 1, 17), (64, 12, 4, 45)}
+    assert len(cases) == 5 * 2 * 2 and {c[4:] for c in cases} == {('shift', 0), ('shift', 1), ('saturated', 0), ('saturated', 1)}
+    assert (PR.RANGE_BATCH, PR.RANGE_LEN) == (2, 300) and all(c[3] > 32 // (c[1] // c[2]) for c in cases)   # past the decode kernel's rows
+    q, k, v, scale = PR.range_data(32, 6, 3, 40, 'saturated')
+    assert q.shape == (2, 40, 6, 32) and k.shape == v.shape == (2, 300, 3, 32)
+    s = scale * np.einsum('bhd,bjhd->bhj', q[:, 0, :3].astype(np.float64), k.astype(np.float64))
+    assert (s.argmax(axis=2) == 299).all()                               # token 0's largest score: the last key, which causal hides
+    q, k, v, scale = PR.range_data(32, 6, 3, 40, 'shift')
+    s = scale * np.einsum('bthd,bjhd->bthj', q[:, :, :3].astype(np.float64), k.astype(np.float64))
+    assert 150 < np.abs(np.median(s, axis=3)).max() <= 210
+    reps = PR.repeat_cases()
+    assert reps[0][:4] == (128, 8, 2, 2 * PR.tokens_per_block(8, 2) + 3) and any(PR.case_id(c)[:16] == PR.case_id(reps[0])[:16] for c in PR.kernel_cases())
+    assert PR.tile_rows(*reps[1][1:3]) < PR.ROWS and PR.head_chunks(*reps[2][1:3])[0] > 1
+    for c in reps:
+        tiles = {-(-int(x) // PR.TILE) % 2 for x in c[5]}
+        assert tiles == {0, 1}, 'an odd and an even number of key tiles'
+        assert (c[6] <= c[5]).all() and (c[6] <= c[3]).all()
+
+
+def _model_fractions(q, k, v, lengths, n, scale, causal, what):
+    ctx, lse = PR.tile_model(q, k, v, lengths, n, scale, causal)
+    worst_ctx, worst_lse = PR.fractions(ctx, lse, q, k, v, lengths, n, scale, causal)
+    print(f'{what}: ctx {worst_ctx:.3f}, lse {worst_lse:.3f} of the GPU bound')
+    assert worst_ctx <= 0.5 and worst_lse <= 0.5
+
+
+@pytest.mark.parametrize('case', PR.group_cases(), ids=PR.case_id)
+def test_float32_tile_model_stays_within_half_the_gpu_bound_on_the_group_grid(case):
+    d, hq, hkv, t, causal, lengths, n, packed, place = case
+    q, k, v = PR.case_data(case)
+    _model_fractions(q, k, v, lengths, n, 1.0 / np.sqrt(d), causal, PR.case_id(case))
+
+
+@pytest.mark.parametrize('case', PR.range_cases(), ids=PR.range_id)
+def test_float32_tile_model_stays_within_half_the_gpu_bound_on_shifted_and_saturated_scores(case):
+    d, hq, hkv, t, kind, causal = case
+    q, k, v, scale = PR.range_data(d, hq, hkv, t, kind)
+    _model_fractions(q, k, v, np.full(PR.RANGE_BATCH, PR.RANGE_LEN), None, scale, causal, PR.range_id(case))
 
 
 @pytest.mark.parametrize('case', PR.kernel_cases(), ids=PR.case_id)
