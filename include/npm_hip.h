@@ -466,6 +466,35 @@ int npm_mha_prefill_fwd(const npm_mha_decode *d, const int32_t *kv_lens, const i
                         int32_t table_pitch, int32_t page_rows);
 const char *npm_last_prefill_kernel(void);
 
+/* ---- half-precision cache: K / V rows stored as IEEE fp16 (opt-in; everything above is unchanged) ----
+ * The cache holds halves; q, ctx, lse, the rows handed to an append and the rows a gather returns stay fp32.  A row is converted
+ * ONCE, by the append, with round to nearest even -- bit for bit NumPy's astype(float16), subnormal results included; |x| >= 65520
+ * becomes +-inf (there is NO clamp: a projection that large is the caller's to scale) -- and converted back exactly wherever it is
+ * read.  Scores, softmax, accumulators and outputs are the fp32 ones: npm_mha_decode_fwd_f16 is BITWISE the fp32 entry point of the
+ * same layout on a cache that holds the rounded values as floats (same split count, tile partition and order of every sum), at
+ * half the bytes per key.  The load policy (NPM_TUNE_DECODE_NT = 0) counts the bytes of the valid part of K, so the fp16 call
+ * switches to nontemporal loads at twice the keys.
+ * One entry point per operation; NULL selects the simpler layout, as in npm_mha_prefill_fwd:
+ *   at_lens / kv_lens == NULL   the uniform call (npm_kv_append at ``at`` / npm_mha_decode_fwd); otherwise the per-sequence one
+ *                               (``at`` is ignored);
+ *   block_table == NULL         a contiguous cache (cache_stride / k_stride_b the batch stride); otherwise a page pool as in the
+ *                               _paged entry points (the stride is the page stride; lengths are then required).
+ * A gather always takes lens (zeros at and past lens[b]; neither such a row nor its table entry is read).
+ * Units and alignment: cache pointers (cache, d->k, d->v) are 16-byte aligned; cache_pitch, cache_stride, d->k_pitch, d->k_stride_b
+ * and the v_ pair count HALVES and are multiples of 8; row_len % 8 == 0; the fp32 side (src, src_pitch, out, q, ctx) keeps the
+ * rules of the fp32 entry points.  npm_mha_decode itself is unchanged: d->k / d->v carry the addresses of the fp16 data.  Head
+ * sizes and the row limit are those of npm_mha_decode_supported (else NPM_E_UNSUPPORTED); a block table without lengths, a bad
+ * page_rows, kv_len < new_tokens on the uniform call and every other violation return what the fp32 entry point of that layout
+ * returns (NPM_E_BAD_ARGUMENT); a refused call launches nothing and writes nothing.
+ * npm_last_decode_kernel() after npm_mha_decode_fwd_f16: the fp32 string of the same layout followed by " kv=f16". */
+int npm_kv_append_f16(const float *src, int64_t src_pitch, void *cache, int64_t cache_pitch, int64_t cache_stride, int32_t batch,
+                      int32_t new_tokens, int32_t row_len, int32_t at, const int32_t *at_lens, const int32_t *new_lens,
+                      const int32_t *block_table, int32_t table_pitch, int32_t page_rows);
+int npm_kv_gather_f16(const void *cache, int64_t cache_pitch, int64_t cache_stride, float *out, int32_t batch, int32_t rows,
+                      int32_t row_len, const int32_t *lens, const int32_t *block_table, int32_t table_pitch, int32_t page_rows);
+int npm_mha_decode_fwd_f16(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens, const int32_t *block_table,
+                           int32_t table_pitch, int32_t page_rows);
+
 /* ---- skinny-M GEMM: the matrix products of a decode step (inference) ----
  * C[M, N] = epilogue(alpha * A[M, K] op(B)) for 1 <= M <= NPM_SKINNY_MAX_M rows, described by the same npm_gemm as npm_sgemm.  These
  * are the products np.matmul / np.einsum make at M = B T rows of new tokens: the q / k / v and output projections of

@@ -56,6 +56,15 @@
 // skip t >= new_lens[b], a gather writes zeros for j >= lens[b] and reads neither that row nor its table entry.  One host
 // function, row_copy, holds what the entry points share (checks, grid, launch); each entry point is its own preconditions -- the
 // paged ones refuse a NULL length array or table even when there is nothing to copy -- and one call.
+//
+// Half-precision cache (npm_kv_append_f16, npm_kv_gather_f16, npm_mha_decode_fwd_f16): the storage type of the cache rows is a
+// template parameter KV of the three kernel templates, float (the instances above, unchanged) or _Float16.  K / V rows are rounded
+// once, by the append (round to nearest even, the hardware's v_cvt_f16_f32: bit for bit NumPy's astype(float16), subnormal results
+// included; |x| >= 65520 becomes +-inf, there is no clamp), and converted back exactly by the loads of load_tile and of the gather.
+// Pitches and strides of an fp16 cache count halves.  The assignment of head-dimension indices to lanes is the fp32 one -- a
+// lane's K load is the 4 consecutive halves (8 bytes) of the 4 floats it loaded before, its V load VW halves -- so every
+// floating-point operation after the load is that of the fp32 instance on the converted values: the result is BITWISE that of
+// the fp32 call on a cache holding the rounded values.  Everything else (q, scores, softmax, accumulators, ctx, lse) stays fp32.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -71,6 +80,9 @@ constexpr int TILE = 16;          // keys per wave tile
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
@@ -79,8 +91,8 @@ int g_nt = 0;                     // NPM_TUNE_DECODE_NT: 0 by size (npm::stream_
 char g_last[96] = "";
 
 struct DecodeArgs {
-    const float *q, *k, *v;
-    long q_pitch, k_pitch, k_sb, v_pitch, v_sb;
+    const float *q, *k, *v;       // k, v: the cache in its storage type KV (halves behind a float pointer for KV = _Float16)
+    long q_pitch, k_pitch, k_sb, v_pitch, v_sb;   // k_ / v_: in elements of KV
     float *ctx;
     long ctx_pitch;
     float *lse;                   // optional [B, Hq, T]
@@ -107,6 +119,23 @@ __device__ __forceinline__ V ld_kv(const float *p) {
     return *reinterpret_cast<const V *>(p);
 }
 
+// The same elements out of an fp16 cache: one load of as many halves, converted exactly (v_cvt_f32_f16; subnormals are kept)
+template <int VW> struct HalfVecOf;
+template <> struct HalfVecOf<4> { using type = f16x4v; };
+template <> struct HalfVecOf<2> { using type = f16x2v; };
+template <> struct HalfVecOf<1> { using type = _Float16; };
+
+template <bool NT, typename V>
+__device__ __forceinline__ V ld_kv(const _Float16 *p) {
+    constexpr int VW = sizeof(V) / sizeof(float);
+    using H = typename HalfVecOf<VW>::type;
+    H h;
+    if (NT) h = __builtin_nontemporal_load(reinterpret_cast<const H *>(p));
+    else h = *reinterpret_cast<const H *>(p);
+    if constexpr (VW == 1) return (float)h;
+    else return __builtin_convertvector(h, V);
+}
+
 template <int VW> __device__ __forceinline__ float comp(const typename VecOf<VW>::type &x, int e) { return x[e]; }
 template <> __device__ __forceinline__ float comp<1>(const float &x, int) { return x; }
 
@@ -116,13 +145,14 @@ template <> __device__ __forceinline__ float comp<1>(const float &x, int) { retu
 // the VL = false instance computes; a block whose key range starts at or past L leaves an empty partial and returns before it
 // loads anything; a row without a visible key (a padded token, L = 0) is stored as ctx = 0, lse = -inf by selection.
 // PG (npm_mha_decode_fwd_paged, implies VL): a.k / a.v are page pools, a.k_sb / a.v_sb the page strides, pg the block table.
-template <int D, int RB, bool NT, bool VL, bool PG>
+// KV: the storage type of the cache, float or _Float16 (npm_mha_decode_fwd_f16); only the loads of load_tile know it.
+template <int D, int RB, bool NT, bool VL, bool PG, typename KV = float>
 __global__ void __launch_bounds__(WAVES * 64)
 mha_decode_kernel(const DecodeArgs a, const int *__restrict__ kv_lens, const int *__restrict__ new_lens, const PageArgs pg) {
 #pragma clang fp contract(off)
     static_assert(VL || !PG, "a paged cache has per-sequence lengths");
-    constexpr int KU = D / 16;                    // 16-byte K loads per lane and tile
-    constexpr int VW = D >= 64 ? 4 : D / 16;      // floats per V load
+    constexpr int KU = D / 16;                    // 4-element K loads per lane and tile (16 bytes; KV = _Float16: 8)
+    constexpr int VW = D >= 64 ? 4 : D / 16;      // elements per V load
     constexpr int DQ = D / (16 * VW);             // V loads per lane and key
     constexpr int NS = KU >= 4 ? 4 : KU;          // score accumulation chains
     using VVec = typename VecOf<VW>::type;
@@ -176,8 +206,8 @@ mha_decode_kernel(const DecodeArgs a, const int *__restrict__ kv_lens, const int
     const int tiles = (L + TILE - 1) / TILE;      // VL: the sequence's own tiles within the split ranges of a.len; every tile below
     const int t_begin = split * a.tiles_per_split;  // holds a key < L, so L >= 1 wherever a load is redirected to key L - 1
     const int t_end = min(tiles, t_begin + a.tiles_per_split);
-    const float *kbase = a.k + (PG ? 0L : (long)b * a.k_sb) + (long)c * D + 4 * g;
-    const float *vbase = a.v + (PG ? 0L : (long)b * a.v_sb) + (long)c * D + VW * n;
+    const KV *kbase = reinterpret_cast<const KV *>(a.k) + (PG ? 0L : (long)b * a.k_sb) + (long)c * D + 4 * g;
+    const KV *vbase = reinterpret_cast<const KV *>(a.v) + (PG ? 0L : (long)b * a.v_sb) + (long)c * D + VW * n;
 
     f32x4v kr[KU];
     VVec vr[4][DQ];
@@ -190,12 +220,12 @@ mha_decode_kernel(const DecodeArgs a, const int *__restrict__ kv_lens, const int
     auto load_tile = [&](int tile, int page) {
         const int key0 = tile * TILE;
         const int in_page = PG ? (1 << pg.shift) - 1 : ~0;                // PG: the row within the page
-        const float *kp = kbase + (PG ? (long)page * a.k_sb : 0L) + (long)(min(key0 + n, L - 1) & in_page) * a.k_pitch;
+        const KV *kp = kbase + (PG ? (long)page * a.k_sb : 0L) + (long)(min(key0 + n, L - 1) & in_page) * a.k_pitch;
 #pragma unroll
         for (int u = 0; u < KU; ++u) kr[u] = ld_kv<NT, f32x4v>(kp + 16 * u);
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
-            const float *vp = vbase + (PG ? (long)page * a.v_sb : 0L) + (long)(min(key0 + 4 * g + w, L - 1) & in_page) * a.v_pitch;
+            const KV *vp = vbase + (PG ? (long)page * a.v_sb : 0L) + (long)(min(key0 + 4 * g + w, L - 1) & in_page) * a.v_pitch;
 #pragma unroll
             for (int dq = 0; dq < DQ; ++dq) vr[w][dq] = ld_kv<NT, VVec>(vp + 16 * VW * dq);
         }
@@ -369,70 +399,94 @@ mha_decode_combine_kernel(const float *__restrict__ part_ml, const float *__rest
 // Where the rows of a cache live.  Contiguous (table == nullptr): row j of sequence b is base + b * stride + j * pitch.  Paged:
 // base is the page pool, stride the page stride and the row is row j & (page_rows - 1) of page table[b * table_pitch + (j >> shift)].
 struct RowLayout {
-    float *base;
+    float *base;                  // an fp16 cache: halves behind the float pointer; pitch and stride count elements of the cache
     long pitch, stride;
     const int *table;
     int table_pitch, shift;
 };
 
-template <bool PG>
-__device__ __forceinline__ float *row_of(const RowLayout &c, long b, int j) {
-    if (PG) return c.base + (long)c.table[b * c.table_pitch + (j >> c.shift)] * c.stride + (long)(j & ((1 << c.shift) - 1)) * c.pitch;
-    return c.base + b * c.stride + (long)j * c.pitch;
+template <bool PG, typename KV = float>
+__device__ __forceinline__ KV *row_of(const RowLayout &c, long b, int j) {
+    KV *base = reinterpret_cast<KV *>(c.base);
+    if (PG) return base + (long)c.table[b * c.table_pitch + (j >> c.shift)] * c.stride + (long)(j & ((1 << c.shift) - 1)) * c.pitch;
+    return base + b * c.stride + (long)j * c.pitch;
 }
+
+// 16 bytes of the cache per thread and step: 4 floats, or 8 halves (then two 16-byte accesses on the fp32 side)
+template <typename KV> struct RowVec { static constexpr int W = 4; };
+template <> struct RowVec<_Float16> { static constexpr int W = 8; };
 
 // row (at + t) of sequence b = src[b * T + t, :row_len], 16 bytes per thread and step.  VL = false (npm_kv_append): at is the scalar
 // and no length is loaded.  VL: at = at_lens[b], and only t < new_lens[b] (NULL: every t) is written; other rows are not touched.
-template <bool VL, bool PG>
+// KV = _Float16 (npm_kv_append_f16): the destination holds halves, rounded to nearest even here (row4: 8-column steps per row).
+template <bool VL, bool PG, typename KV = float>
 __global__ void __launch_bounds__(256)
 kv_append_kernel(const float *__restrict__ src, long src_pitch, const RowLayout dst, int tokens, int row4, int at,
                  const int *__restrict__ at_lens, const int *__restrict__ new_lens, long total) {
     static_assert(VL || !PG, "a paged cache has per-sequence lengths");
+    constexpr int W = RowVec<KV>::W;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int col = (int)(i % row4) * 4;
+        const int col = (int)(i % row4) * W;
         const long row = i / row4;
         const long b = row / tokens;
         const int t = (int)(row - b * tokens);
         if (VL && new_lens && t >= new_lens[b]) continue;
-        *reinterpret_cast<f32x4v *>(row_of<PG>(dst, b, (VL ? at_lens[b] : at) + t) + col) =
-            *reinterpret_cast<const f32x4v *>(src + row * src_pitch + col);
+        KV *to = row_of<PG, KV>(dst, b, (VL ? at_lens[b] : at) + t) + col;
+        const float *from = src + row * src_pitch + col;
+        if constexpr (W == 4) {
+            *reinterpret_cast<f32x4v *>(to) = *reinterpret_cast<const f32x4v *>(from);
+        } else {
+            const f16x4v lo = __builtin_convertvector(*reinterpret_cast<const f32x4v *>(from), f16x4v);
+            const f16x4v hi = __builtin_convertvector(*reinterpret_cast<const f32x4v *>(from + 4), f16x4v);
+            *reinterpret_cast<f16x8v *>(to) = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        }
     }
 }
 
 // out[b, j, :row_len] = j < lens[b] ? row j of sequence b : 0 for j < rows; out is [B, rows, row_len], contiguous.  Neither a row at
 // or past lens[b] nor its table entry is read.
-template <bool PG>
+// KV = _Float16 (npm_kv_gather_f16): the source holds halves, converted exactly (row4: 8-column steps per row).
+template <bool PG, typename KV = float>
 __global__ void __launch_bounds__(256)
 kv_gather_kernel(const RowLayout src, float *__restrict__ out, int rows, int row4, const int *__restrict__ lens, long total) {
+    constexpr int W = RowVec<KV>::W;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        const int col = (int)(i % row4) * 4;
+        const int col = (int)(i % row4) * W;
         const long row = i / row4;
         const long b = row / rows;
         const int j = (int)(row - b * rows);
-        f32x4v x{0.f, 0.f, 0.f, 0.f};
-        if (j < lens[b]) x = *reinterpret_cast<const f32x4v *>(row_of<PG>(src, b, j) + col);
-        *reinterpret_cast<f32x4v *>(out + row * (4L * row4) + col) = x;
+        if constexpr (W == 4) {
+            f32x4v x{0.f, 0.f, 0.f, 0.f};
+            if (j < lens[b]) x = *reinterpret_cast<const f32x4v *>(row_of<PG, KV>(src, b, j) + col);
+            *reinterpret_cast<f32x4v *>(out + row * (4L * row4) + col) = x;
+        } else {
+            f16x8v h = f16x8v((_Float16)0.f);
+            if (j < lens[b]) h = *reinterpret_cast<const f16x8v *>(row_of<PG, KV>(src, b, j) + col);
+            float *to = out + row * ((long)W * row4) + col;
+            *reinterpret_cast<f32x4v *>(to) = __builtin_convertvector(__builtin_shufflevector(h, h, 0, 1, 2, 3), f32x4v);
+            *reinterpret_cast<f32x4v *>(to + 4) = __builtin_convertvector(__builtin_shufflevector(h, h, 4, 5, 6, 7), f32x4v);
+        }
     }
 }
 
 // VL = false (npm_mha_decode_fwd): the instances that never look at the length arrays; PG: the ones that read through a block table
-template <int D, int RB, bool VL, bool PG>
+template <int D, int RB, bool VL, bool PG, typename KV>
 void launch_decode(const DecodeArgs &a, const int *kv_lens, const int *new_lens, const PageArgs &pg, dim3 grid, bool nt, hipStream_t s) {
-    if (nt) hipLaunchKernelGGL((mha_decode_kernel<D, RB, true, VL, PG>), grid, dim3(WAVES * 64), 0, s, a, kv_lens, new_lens, pg);
-    else hipLaunchKernelGGL((mha_decode_kernel<D, RB, false, VL, PG>), grid, dim3(WAVES * 64), 0, s, a, kv_lens, new_lens, pg);
+    if (nt) hipLaunchKernelGGL((mha_decode_kernel<D, RB, true, VL, PG, KV>), grid, dim3(WAVES * 64), 0, s, a, kv_lens, new_lens, pg);
+    else hipLaunchKernelGGL((mha_decode_kernel<D, RB, false, VL, PG, KV>), grid, dim3(WAVES * 64), 0, s, a, kv_lens, new_lens, pg);
 }
 
-template <int D>
+template <int D, typename KV>
 void launch_decode_rb(const DecodeArgs &a, const int *kv_lens, const int *new_lens, const PageArgs &pg, dim3 grid, int rb, bool nt,
                       hipStream_t s) {
     if (pg.table) {
-        if (rb == 1) launch_decode<D, 1, true, true>(a, kv_lens, new_lens, pg, grid, nt, s);
-        else launch_decode<D, 2, true, true>(a, kv_lens, new_lens, pg, grid, nt, s);
+        if (rb == 1) launch_decode<D, 1, true, true, KV>(a, kv_lens, new_lens, pg, grid, nt, s);
+        else launch_decode<D, 2, true, true, KV>(a, kv_lens, new_lens, pg, grid, nt, s);
     } else if (kv_lens) {
-        if (rb == 1) launch_decode<D, 1, true, false>(a, kv_lens, new_lens, pg, grid, nt, s);
-        else launch_decode<D, 2, true, false>(a, kv_lens, new_lens, pg, grid, nt, s);
-    } else if (rb == 1) launch_decode<D, 1, false, false>(a, nullptr, nullptr, pg, grid, nt, s);
-    else launch_decode<D, 2, false, false>(a, nullptr, nullptr, pg, grid, nt, s);
+        if (rb == 1) launch_decode<D, 1, true, false, KV>(a, kv_lens, new_lens, pg, grid, nt, s);
+        else launch_decode<D, 2, true, false, KV>(a, kv_lens, new_lens, pg, grid, nt, s);
+    } else if (rb == 1) launch_decode<D, 1, false, false, KV>(a, nullptr, nullptr, pg, grid, nt, s);
+    else launch_decode<D, 2, false, false, KV>(a, nullptr, nullptr, pg, grid, nt, s);
 }
 
 // page_rows -> log2, or -1 unless it is a power of two >= TILE
@@ -478,10 +532,13 @@ extern "C" const char *npm_last_decode_kernel(void) { return g_last; }
 
 // npm_mha_decode_fwd (kv_lens == nullptr), npm_mha_decode_fwd_varlen and npm_mha_decode_fwd_paged (block_table != nullptr): one
 // host path, so that the split count, the tile partition and the load policy of a varlen or paged call are those of the uniform
-// call at d->kv_len.
+// call at d->kv_len.  KV = _Float16 (npm_mha_decode_fwd_f16): d->k / d->v hold halves and their pitches and strides count halves
+// (multiples of 8: 16 bytes); the same checks, split count and partition, and the load policy on the BYTES of the valid part of K.
+template <typename KV = float>
 static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens,
                       const int32_t *block_table = nullptr, int32_t table_pitch = 0, int32_t page_rows = 0) {
     const bool varlen = kv_lens != nullptr, paged = block_table != nullptr;
+    constexpr int KV_ALIGN = 16 / sizeof(KV);                          // elements of the cache in 16 bytes
     NPM_REQUIRE_INIT();
     NPM_ARG(d != nullptr);
     PageArgs pg{};
@@ -501,8 +558,8 @@ static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *
         return npm::fail(NPM_E_UNSUPPORTED, "%s: head_dim %d with %d rows per K / V head is not supported "
                          "(head_dim in {16, 32, 64, 128}, rows <= %d)", name, D, rows, NPM_DECODE_MAX_ROWS);
     NPM_ARG(aligned16(d->q) && aligned16(d->k) && aligned16(d->v) && aligned16(d->ctx));
-    NPM_ARG(d->q_pitch % 4 == 0 && d->k_pitch % 4 == 0 && d->v_pitch % 4 == 0 && d->ctx_pitch % 4 == 0);
-    NPM_ARG(d->k_stride_b % 4 == 0 && d->v_stride_b % 4 == 0);
+    NPM_ARG(d->q_pitch % 4 == 0 && d->k_pitch % KV_ALIGN == 0 && d->v_pitch % KV_ALIGN == 0 && d->ctx_pitch % 4 == 0);
+    NPM_ARG(d->k_stride_b % KV_ALIGN == 0 && d->v_stride_b % KV_ALIGN == 0);
     NPM_ARG(d->q_pitch >= (int64_t)d->heads * D && d->ctx_pitch >= (int64_t)d->heads * D);
     NPM_ARG(d->k_pitch >= (int64_t)d->kv_heads * D && d->v_pitch >= (int64_t)d->kv_heads * D);
     NPM_ARG(d->batch <= 65535 && d->kv_heads <= 65535);
@@ -533,12 +590,12 @@ static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *
     // Each K / V byte is read once by one block.  Measured (tools/decode_bench.py, profiles/r08_decode_bench.log): from 64 MB of
     // K + V up the nontemporal hint is 3 - 13 % faster (the stream does not displace itself in the L2s and the Infinity Cache);
     // below that plain loads are 0 - 3 % faster.  The project's rule for streaming tensors (32 MB each) draws the same line.
-    const bool nt = g_nt == 1 || (g_nt == 0 && npm::stream_nt_enabled(sizeof(float) * (size_t)d->batch * d->kv_len * d->kv_heads * D));
+    const bool nt = g_nt == 1 || (g_nt == 0 && npm::stream_nt_enabled(sizeof(KV) * (size_t)d->batch * d->kv_len * d->kv_heads * D));
     switch (D) {
-        case 16: launch_decode_rb<16>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
-        case 32: launch_decode_rb<32>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
-        case 64: launch_decode_rb<64>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
-        default: launch_decode_rb<128>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+        case 16: launch_decode_rb<16, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+        case 32: launch_decode_rb<32, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+        case 64: launch_decode_rb<64, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+        default: launch_decode_rb<128, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
     }
     NPM_CHECK_LAUNCH();
     if (splits > 1) {
@@ -560,7 +617,8 @@ static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *
     }
     int at = snprintf(g_last, sizeof g_last, "mha_decode_kernel D=%d rows=%d splits=%d causal=%d%s", D, rows, splits, a.causal,
                       varlen ? " varlen=1" : "");
-    if (paged) snprintf(g_last + at, sizeof g_last - at, " paged=%d", page_rows);
+    if (paged) at += snprintf(g_last + at, sizeof g_last - at, " paged=%d", page_rows);
+    if (sizeof(KV) == 2) snprintf(g_last + at, sizeof g_last - at, " kv=f16");
     return NPM_OK;
 }
 
@@ -580,10 +638,25 @@ extern "C" int npm_mha_decode_fwd_paged(const npm_mha_decode *d, const int32_t *
     return decode_fwd("npm_mha_decode_fwd_paged", d, kv_lens, new_lens, block_table, table_pitch, page_rows);
 }
 
+// The three layouts over an fp16 cache: NULL kv_lens is npm_mha_decode_fwd, NULL block_table npm_mha_decode_fwd_varlen, else
+// npm_mha_decode_fwd_paged -- with the refusals of that entry point.
+extern "C" int npm_mha_decode_fwd_f16(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens,
+                                      const int32_t *block_table, int32_t table_pitch, int32_t page_rows) {
+    if (block_table != nullptr) {
+        if (kv_lens == nullptr) return npm::fail(NPM_E_BAD_ARGUMENT, "npm_mha_decode_fwd_f16: a block table needs kv_lens");
+        if (page_shift(page_rows) < 0)
+            return npm::fail(NPM_E_BAD_ARGUMENT, "npm_mha_decode_fwd_f16: page_rows %d is not a power of two >= %d", page_rows, TILE);
+    }
+    return decode_fwd<_Float16>("npm_mha_decode_fwd_f16", d, kv_lens, new_lens, block_table, table_pitch, page_rows);
+}
+
 // What the five row-copy entry points share, after NPM_REQUIRE_INIT and the preconditions that hold even for an empty call: the
 // checks, the grid and the launch.  ``rows`` [batch * count, row_len] with pitch rows_pitch is the source of an append (gather =
 // false) or the contiguous destination of a gather; ``lens``: at_lens of a ragged append (NULL: the uniform one at ``at``) or the
-// lengths of a gather; page_rows > 0: ``cache`` is paged.  An empty call is NPM_OK whatever the pointers are.
+// lengths of a gather; page_rows > 0: ``cache`` is paged.  An empty call is NPM_OK whatever the pointers are.  KV = _Float16: the
+// cache holds halves (its pitch and stride count halves), ``rows`` stays fp32; 8 columns per thread, so everything on the fp16 side
+// and row_len are multiples of 8.
+template <typename KV = float>
 static int row_copy(const char *name, bool gather, const float *rows, int64_t rows_pitch, const RowLayout &cache, int32_t page_rows,
                     int32_t batch, int32_t count, int32_t row_len, bool ragged, int32_t at, const int32_t *lens,
                     const int32_t *new_lens) {
@@ -595,35 +668,36 @@ static int row_copy(const char *name, bool gather, const float *rows, int64_t ro
     if (batch == 0 || count == 0 || row_len == 0) return NPM_OK;
     ROW_ARG(rows != nullptr && cache.base != nullptr && (lens != nullptr || !ragged));
     ROW_ARG(aligned16(rows) && aligned16(cache.base));
-    ROW_ARG(row_len % 4 == 0 && rows_pitch % 4 == 0 && cache.pitch % 4 == 0 && cache.stride % 4 == 0);
+    constexpr int W = RowVec<KV>::W;
+    ROW_ARG(row_len % W == 0 && rows_pitch % 4 == 0 && cache.pitch % W == 0 && cache.stride % W == 0);
     ROW_ARG(rows_pitch >= row_len && cache.pitch >= row_len && (!page_rows || cache.stride >= (int64_t)page_rows * cache.pitch));
 #undef ROW_ARG
-    const long total = (long)batch * count * (row_len / 4);
+    const long total = (long)batch * count * (row_len / W);
     const dim3 grid((unsigned)std::min<long>((total + 255) / 256, 2048)), block(256);
     hipStream_t s = npm::ctx().stream;
-    const int row4 = row_len / 4;
+    const int row4 = row_len / W;
     if (gather) {
         float *out = const_cast<float *>(rows);                       // the entry point's own float *out
-        if (page_rows) hipLaunchKernelGGL(kv_gather_kernel<true>, grid, block, 0, s, cache, out, count, row4, lens, total);
-        else hipLaunchKernelGGL(kv_gather_kernel<false>, grid, block, 0, s, cache, out, count, row4, lens, total);
+        if (page_rows) hipLaunchKernelGGL((kv_gather_kernel<true, KV>), grid, block, 0, s, cache, out, count, row4, lens, total);
+        else hipLaunchKernelGGL((kv_gather_kernel<false, KV>), grid, block, 0, s, cache, out, count, row4, lens, total);
     } else if (page_rows) {
-        hipLaunchKernelGGL((kv_append_kernel<true, true>), grid, block, 0, s, rows, (long)rows_pitch, cache, count, row4, at, lens, new_lens, total);
+        hipLaunchKernelGGL((kv_append_kernel<true, true, KV>), grid, block, 0, s, rows, (long)rows_pitch, cache, count, row4, at, lens, new_lens, total);
     } else if (ragged) {
-        hipLaunchKernelGGL((kv_append_kernel<true, false>), grid, block, 0, s, rows, (long)rows_pitch, cache, count, row4, at, lens, new_lens, total);
+        hipLaunchKernelGGL((kv_append_kernel<true, false, KV>), grid, block, 0, s, rows, (long)rows_pitch, cache, count, row4, at, lens, new_lens, total);
     } else {
-        hipLaunchKernelGGL((kv_append_kernel<false, false>), grid, block, 0, s, rows, (long)rows_pitch, cache, count, row4, at, lens, new_lens, total);
+        hipLaunchKernelGGL((kv_append_kernel<false, false, KV>), grid, block, 0, s, rows, (long)rows_pitch, cache, count, row4, at, lens, new_lens, total);
     }
     NPM_CHECK_LAUNCH();
     return NPM_OK;
 }
 
-static RowLayout contiguous(const float *cache, int64_t pitch, int64_t stride_b) {
-    return RowLayout{const_cast<float *>(cache), (long)pitch, (long)stride_b, nullptr, 0, 0};
+static RowLayout contiguous(const void *cache, int64_t pitch, int64_t stride_b) {
+    return RowLayout{static_cast<float *>(const_cast<void *>(cache)), (long)pitch, (long)stride_b, nullptr, 0, 0};
 }
 
-static RowLayout paged(const float *pool, int64_t row_pitch, int64_t page_stride, const int32_t *table, int32_t table_pitch,
+static RowLayout paged(const void *pool, int64_t row_pitch, int64_t page_stride, const int32_t *table, int32_t table_pitch,
                        int32_t page_rows) {
-    return RowLayout{const_cast<float *>(pool), (long)row_pitch, (long)page_stride, table, table_pitch, page_shift(page_rows)};
+    return RowLayout{static_cast<float *>(const_cast<void *>(pool)), (long)row_pitch, (long)page_stride, table, table_pitch, page_shift(page_rows)};
 }
 
 extern "C" int npm_kv_append(const float *src, int64_t src_pitch, float *cache, int64_t cache_pitch, int64_t cache_stride_b,
@@ -665,4 +739,34 @@ extern "C" int npm_kv_gather_paged(const float *pool, int64_t row_pitch, int64_t
     NPM_ARG(lens != nullptr && block_table != nullptr && table_pitch >= 0 && page_shift(page_rows) >= 0);
     return row_copy("npm_kv_gather_paged", true, out, row_len, paged(pool, row_pitch, page_stride, block_table, table_pitch, page_rows),
                     page_rows, batch, rows, row_len, true, 0, lens, nullptr);
+}
+
+// The row copies of an fp16 cache, each the entry point of its layout above: at_lens == NULL is npm_kv_append at ``at``,
+// block_table == NULL the contiguous cache (cache_stride the batch stride), else the page pool (cache_stride the page stride).
+extern "C" int npm_kv_append_f16(const float *src, int64_t src_pitch, void *cache, int64_t cache_pitch, int64_t cache_stride,
+                                 int32_t batch, int32_t new_tokens, int32_t row_len, int32_t at, const int32_t *at_lens,
+                                 const int32_t *new_lens, const int32_t *block_table, int32_t table_pitch, int32_t page_rows) {
+    NPM_REQUIRE_INIT();
+    if (block_table != nullptr) {
+        NPM_ARG(at_lens != nullptr && table_pitch >= 0 && page_shift(page_rows) >= 0);
+        return row_copy<_Float16>("npm_kv_append_f16", false, src, src_pitch,
+                                  paged(cache, cache_pitch, cache_stride, block_table, table_pitch, page_rows), page_rows, batch,
+                                  new_tokens, row_len, true, 0, at_lens, new_lens);
+    }
+    return row_copy<_Float16>("npm_kv_append_f16", false, src, src_pitch, contiguous(cache, cache_pitch, cache_stride), 0, batch,
+                              new_tokens, row_len, at_lens != nullptr, at_lens ? 0 : at, at_lens, new_lens);
+}
+
+extern "C" int npm_kv_gather_f16(const void *cache, int64_t cache_pitch, int64_t cache_stride, float *out, int32_t batch,
+                                 int32_t rows, int32_t row_len, const int32_t *lens, const int32_t *block_table,
+                                 int32_t table_pitch, int32_t page_rows) {
+    NPM_REQUIRE_INIT();
+    if (block_table != nullptr) {
+        NPM_ARG(lens != nullptr && table_pitch >= 0 && page_shift(page_rows) >= 0);
+        return row_copy<_Float16>("npm_kv_gather_f16", true, out, row_len,
+                                  paged(cache, cache_pitch, cache_stride, block_table, table_pitch, page_rows), page_rows, batch,
+                                  rows, row_len, true, 0, lens, nullptr);
+    }
+    return row_copy<_Float16>("npm_kv_gather_f16", true, out, row_len, contiguous(cache, cache_pitch, cache_stride), 0, batch, rows,
+                              row_len, true, 0, lens, nullptr);
 }

@@ -550,6 +550,27 @@ class ByteBuffer:
         return out
 
 
+class HalfBuffer(ByteBuffer):
+    """Raw device storage of ``shape`` IEEE fp16 elements: the K or V tensor of a half-precision ``KVCache``.  It has a shape, an
+    address and a size, and no arithmetic: nothing outside the cache classes reads it as floats (``npm_kv_gather_f16`` is how its
+    rows come back as fp32).  ``numpy()``: the stored halves, for tests."""
+
+    __slots__ = ('shape',)
+
+    def __init__(self, shape: Sequence[int]):
+        self.shape = tuple(int(s) for s in shape)
+        ByteBuffer.__init__(self, 2 * _prod(self.shape))
+
+    def numpy(self) -> np.ndarray:
+        return ByteBuffer.numpy(self).view(np.float16).reshape(self.shape)
+
+    def __deepcopy__(self, memo):
+        out = HalfBuffer.__new__(HalfBuffer)
+        out._buf = self._buf.__deepcopy__(memo)
+        out.ptr, out.nbytes, out.shape = out._buf.ptr, self.nbytes, self.shape
+        return out
+
+
 def bytes_from_host(value: np.ndarray) -> ByteBuffer:
     host = np.ascontiguousarray(value).view(np.uint8)
     out = ByteBuffer(host.nbytes)
@@ -1041,12 +1062,27 @@ def mha_decode_supported(head_dim: int, group_rows: int, value_dim: Optional[int
 class KVLayout(NamedTuple):
     """Where the rows of one cache tensor live, as the entry points of include/npm_hip.h take it.  Contiguous: row j of sequence b
     is ``pitch`` floats long at ``b * stride + j * pitch``.  Paged (``table``: the DEVICE address of the block table, int32
-    [B, table_pitch]): ``stride`` is that of a page and the row is row ``j % page_rows`` of page ``table[b, j // page_rows]``."""
+    [B, table_pitch]): ``stride`` is that of a page and the row is row ``j % page_rows`` of page ``table[b, j // page_rows]``.
+    ``dtype`` 'f16': the tensor holds halves (``pitch`` and ``stride`` count elements either way) and the calls are the ``_f16``
+    entry points."""
     pitch: int
     stride: int
     table: Optional[int] = None
     table_pitch: int = 0
     page_rows: int = 0
+    dtype: str = 'f32'
+
+
+KV_ITEMSIZE = {'f32': 4, 'f16': 2}            # the storage types of a KVCache and their bytes per element
+
+
+def _kv_dtype(dtype, kv_heads: int, key_dim: int, value_dim: int) -> str:
+    if dtype not in KV_ITEMSIZE:
+        raise ValueError(f"KVCache: dtype must be one of {sorted(KV_ITEMSIZE)}, got {dtype!r}")
+    if dtype == 'f16' and (kv_heads * key_dim % 8 or kv_heads * value_dim % 8):
+        raise ValueError(f'KVCache: an f16 cache moves 8 halves at a time: rows of {kv_heads * key_dim} / {kv_heads * value_dim} '
+                         'elements are not multiples of 8')
+    return dtype
 
 
 def kv_append(src: Mat, dst: int, layout: KVLayout, batch: int, tokens: int, at: int, lens, rows: int) -> None:
@@ -1056,6 +1092,12 @@ def kv_append(src: Mat, dst: int, layout: KVLayout, batch: int, tokens: int, at:
     (npm_kv_append_varlen; through the block table of a paged ``layout`` npm_kv_append_paged, which always has ``lens``).  The
     caller has checked that the rows fit; ``rows``: the rows written, for the timer."""
     row = layout.pitch
+    if layout.dtype == 'f16':
+        at_lens, new_lens = (None, None) if lens is None else lens
+        with _timed('kv_append', nbytes=6.0 * rows * row):
+            _C.check(_C.lib().npm_kv_append_f16(src.ptr, src.ld, dst, row, layout.stride, batch, tokens, row, at, at_lens, new_lens,
+                                                layout.table, layout.table_pitch, layout.page_rows), 'npm_kv_append_f16')
+        return
     with _timed('kv_append', nbytes=8.0 * rows * row):
         if layout.table is not None:
             _C.check(_C.lib().npm_kv_append_paged(src.ptr, src.ld, dst, row, layout.stride, batch, tokens, row, lens[0], lens[1],
@@ -1073,6 +1115,11 @@ def kv_gather_rows(src: int, layout: KVLayout, out: DeviceArray, lens: int) -> N
     of [B] int32."""
     b, rows, row = out.shape[0], out.shape[1], layout.pitch
     assert out.size == b * rows * row
+    if layout.dtype == 'f16':
+        with _timed('kv_gather', nbytes=6.0 * b * rows * row):
+            _C.check(_C.lib().npm_kv_gather_f16(src, row, layout.stride, out.ptr, b, rows, row, lens, layout.table, layout.table_pitch,
+                                                layout.page_rows), 'npm_kv_gather_f16')
+        return
     with _timed('kv_gather', nbytes=8.0 * b * rows * row):
         if layout.table is not None:
             _C.check(_C.lib().npm_kv_gather_paged(src, row, layout.stride, out.ptr, b, rows, row, lens, layout.table, layout.table_pitch,
@@ -1122,6 +1169,12 @@ def mha_decode(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, s
     c, ctx, lse, layout = _decode_desc(q, cache, heads, tokens, kv_len, scale, causal, want_lse)
     b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
     keys = b * kv_len if keys is None else int(keys)
+    if cache.dtype == 'f16':
+        kv_lens, new_lens = (None, None) if lens is None else lens
+        with _timed('mha_decode', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + hkv * keys)):
+            _C.check(_C.lib().npm_mha_decode_fwd_f16(C.byref(c), kv_lens, new_lens, layout.table, layout.table_pitch, layout.page_rows),
+                     'npm_mha_decode_fwd_f16')
+        return ctx, lse
     with _timed('mha_decode', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + 2 * hkv * keys)):
         if layout.table is not None:
             _C.check(_C.lib().npm_mha_decode_fwd_paged(C.byref(c), lens[0], lens[1], layout.table, layout.table_pitch, layout.page_rows),
@@ -1177,26 +1230,44 @@ class KVCache:
     attention that follows it).
 
     ``append``, ``attend`` and ``gather`` are written once, here: where the rows live is ``layout(x)``, which the wrappers above
-    turn into the entry point.  ``paged``: whether that is a page pool (``PagedKVCache``)."""
+    turn into the entry point.  ``paged``: whether that is a page pool (``PagedKVCache``).
+
+    ``dtype`` 'f16': ``k`` and ``v`` are ``HalfBuffer`` s of the same geometry and half the bytes.  Rows are rounded to IEEE fp16
+    once, by the append (round to nearest even; |x| >= 65520 becomes inf), and every reader -- the decode kernel, ``gather`` -- sees
+    them as stored, converted back exactly (npm_kv_append_f16 / npm_mha_decode_fwd_f16 / npm_kv_gather_f16); there is no fp16
+    prefill kernel.  ``itemsize`` is the bytes per stored element and ``nbytes`` those of K + V."""
 
     paged = False
 
-    def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None):
+    def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None, dtype: str = 'f32'):
         value_dim = key_dim if value_dim is None else value_dim
         if min(batch, capacity, kv_heads, key_dim, value_dim) < 1:
             raise ValueError('KVCache: batch, capacity, kv_heads and the head sizes must be positive')
+        self.dtype = _kv_dtype(dtype, int(kv_heads), int(key_dim), int(value_dim))
         self.batch, self.capacity, self.kv_heads = int(batch), int(capacity), int(kv_heads)
         self.key_dim, self.value_dim = int(key_dim), int(value_dim)
-        self.k = empty([batch, capacity, kv_heads, key_dim])
-        self.v = empty([batch, capacity, kv_heads, value_dim])
+        self.k = self._storage([batch, capacity, kv_heads, key_dim])
+        self.v = self._storage([batch, capacity, kv_heads, value_dim])
         self.lengths = np.zeros([self.batch], dtype=np.int64)
         self._mirror = None               # (host int32 [3, B]: before, new, after; ByteBuffer) of the last ragged call
         self.frozen = False
 
-    def layout(self, x: DeviceArray) -> KVLayout:
-        """Where the rows of ``x`` (``k`` or ``v``) live."""
+    def _storage(self, shape):
+        return empty(shape) if self.dtype == 'f32' else HalfBuffer(shape)
+
+    @property
+    def itemsize(self) -> int:
+        return KV_ITEMSIZE[self.dtype]
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of K + V storage."""
+        return self.k.nbytes + self.v.nbytes
+
+    def layout(self, x) -> KVLayout:
+        """Where the rows of ``x`` (``k`` or ``v``) live; pitches in elements."""
         row = self.kv_heads * x.shape[3]
-        return KVLayout(row, self.capacity * row)
+        return KVLayout(row, self.capacity * row, dtype=self.dtype)
 
     @property
     def ragged(self) -> bool:
@@ -1296,7 +1367,7 @@ class KVCache:
         for src, dst in ((k, self.k), (v, self.v)):
             if src is not None:
                 layout = self.layout(dst)
-                kv_append(src, dst.ptr + 4 * b * layout.stride, layout, 1, rows, 0, None, rows)
+                kv_append(src, dst.ptr + self.itemsize * b * layout.stride, layout, 1, rows, 0, None, rows)
         self.lengths[b] = rows
 
     def attend(self, q: Mat, heads: int, tokens: int, scale: float, causal: bool, want_lse: bool = False, new_lengths=None,
@@ -1307,6 +1378,9 @@ class KVCache:
         number of rows (a uniform cache shorter than the query -- a frozen one -- takes its per-sequence call)."""
         if kernel not in ('decode', 'prefill'):
             raise ValueError(f"KVCache.attend: kernel must be 'decode' or 'prefill', got {kernel!r}")
+        if kernel == 'prefill' and self.dtype != 'f32':
+            raise ValueError(f"KVCache.attend: the prefill kernel reads fp32 caches only; an {self.dtype} cache takes kernel='decode' "
+                             'or gather()')
         attend = mha_prefill if kernel == 'prefill' else mha_decode
         n = self.new_lengths(tokens, new_lengths)
         if self._scalar_call(n) and (kernel == 'decode' or tokens <= int(self.lengths[0])):
@@ -1350,10 +1424,11 @@ class PagedKVCache(KVCache):
     paged = True
 
     def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None, *, page_size: int,
-                 pages: Optional[int] = None):
+                 pages: Optional[int] = None, dtype: str = 'f32'):
         value_dim = key_dim if value_dim is None else value_dim
         if min(batch, capacity, kv_heads, key_dim, value_dim) < 1:
             raise ValueError('PagedKVCache: batch, capacity, kv_heads and the head sizes must be positive')
+        self.dtype = _kv_dtype(dtype, int(kv_heads), int(key_dim), int(value_dim))
         page_size = int(page_size)
         if page_size < 16 or page_size & (page_size - 1):
             raise ValueError(f'PagedKVCache: page_size must be a power of two >= 16, got {page_size}')
@@ -1364,14 +1439,14 @@ class PagedKVCache(KVCache):
         self.pages = self.batch * self.pages_per_sequence if pages is None else int(pages)
         if self.pages < 1:
             raise ValueError(f'PagedKVCache: pages must be positive, got {pages}')
-        self.k = empty([self.pages, page_size, kv_heads, key_dim])
-        self.v = empty([self.pages, page_size, kv_heads, value_dim])
+        self.k = self._storage([self.pages, page_size, kv_heads, key_dim])
+        self.v = self._storage([self.pages, page_size, kv_heads, value_dim])
         self.table_uploads = 0
         self.reset()
 
-    def layout(self, x: DeviceArray) -> KVLayout:
+    def layout(self, x) -> KVLayout:
         row = self.kv_heads * x.shape[3]
-        return KVLayout(row, self.page_size * row, self._device_table(), self.pages_per_sequence, self.page_size)
+        return KVLayout(row, self.page_size * row, self._device_table(), self.pages_per_sequence, self.page_size, self.dtype)
 
     def reset(self) -> None:
         KVCache.reset(self)

@@ -251,23 +251,32 @@ class MultiHeadAttention(layer.StatefulLayer):
         return out
 
     # -- incremental decoding ------------------------------------------------------------------
-    def make_cache(self, batch: int, capacity: int, page_size: Optional[int] = None, pages: Optional[int] = None) -> D.KVCache:
+    def make_cache(self, batch: int, capacity: int, page_size: Optional[int] = None, pages: Optional[int] = None,
+                   dtype: str = 'f32') -> D.KVCache:
         """An empty key / value cache for ``batch`` sequences of up to ``capacity`` tokens (Hkv heads: grouped-query attention
         keeps its smaller cache).  The layer must have its parameters (one forward, or a weight binder).
 
         ``page_size`` (a power of two >= 16): a ``device.PagedKVCache`` -- rows live in a pool of ``pages`` pages (None: enough
-        for every sequence to reach ``capacity``) that sequences take as they grow and give back with ``cache.release(b)``."""
+        for every sequence to reach ``capacity``) that sequences take as they grow and give back with ``cache.release(b)``.
+
+        ``dtype`` 'f16': K / V rows are stored as IEEE fp16 (half the bytes; see ``device.KVCache``) and every attention over the
+        cache sees them as stored.  It needs the head sizes the decode kernel takes."""
         if not self._initialized:
             raise RuntimeError('make_cache: the layer has no parameters yet (run one forward, or bind weights, first)')
+        if dtype not in D.KV_ITEMSIZE:
+            raise ValueError(f"make_cache: dtype must be one of {sorted(D.KV_ITEMSIZE)}, got {dtype!r}")
+        dk, dv = self._key_dim, self._value_dim
+        if dtype != 'f32' and not (dk == dv and dk in (16, 32, 64, 128)):
+            raise NotImplementedError(f'an {dtype} cache needs head sizes Dk == Dv in {{16, 32, 64, 128}} (the decode kernel and the '
+                                      f'fused masked forward on the gathered rows), got {dk} / {dv}')
         if page_size is None:
             if pages is not None:
                 raise ValueError('make_cache: pages= sizes the pool of a paged cache: it needs page_size=')
-            return D.KVCache(batch, capacity, self._num_kv_heads, self._key_dim, self._value_dim)
-        dk, dv = self._key_dim, self._value_dim
+            return D.KVCache(batch, capacity, self._num_kv_heads, dk, dv, dtype=dtype)
         if not (D.mha_decode_supported(dk, self._num_heads // self._num_kv_heads, dv) or D.mha_core_supported(dk, dv, any_math=True)):
             raise NotImplementedError('a paged cache needs head sizes Dk == Dv in {16, 32, 64, 128} (the decode kernel or '
                                       'the fused masked forward); the GEMM composition has no masked softmax')
-        return D.PagedKVCache(batch, capacity, self._num_kv_heads, dk, dv, page_size=page_size, pages=pages)
+        return D.PagedKVCache(batch, capacity, self._num_kv_heads, dk, dv, page_size=page_size, pages=pages, dtype=dtype)
 
     def fill_cache(self, cache: D.KVCache, key, value=None, lengths=None) -> D.KVCache:
         """Cross-attention: project ``key`` / ``value`` [B, Skv, F] once into ``cache`` and freeze it; ``forward(x, cache=cache)``
@@ -302,7 +311,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         # a paged cache has no [B, capacity, Hkv, D] tensor to hand to the uniform paths: it always takes the per-sequence route,
         # whose kernels read through the block table (uniform lengths are bitwise the uniform entry point there)
         ragged = new_lengths is not None or cache.ragged or cache.paged
-        if ragged and not (D.mha_decode_supported(dk, h // hkv * t, dv) or D.mha_core_supported(dk, dv, any_math=True)):
+        if (ragged or cache.dtype != 'f32') and not (D.mha_decode_supported(dk, h // hkv * t, dv) or D.mha_core_supported(dk, dv, any_math=True)):
             raise NotImplementedError('per-sequence lengths need head sizes Dk == Dv in {16, 32, 64, 128} (the decode kernel or '
                                       'the fused masked forward); the GEMM composition has no masked softmax')
         if not cross:
@@ -351,6 +360,12 @@ class MultiHeadAttention(layer.StatefulLayer):
         if t <= length and D.mha_decode_supported(dk, h // hkv * t, dv):     # (the kernel's contract: L >= T, causal or not)
             self._cached_path = 'decode'
             return cache.attend(q, h, t, scale, causal)[0]
+        if cache.dtype != 'f32':
+            # a half-precision cache is attended to AS STORED, the new tokens' own rows included: whatever the decode kernel
+            # does not take is the fused masked forward on the gathered fp32 copies of the stored rows -- never the fresh
+            # projection, the cache tensors themselves or the prefill kernel
+            before = cache.lengths - t if causal else cache.lengths
+            return self._attend_ragged(q, cache, t, causal, None, before, None, decode_ok=False)
         if D.PREFILL_KERNEL and D.mha_prefill_supported(dk, dv) and not (fresh is not None and length == t):
             # more rows than the decode kernel takes on top of cached rows, or over a frozen cache: the prefill kernel reads the
             # cache in place (no copy of the valid rows, no mask).  A prefill from empty stays below: the fused forward reads
@@ -387,17 +402,21 @@ class MultiHeadAttention(layer.StatefulLayer):
                        Mat(ctx.ptr + 4 * (first * h * dv + g * pv), h * dv, t * h * dv, dv), batch=(b, hkv))
         return ctx
 
-    def _attend_ragged(self, q: Mat, cache: D.KVCache, t: int, causal: bool, fresh, before: np.ndarray, new_lengths) -> D.DeviceArray:
+    def _attend_ragged(self, q: Mat, cache: D.KVCache, t: int, causal: bool, fresh, before: np.ndarray, new_lengths,
+                       decode_ok: bool = True) -> D.DeviceArray:
         """``_attend_cached`` when the sequences differ: ``before`` [B] rows were valid before this call, sequence b brings
         ``new_lengths[b]`` (None: T) of the T padded query rows.  Row t < n[b] sees keys j <= before[b] + t (causal) or
-        j < lengths[b] (frozen cache)."""
+        j < lengths[b] (frozen cache).  A half-precision cache is attended to as stored: the decode kernel, or the fused masked
+        forward on ``cache.gather`` -- not the prefill kernel, not ``fresh``.  ``decode_ok`` False: the caller (a uniform
+        half-precision cache) has found that the decode kernel does not take the call."""
         h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
         b, scale = cache.batch, 1.0 / math.sqrt(self._key_dim)
         n = np.full([b], t, dtype=np.int64) if new_lengths is None else new_lengths
-        if D.mha_decode_supported(dk, h // hkv * t, dv):
+        stored = cache.dtype != 'f32'
+        if decode_ok and D.mha_decode_supported(dk, h // hkv * t, dv):
             self._cached_path = 'decode'
             return cache.attend(q, h, t, scale, causal, new_lengths=n)[0]
-        if D.PREFILL_KERNEL and D.mha_prefill_supported(dk, dv):
+        if not stored and D.PREFILL_KERNEL and D.mha_prefill_supported(dk, dv):
             # a ragged prefill, a chunk of one, a sequence admitted beside decoding ones, a paged or a frozen cache: the prefill
             # kernel over the cache in place, through the block table -- lengths and causality are arithmetic on the device
             self._cached_path = 'prefill'
@@ -406,7 +425,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         # skips what lies past them.  K / V: the fresh projection when every sequence started empty (keys = T; the rows of padded
         # tokens are masked), else the valid rows gathered with zeros behind them (P = 0 times stale memory could be NaN).
         self._cached_path = 'fused_masked'
-        if fresh is not None and not before.any():
+        if fresh is not None and not stored and not before.any():
             keys, (k, v) = t, fresh
         else:
             keys = cache.max_length

@@ -321,7 +321,7 @@ class TransformerDecoder(layer.Layer):
 
     # -- incremental decoding (inference) ------------------------------------------------------------------------------
     def start_decoding(self, kv, capacity: int, kv_lengths=None, *, page_size: Optional[int] = None, pages: Optional[int] = None,
-                       memory_capacity: Optional[int] = None) -> 'DecodeState':
+                       memory_capacity: Optional[int] = None, cache_dtype: str = 'f32') -> 'DecodeState':
         """Caches for ``decode``: an empty self-attention cache of ``capacity`` tokens per sequence and the cross-attention's
         keys / values, projected from ``kv`` [B, Skv, F] once.  ``kv_lengths`` [B]: ``kv`` is padded on the right and sequence b
         has only that many memory rows.  The layer must have its parameters (one forward, or bound weights).
@@ -329,7 +329,12 @@ class TransformerDecoder(layer.Layer):
         ``page_size`` (and ``pages``): the self-attention cache is a ``device.PagedKVCache`` -- ``DecodeState.release(b)`` returns
         a finished sequence's pages and ``admit`` puts a new sequence into its slot.  The cross-attention cache stays contiguous
         (the memory fixes its size); ``memory_capacity`` (default Skv) is its row count, so that a sequence admitted later may
-        bring a longer memory than the first batch had."""
+        bring a longer memory than the first batch had.
+
+        ``cache_dtype`` 'f16': both caches -- the self-attention one and the frozen cross-attention one -- store their K / V rows as
+        IEEE fp16 (``MultiHeadAttention.make_cache(dtype=)``): half the cache bytes, attention over the rows as stored."""
+        if cache_dtype not in D.KV_ITEMSIZE:
+            raise ValueError(f"start_decoding: cache_dtype must be one of {sorted(D.KV_ITEMSIZE)}, got {cache_dtype!r}")
         if not (self._initialized and self._self_attention._initialized and self._cross_attention._initialized):
             raise RuntimeError('start_decoding: the decoder has no parameters yet (run one forward, or bind weights, first)')
         kv = D.as_device(kv)
@@ -337,10 +342,10 @@ class TransformerDecoder(layer.Layer):
         rows = seq_kv if memory_capacity is None else int(memory_capacity)
         if rows < seq_kv:
             raise ValueError(f'start_decoding: memory_capacity {rows} is less than the {seq_kv} memory rows given')
-        cross = self._cross_attention.fill_cache(self._cross_attention.make_cache(batch, rows), kv, lengths=kv_lengths)
+        cross = self._cross_attention.fill_cache(self._cross_attention.make_cache(batch, rows, dtype=cache_dtype), kv, lengths=kv_lengths)
         if page_size is None and pages is None:
-            return DecodeState(self._self_attention.make_cache(batch, capacity), cross)
-        return DecodeState(self._self_attention.make_cache(batch, capacity, page_size=page_size, pages=pages), cross)
+            return DecodeState(self._self_attention.make_cache(batch, capacity, dtype=cache_dtype), cross)
+        return DecodeState(self._self_attention.make_cache(batch, capacity, page_size=page_size, pages=pages, dtype=cache_dtype), cross)
 
     def admit(self, state: 'DecodeState', b: int, kv_b, kv_length: Optional[int] = None) -> None:
         """A new sequence into slot ``b`` of a running batch (``state.release(b)`` emptied it): its memory ``kv_b`` [1, Skv, F]
