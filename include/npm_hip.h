@@ -494,6 +494,17 @@ int npm_kv_gather_f16(const void *cache, int64_t cache_pitch, int64_t cache_stri
                       int32_t row_len, const int32_t *lens, const int32_t *block_table, int32_t table_pitch, int32_t page_rows);
 int npm_mha_decode_fwd_f16(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens, const int32_t *block_table,
                            int32_t table_pitch, int32_t page_rows);
+/* npm_mha_prefill_fwd over an fp16 cache: the same arguments, layouts (kv_lens / block_table NULL or not), refusals and error codes,
+ * except that d->k / d->v point at halves, their pitches and strides (the page stride d->k_stride_b included) count HALVES and are
+ * multiples of 8 (the fp32 entry point: 4 floats), and every pointer is 16-byte aligned.  The kernel (mha_prefill_f16_kernel, the
+ * same body as mha_prefill_kernel) loads 8 halves per 16-byte piece and converts them exactly on the way into LDS, which then
+ * holds the fp32 tiles of the fp32 kernel in the same layout; everything behind that is the same code.  Hence the call is BITWISE
+ * npm_mha_prefill_fwd of the same layout on a cache that holds the rounded values as floats, ctx and lse, and inherits its
+ * identities (paged = contiguous, a sequence in a batch = that sequence alone, kv_lens == NULL = all lengths equal).  Nothing at or
+ * past row L_b is read into a result; a block without a live row loads nothing.  head_dim as npm_mha_prefill_supported.
+ * npm_last_prefill_kernel() afterwards: the fp32 string of the same layout followed by " kv=f16". */
+int npm_mha_prefill_fwd_f16(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens, const int32_t *block_table,
+                            int32_t table_pitch, int32_t page_rows);
 
 /* ---- skinny-M GEMM: the matrix products of a decode step (inference) ----
  * C[M, N] = epilogue(alpha * A[M, K] op(B)) for 1 <= M <= NPM_SKINNY_MAX_M rows, described by the same npm_gemm as npm_sgemm.  These

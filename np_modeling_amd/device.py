@@ -1191,10 +1191,14 @@ def mha_decode(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, s
 # over the cache instead of the fused training forward on gathered K / V with a host-built mask.  Off by default: the gather /
 # mask path stays what every call sequence is until the switch is flipped (measured: tools/prefill_bench.py).
 PREFILL_KERNEL = os.environ.get('NPM_PREFILL_KERNEL', '0') != '0'
+# The same switch for half-precision caches, independent of the one above: whatever the decode kernel does not take runs
+# npm_mha_prefill_fwd_f16 over the stored halves in place instead of the fused training forward on gathered fp32 copies.  Off by
+# default: every call sequence is then what it was before the entry point existed (measured: tools/prefill_kv16_bench.py).
+PREFILL_KERNEL_F16 = os.environ.get('NPM_PREFILL_KERNEL_F16', '0') != '0'
 
 
 def mha_prefill_supported(head_dim: int, value_dim: Optional[int] = None) -> bool:
-    """Whether ``npm_mha_prefill_fwd`` takes this head size (any number of rows).  Exact-fp32 MFMA only, like
+    """Whether ``npm_mha_prefill_fwd`` / ``npm_mha_prefill_fwd_f16`` take this head size (any number of rows).  Exact-fp32 MFMA only, like
     ``mha_decode_supported``: false under a split math mode."""
     if not ATTN_CORE or (value_dim is not None and value_dim != head_dim) or _C.current_math() != 'f32':
         return False
@@ -1205,12 +1209,19 @@ def mha_prefill(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, 
                 lens=None, keys: Optional[int] = None):
     """``mha_decode`` without its limit on the rows (include/npm_hip.h npm_mha_prefill_fwd): ctx [B, T, Hq, D] (and lse
     [B, Hq, T] or None) of ``tokens`` query rows per sequence over ``cache``, read in place -- through the block table of a paged
-    cache -- with ``lens`` = (kv_lens, new_lens) as there.  No mask and no gathered copy exist."""
+    cache -- with ``lens`` = (kv_lens, new_lens) as there.  No mask and no gathered copy exist.  An fp16 cache takes
+    ``npm_mha_prefill_fwd_f16`` (bitwise the fp32 call on the rounded values); this is the low-level call, whatever
+    ``PREFILL_KERNEL_F16`` says."""
     assert cache.key_dim == cache.value_dim and 0 <= kv_len <= cache.capacity and (lens is not None or tokens <= kv_len)
     c, ctx, lse, layout = _decode_desc(q, cache, heads, tokens, kv_len, scale, causal, want_lse)
     b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
     keys = b * kv_len if keys is None else int(keys)
     kv_lens, new_lens = (None, None) if lens is None else lens
+    if cache.dtype == 'f16':
+        with _timed('mha_prefill', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + hkv * keys)):
+            _C.check(_C.lib().npm_mha_prefill_fwd_f16(C.byref(c), kv_lens, new_lens, layout.table, layout.table_pitch, layout.page_rows),
+                     'npm_mha_prefill_fwd_f16')
+        return ctx, lse
     with _timed('mha_prefill', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + 2 * hkv * keys)):
         _C.check(_C.lib().npm_mha_prefill_fwd(C.byref(c), kv_lens, new_lens, layout.table, layout.table_pitch, layout.page_rows),
                  'npm_mha_prefill_fwd')
@@ -1234,8 +1245,9 @@ class KVCache:
 
     ``dtype`` 'f16': ``k`` and ``v`` are ``HalfBuffer`` s of the same geometry and half the bytes.  Rows are rounded to IEEE fp16
     once, by the append (round to nearest even; |x| >= 65520 becomes inf), and every reader -- the decode kernel, ``gather`` -- sees
-    them as stored, converted back exactly (npm_kv_append_f16 / npm_mha_decode_fwd_f16 / npm_kv_gather_f16); there is no fp16
-    prefill kernel.  ``itemsize`` is the bytes per stored element and ``nbytes`` those of K + V."""
+    them as stored, converted back exactly (npm_kv_append_f16 / npm_mha_decode_fwd_f16 / npm_kv_gather_f16, and
+    npm_mha_prefill_fwd_f16 behind ``PREFILL_KERNEL_F16``).  ``itemsize`` is the bytes per stored element and ``nbytes`` those of
+    K + V."""
 
     paged = False
 
@@ -1375,12 +1387,13 @@ class KVCache:
         """``mha_decode`` of ``tokens`` query rows per sequence over the valid rows; with ``new_lengths`` (or a ragged or paged
         cache) its ragged call: rows t >= n[b] are padding and come back as zeros.  ``causal``: the n[b] new tokens are the last
         n[b] valid rows of sequence b (they were appended first).  ``kernel='prefill'``: ``mha_prefill``, the same contract for any
-        number of rows (a uniform cache shorter than the query -- a frozen one -- takes its per-sequence call)."""
+        number of rows (a uniform cache shorter than the query -- a frozen one -- takes its per-sequence call); on an fp16 cache
+        only with ``PREFILL_KERNEL_F16`` on."""
         if kernel not in ('decode', 'prefill'):
             raise ValueError(f"KVCache.attend: kernel must be 'decode' or 'prefill', got {kernel!r}")
-        if kernel == 'prefill' and self.dtype != 'f32':
-            raise ValueError(f"KVCache.attend: the prefill kernel reads fp32 caches only; an {self.dtype} cache takes kernel='decode' "
-                             'or gather()')
+        if kernel == 'prefill' and self.dtype != 'f32' and not PREFILL_KERNEL_F16:
+            raise ValueError(f"KVCache.attend: the prefill kernel reads an {self.dtype} cache only with PREFILL_KERNEL_F16 on "
+                             "(NPM_PREFILL_KERNEL_F16=1); without it the cache takes kernel='decode' or gather()")
         attend = mha_prefill if kernel == 'prefill' else mha_decode
         n = self.new_lengths(tokens, new_lengths)
         if self._scalar_call(n) and (kernel == 'decode' or tokens <= int(self.lengths[0])):

@@ -62,6 +62,11 @@ straight over the cache under ``f32`` math and a supported head size: everything
 frozen caches, and the uniform contiguous cache with rows already in it or frozen -- no gathered K / V, no mask, no copy per
 sequence.  One case stays on ``'fused_masked'``: a uniform contiguous prefill from empty, where the fused forward reads the fresh
 projection in place.  With the switch off every call sequence is what it was.
+
+Half-precision caches have a switch of their own (``device.PREFILL_KERNEL_F16``, environment ``NPM_PREFILL_KERNEL_F16=1``; off by
+default, independent of the one above): a cached forward over an ``f16`` cache that the decode kernel does not take then runs
+``npm_mha_prefill_fwd_f16`` over the stored halves in place -- a prefill from empty included, since such a cache is attended to as
+stored -- instead of the fused forward on ``cache.gather``'s fp32 copies.  Under a split math mode the gathered path stays.
 """
 
 from __future__ import annotations
@@ -362,8 +367,12 @@ class MultiHeadAttention(layer.StatefulLayer):
             return cache.attend(q, h, t, scale, causal)[0]
         if cache.dtype != 'f32':
             # a half-precision cache is attended to AS STORED, the new tokens' own rows included: whatever the decode kernel
-            # does not take is the fused masked forward on the gathered fp32 copies of the stored rows -- never the fresh
-            # projection, the cache tensors themselves or the prefill kernel
+            # does not take is the prefill kernel over the stored halves in place (PREFILL_KERNEL_F16; a prefill from empty
+            # too: the fresh projection is not what later steps will see), else the fused masked forward on the gathered fp32
+            # copies of the stored rows -- never the fresh projection or the cache tensors themselves
+            if D.PREFILL_KERNEL_F16 and D.mha_prefill_supported(dk, dv):
+                self._cached_path = 'prefill'
+                return cache.attend(q, h, t, scale, causal, kernel='prefill')[0]
             before = cache.lengths - t if causal else cache.lengths
             return self._attend_ragged(q, cache, t, causal, None, before, None, decode_ok=False)
         if D.PREFILL_KERNEL and D.mha_prefill_supported(dk, dv) and not (fresh is not None and length == t):
@@ -406,9 +415,9 @@ class MultiHeadAttention(layer.StatefulLayer):
                        decode_ok: bool = True) -> D.DeviceArray:
         """``_attend_cached`` when the sequences differ: ``before`` [B] rows were valid before this call, sequence b brings
         ``new_lengths[b]`` (None: T) of the T padded query rows.  Row t < n[b] sees keys j <= before[b] + t (causal) or
-        j < lengths[b] (frozen cache).  A half-precision cache is attended to as stored: the decode kernel, or the fused masked
-        forward on ``cache.gather`` -- not the prefill kernel, not ``fresh``.  ``decode_ok`` False: the caller (a uniform
-        half-precision cache) has found that the decode kernel does not take the call."""
+        j < lengths[b] (frozen cache).  A half-precision cache is attended to as stored: the decode kernel, the prefill kernel
+        (``PREFILL_KERNEL_F16``), or the fused masked forward on ``cache.gather`` -- not ``fresh``.  ``decode_ok`` False: the
+        caller (a uniform half-precision cache) has found that neither kernel takes the call."""
         h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
         b, scale = cache.batch, 1.0 / math.sqrt(self._key_dim)
         n = np.full([b], t, dtype=np.int64) if new_lengths is None else new_lengths
@@ -416,7 +425,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         if decode_ok and D.mha_decode_supported(dk, h // hkv * t, dv):
             self._cached_path = 'decode'
             return cache.attend(q, h, t, scale, causal, new_lengths=n)[0]
-        if not stored and D.PREFILL_KERNEL and D.mha_prefill_supported(dk, dv):
+        if (D.PREFILL_KERNEL_F16 if stored else D.PREFILL_KERNEL) and D.mha_prefill_supported(dk, dv):
             # a ragged prefill, a chunk of one, a sequence admitted beside decoding ones, a paged or a frozen cache: the prefill
             # kernel over the cache in place, through the block table -- lengths and causality are arithmetic on the device
             self._cached_path = 'prefill'
