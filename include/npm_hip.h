@@ -506,6 +506,24 @@ int npm_mha_decode_fwd_f16(const npm_mha_decode *d, const int32_t *kv_lens, cons
 int npm_mha_prefill_fwd_f16(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens, const int32_t *block_table,
                             int32_t table_pitch, int32_t page_rows);
 
+/* ---- rotary position embedding (RoPE), in place ----
+ * Rotates the first `heads` heads of every row b * tokens + t (b < batch, t < tokens) of x: head h of a row is the head_dim floats
+ * at x[row * pitch + h * head_dim]; whatever lies behind them in the row (the V heads of a packed [B, T, H + 2 Hkv, D] projection,
+ * when heads = H + Hkv) is not touched.  With half = head_dim / 2 (head_dim even), element i < half is paired with element
+ * i + half ("rotate-half"), and for the row's position p = (at_lens ? at_lens[b] : at) + t
+ *   c = cos[p * half + i], s = sin[p * half + i]      (fp32 tables [table_rows, half] made by the caller: the angle of (p, i) is
+ *                                                      p * base ** (-i / half); no trigonometry is computed on the device)
+ *   inverse == 0:  y[i] = x[i] * c - x[i + half] * s    y[i + half] = x[i + half] * c + x[i] * s
+ *   inverse != 0:  y[i] = x[i] * c + x[i + half] * s    y[i + half] = x[i + half] * c - x[i] * s     (the transpose: for gradients)
+ * Every product and every sum is rounded to fp32 on its own (no fused multiply-add): bitwise what NumPy gives for these
+ * expressions on float32 arrays.  at_lens: device array of batch int32, read by the kernel (NULL: the scalar `at`).  A row whose
+ * position is outside 0 .. table_rows - 1 is left untouched, and nothing past a table is read, whatever at_lens holds; with the
+ * scalar, at < 0 or at + tokens > table_rows is NPM_E_BAD_ARGUMENT.  NPM_E_BAD_ARGUMENT too for an odd head_dim, a size < 1,
+ * pitch < heads * head_dim and a NULL x, cos or sin.  head_dim % 8 == 0, pitch % 4 == 0 and 16-byte aligned x, cos and sin move
+ * 16 bytes per access; everything else takes a scalar kernel with the same arithmetic and the same bits. */
+int npm_rope(float *x, int64_t pitch, int32_t batch, int32_t tokens, int32_t heads, int32_t head_dim, const float *cos,
+             const float *sin, int32_t table_rows, int32_t at, const int32_t *at_lens, int32_t inverse);
+
 /* ---- skinny-M GEMM: the matrix products of a decode step (inference) ----
  * C[M, N] = epilogue(alpha * A[M, K] op(B)) for 1 <= M <= NPM_SKINNY_MAX_M rows, described by the same npm_gemm as npm_sgemm.  These
  * are the products np.matmul / np.einsum make at M = B T rows of new tokens: the q / k / v and output projections of

@@ -27,6 +27,7 @@ int colsum_launch(const float *x, float *out, long rows, long cols, long ld);
 void set_ln_bwd_blocks(int blocks_per_cu);
 void set_ln_nt_split(int mode);
 void set_ew_grid_cap(int blocks);
+int ew_grid_cap();           // blocks a grid-stride elementwise launch may use (NPM_TUNE_EW_GRID_CAP; npm_rope.hip shares it)
 void set_stream_nt(int on);
 // streaming tensors of at least 32 MB move with the nontemporal cache hint (npm_rowops.hip; NPM_TUNE_STREAM_NT)
 bool stream_nt_enabled(size_t bytes);

@@ -727,6 +727,7 @@ void set_ln_nt_split(int v) { g_ln_nt_split = v; }
 void set_stream_nt(int v) { g_stream_nt = v != 0; }
 bool stream_nt_enabled(size_t bytes) { return stream_nt(bytes); }
 void set_ew_grid_cap(int v) { g_ew_grid_cap = v > 0 ? v : (1 << 20); }
+int ew_grid_cap() { return g_ew_grid_cap; }
 int colsum_launch(const float *x, float *out, long rows, long cols, long ld) { return colsum_impl(x, out, rows, cols, ld); }
 }  // namespace npm
 

@@ -1228,6 +1228,49 @@ def mha_prefill(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, 
     return ctx, lse
 
 
+def rope_tables(rows: int, head_dim: int, base: float):
+    """(cos, sin) float32 [rows, head_dim / 2] of rotary position embeddings: the angle of position p and pair i is
+    p * base ** (-i / half), computed in float64 on the host and rounded once.  Row p does not depend on ``rows``."""
+    half = head_dim // 2
+    inv_freq = float(base) ** (-np.arange(half, dtype=np.float64) / half)
+    angle = np.arange(rows, dtype=np.float64)[:, None] * inv_freq[None, :]
+    return np.cos(angle).astype(np.float32), np.sin(angle).astype(np.float32)
+
+
+class RopeTable:
+    """The cos / sin tables of one attention layer's rotary position embedding on the device (``rope_tables``).  ``ensure(rows)``
+    makes them cover positions 0 .. rows - 1: the row count is rounded up to a power of two, so a decode loop does not upload
+    them again every step; a layer sizes them once in ``make_cache``."""
+
+    def __init__(self, head_dim: int, base: float):
+        if head_dim < 2 or head_dim % 2:
+            raise ValueError(f'rotary position embedding pairs element i with element i + D / 2: the head size {head_dim} is odd')
+        if not base > 0:
+            raise ValueError(f'rope_base must be a positive number, got {base!r}')
+        self.head_dim, self.base = int(head_dim), float(base)
+        self.rows = 0
+        self.cos = self.sin = None
+
+    def ensure(self, rows: int) -> 'RopeTable':
+        if rows > self.rows:
+            self.rows = 1 << max(int(rows) - 1, 0).bit_length()
+            self.cos, self.sin = (from_host(t) for t in rope_tables(self.rows, self.head_dim, self.base))
+        return self
+
+
+def rope(x: Mat, batch: int, tokens: int, heads: int, head_dim: int, table: RopeTable, at: int = 0, at_lens: Optional[int] = None,
+         inverse: bool = False) -> None:
+    """Rotates, in place, the first ``heads`` heads of the rows b * tokens + t of ``x`` (array, row pitch) by the angles of
+    position (``at_lens[b]`` or ``at``) + t (include/npm_hip.h npm_rope); ``inverse``: the transposed rotation, for gradients.
+    ``at_lens``: the DEVICE address of [B] int32.  Whatever lies behind the ``heads`` heads in a row -- the V part of a packed
+    projection -- is not touched.  ``table`` covers the positions (``RopeTable.ensure``)."""
+    assert table.head_dim == head_dim and (at_lens is not None or at + tokens <= table.rows), (head_dim, at, tokens, table.rows)
+    rows = batch * tokens
+    with _timed('rope', nbytes=8.0 * rows * heads * head_dim + 4.0 * head_dim * min(rows, table.rows)):
+        _C.check(_C.lib().npm_rope(x.ptr, x.ld, batch, tokens, heads, head_dim, table.cos.ptr, table.sin.ptr, table.rows, int(at),
+                                   at_lens, int(bool(inverse))), 'npm_rope')
+
+
 class KVCache:
     """Keys and values of the tokens seen so far: ``k`` [B, capacity, Hkv, Dk] and ``v`` [B, capacity, Hkv, Dv] on the device,
     of which the first ``lengths[b]`` rows of sequence b are valid.  Rows at and past that hold whatever was there; nothing reads

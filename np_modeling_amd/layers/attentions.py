@@ -67,6 +67,19 @@ Half-precision caches have a switch of their own (``device.PREFILL_KERNEL_F16``,
 default, independent of the one above): a cached forward over an ``f16`` cache that the decode kernel does not take then runs
 ``npm_mha_prefill_fwd_f16`` over the stored halves in place -- a prefill from empty included, since such a cache is attended to as
 stored -- instead of the fused forward on ``cache.gather``'s fp32 copies.  Under a split math mode the gathered path stays.
+
+Rotary position embeddings (``rope_base``, default None: the reference has no positional encoding and neither has this layer).
+With a positive ``rope_base`` the projected q and k are rotated in place by their positions -- element i < Dk / 2 of a head pairs
+with element i + Dk / 2, angle p * rope_base ** (-2 i / Dk); Dk must be even, v is never rotated -- by ``npm_rope``
+(csrc/npm_rope.hip) from cos / sin tables made on the host (``device.RopeTable``): ONE launch on the packed projection (the q and
+k heads are adjacent in every row), two on separate tensors, each side counted from position 0.  It runs in front of the fused
+core or the GEMM composition in every math mode (exact fp32 element-wise work); ``_q`` / ``_k`` are saved rotated, and the backward
+applies the transposed rotation to dq / dk between the attention gradient and the in-projection gradient GEMMs.  With a cache the
+new tokens are rotated at the positions ``cache.lengths[b] + t`` BEFORE ``cache.append`` -- the scalar ``cache.length`` for a
+uniform contiguous cache, else the ``before`` row of the cache's device length mirror, which the append then finds uploaded -- so
+the cache, the decode and prefill kernels and the fp16 rounding see rotated rows and need nothing of their own; ``make_cache``
+sizes the tables for ``capacity``.  A frozen cross-attention cache has no query position: ``fill_cache`` and a cached forward over
+one raise NotImplementedError.  ``rope_base=None`` launches nothing and allocates nothing: every call sequence is what it was.
 """
 
 from __future__ import annotations
@@ -90,10 +103,14 @@ def _from(x: D.DeviceArray, offset: int) -> D.DeviceArray:
 
 
 class MultiHeadAttention(layer.StatefulLayer):
-    def __init__(self, num_heads: int, *args, num_kv_heads: Optional[int] = None, **kwargs):
+    def __init__(self, num_heads: int, *args, num_kv_heads: Optional[int] = None, rope_base: Optional[float] = None, **kwargs):
         super().__init__(*args, **kwargs)
         self._num_heads = num_heads
         self._num_kv_heads = num_heads if num_kv_heads is None else num_kv_heads
+        if rope_base is not None and not rope_base > 0:
+            raise ValueError(f'rope_base must be None or a positive number, got {rope_base!r}')
+        self._rope_base = None if rope_base is None else float(rope_base)   # None: no rotation, no table, no launch
+        self._rope = None                                                   # device.RopeTable, made at the first use
         self._softmax = activations.Softmax()
         self._cached_forward = False    # the last forward ran with a cache: it saved nothing a backward could use
         self._cached_path = None        # 'decode' | 'prefill' | 'fused_masked' | 'gemm': how the last cached forward attended
@@ -114,6 +131,8 @@ class MultiHeadAttention(layer.StatefulLayer):
         assert hkv >= 1 and h % hkv == 0, f'num_heads {h} is not a multiple of num_kv_heads {hkv}'
         assert key.shape[2] % h == 0
         self._key_dim = dk = key.shape[2] // h
+        if self._rope_base is not None and dk % 2:
+            raise ValueError(f'rope_base: rotary position embedding needs an even head size Dk, got {dk}')
         assert value.shape[2] % h == 0
         self._value_dim = dv = value.shape[2] // h
         # Draw order wq, wk, wv, wo, bq, bk, bv, bo (attentions.py:46-65).  When the three in-projections
@@ -156,6 +175,24 @@ class MultiHeadAttention(layer.StatefulLayer):
 
     def _numel(self) -> int:
         return sum(self._param(p).size for p in _PARAMS) + 4 * len(_PARAMS)
+
+    def _rope_table(self, rows: int) -> D.RopeTable:
+        """The layer's cos / sin tables, covering positions 0 .. rows - 1 (``rope_base`` is set)."""
+        if self._rope is None:
+            self._rope = D.RopeTable(self._key_dim, self._rope_base)
+        return self._rope.ensure(rows)
+
+    def _rotate(self, packed, q: D.DeviceArray, k: D.DeviceArray, b: int, sq: int, skv: int, inverse: bool = False) -> None:
+        """Rotary position embedding on q [B, Sq, H, Dk] and k [B, Skv, Hkv, Dk] in place, each counted from position 0 (or
+        their gradients: ``inverse``).  ``packed``: they are the first H + Hkv heads of the rows of one [B, S, H + 2 Hkv, D]
+        buffer ``q``, which one launch rotates; the V heads behind them are not touched."""
+        h, hkv, dk = self._num_heads, self._num_kv_heads, self._key_dim
+        table = self._rope_table(max(sq, skv))
+        if packed:
+            D.rope(Mat(q, (h + 2 * hkv) * dk), b, sq, h + hkv, dk, table, inverse=inverse)
+        else:
+            D.rope(Mat(q, h * dk), b, sq, h, dk, table, inverse=inverse)
+            D.rope(Mat(k, hkv * dk), b, skv, hkv, dk, table, inverse=inverse)
 
     def _segments(self):
         """Parameters in the order ``_backward_impl`` produces their gradients (device.ParamArena segments)."""
@@ -221,6 +258,8 @@ class MultiHeadAttention(layer.StatefulLayer):
             D.gemm(b * sq, h * dk, f, Mat(query, f), Mat(wq, f), Mat(q, h * dk), trans_b=True, bias=bq)
             D.gemm(b * skv, fkv, f, Mat(key, f), Mat(wk, f), Mat(k, fkv), trans_b=True, bias=bk)
             D.gemm(b * skv, fvkv, fv, Mat(value, fv), Mat(wv, fv), Mat(v, fvkv), trans_b=True, bias=bv)
+        if self._rope_base is not None:                                 # q and k are saved rotated: what the backward needs
+            self._rotate(packed, q, k, b, sq, skv)
         self._q, self._k, self._v = q, k, v
         pq, pk, pv = pitch or h * dk, pitch or fkv, pitch or fvkv       # row pitches of q, k, v
         self._pitches = (pq, pk, pv)
@@ -274,6 +313,8 @@ class MultiHeadAttention(layer.StatefulLayer):
         if dtype != 'f32' and not (dk == dv and dk in (16, 32, 64, 128)):
             raise NotImplementedError(f'an {dtype} cache needs head sizes Dk == Dv in {{16, 32, 64, 128}} (the decode kernel and the '
                                       f'fused masked forward on the gathered rows), got {dk} / {dv}')
+        if self._rope_base is not None:
+            self._rope_table(capacity)                                   # sized once: decoding up to the capacity never grows it
         if page_size is None:
             if pages is not None:
                 raise ValueError('make_cache: pages= sizes the pool of a paged cache: it needs page_size=')
@@ -287,6 +328,9 @@ class MultiHeadAttention(layer.StatefulLayer):
         """Cross-attention: project ``key`` / ``value`` [B, Skv, F] once into ``cache`` and freeze it; ``forward(x, cache=cache)``
         then attends to all of it, not causally, and appends nothing.  ``lengths`` [B]: the memory is padded on the right and
         sequence b has only ``lengths[b]`` rows; the rest is neither stored nor attended to."""
+        if self._rope_base is not None:
+            raise NotImplementedError('fill_cache with rope_base: a cross-attention chunk has no defined query position over a '
+                                      'frozen cache; rotary position embedding is for self-attention caches')
         key = D.as_device(key)
         value = key if value is None else D.as_device(value)
         h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
@@ -312,6 +356,9 @@ class MultiHeadAttention(layer.StatefulLayer):
         assert f == h * dk and (cache.batch, cache.kv_heads, cache.key_dim, cache.value_dim) == (b, hkv, dk, dv), \
             f'cache made for {(cache.batch, cache.kv_heads, cache.key_dim, cache.value_dim)}, used with {(b, hkv, dk, dv)}'
         cross = cache.frozen
+        rope = self._rope_base is not None
+        if rope and cross:
+            raise NotImplementedError('a frozen (cross-attention) cache with rope_base: the query chunk has no defined position')
         new_lengths = cache.new_lengths(t, new_lengths)                  # None when it says what T says
         # a paged cache has no [B, capacity, Hkv, D] tensor to hand to the uniform paths: it always takes the per-sequence route,
         # whose kernels read through the block table (uniform lengths are bitwise the uniform entry point there)
@@ -336,7 +383,8 @@ class MultiHeadAttention(layer.StatefulLayer):
         else:
             # ONE GEMM over M = B T rows makes q, k and v where the parameters are adjacent; K and V rows then go into the cache
             # straight out of the packed buffer (npm_kv_append reads with its row pitch)
-            if dk == dv and D.PACK_QKV and self._params_adjacent():
+            packed = dk == dv and D.PACK_QKV and self._params_adjacent()
+            if packed:
                 width = f + 2 * fkv
                 qkv = D.empty([b, t, h + 2 * hkv, dk])
                 D.gemm(b * t, width, f, Mat(query, f), Mat(wq, f), Mat(qkv, width), trans_b=True, bias=bq, skinny_ok=True)
@@ -348,6 +396,20 @@ class MultiHeadAttention(layer.StatefulLayer):
                 D.gemm(b * t, fkv, f, Mat(query, f), Mat(wk, f), Mat(ka, fkv), trans_b=True, bias=bk, skinny_ok=True)
                 D.gemm(b * t, fvkv, f, Mat(query, f), Mat(wv, f), Mat(va, fvkv), trans_b=True, bias=bv, skinny_ok=True)
                 q, fresh = Mat(qa, f), (Mat(ka, fkv), Mat(va, fvkv))
+            if rope:
+                # q and the fresh k rows at positions lengths[b] + t, BEFORE they are stored: the cache, its kernels and the
+                # fp16 rounding see rotated rows and need nothing of their own.  Per-sequence positions are the `before` row of
+                # the length mirror; the append below finds the same numbers there and uploads nothing.
+                if cache._scalar_call(new_lengths):
+                    at, at_lens = cache.length, None
+                else:
+                    at, at_lens = 0, cache._device_lengths(cache.lengths, cache._counts(t, new_lengths))[0]
+                table = self._rope_table(cache.max_length + t)
+                if packed:                                               # q and k heads are adjacent in every row: one launch
+                    D.rope(q, b, t, h + hkv, dk, table, at, at_lens)
+                else:
+                    D.rope(q, b, t, h, dk, table, at, at_lens)
+                    D.rope(fresh[0], b, t, hkv, dk, table, at, at_lens)
             cache.append(fresh[0], fresh[1], t, new_lengths)
         if ragged:
             ctx = self._attend_ragged(q, cache, t, not cross, fresh, before, new_lengths)
@@ -554,6 +616,8 @@ class MultiHeadAttention(layer.StatefulLayer):
             D.gemm(skv, dk, sq, Mat(datt, skv, h * sq * skv, sq * skv), Mat(q, pq, sq * pq, dk),
                    Mat(dk_, gk, skv * gk, dk), trans_a=True, batch=(b, h))                        # datt_h^T q_h
 
+        if self._rope_base is not None:     # dq, dk are gradients of the ROTATED q, k: the transposed rotation takes them back
+            self._rotate(packed, dq, dk_, b, sq, skv, inverse=True)
         # in-projections (attentions.py:167-188): dw = dproj^T x ; dx = dproj w
         if packed:
             D.gemm(width, f, m_q, Mat(dqkv, width), Mat(query, f), Mat(dw_all, f), trans_a=True, asum_out=db_all)

@@ -13,6 +13,11 @@ overlap the rest of the backward pass.
 ``num_kv_heads`` (default None: multi-head attention) makes every attention layer grouped-query attention with that many
 key / value heads (attentions.py); nothing else changes.
 
+``rope_base`` (default None: no positional information, as the reference) turns on rotary position embeddings in the
+self-attention (attentions.py): q and k are rotated by their positions, counted from 0, in forward, backward and incremental
+decoding -- where a sequence's position is its row count in the cache, so one admitted into a freed slot starts at 0 again.  The
+decoder's cross-attention never rotates.
+
 ``TransformerDecoder(causal=True)`` gives the self-attention a lower-triangular mask (the decoder everybody means by the word;
 the reference's passes none, transformer.py:127), and ``start_decoding`` / ``decode`` run it incrementally over key / value
 caches (inference; the reference marks the gap: ``# TODO: support cache``, transformer.py:120).  With ``causal=True`` and no
@@ -79,9 +84,9 @@ def _block_backward(dy, norm, dropout, norm_first: bool, body_backward, optimize
 
 class TransformerEncoder(layer.Layer):
     def __init__(self, num_heads: int, hidden_units: int, norm_first: bool, drop_rate: float = 0.0,
-                 *args, num_kv_heads: Optional[int] = None, **kwargs):
+                 *args, num_kv_heads: Optional[int] = None, rope_base: Optional[float] = None, **kwargs):
         super().__init__(*args, **kwargs)
-        self._self_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)
+        self._self_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads, rope_base=rope_base)
         self._dense1 = mlp.Dense(units=hidden_units)
         self._norm1 = normalizations.LayerNormalization()
         self._norm2 = normalizations.LayerNormalization()
@@ -219,14 +224,14 @@ class TransformerDecoder(layer.Layer):
     ``dkv = dkey + dvalue`` of the cross-attention (transformer.py:186)."""
 
     def __init__(self, num_heads: int, hidden_units: int, norm_first: bool, drop_rate: float = 0.0,
-                 *args, num_kv_heads: Optional[int] = None, causal: bool = False, **kwargs):
+                 *args, num_kv_heads: Optional[int] = None, causal: bool = False, rope_base: Optional[float] = None, **kwargs):
         super().__init__(*args, **kwargs)
         self._num_heads = num_heads
         self._causal = bool(causal)
         self._causal_masks = {}         # (B, Sq) -> device.AttnMask: bytes and tile summary stay on the device between steps
         self._decoded = False           # decode() ran since the last forward: the saved activations are not that forward's
-        self._self_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)
-        self._cross_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)
+        self._self_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads, rope_base=rope_base)
+        self._cross_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)   # never rotates: no query position
         self._dense1 = mlp.Dense(units=hidden_units)
         self._norm1 = normalizations.LayerNormalization()
         self._norm2 = normalizations.LayerNormalization()
