@@ -551,6 +551,36 @@ int npm_sgemm_skinny_splits(int n, int k, int trans_b);
  * nt=<0|1>" (nt: nontemporal weight loads); "" before the first call. */
 const char *npm_last_skinny_kernel(void);
 
+/* ---- half-precision weight copies for the skinny-M GEMM (opt-in; everything above is unchanged) ----
+ * A decode step is a stream over its weights, so the six matrices it reads may be kept a second time as IEEE fp16 and streamed at
+ * half the bytes.  The pattern is the fp16 cache's: convert ONCE (npm_cvt_f32_f16), read in place, accumulate in fp32.
+ *
+ * npm_cvt_f32_f16 converts a pitched 2-D array (rows x cols; each pitch counts elements of its own side's type and is >= cols) with
+ * round to nearest even -- bit for bit NumPy's astype(float16), subnormal results kept; |x| >= 65520 becomes +-inf: there is NO
+ * clamp, as in npm_kv_append_f16 -- and npm_cvt_f16_f32 is the exact way back.  Row kernels: 16-byte accesses when cols and the
+ * fp16 pitch are multiples of 8, the fp32 pitch is a multiple of 4 and both pointers are 16-byte aligned, else one element per
+ * thread with the same bits.  rows == 0 or cols == 0 returns NPM_OK whatever the pointers are; a negative size, a pitch below
+ * cols or a NULL pointer is NPM_E_BAD_ARGUMENT.
+ *
+ * npm_sgemm_skinny_w16 is npm_sgemm_skinny -- the same descriptor, rules, epilogues, split count (npm_sgemm_skinny_splits), combine
+ * kernel and refusals -- except that g->b points at halves: ldb counts halves and is a multiple of 8, b is 16-byte aligned.  A, C,
+ * bias, residual, aux and alpha stay fp32.  Each weight element is converted exactly in registers (v_cvt_f32_f16) and enters the
+ * same v_mfma_f32_16x16x4_f32 chain, contraction off.  The kernel keeps the lane-to-k mapping of the fp32 instance (a lane's
+ * 16-byte weight load becomes an 8-byte one), so the call is BITWISE
+ * npm_sgemm_skinny on a B that holds the rounded values as floats, and inherits its identities: row r of an M-row call is the
+ * M = 1 call on that row, two identical calls and either load hint give the same bits, nothing outside the operands is read.  The
+ * nontemporal rule (NPM_TUNE_SKINNY_NT = 0) counts the bytes stored, 2 N K.  npm_last_skinny_kernel() afterwards: the fp32 string
+ * followed by " w=f16".  Measured on one MI355X (tools/skinny_w16_bench.py): at d 1024 / hidden 4096 the six products
+ * of a decode step are bound by their two launches, not by weight bytes -- w16 / fp32 is 0.85 - 0.88 on dense2 (K 4096) and 0.93 - 0.94
+ * on dense1 at M <= 16, within the spread elsewhere; a decode step was 1 - 3 % slower on the variant with four chunks per step and has not been measured on
+ * the shipped instance.  What the copies buy today is the rounded
+ * model; they cost 2 N K more bytes of memory. */
+int npm_cvt_f32_f16(const float *src, int64_t src_pitch, void *dst, int64_t dst_pitch, int64_t rows, int64_t cols);
+int npm_cvt_f16_f32(const void *src, int64_t src_pitch, float *dst, int64_t dst_pitch, int64_t rows, int64_t cols);
+int npm_sgemm_skinny_w16(const npm_gemm *g);
+/* 1 when npm_sgemm_skinny_w16 takes this call, else 0; never sets an error. */
+int npm_sgemm_skinny_w16_supported(const npm_gemm *g);
+
 /* ---- around the path ("next" rows of SURVEY.md section 8f): keeps a Trainer step on the device ---- */
 /* Adam with the reference's numerics (optimizer.py:53-67): fp64 moments m, v (device buffers of n doubles,
  * zero-initialised with npm_fill_f64), bias correction with step >= 1, epsilon inside the sqrt */

@@ -174,6 +174,10 @@ SIGNATURES = {
     'npm_sgemm_skinny': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_supported': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_splits': [C.c_int, C.c_int, C.c_int],
+    'npm_cvt_f32_f16': [_P, _I64, _P, _I64, _I64, _I64],
+    'npm_cvt_f16_f32': [_P, _I64, _P, _I64, _I64, _I64],
+    'npm_sgemm_skinny_w16': [C.POINTER(npm_gemm)],
+    'npm_sgemm_skinny_w16_supported': [C.POINTER(npm_gemm)],
     'npm_adam_step': [_P, _P, _P, _P, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int],
     'npm_fill_f64': [_P, C.c_double, _SZ],
     'npm_mse_fwd': [_P, _P, _SZ, C.POINTER(C.c_double)],
@@ -437,7 +441,7 @@ SKINNY_MAX_M, SKINNY_MAX_SPLITS = 64, 64        # include/npm_hip.h NPM_SKINNY_M
 
 
 def last_skinny_kernel() -> str:
-    """What the most recent npm_sgemm_skinny launched (include/npm_hip.h npm_last_skinny_kernel)."""
+    """What the most recent npm_sgemm_skinny / npm_sgemm_skinny_w16 launched (include/npm_hip.h npm_last_skinny_kernel)."""
     return lib().npm_last_skinny_kernel().decode()
 
 

@@ -719,6 +719,58 @@ layernorm_bwd_dx_generic(const float *__restrict__ dz, const float *__restrict__
     }
 }
 
+// ---------------------------------------------------------------------------------
+// fp32 <-> IEEE fp16 over a pitched 2-D array (npm_cvt_f32_f16 / npm_cvt_f16_f32): the weight copies of npm_sgemm_skinny_w16
+// ---------------------------------------------------------------------------------
+// One thread per 8 columns: 16 bytes on the fp16 side, two 16-byte accesses on the fp32 side.  TO_HALF rounds to nearest even
+// (v_cvt_f16_f32: bit for bit NumPy's astype(float16), subnormal results kept, |x| >= 65520 -> inf); the way back is exact.
+// VEC = false: one thread per element, for shapes and addresses the 16-byte accesses do not take -- the same bits.
+typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
+
+template <bool TO_HALF, bool VEC>
+__global__ void __launch_bounds__(256)
+cvt_kernel(const void *__restrict__ src, long src_pitch, void *__restrict__ dst, long dst_pitch, long per_row, long total) {
+    constexpr int W = VEC ? 8 : 1;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long row = i / per_row, col = (i - row * per_row) * W;
+        if constexpr (TO_HALF) {
+            const float *from = static_cast<const float *>(src) + row * src_pitch + col;
+            _Float16 *to = static_cast<_Float16 *>(dst) + row * dst_pitch + col;
+            if constexpr (VEC) {
+                const f16x4v lo = __builtin_convertvector(*reinterpret_cast<const f32x4v *>(from), f16x4v);
+                const f16x4v hi = __builtin_convertvector(*reinterpret_cast<const f32x4v *>(from + 4), f16x4v);
+                *reinterpret_cast<f16x8v *>(to) = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+            } else {
+                *to = (_Float16)*from;
+            }
+        } else {
+            const _Float16 *from = static_cast<const _Float16 *>(src) + row * src_pitch + col;
+            float *to = static_cast<float *>(dst) + row * dst_pitch + col;
+            if constexpr (VEC) {
+                const f16x8v h = *reinterpret_cast<const f16x8v *>(from);
+                *reinterpret_cast<f32x4v *>(to) = __builtin_convertvector(__builtin_shufflevector(h, h, 0, 1, 2, 3), f32x4v);
+                *reinterpret_cast<f32x4v *>(to + 4) = __builtin_convertvector(__builtin_shufflevector(h, h, 4, 5, 6, 7), f32x4v);
+            } else {
+                *to = (float)*from;
+            }
+        }
+    }
+}
+
+// half_pitch / f32_pitch: the pitch of whichever side holds that type, in its own elements
+template <bool TO_HALF>
+int cvt_launch(const void *src, long src_pitch, void *dst, long dst_pitch, long rows, long cols) {
+    const long half_pitch = TO_HALF ? dst_pitch : src_pitch, f32_pitch = TO_HALF ? src_pitch : dst_pitch;
+    const bool vec = cols % 8 == 0 && half_pitch % 8 == 0 && f32_pitch % 4 == 0 && aligned16(src) && aligned16(dst);
+    const long per_row = vec ? cols / 8 : cols, total = rows * per_row;
+    hipStream_t s = npm::ctx().stream;
+    if (vec) hipLaunchKernelGGL((cvt_kernel<TO_HALF, true>), dim3(grid_for(total)), dim3(256), 0, s, src, src_pitch, dst, dst_pitch, per_row, total);
+    else hipLaunchKernelGGL((cvt_kernel<TO_HALF, false>), dim3(grid_for(total)), dim3(256), 0, s, src, src_pitch, dst, dst_pitch, per_row, total);
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
+}
+
 }  // namespace
 
 namespace npm {
@@ -774,6 +826,22 @@ int npm_scale(const float *x, float *y, float alpha, size_t n) {
     NPM_REQUIRE_INIT();
     NPM_ARG((x && y) || n == 0);
     return ew1(x, y, n, ScaleF{alpha});
+}
+
+int npm_cvt_f32_f16(const float *src, int64_t src_pitch, void *dst, int64_t dst_pitch, int64_t rows, int64_t cols) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(rows >= 0 && cols >= 0 && src_pitch >= cols && dst_pitch >= cols);
+    if (rows == 0 || cols == 0) return NPM_OK;
+    NPM_ARG(src != nullptr && dst != nullptr);
+    return cvt_launch<true>(src, src_pitch, dst, dst_pitch, rows, cols);
+}
+
+int npm_cvt_f16_f32(const void *src, int64_t src_pitch, float *dst, int64_t dst_pitch, int64_t rows, int64_t cols) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(rows >= 0 && cols >= 0 && src_pitch >= cols && dst_pitch >= cols);
+    if (rows == 0 || cols == 0) return NPM_OK;
+    NPM_ARG(src != nullptr && dst != nullptr);
+    return cvt_launch<false>(src, src_pitch, dst, dst_pitch, rows, cols);
 }
 
 int npm_colsum(const float *x, float *out, int64_t rows, int64_t cols, int64_t ld) {

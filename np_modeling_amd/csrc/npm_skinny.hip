@@ -31,6 +31,16 @@
 // selection (their loads are redirected to row 0), rows >= N of an NT B and columns >= N of an NN B are redirected to valid ones
 // and their results never stored, and a K chunk past a wave's range is neither loaded past K nor multiplied.
 // Floating-point contraction is off in these kernels: each fma is written out.
+//
+// Half-precision weights (npm_sgemm_skinny_w16): the same kernel template with WT = _Float16.  B holds IEEE halves (ldb counts
+// halves); a lane loads the SAME four elements as the float instance -- 8 bytes instead of 16 -- and converts them exactly
+// (v_cvt_f32_f16) when the step is consumed, so the MFMA operands, the chunk order and every sum are those of the float instance on
+// the rounded weights: the result is bitwise npm_sgemm_skinny's on a B of rounded floats, and every identity above carries over.
+// Halving the load width halves the bytes in flight per wave, which is what cost the fp16 KV cache its 2x.  Loading
+// FOUR chunks per step instead of two (the same bytes in flight, twice the load instructions) was built and measured: it is the
+// slower one, because a wave of these products has two to four chunks in all and a step of four leaves nothing to overlap
+// (DESIGN.md 4.1c has the numbers), so the halves instance keeps the float instance's step.  A 16-byte load of halves would need
+// another lane-to-k mapping (8 k per lane in NT) or 128-column strips (8 columns per lane in NN); it was not built.
 #include <algorithm>
 #include <cstring>
 
@@ -45,6 +55,7 @@ constexpr int STEP = 2;           // chunks loaded together, one step ahead
 constexpr int AUTO_MAX_SPLITS = 16;   // the automatic rule's ceiling (NPM_TUNE_SKINNY_SPLITS may force up to NPM_SKINNY_MAX_SPLITS)
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
@@ -74,6 +85,17 @@ __device__ __forceinline__ f32x4v ld_w(const float *p) {
     return *reinterpret_cast<const f32x4v *>(p);
 }
 
+// The same four elements of a weight matrix stored as halves (npm_sgemm_skinny_w16): one 8-byte load, kept as loaded until use
+template <bool NT>
+__device__ __forceinline__ f16x4v ld_w(const _Float16 *p) {
+    if (NT) return __builtin_nontemporal_load(reinterpret_cast<const f16x4v *>(p));
+    return *reinterpret_cast<const f16x4v *>(p);
+}
+
+// four weights as the MFMA takes them: as they are, or converted exactly (v_cvt_f32_f16; subnormals are kept)
+__device__ __forceinline__ f32x4v widen(f32x4v w) { return w; }
+__device__ __forceinline__ f32x4v widen(f16x4v w) { return __builtin_convertvector(w, f32x4v); }
+
 // alpha, bias, residual (may alias C: read before the store of the same thread), saved pre-activation, ReLU -- npm_sgemm's order
 __device__ __forceinline__ void epilogue_store(const SkinnyArgs &a, f32x4v v, int row, int col) {
 #pragma clang fp contract(off)
@@ -88,11 +110,15 @@ __device__ __forceinline__ void epilogue_store(const SkinnyArgs &a, f32x4v v, in
     *reinterpret_cast<f32x4v *>(a.c + (long)row * a.ldc + col) = v;
 }
 
-// RB: 16-row blocks (M <= 16 RB); TB: B is [N, K] (NT layout); NT: nontemporal weight loads
-template <int RB, bool TB, bool NT>
+// RB: 16-row blocks (M <= 16 RB); TB: B is [N, K] (NT layout); NT: nontemporal weight loads; WT: a.b holds floats, or halves
+// (behind the float pointer; ldb then counts halves) that are converted exactly on their way into the MFMAs -- the lane-to-k
+// mapping, the chunk order and every sum are those of the float instance, so the result is bitwise the float instance's on the
+// rounded weights
+template <int RB, bool TB, bool NT, typename WT = float>
 __global__ void __launch_bounds__(WAVES * 64, 2)
 sgemm_skinny_kernel(const SkinnyArgs a) {
 #pragma clang fp contract(off)
+    typedef WT wvec __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) float s_acc[WAVES][16][STRIP + 4];
 
     const int n0 = blockIdx.x * STRIP, split = blockIdx.y;
@@ -115,13 +141,14 @@ sgemm_skinny_kernel(const SkinnyArgs a) {
     }
     // TB: bp[t] is row n0 + 16 t + c of B (a tile at or past N: row N - 1, never stored); else bp[0] is column n0 + 4 c of k row
     // 4 g (a column at or past N: column 0, never stored)
-    const float *bp[4];
+    const WT *const b = reinterpret_cast<const WT *>(a.b);
+    const WT *bp[4];
     if (TB) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) bp[t] = a.b + (long)min(n0 + 16 * t + c, a.n - 1) * a.ldb + 4 * g;
+        for (int t = 0; t < 4; ++t) bp[t] = b + (long)min(n0 + 16 * t + c, a.n - 1) * a.ldb + 4 * g;
     } else {
         const int col = n0 + 4 * c;
-        bp[0] = a.b + (col < a.n ? col : 0) + (long)(4 * g) * a.ldb;
+        bp[0] = b + (col < a.n ? col : 0) + (long)(4 * g) * a.ldb;
     }
 
     f32x4v acc[RB][4];
@@ -130,9 +157,10 @@ sgemm_skinny_kernel(const SkinnyArgs a) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[rb][t] = f32x4v{0.f, 0.f, 0.f, 0.f};
 
-    f32x4v wr[STEP][4], ar[STEP][RB];
+    wvec wr[STEP][4];
+    f32x4v ar[STEP][RB];
     // chunk q + j of a step (clamped to the last chunk of K: the odd chunk behind a wave's range is loaded in bounds, never used)
-    auto load_step = [&](int q, f32x4v (&w)[STEP][4], f32x4v (&x)[STEP][RB]) {
+    auto load_step = [&](int q, wvec (&w)[STEP][4], f32x4v (&x)[STEP][RB]) {
 #pragma unroll
         for (int j = 0; j < STEP; ++j) {
             const long k0 = (long)CHUNK * min(q + j, a.chunks - 1);
@@ -149,7 +177,7 @@ sgemm_skinny_kernel(const SkinnyArgs a) {
 #pragma unroll
         for (int j = 0; j < STEP; ++j) {
 #pragma unroll
-            for (int t = 0; t < 4; ++t) wc[j][t] = wr[j][t];
+            for (int t = 0; t < 4; ++t) wc[j][t] = widen(wr[j][t]);
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) xc[j][rb] = live[rb] ? ar[j][rb] : f32x4v{0.f, 0.f, 0.f, 0.f};
         }
@@ -217,19 +245,19 @@ sgemm_skinny_combine_kernel(const SkinnyArgs a, int splits) {
     if (valid && j == 0) epilogue_store(a, o, r, col);
 }
 
-template <int RB, bool TB>
+template <int RB, bool TB, typename WT>
 void launch_nt(const SkinnyArgs &a, dim3 grid, bool nt, hipStream_t s) {
-    if (nt) hipLaunchKernelGGL((sgemm_skinny_kernel<RB, TB, true>), grid, dim3(WAVES * 64), 0, s, a);
-    else hipLaunchKernelGGL((sgemm_skinny_kernel<RB, TB, false>), grid, dim3(WAVES * 64), 0, s, a);
+    if (nt) hipLaunchKernelGGL((sgemm_skinny_kernel<RB, TB, true, WT>), grid, dim3(WAVES * 64), 0, s, a);
+    else hipLaunchKernelGGL((sgemm_skinny_kernel<RB, TB, false, WT>), grid, dim3(WAVES * 64), 0, s, a);
 }
 
-template <bool TB>
+template <bool TB, typename WT>
 void launch_rb(const SkinnyArgs &a, dim3 grid, int rb, bool nt, hipStream_t s) {
     switch (rb) {
-        case 1: launch_nt<1, TB>(a, grid, nt, s); break;
-        case 2: launch_nt<2, TB>(a, grid, nt, s); break;
-        case 3: launch_nt<3, TB>(a, grid, nt, s); break;
-        default: launch_nt<4, TB>(a, grid, nt, s); break;
+        case 1: launch_nt<1, TB, WT>(a, grid, nt, s); break;
+        case 2: launch_nt<2, TB, WT>(a, grid, nt, s); break;
+        case 3: launch_nt<3, TB, WT>(a, grid, nt, s); break;
+        default: launch_nt<4, TB, WT>(a, grid, nt, s); break;
     }
 }
 
@@ -237,7 +265,8 @@ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 const int EPI_OK = NPM_EPI_BIAS | NPM_EPI_RESIDUAL | NPM_EPI_RELU | NPM_EPI_RELU_SAVE;
 
-bool supported(const npm_gemm *g) {
+// w16: g->b points at halves (npm_sgemm_skinny_w16): ldb counts halves and a 16-byte row start takes a multiple of 8 of them
+bool supported(const npm_gemm *g, bool w16 = false) {
     if (g == nullptr) return false;
     if (g->trans_a != 0 || (g->trans_b != 0 && g->trans_b != 1)) return false;
     if (g->batch0 != 1 || g->batch1 != 1) return false;
@@ -245,7 +274,7 @@ bool supported(const npm_gemm *g) {
     if (g->n < 16 || g->n % 16 || g->k < 16 || g->k % 16) return false;
     if (g->a == nullptr || g->b == nullptr || g->c == nullptr) return false;
     if (!aligned16(g->a) || !aligned16(g->b) || !aligned16(g->c)) return false;
-    if (g->lda % 4 || g->ldb % 4 || g->ldc % 4) return false;
+    if (g->lda % 4 || g->ldb % (w16 ? 8 : 4) || g->ldc % 4) return false;
     if (g->lda < g->k || g->ldb < (g->trans_b ? g->k : g->n) || g->ldc < g->n) return false;
     if (g->epilogue & ~EPI_OK) return false;
     if ((g->epilogue & NPM_EPI_RELU) && (g->epilogue & NPM_EPI_RELU_SAVE)) return false;
@@ -291,13 +320,11 @@ extern "C" int npm_sgemm_skinny_splits(int n, int k, int trans_b) {
 
 extern "C" const char *npm_last_skinny_kernel(void) { return g_last; }
 
-extern "C" int npm_sgemm_skinny(const npm_gemm *g) {
-    NPM_REQUIRE_INIT();
-    NPM_ARG(g != nullptr);
-    if (!supported(g))
-        return npm::fail(NPM_E_UNSUPPORTED, "npm_sgemm_skinny: not supported (trans_a = 0, no batch, 1 <= m <= %d, n and k multiples "
-                         "of 16, 16-byte aligned operands, pitches multiples of 4 floats and at least the widths, epilogue of "
-                         "bias / residual / ReLU / saved ReLU only, no colsum / bsum / asum / rowdot / split_k)", NPM_SKINNY_MAX_M);
+namespace {
+
+// npm_sgemm_skinny and npm_sgemm_skinny_w16 behind their argument checks: WT is what g->b points at
+template <typename WT>
+int run(const npm_gemm *g) {
     const int splits = npm_sgemm_skinny_splits(g->n, g->k, g->trans_b);
     const int rb = (g->m + 15) / 16;
     SkinnyArgs a{};
@@ -321,18 +348,41 @@ extern "C" int npm_sgemm_skinny(const npm_gemm *g) {
         a.part = static_cast<float *>(part.ptr);
     }
     // Each weight byte is read once by one wave: the project's rule for streaming tensors (NPM_TUNE_STREAM_NT, 32 MB) on the
-    // weight bytes, NPM_TUNE_SKINNY_NT to force either way.
-    const bool nt = g_nt == 1 || (g_nt == 0 && npm::stream_nt_enabled(sizeof(float) * (size_t)g->n * g->k));
+    // weight bytes as stored, NPM_TUNE_SKINNY_NT to force either way.
+    const bool nt = g_nt == 1 || (g_nt == 0 && npm::stream_nt_enabled(sizeof(WT) * (size_t)g->n * g->k));
     const dim3 grid((g->n + STRIP - 1) / STRIP, splits);
-    if (g->trans_b) launch_rb<true>(a, grid, rb, nt, s);
-    else launch_rb<false>(a, grid, rb, nt, s);
+    if (g->trans_b) launch_rb<true, WT>(a, grid, rb, nt, s);
+    else launch_rb<false, WT>(a, grid, rb, nt, s);
     NPM_CHECK_LAUNCH();
     if (splits > 1) {
         const int total = g->m * (g->n / 4) * COMBINE_LANES;
         hipLaunchKernelGGL(sgemm_skinny_combine_kernel, dim3((total + 255) / 256), dim3(256), 0, s, a, splits);
         NPM_CHECK_LAUNCH();
     }
-    snprintf(g_last, sizeof g_last, "sgemm_skinny_kernel %s M=%d N=%d K=%d rb=%d splits=%d nt=%d", g->trans_b ? "NT" : "NN", g->m,
-             g->n, g->k, rb, splits, nt ? 1 : 0);
+    snprintf(g_last, sizeof g_last, "sgemm_skinny_kernel %s M=%d N=%d K=%d rb=%d splits=%d nt=%d%s", g->trans_b ? "NT" : "NN", g->m,
+             g->n, g->k, rb, splits, nt ? 1 : 0, sizeof(WT) == 2 ? " w=f16" : "");
     return NPM_OK;
+}
+
+}  // namespace
+
+extern "C" int npm_sgemm_skinny(const npm_gemm *g) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(g != nullptr);
+    if (!supported(g))
+        return npm::fail(NPM_E_UNSUPPORTED, "npm_sgemm_skinny: not supported (trans_a = 0, no batch, 1 <= m <= %d, n and k multiples "
+                         "of 16, 16-byte aligned operands, pitches multiples of 4 floats and at least the widths, epilogue of "
+                         "bias / residual / ReLU / saved ReLU only, no colsum / bsum / asum / rowdot / split_k)", NPM_SKINNY_MAX_M);
+    return run<float>(g);
+}
+
+extern "C" int npm_sgemm_skinny_w16_supported(const npm_gemm *g) { return supported(g, true) ? 1 : 0; }
+
+extern "C" int npm_sgemm_skinny_w16(const npm_gemm *g) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(g != nullptr);
+    if (!supported(g, true))
+        return npm::fail(NPM_E_UNSUPPORTED, "npm_sgemm_skinny_w16: not supported (what npm_sgemm_skinny takes, with b pointing at "
+                         "halves: ldb a multiple of 8 halves and at least the width, b 16-byte aligned; 1 <= m <= %d)", NPM_SKINNY_MAX_M);
+    return run<_Float16>(g);
 }

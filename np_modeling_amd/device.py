@@ -678,6 +678,17 @@ def _skinny_entry_points(lib) -> bool:
     return _SKINNY_LIB[1]
 
 
+_W16_LIB = (None, False)
+
+
+def _w16_entry_points(lib) -> bool:
+    """Whether the loaded library handle has npm_sgemm_skinny_w16 (an earlier library, or a host simulator of one, does not)."""
+    global _W16_LIB
+    if _W16_LIB[0] is not lib:
+        _W16_LIB = (lib, hasattr(lib, 'npm_sgemm_skinny_w16') and hasattr(lib, 'npm_sgemm_skinny_w16_supported'))
+    return _W16_LIB[1]
+
+
 class KernelTimer:
     """Brackets every kernel-wrapper call with HIP events on the compute stream and books its
     ALGORITHMIC work (flops for GEMMs, bytes for the HBM-bound kernels; DESIGN.md has the
@@ -727,14 +738,90 @@ class _timed:
 
 
 class Mat:
-    """Operand descriptor for :func:`gemm`: base pointer, row pitch, two batch strides."""
+    """Operand descriptor for :func:`gemm`: base pointer, row pitch, two batch strides.  ``half`` (a B operand only): a
+    ``HalfView`` of the same matrix stored as IEEE fp16 with the same pitch, counted in halves (``HalfWeights.view``)."""
 
-    __slots__ = ('ptr', 'ld', 's0', 's1', '_keep')
+    __slots__ = ('ptr', 'ld', 's0', 's1', '_keep', 'half')
 
-    def __init__(self, array_or_ptr, ld: int, s0: int = 0, s1: int = 0):
+    def __init__(self, array_or_ptr, ld: int, s0: int = 0, s1: int = 0, half: Optional['HalfView'] = None):
         self._keep = array_or_ptr          # keeps a temporary alive until the launch is queued
         self.ptr = array_or_ptr.ptr if isinstance(array_or_ptr, DeviceArray) else int(array_or_ptr)
         self.ld, self.s0, self.s1 = int(ld), int(s0), int(s1)
+        self.half = half
+
+
+class HalfView:
+    """Where the fp16 copy of one weight matrix starts inside a ``HalfWeights`` buffer (which it keeps alive)."""
+
+    __slots__ = ('ptr', '_keep')
+
+    def __init__(self, ptr: int, keep):
+        self.ptr, self._keep = int(ptr), keep
+
+
+class HalfWeights:
+    """A SNAPSHOT of weight matrices as IEEE fp16, for the matrix products of decode steps (``gemm`` with ``Mat(..., half=)``;
+    include/npm_hip.h npm_sgemm_skinny_w16): ``sources`` is a list of (layer, attribute); each parameter is converted once with
+    ``npm_cvt_f32_f16`` (round to nearest even, no clamp) and read in place from then on.  Sources that are adjacent in device
+    memory stay adjacent in ONE half buffer, in the same order and at the same element offsets -- so the packed q / k / v
+    projection remains one product over one half matrix.
+
+    The snapshot is of the weights AS THEY WERE.  It records each source's address and shape; ``view`` raises RuntimeError when
+    either differs (a rebound parameter: a weight binder, a test, a re-packed arena).  A change of the VALUES in place -- an
+    optimizer step -- cannot be seen: the halves then go on describing the earlier weights until ``refresh()`` converts again."""
+
+    def __init__(self, sources):
+        self._sources = [(owner, str(attribute)) for owner, attribute in sources]
+        self._entries = {}             # (id(owner), attribute) -> (HalfView, source ptr, source shape)
+        self.refresh()
+
+    def refresh(self) -> 'HalfWeights':
+        """Convert every source again, from where it lives now."""
+        lib = _C.lib()
+        if not hasattr(lib, 'npm_cvt_f32_f16'):
+            raise _C.NpmError('half-precision weights need npm_cvt_f32_f16, which the loaded library does not have')
+        params = [(owner, attribute, owner._param(attribute)) for owner, attribute in self._sources]
+        self._entries = {}
+        i = 0
+        while i < len(params):
+            j = i + 1                                       # params[i:j]: one run of sources adjacent in memory
+            while j < len(params) and params[j][2].ptr == params[j - 1][2].ptr + params[j - 1][2].nbytes:
+                j += 1
+            total = sum(p.size for _, _, p in params[i:j])
+            buf = HalfBuffer([total])
+            first = params[i][2]
+            cols = first.shape[-1] if all(p.shape[-1] == first.shape[-1] for _, _, p in params[i:j]) else total
+            if total:
+                with _timed('cvt_f32_f16', nbytes=6.0 * total):
+                    _C.check(lib.npm_cvt_f32_f16(first.ptr, cols, buf.ptr, cols, total // cols, cols), 'npm_cvt_f32_f16')
+            offset = 0
+            for owner, attribute, p in params[i:j]:
+                self._entries[id(owner), attribute] = (HalfView(buf.ptr + 2 * offset, buf), p.ptr, tuple(p.shape))
+                offset += p.size
+            i = j
+        return self
+
+    def __contains__(self, key) -> bool:
+        owner, attribute = key
+        return (id(owner), attribute) in self._entries
+
+    def view(self, owner, attribute: str) -> HalfView:
+        """The fp16 copy of ``owner``'s parameter ``attribute``; RuntimeError when the parameter is no longer the array the
+        snapshot was taken of."""
+        view, ptr, shape = self._entries[id(owner), attribute]
+        now = owner._param(attribute)
+        if now.ptr != ptr or tuple(now.shape) != shape:
+            raise RuntimeError(f'HalfWeights: {type(owner).__name__}.{attribute} was rebound after the snapshot was taken (then '
+                               f'{shape} at {ptr:#x}, now {tuple(now.shape)} at {now.ptr:#x}): refresh() it, or take a new one')
+        return view
+
+    def numpy(self, owner, attribute: str) -> np.ndarray:
+        """The stored halves of one source, for tests."""
+        view, _, shape = self._entries[id(owner), attribute]
+        host = np.empty(shape, dtype=np.float16)
+        if host.size:
+            _C.check(_C.lib().npm_d2h(host.ctypes.data, view.ptr, host.nbytes), 'npm_d2h')
+        return host
 
 
 def gemm(m: int, n: int, k: int, a: Mat, b: Mat, c: Mat, *, trans_a: bool = False, trans_b: bool = False,
@@ -750,6 +837,10 @@ def gemm(m: int, n: int, k: int, a: Mat, b: Mat, c: Mat, *, trans_a: bool = Fals
     the math mode is f32, the loaded library has the entry point and ``npm_sgemm_skinny_supported`` takes the call; otherwise it
     is the ``npm_sgemm`` call it always was.  ``save_optional``: nobody reads ``relu_save``'s pre-activation (inference), so the
     skinny route applies the ReLU without storing it.
+    ``b.half`` (un-batched, ``trans_a`` False): B is read from its fp16 copy.  Under the conditions above, with
+    ``npm_sgemm_skinny_w16`` in the library and its predicate true, that is one ``npm_sgemm_skinny_w16`` launch over the halves in
+    place.  EVERY other call converts the halves into pooled fp32 scratch (``npm_cvt_f16_f32``) and runs ``npm_sgemm`` on that,
+    so the product is the one on the rounded weights at every m, math mode and switch setting -- never the fp32 weights.
     ``rowdot=(X, out, scale)``: besides C = A @ B, out[n // 128, m] (zeros on entry) += scale * sum over each block of 128
     columns of C * X -- the attention backward's row term dctx . ctx per head of size 128, taken where dctx is produced.
     ``colsum_out`` ([batch1, n]) receives the column sums of the stored C (a bias gradient
@@ -800,6 +891,27 @@ def gemm(m: int, n: int, k: int, a: Mat, b: Mat, c: Mat, *, trans_a: bool = Fals
     nb = batch[0] * batch[1]
     unique = 4.0 * nb * (m * k + k * n + m * n * (1 + (residual is not None) + (relu_save is not None) +
                                                   (relu_mask is not None) + (softmax_bwd is not None) + (rowdot is not None)))
+    if b.half is not None:
+        assert nb == 1 and not trans_a, 'a half operand is the B of an un-batched NN / NT product'
+        assert colsum_out is None and bsum_out is None and asum_out is None, 'a half operand goes with no column-sum output'
+        lib = _C.lib()
+        if skinny_ok and SKINNY_GEMM and 0 < m <= SKINNY_MAX_M and _w16_entry_points(lib) and _C.current_math() == 'f32':
+            gs = _C.npm_gemm.from_buffer_copy(g)
+            gs.b = b.half.ptr
+            if save_optional and epi & _C.EPI_RELU_SAVE:
+                gs.epilogue, gs.aux, gs.ldaux = (epi & ~_C.EPI_RELU_SAVE) | _C.EPI_RELU, None, 0
+            if lib.npm_sgemm_skinny_w16_supported(C.byref(gs)):
+                with _timed('sgemm_skinny_w16_' + layout, flops=2.0 * m * n * k, nbytes=unique - 2.0 * k * n):
+                    _C.check(lib.npm_sgemm_skinny_w16(C.byref(gs)), 'npm_sgemm_skinny_w16')
+                return
+        rows, cols = (n, k) if trans_b else (k, n)
+        rounded = empty([rows, cols])                  # pooled; stream order keeps it alive until the product has read it
+        with _timed('cvt_f16_f32', nbytes=6.0 * rows * cols):
+            _C.check(lib.npm_cvt_f16_f32(b.half.ptr, b.ld, rounded.ptr, cols, rows, cols), 'npm_cvt_f16_f32')
+        g.b, g.ldb = rounded.ptr, cols
+        with _timed('sgemm_' + layout, flops=2.0 * m * n * k, nbytes=unique):
+            _C.check(lib.npm_sgemm(C.byref(g)), 'npm_sgemm')
+        return
     if skinny_ok and SKINNY_GEMM and 0 < m <= SKINNY_MAX_M:
         lib = _C.lib()
         if _skinny_entry_points(lib) and _C.current_math() == 'f32':

@@ -80,6 +80,13 @@ uniform contiguous cache, else the ``before`` row of the cache's device length m
 the cache, the decode and prefill kernels and the fp16 rounding see rotated rows and need nothing of their own; ``make_cache``
 sizes the tables for ``capacity``.  A frozen cross-attention cache has no query position: ``fill_cache`` and a cached forward over
 one raise NotImplementedError.  ``rope_base=None`` launches nothing and allocates nothing: every call sequence is what it was.
+
+Half-precision weight copies (opt-in).  ``half_weights()`` returns a ``device.HalfWeights`` snapshot of wq / wk / wv (one half
+buffer when they are adjacent, so the packed projection stays one product) and wo; ``forward(x, cache=cache, weights=hw)`` reads
+the projections of that cached forward from it: ``npm_sgemm_skinny_w16`` over the halves in place where the skinny-M GEMM
+applies, else the halves converted back and ``npm_sgemm`` -- the rounded weights either way, whatever M is.  Biases stay fp32; the
+cache, whatever its layout or type, does not look at the weights.  ``weights=`` without ``cache=`` raises ValueError; a snapshot
+whose parameter was rebound since raises RuntimeError (``hw.refresh()``).  Without the keyword nothing changes.
 """
 
 from __future__ import annotations
@@ -200,13 +207,22 @@ class MultiHeadAttention(layer.StatefulLayer):
                 [(self, '_bq'), (self, '_bk'), (self, '_bv')]]
 
     # -- forward -------------------------------------------------------------------------
-    def forward(self, query, key=None, value=None, mask=None, cache=None, new_lengths=None):
+    def half_weights(self) -> D.HalfWeights:
+        """A snapshot of wq / wk / wv / wo as IEEE fp16 for ``forward(x, cache=cache, weights=...)``: of the weights as they are
+        NOW (``device.HalfWeights``; ``refresh()`` after the parameters changed)."""
+        if not self._initialized:
+            raise RuntimeError('half_weights: the layer has no parameters yet (run one forward, or bind weights, first)')
+        return D.HalfWeights([(self, p) for p in ('_wq', '_wk', '_wv', '_wo')])
+
+    def forward(self, query, key=None, value=None, mask=None, cache=None, new_lengths=None, weights=None):
+        if weights is not None and cache is None:
+            raise ValueError('weights= (half-precision weight copies) serves the cached forward of incremental decoding: it needs cache=')
         query = D.as_device(query)
         if cache is not None:
             if key is not None or value is not None or mask is not None:
                 raise ValueError('with a cache, forward takes the new query tokens only: cross-attention keys and values go '
                                  'through fill_cache(cache, key, value), and the causal rule is implied')
-            return self._forward_cached(query, cache, new_lengths=new_lengths)
+            return self._forward_cached(query, cache, new_lengths=new_lengths, weights=weights)
         if new_lengths is not None:
             raise ValueError('new_lengths counts the tokens a ragged batch adds to a cache: it needs cache=')
         key = query if key is None else D.as_device(key)
@@ -346,11 +362,13 @@ class MultiHeadAttention(layer.StatefulLayer):
         cache.frozen = True
         return cache
 
-    def _forward_cached(self, query: D.DeviceArray, cache: D.KVCache, residual: Optional[D.DeviceArray] = None, new_lengths=None):
+    def _forward_cached(self, query: D.DeviceArray, cache: D.KVCache, residual: Optional[D.DeviceArray] = None, new_lengths=None,
+                        weights: Optional[D.HalfWeights] = None):
         """``forward(query, cache=cache)``: self-attention over a growing cache (causal), or cross-attention over a frozen one.
         ``new_lengths`` [B]: ``query`` is padded on the right and sequence b brings n[b] <= T tokens.  The projections are
         row-wise, so the padded rows (which must be finite) ride along; their K / V are not stored and their outputs are
-        unspecified but finite."""
+        unspecified but finite.  ``weights``: the projections read the fp16 copies of this snapshot (every weight this call
+        multiplies by must be in it)."""
         h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
         b, t, f = query.shape
         assert f == h * dk and (cache.batch, cache.kv_heads, cache.key_dim, cache.value_dim) == (b, hkv, dk, dv), \
@@ -376,9 +394,13 @@ class MultiHeadAttention(layer.StatefulLayer):
         bq, bk, bv, bo = (self._param(p) for p in ('_bq', '_bk', '_bv', '_bo'))
         fkv, fvkv = hkv * dk, hkv * dv
         fresh = None                                                     # the new tokens' own (k, v) Mats, self-attention only
+
+        def half(attribute):                                             # RuntimeError if the parameter was rebound since the snapshot
+            return None if weights is None else weights.view(self, attribute)
+
         if cross:
             q = D.empty([b, t, h, dk])
-            D.gemm(b * t, f, f, Mat(query, f), Mat(wq, f), Mat(q, f), trans_b=True, bias=bq, skinny_ok=True)
+            D.gemm(b * t, f, f, Mat(query, f), Mat(wq, f, half=half('_wq')), Mat(q, f), trans_b=True, bias=bq, skinny_ok=True)
             q = Mat(q, f)
         else:
             # ONE GEMM over M = B T rows makes q, k and v where the parameters are adjacent; K and V rows then go into the cache
@@ -387,14 +409,16 @@ class MultiHeadAttention(layer.StatefulLayer):
             if packed:
                 width = f + 2 * fkv
                 qkv = D.empty([b, t, h + 2 * hkv, dk])
-                D.gemm(b * t, width, f, Mat(query, f), Mat(wq, f), Mat(qkv, width), trans_b=True, bias=bq, skinny_ok=True)
+                # (adjacent parameters at unchanged addresses were adjacent when the snapshot was taken: so are their halves)
+                wq_half, _, _ = half('_wq'), half('_wk'), half('_wv')
+                D.gemm(b * t, width, f, Mat(query, f), Mat(wq, f, half=wq_half), Mat(qkv, width), trans_b=True, bias=bq, skinny_ok=True)
                 q = Mat(qkv, width)
                 fresh = (Mat(qkv.flat_view(f, [qkv.size - f]), width), Mat(qkv.flat_view(f + fkv, [qkv.size - f - fkv]), width))
             else:
                 qa, ka, va = D.empty([b, t, h, dk]), D.empty([b, t, hkv, dk]), D.empty([b, t, hkv, dv])
-                D.gemm(b * t, f, f, Mat(query, f), Mat(wq, f), Mat(qa, f), trans_b=True, bias=bq, skinny_ok=True)
-                D.gemm(b * t, fkv, f, Mat(query, f), Mat(wk, f), Mat(ka, fkv), trans_b=True, bias=bk, skinny_ok=True)
-                D.gemm(b * t, fvkv, f, Mat(query, f), Mat(wv, f), Mat(va, fvkv), trans_b=True, bias=bv, skinny_ok=True)
+                D.gemm(b * t, f, f, Mat(query, f), Mat(wq, f, half=half('_wq')), Mat(qa, f), trans_b=True, bias=bq, skinny_ok=True)
+                D.gemm(b * t, fkv, f, Mat(query, f), Mat(wk, f, half=half('_wk')), Mat(ka, fkv), trans_b=True, bias=bk, skinny_ok=True)
+                D.gemm(b * t, fvkv, f, Mat(query, f), Mat(wv, f, half=half('_wv')), Mat(va, fvkv), trans_b=True, bias=bv, skinny_ok=True)
                 q, fresh = Mat(qa, f), (Mat(ka, fkv), Mat(va, fvkv))
             if rope:
                 # q and the fresh k rows at positions lengths[b] + t, BEFORE they are stored: the cache, its kernels and the
@@ -416,7 +440,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         else:
             ctx = self._attend_cached(q, cache, t, causal=not cross, fresh=fresh)
         out = D.empty([b, t, f])
-        D.gemm(b * t, f, h * dv, Mat(ctx, h * dv), Mat(wo, h * dv), Mat(out, f), trans_b=True, bias=bo,
+        D.gemm(b * t, f, h * dv, Mat(ctx, h * dv), Mat(wo, h * dv, half=half('_wo')), Mat(out, f), trans_b=True, bias=bo,
                residual=None if residual is None else Mat(residual, f), skinny_ok=True)
         return out
 

@@ -33,16 +33,18 @@ class Linear(layer.StatefulLayer):
         return self._forward_impl(D.as_device(x))
 
     def _forward_impl(self, x: D.DeviceArray, residual: Optional[D.DeviceArray] = None,
-                      relu_pre: Optional[D.DeviceArray] = None, decode: bool = False) -> D.DeviceArray:
+                      relu_pre: Optional[D.DeviceArray] = None, decode: bool = False,
+                      half: Optional[D.HalfView] = None) -> D.DeviceArray:
         """y = x @ w + b (+ residual) ; with ``relu_pre`` given: relu_pre = y, return max(y, 0).  ``decode``: a decode step
-        (inference) -- the product may run on the skinny-M GEMM, which does not store ``relu_pre``."""
+        (inference) -- the product may run on the skinny-M GEMM, which does not store ``relu_pre``.  ``half``: the fp16 copy of
+        ``w`` (``device.HalfWeights.view``), read instead of ``w``."""
         w, b = self._param('_w'), self._param('_b')
         k, n = w.shape
         assert x.shape[-1] == k, f'{x.shape} vs {w.shape}'
         self._x = x
         m = x.size // k if k else 0
         y = D.empty(tuple(x.shape[:-1]) + (n,))
-        D.gemm(m, n, k, Mat(x, k), Mat(w, n), Mat(y, n), bias=b,
+        D.gemm(m, n, k, Mat(x, k), Mat(w, n, half=half), Mat(y, n), bias=b,
                residual=None if residual is None else Mat(residual, n),
                relu_save=None if relu_pre is None else Mat(relu_pre, n), skinny_ok=decode, save_optional=decode)
         return y
@@ -111,14 +113,14 @@ class Dense(layer.StatefulLayer):
     def _fused_relu(self) -> bool:
         return type(self._activation) is activations.ReLU
 
-    def forward(self, x, decode: bool = False):
+    def forward(self, x, decode: bool = False, half: Optional[D.HalfView] = None):
         x = D.as_device(x)
         if self._fused_relu():
             pre = D.empty(tuple(x.shape[:-1]) + (self._linear._output_units,))
-            y = self._linear._forward_impl(x, relu_pre=pre, decode=decode)
+            y = self._linear._forward_impl(x, relu_pre=pre, decode=decode, half=half)
             self._activation._x = pre            # what ReLU.forward would have cached (decode: possibly unwritten; no backward follows)
             return y
-        return self._activation.forward(self._linear._forward_impl(x, decode=decode))
+        return self._activation.forward(self._linear._forward_impl(x, decode=decode, half=half))
 
     def backward(self, dy, optimizer_):
         lin = self._linear

@@ -326,7 +326,7 @@ class TransformerDecoder(layer.Layer):
 
     # -- incremental decoding (inference) ------------------------------------------------------------------------------
     def start_decoding(self, kv, capacity: int, kv_lengths=None, *, page_size: Optional[int] = None, pages: Optional[int] = None,
-                       memory_capacity: Optional[int] = None, cache_dtype: str = 'f32') -> 'DecodeState':
+                       memory_capacity: Optional[int] = None, cache_dtype: str = 'f32', weights: Optional[str] = None) -> 'DecodeState':
         """Caches for ``decode``: an empty self-attention cache of ``capacity`` tokens per sequence and the cross-attention's
         keys / values, projected from ``kv`` [B, Skv, F] once.  ``kv_lengths`` [B]: ``kv`` is padded on the right and sequence b
         has only that many memory rows.  The layer must have its parameters (one forward, or bound weights).
@@ -337,7 +337,16 @@ class TransformerDecoder(layer.Layer):
         bring a longer memory than the first batch had.
 
         ``cache_dtype`` 'f16': both caches -- the self-attention one and the frozen cross-attention one -- store their K / V rows as
-        IEEE fp16 (``MultiHeadAttention.make_cache(dtype=)``): half the cache bytes, attention over the rows as stored."""
+        IEEE fp16 (``MultiHeadAttention.make_cache(dtype=)``): half the cache bytes, attention over the rows as stored.
+
+        ``weights`` 'f16' (default None): the six matrices a decode step streams -- the self-attention's q / k / v and output
+        projections, the cross-attention's query and output projections, ``dense1`` and ``dense2`` -- are copied ONCE as IEEE fp16
+        (``device.HalfWeights``, kept in ``DecodeState.weights``) and ``decode`` reads those: half the weight bytes per step, the
+        model whose six matrices are the rounded ones at every chunk size.  Biases and LayerNorm parameters stay fp32, and so do
+        the memory projections here and in ``admit``.  The snapshot is of the weights as they are now: after they change,
+        ``state.weights.refresh()``.  None allocates and launches nothing new."""
+        if weights not in (None, 'f16'):
+            raise ValueError(f"start_decoding: weights must be None or 'f16', got {weights!r}")
         if cache_dtype not in D.KV_ITEMSIZE:
             raise ValueError(f"start_decoding: cache_dtype must be one of {sorted(D.KV_ITEMSIZE)}, got {cache_dtype!r}")
         if not (self._initialized and self._self_attention._initialized and self._cross_attention._initialized):
@@ -349,8 +358,20 @@ class TransformerDecoder(layer.Layer):
             raise ValueError(f'start_decoding: memory_capacity {rows} is less than the {seq_kv} memory rows given')
         cross = self._cross_attention.fill_cache(self._cross_attention.make_cache(batch, rows, dtype=cache_dtype), kv, lengths=kv_lengths)
         if page_size is None and pages is None:
-            return DecodeState(self._self_attention.make_cache(batch, capacity, dtype=cache_dtype), cross)
-        return DecodeState(self._self_attention.make_cache(batch, capacity, page_size=page_size, pages=pages, dtype=cache_dtype), cross)
+            state = DecodeState(self._self_attention.make_cache(batch, capacity, dtype=cache_dtype), cross)
+        else:
+            state = DecodeState(self._self_attention.make_cache(batch, capacity, page_size=page_size, pages=pages, dtype=cache_dtype), cross)
+        if weights == 'f16':
+            state.weights = self._half_weights()
+        return state
+
+    def _half_weights(self) -> D.HalfWeights:
+        """The six matrices of a decode step as halves, in the order the step reads them."""
+        sa, ca, lin1, lin2 = self._self_attention, self._cross_attention, self._dense1._linear, self._dense2
+        if not (self._dense1._initialized and lin2._initialized):
+            raise RuntimeError("start_decoding(weights='f16'): the feed-forward layers have no parameters yet (run one forward, or "
+                               'bind weights, first)')
+        return D.HalfWeights([(sa, '_wq'), (sa, '_wk'), (sa, '_wv'), (sa, '_wo'), (ca, '_wq'), (ca, '_wo'), (lin1, '_w'), (lin2, '_w')])
 
     def admit(self, state: 'DecodeState', b: int, kv_b, kv_length: Optional[int] = None) -> None:
         """A new sequence into slot ``b`` of a running batch (``state.release(b)`` emptied it): its memory ``kv_b`` [1, Skv, F]
@@ -396,20 +417,23 @@ class TransformerDecoder(layer.Layer):
         self._decoded = True
         pre = self._norm_first
         sa, ca = self._self_attention, self._cross_attention
+        hw = state.weights                                                # None, or the fp16 copies of the six matrices below
         h = self._norm1._forward_impl(q) if pre else q
-        out = sa._forward_cached(h, state.self_cache, residual=q, new_lengths=new_lengths)
+        out = sa._forward_cached(h, state.self_cache, residual=q, new_lengths=new_lengths, weights=hw)
         if not pre:
             out = self._norm1._forward_impl(out)
         skip = out
         h = self._norm2._forward_impl(out) if pre else out
-        out = ca._forward_cached(h, state.cross_cache, residual=skip, new_lengths=new_lengths)
+        out = ca._forward_cached(h, state.cross_cache, residual=skip, new_lengths=new_lengths, weights=hw)
         if not pre:
             out = self._norm2._forward_impl(out)
         out = out.reshape(-1, features)
         skip = out
         h = self._norm3._forward_impl(out) if pre else out
         self._ensure(self._dense1, h)
-        out = self._dense2._forward_impl(self._dense1.forward(h, decode=True), residual=skip, decode=True)
+        half1 = None if hw is None else hw.view(self._dense1._linear, '_w')
+        half2 = None if hw is None else hw.view(self._dense2, '_w')
+        out = self._dense2._forward_impl(self._dense1.forward(h, decode=True, half=half1), residual=skip, decode=True, half=half2)
         if not pre:
             out = self._norm3._forward_impl(out)
         return out.reshape(batch, tokens, features)
@@ -503,12 +527,13 @@ class TransformerDecoder(layer.Layer):
 class DecodeState:
     """What ``TransformerDecoder.decode`` carries from step to step: the self-attention's growing key / value cache and the
     cross-attention's frozen one (``device.KVCache``).  ``position``: tokens decoded so far while that is the same number for
-    every sequence (it raises once a ragged batch made them differ); ``positions``: the number per sequence."""
+    every sequence (it raises once a ragged batch made them differ); ``positions``: the number per sequence.  ``weights``: None,
+    or the ``device.HalfWeights`` snapshot ``start_decoding(..., weights='f16')`` took -- ``release`` and ``admit`` leave it alone."""
 
-    __slots__ = ('self_cache', 'cross_cache')
+    __slots__ = ('self_cache', 'cross_cache', 'weights')
 
-    def __init__(self, self_cache: D.KVCache, cross_cache: D.KVCache):
-        self.self_cache, self.cross_cache = self_cache, cross_cache
+    def __init__(self, self_cache: D.KVCache, cross_cache: D.KVCache, weights: Optional[D.HalfWeights] = None):
+        self.self_cache, self.cross_cache, self.weights = self_cache, cross_cache, weights
 
     def release(self, b) -> None:
         """Sequence ``b`` (an index or several) has finished: its self-attention pages go back to the pool and both caches hold
