@@ -582,8 +582,12 @@ int npm_sgemm_skinny_w16(const npm_gemm *g);
 int npm_sgemm_skinny_w16_supported(const npm_gemm *g);
 
 /* ---- around the path ("next" rows of SURVEY.md section 8f): keeps a Trainer step on the device ---- */
-/* Adam with the reference's numerics (optimizer.py:53-67): fp64 moments m, v (device buffers of n doubles,
- * zero-initialised with npm_fill_f64), bias correction with step >= 1, epsilon inside the sqrt */
+/* Adam as the reference computes it (optimizer.py:53-67), operation for operation: (1 - beta1) * g and (1 - beta2) * (g * g) are
+ * float32 products (the gradient is float32 and the scalars do not widen it), the moments m, v are fp64 (device buffers of n
+ * doubles, zero-initialised with npm_fill_f64; beta * moment + term without contraction), bias correction with step >= 1 (step < 1:
+ * NPM_E_BAD_ARGUMENT), epsilon inside the sqrt, the subtraction in fp64 and ONE rounding to the float32 parameter.  The moments are
+ * the reference's bit for bit; the parameter is, up to ties of the fp64 divide / root.  npm_fill_f64: value 0.0
+ * only (anything else NPM_E_UNSUPPORTED). */
 int npm_adam_step(float *var, const float *grad, double *m, double *v, size_t n, double lr, double beta1,
                   double beta2, double eps, int step);
 int npm_fill_f64(double *dst, double value, size_t n);

@@ -11,15 +11,24 @@ inline int grid_for(size_t n, int cap = 4096) {
     return (int)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)cap));
 }
 
-// reference optimizer.py:53-67 -- fp64 moments, bias correction, epsilon INSIDE the square root,
-// the subtraction itself in fp64 (NumPy's `f32 -= f64` runs the fp64 loop) and ONE rounding to the fp32 parameter.
+// reference optimizer.py:53-67, operation for operation.  The gradient is a float32 array and the reference's Python scalars do
+// not widen it, so (a) (1 - beta1) * g and (b) (1 - beta2) * g**2 are float32 products -- g * g rounded, then the product with
+// omb2 = float(1 - beta2) rounded again -- and only then meet the fp64 moments; (c) beta * moment + term is an fp64 product and
+// an fp64 sum, each rounded on its own (NumPy has no fused multiply-add: contraction is off here); (d) bias correction, epsilon
+// INSIDE the square root, the subtraction itself in fp64 (NumPy's `f32 -= f64` runs the fp64 loop) and ONE rounding to the fp32
+// parameter.  Exact: both moments, bit for bit (fp32 / fp64 multiplies and adds only).  The parameter is bit-equal wherever the
+// fp64 divide and square root are correctly rounded; one of them an ulp off can move the parameter by one fp32 ulp only where
+// var - step lies within ~2^-40 |step| of a rounding boundary (tests/optim_cases.py counts those elements).
 __global__ void __launch_bounds__(256)
 adam_kernel(float *__restrict__ var, const float *__restrict__ grad, double *__restrict__ m, double *__restrict__ v,
-            size_t n, double lr, double beta1, double beta2, double eps, double corr1, double corr2) {
+            size_t n, double lr, double beta1, double beta2, double eps, double corr1, double corr2, float omb1, float omb2) {
+#pragma clang fp contract(off)
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const double g = (double)grad[i];
-        const double nm = beta1 * m[i] + (1.0 - beta1) * g;
-        const double nv = beta2 * v[i] + (1.0 - beta2) * g * g;
+        const float g = grad[i];
+        const float gg = g * g;
+        const double t1 = (double)(omb1 * g), t2 = (double)(omb2 * gg);
+        const double bm = beta1 * m[i], bv = beta2 * v[i];
+        const double nm = bm + t1, nv = bv + t2;
         m[i] = nm;
         v[i] = nv;
         const double step = lr * ((nm / corr1) / sqrt(nv / corr2 + eps));
@@ -155,7 +164,7 @@ int npm_adam_step(float *var, const float *grad, double *m, double *v, size_t n,
     NPM_ARG(var && grad && m && v);
     const double corr1 = 1.0 - pow(beta1, (double)step), corr2 = 1.0 - pow(beta2, (double)step);
     hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, npm::ctx().stream, var, grad, m, v, n, lr, beta1,
-                       beta2, eps, corr1, corr2);
+                       beta2, eps, corr1, corr2, (float)(1.0 - beta1), (float)(1.0 - beta2));
     NPM_CHECK_LAUNCH();
     return NPM_OK;
 }

@@ -456,14 +456,15 @@ class UpdateQueue:
             self.run()
 
     def axpy(self, var: 'DeviceArray', grad: 'DeviceArray', alpha: float) -> None:
-        self._keep.append(grad)                     # a temporary (``lr * host_array``) must outlive the deferred launch
         self._enqueue(_Pending(var.ptr, grad.ptr, var.size, ('axpy', alpha), var._buf, grad._buf))
+        self._keep.append(grad)                     # a temporary (``lr * host_array``) must outlive the deferred launch; AFTER
+        #                                             _enqueue, whose drain of an overlapping update ends with ``_keep = []``
 
     def adam(self, var: 'DeviceArray', grad: 'DeviceArray', first_ptr: int, second_ptr: int, hyper: tuple, owner) -> None:
         """``hyper`` = (lr, beta1, beta2, epsilon, step); ``owner`` keeps the moment buffers alive until run()."""
-        self._keep += [owner, grad]
         self._enqueue(_Pending(var.ptr, grad.ptr, var.size, ('adam',) + tuple(hyper), var._buf, grad._buf,
                                ((first_ptr, 8), (second_ptr, 8))))
+        self._keep += [owner, grad]                 # after _enqueue: a drain in there empties _keep, and this update is still pending
 
     def run(self) -> None:
         _C._ORDER_HOOK = None                       # the launches below are the queue itself

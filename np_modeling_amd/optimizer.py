@@ -8,8 +8,9 @@ classes here are the same contract for machines where the reference is not impor
 
 * SGD as one device ``axpy`` per parameter (``lr * grad`` stays symbolic until ``-=`` consumes it), and
 * Adam as one kernel per parameter (``npm_adam_step``) on fp64 moments resident in HBM, with the reference's
-  numerics: bias-corrected moments, epsilon INSIDE the square root, state keyed by ``f'{id(obj)}.{attribute}'``.
-  Host arrays take an equivalent NumPy path.
+  arithmetic operation for operation: the gradient products in the gradient's own float32, bias-corrected fp64 moments,
+  epsilon INSIDE the square root, one rounding of the parameter; state keyed by ``f'{id(obj)}.{attribute}'``.
+  Host arrays take the same arithmetic in NumPy.
 
 Inside ``device.coalesced_updates()`` (what ``parallel.GradScope`` wraps a backward's deferred updates in) the launches
 of parameters that are neighbours in memory -- a layer's ``device.ParamArena`` -- are joined: ONE axpy / ONE Adam kernel
@@ -94,7 +95,7 @@ class AdamOptimizer(Optimizer):
             and gradient.size == variable.size
         if on_device:
             return self._step_on_device(identifier, variable, gradient)
-        return self._step_on_host(identifier, variable, np.asarray(gradient, dtype=np.float64))
+        return self._step_on_host(identifier, variable, np.asarray(gradient))      # in its own dtype, as the reference uses it
 
     def _moments_for(self, variable, old):
         """The moments of ``variable`` at its offset inside its block's moment buffers.  A parameter that moved (into an

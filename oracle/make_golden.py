@@ -3,7 +3,8 @@
 Run in the build container only (needs /root/reference, which never travels to the
 GPU box):
 
-    PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py              (every fixture)
+    PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py adam_steps   (tests/golden/adam_steps.npz alone)
 
 It imports the reference package read-only, runs every hot-path layer
 with ``np.random.seed`` fixed, and stores inputs, initial params, outputs, input
@@ -217,6 +218,28 @@ def gen_train(layers, optimizer, train):
         save('train_mlp_' + opt_name, x=x, targets=t, losses=losses, lr=np.float64(1e-4), **final)
 
 
+def gen_adam_steps(optimizer):
+    """Three steps of the reference's own AdamOptimizer.update_variable on one float32 parameter of 1031 elements (lr 1e-2, the
+    other hyper-parameters at their defaults): the parameter and both moments after every step.  Gradients: standard normal with
+    zeros, +-0, and magnitudes whose squares are a float32 denormal and 1e38.  tests/test_gpu_optim.py holds npm_adam_step to these
+    arrays bit for bit; tests/test_optim_host.py holds the NumPy model of tests/optim_reference.py to them."""
+    rng = np.random.default_rng(1031)
+    n = 1031
+    p0 = rng.standard_normal(n).astype(np.float32)
+    opt = optimizer.AdamOptimizer(1e-2)
+    arrays = dict(p0=p0, hyper=np.array([opt.learning_rate, opt.beta1, opt.beta2, opt.epsilon], dtype=np.float64))
+    p = p0.copy()
+    for step in (1, 2, 3):
+        g = rng.standard_normal(n).astype(np.float32)
+        g[96::97] = 0.0
+        g[200:216] = np.tile(np.array([1e-20, -1e19, -1e-20, 1e19], dtype=np.float32), 4)
+        g[500:516] = np.tile(np.array([0.0, -0.0], dtype=np.float32), 8)
+        p = opt.update_variable('p', p, g)
+        assert p.dtype == np.float32
+        arrays.update({f'g{step}': g, f'p{step}': p.copy(), f'm{step}': opt._momentums['p'].copy(), f'v{step}': opt._velocities['p'].copy()})
+    save('adam_steps', **arrays)
+
+
 def gen_refshape(layers, name):
     """Fixtures at the reference's own test shapes and at the head sizes the fused attention kernels take
     (recipes, flow and rationale: tests/refshapes.py).  Stored: the reference's outputs as float32, the raw gradients
@@ -313,6 +336,10 @@ def gen_refshape(layers, name):
 def main():
     os.makedirs(OUT, exist_ok=True)
     layers, optimizer, loss, train = _ref()
+    if sys.argv[1:] == ['adam_steps']:            # this fixture alone
+        gen_adam_steps(optimizer)
+        return
+    gen_adam_steps(optimizer)
     gen_dense(layers, True, 'dense')
     gen_dense(layers, False, 'linear')
     gen_activations(layers)

@@ -718,7 +718,7 @@ def adam_step(param, grad, state: dict, lr, beta1=0.9, beta2=0.999, eps=1e-7):
     m_hat = m / (1 - beta1 ** t)
     v_hat = v / (1 - beta2 ** t)
     out = param.copy()
-    out -= (lr * (m_hat / np.sqrt(v_hat + eps))).astype(param.dtype)
+    out -= lr * (m_hat / np.sqrt(v_hat + eps))          # in place, fp64 operand: the fp64 loop and ONE rounding, as the reference's
     state.update(t=t + 1, m=m, v=v)
     return out
 

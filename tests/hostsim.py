@@ -381,47 +381,79 @@ class HostSim:
 
     # ---- around the path -------------------------------------------------------------------------
     def npm_fill_f64(self, dst, value, n):
+        if int(n) == 0:
+            return 0
+        if not _addr(dst):
+            return 10002
+        if value != 0.0:
+            return 10003                                    # only 0.0 is supported
         np.ctypeslib.as_array((C.c_double * int(n)).from_address(_addr(dst)))[:] = value
         return 0
 
     def npm_adam_step(self, var, grad, m, v, n, lr, beta1, beta2, eps, step):
+        """csrc/npm_optim.hip adam_kernel = reference optimizer.py:58-63: the two gradient products in float32, the rest in float64."""
         self.calls.append('npm_adam_step')
         n = int(n)
+        if step < 1:
+            return 10002
+        if n == 0:
+            return 0
+        if not (_addr(var) and _addr(grad) and _addr(m) and _addr(v)):
+            return 10002
         mm = np.ctypeslib.as_array((C.c_double * n).from_address(_addr(m)))
         vv = np.ctypeslib.as_array((C.c_double * n).from_address(_addr(v)))
-        g = _vec(grad, n).astype(np.float64)
-        mm[:] = beta1 * mm + (1 - beta1) * g
-        vv[:] = beta2 * vv + (1 - beta2) * g ** 2
-        upd = lr * ((mm / (1 - beta1 ** step)) / np.sqrt(vv / (1 - beta2 ** step) + eps))
+        g = _vec(grad, n)                                   # float32: the two products below stay float32
+        with np.errstate(all='ignore'):
+            mm[:] = beta1 * mm + np.float32(1 - beta1) * g
+            vv[:] = beta2 * vv + np.float32(1 - beta2) * (g * g)
+            upd = lr * ((mm / (1 - beta1 ** step)) / np.sqrt(vv / (1 - beta2 ** step) + eps))
         w = _vec(var, n)
         w -= upd                                            # fp64 loop, one rounding (as NumPy's f32 -= f64)
         return 0
 
     def npm_mse_fwd(self, y, t, n, out):
+        if int(n) == 0 or not (_addr(y) and _addr(t)):
+            return 10002
         d = _vec(y, n).astype(np.float64) - _vec(t, n)
         _deref(out).value = float((d * d).sum() / int(n))
         return 0
 
     def npm_mse_bwd(self, y, t, dy, n):
+        if int(n) == 0:
+            return 0
         _vec(dy, n)[:] = np.float32(2.0 / int(n)) * (_vec(y, n) - _vec(t, n))
         return 0
 
     def npm_xent_fwd(self, y, t, n, out):
-        _deref(out).value = float(-(_vec(t, n).astype(np.float64) * np.log(_vec(y, n).astype(np.float64))).sum())
+        if int(n) == 0 or not (_addr(y) and _addr(t)):
+            return 10002
+        with np.errstate(all='ignore'):
+            _deref(out).value = float(-(_vec(t, n).astype(np.float64) * np.log(_vec(y, n).astype(np.float64))).sum())
         return 0
 
     def npm_xent_bwd(self, y, t, dy, n):
-        _vec(dy, n)[:] = -_vec(t, n) / _vec(y, n)
+        if int(n) == 0:
+            return 0
+        with np.errstate(all='ignore'):
+            _vec(dy, n)[:] = -_vec(t, n) / _vec(y, n)
         return 0
 
     def npm_mask_scale(self, x, mask, y, n, keep):
         self.calls.append('npm_mask_scale')
+        if int(n) == 0:
+            return 0
+        if not (_addr(x) and _addr(mask) and _addr(y) and keep > 0):
+            return 10002
         mk = np.ctypeslib.as_array((C.c_ubyte * int(n)).from_address(_addr(mask)))
         _vec(y, n)[:] = np.where(mk != 0, _vec(x, n) / np.float32(keep), 0)
         return 0
 
     def npm_dropout_philox(self, x, y, mask, n, keep, seed, offset):
         self.calls.append('npm_dropout_philox')
+        if int(n) == 0:
+            return 0
+        if not _addr(mask) or bool(_addr(x)) != bool(_addr(y)) or not 0.0 < keep <= 1.0:
+            return 10002
         keep_mask = O.dropout_philox_mask(int(n), float(keep), int(seed), int(offset))
         np.ctypeslib.as_array((C.c_ubyte * int(n)).from_address(_addr(mask)))[:] = keep_mask
         if _addr(y):                               # x = y = NULL: the mask only
