@@ -506,6 +506,34 @@ int npm_mha_decode_fwd_f16(const npm_mha_decode *d, const int32_t *kv_lens, cons
 int npm_mha_prefill_fwd_f16(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens, const int32_t *block_table,
                             int32_t table_pitch, int32_t page_rows);
 
+/* ---- sliding-window (local) causal attention over a cache (opt-in; everything above is unchanged) ----
+ * window = W >= 1: a query at absolute position p sees keys max(0, p - W + 1) .. p, itself included.  Row t < n_b of sequence b
+ * has the upper limit of the causal calls above, limit = L_b - n_b + t + 1, and sees keys floor <= j < limit with
+ * floor = max(0, limit - W).  Nothing below a row's floor enters its result, whatever those cache rows hold (the rule rows >= L_b
+ * have): such a key gets score -inf by selection, V rows below the smallest floor of a tile's users are zeroed by selection, a
+ * tile wholly below that floor is never loaded and its block-table entry never read -- the pages there may have been given back.
+ * Per-sequence layouts only, arguments as the _f16 entry points take them: kv_lens is required; block_table == NULL is a
+ * contiguous cache, else a page pool; kv_f16 != 0: d->k / d->v point at halves, pitches and strides count halves.  Refusals are
+ * those of the entry point of the same layout and storage type; in addition NPM_E_BAD_ARGUMENT for window < 1, d->causal == 0
+ * and kv_lens == NULL.  A refused call launches nothing.
+ * npm_mha_decode_fwd_window (rows <= NPM_DECODE_MAX_ROWS): the key walk of sequence b starts at its first live tile
+ * lo_b = max(0, L_b - n_b + 1 - W) / 16 and the split partition is laid over the window: with keys_bound = min(d->kv_len,
+ * W + new_tokens - 1) the split count is npm_mha_decode_splits(batch, kv_heads, keys_bound) (= npm_mha_decode_window_splits),
+ * tiles_per_split covers the most 16-key tiles an interval of keys_bound keys can touch, split s takes tiles lo_b + s *
+ * tiles_per_split ..; scratch, grid and the load policy follow keys_bound.  W >= d->kv_len: BITWISE the unwindowed entry point of
+ * the same layout and storage type.  Paged is bitwise contiguous on the same rows, fp16 bitwise the fp32 call on the rounded
+ * values; a row without a visible key is ctx = 0, lse = -inf by selection.
+ * npm_mha_prefill_fwd_window (any number of rows): a block's walk starts at the tile of the smallest floor of its live rows and a
+ * wave skips tiles wholly below its own rows' smallest floor; keys are not split, so the identities of npm_mha_prefill_fwd[_f16]
+ * carry over bitwise, and W >= every L_b is bitwise that call.
+ * npm_last_decode_kernel() / npm_last_prefill_kernel() afterwards: the string of the same layout and storage type followed by
+ * " window=<W>". */
+int npm_mha_decode_fwd_window(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens, const int32_t *block_table,
+                              int32_t table_pitch, int32_t page_rows, int32_t window, int32_t kv_f16);
+int npm_mha_prefill_fwd_window(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens, const int32_t *block_table,
+                               int32_t table_pitch, int32_t page_rows, int32_t window, int32_t kv_f16);
+int npm_mha_decode_window_splits(int batch, int kv_heads, int kv_len, int new_tokens, int window);
+
 /* ---- rotary position embedding (RoPE), in place ----
  * Rotates the first `heads` heads of every row b * tokens + t (b < batch, t < tokens) of x: head h of a row is the head_dim floats
  * at x[row * pitch + h * head_dim]; whatever lies behind them in the row (the V heads of a packed [B, T, H + 2 Hkv, D] projection,

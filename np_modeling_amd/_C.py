@@ -170,6 +170,9 @@ SIGNATURES = {
     'npm_kv_gather_f16': [_P, _I64, _I64, _P, _I32, _I32, _I32, _P, _P, _I32, _I32],
     'npm_mha_decode_fwd_f16': [C.POINTER(npm_mha_decode), _P, _P, _P, _I32, _I32],
     'npm_mha_prefill_fwd_f16': [C.POINTER(npm_mha_decode), _P, _P, _P, _I32, _I32],
+    'npm_mha_decode_fwd_window': [C.POINTER(npm_mha_decode), _P, _P, _P, _I32, _I32, _I32, _I32],
+    'npm_mha_prefill_fwd_window': [C.POINTER(npm_mha_decode), _P, _P, _P, _I32, _I32, _I32, _I32],
+    'npm_mha_decode_window_splits': [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     'npm_rope': [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _I32],
     'npm_sgemm_skinny': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_supported': [C.POINTER(npm_gemm)],

@@ -88,7 +88,7 @@ typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 
 int g_splits = 0;                 // NPM_TUNE_DECODE_SPLITS: 0 automatic, n > 0 forced
 int g_nt = 0;                     // NPM_TUNE_DECODE_NT: 0 by size (npm::stream_nt_enabled of the valid K bytes), 1 always, 2 never
-char g_last[96] = "";
+char g_last[128] = "";
 
 struct DecodeArgs {
     const float *q, *k, *v;       // k, v: the cache in its storage type KV (halves behind a float pointer for KV = _Float16)
@@ -100,6 +100,7 @@ struct DecodeArgs {
     float *part_acc;              //             [B, Hkv, splits, RP, D]
     int heads, kv_heads, tokens, len, causal, rows, tiles_per_split;
     float c, scale;               // scale * log2(e), scale
+    int window;                   // npm_mha_decode_fwd_window: keys a row sees, itself included (read by the WN instances only)
 };
 
 // npm_*_paged: row j of sequence b is row (j & (rows - 1)) of page table[b * pitch + (j >> shift)]; rows = 1 << shift
@@ -150,214 +151,23 @@ template <int D, int RB, bool NT, bool VL, bool PG, typename KV = float>
 __global__ void __launch_bounds__(WAVES * 64)
 mha_decode_kernel(const DecodeArgs a, const int *__restrict__ kv_lens, const int *__restrict__ new_lens, const PageArgs pg) {
 #pragma clang fp contract(off)
-    static_assert(VL || !PG, "a paged cache has per-sequence lengths");
-    constexpr int KU = D / 16;                    // 4-element K loads per lane and tile (16 bytes; KV = _Float16: 8)
-    constexpr int VW = D >= 64 ? 4 : D / 16;      // elements per V load
-    constexpr int DQ = D / (16 * VW);             // V loads per lane and key
-    constexpr int NS = KU >= 4 ? 4 : KU;          // score accumulation chains
-    using VVec = typename VecOf<VW>::type;
-    __shared__ __attribute__((aligned(16))) float s_acc[WAVES][16][D + 4];
-    __shared__ float s_m[WAVES][16], s_l[WAVES][16];
-
-    const int split = blockIdx.x, c = blockIdx.y, b = blockIdx.z;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = lane & 15, g = lane >> 4;
-    const int T = a.tokens, R = a.rows;
-    // VL: block-uniform loads of the sequence's own lengths (scalar loads; nothing is stored through the scalar unit)
-    const int L = VL ? kv_lens[b] : a.len;
-    const int nb = VL ? (new_lens ? new_lens[b] : T) : T;
-    if (VL && a.part_acc && split * a.tiles_per_split * TILE >= L) {
-        // nothing of this sequence lies in the split's key range: the empty partial (its acc is never read), before any load
-        if (threadIdx.x < RB * 16) {
-            const long prow = (((long)b * a.kv_heads + c) * gridDim.x + split) * (RB * 16) + threadIdx.x;
-            a.part_ml[2 * prow] = -INFINITY;
-            a.part_ml[2 * prow + 1] = 0.f;
-        }
-        return;
-    }
-
-    // this lane's query rows (one per row block): head c + (r / T) Hkv, token r % T; padding rows are zeros and never stored
-    // (VL: so are the rows of tokens at and past nb, which are stored as ctx = 0, lse = -inf)
-    f32x4v q[RB][KU];
-    int limit[RB];                                // keys this row may see: j < limit
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-        const int r = rb * 16 + n;
-        const int t = r % T, h = c + (r / T) * a.kv_heads;
-        const bool live = VL ? r < R && t < nb : r < R;
-        limit[rb] = live ? (a.causal ? L - nb + t + 1 : L) : 0;
-        const float *src = a.q + ((long)b * T + t) * a.q_pitch + (long)h * D + 4 * g;
-#pragma unroll
-        for (int u = 0; u < KU; ++u) q[rb][u] = live ? *reinterpret_cast<const f32x4v *>(src + 16 * u) : f32x4v{0.f, 0.f, 0.f, 0.f};
-    }
-
-    f32x4v acc[RB][DQ][VW];
-    float m[RB], l[RB];
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-        m[rb] = -INFINITY;
-        l[rb] = 0.f;
-#pragma unroll
-        for (int dq = 0; dq < DQ; ++dq)
-#pragma unroll
-            for (int e = 0; e < VW; ++e) acc[rb][dq][e] = f32x4v{0.f, 0.f, 0.f, 0.f};
-    }
-
-    const int tiles = (L + TILE - 1) / TILE;      // VL: the sequence's own tiles within the split ranges of a.len; every tile below
-    const int t_begin = split * a.tiles_per_split;  // holds a key < L, so L >= 1 wherever a load is redirected to key L - 1
-    const int t_end = min(tiles, t_begin + a.tiles_per_split);
-    const KV *kbase = reinterpret_cast<const KV *>(a.k) + (PG ? 0L : (long)b * a.k_sb) + (long)c * D + 4 * g;
-    const KV *vbase = reinterpret_cast<const KV *>(a.v) + (PG ? 0L : (long)b * a.v_sb) + (long)c * D + VW * n;
-
-    f32x4v kr[KU];
-    VVec vr[4][DQ];
-    // PG: the page of a tile, a function of b, the tile index and kernel arguments only -- wave-uniform, a scalar load.  The index
-    // is clamped to the page of key L - 1 (callers have L >= 1), so a look-ahead past the sequence's last tile reads a page in use.
-    auto page_of = [&](int tile) -> int {
-        const int idx = __builtin_amdgcn_readfirstlane(min(tile * TILE, L - 1) >> pg.shift);
-        return pg.table[(long)b * pg.pitch + idx];
-    };
-    auto load_tile = [&](int tile, int page) {
-        const int key0 = tile * TILE;
-        const int in_page = PG ? (1 << pg.shift) - 1 : ~0;                // PG: the row within the page
-        const KV *kp = kbase + (PG ? (long)page * a.k_sb : 0L) + (long)(min(key0 + n, L - 1) & in_page) * a.k_pitch;
-#pragma unroll
-        for (int u = 0; u < KU; ++u) kr[u] = ld_kv<NT, f32x4v>(kp + 16 * u);
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const KV *vp = vbase + (PG ? (long)page * a.v_sb : 0L) + (long)(min(key0 + 4 * g + w, L - 1) & in_page) * a.v_pitch;
-#pragma unroll
-            for (int dq = 0; dq < DQ; ++dq) vr[w][dq] = ld_kv<NT, VVec>(vp + 16 * VW * dq);
-        }
-    };
-
-    int tile = t_begin + wave;
-    int page_next = 0;                            // PG: the page of tile + WAVES, looked up one step before its loads
-    if (tile < t_end) {
-        load_tile(tile, PG ? page_of(tile) : 0);
-        if (PG) page_next = page_of(tile + WAVES);
-    }
-    for (; tile < t_end; tile += WAVES) {
-        const int key0 = tile * TILE;
-        // S^T = K Q^T
-        // NS independent accumulation chains (16-byte load u feeds chain u % NS), summed pairwise: shorter dependent MFMA chains,
-        // and a score that is the sum of like-signed terms (a key aligned with the query) loses half the bits a single chain of
-        // D / 4 steps loses
-        f32x4v sp[RB][NS], s[RB];
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int i = 0; i < NS; ++i) sp[rb][i] = f32x4v{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int u = 0; u < KU; ++u)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int rb = 0; rb < RB; ++rb) sp[rb][u % NS] = MFMA16(kr[u][e], q[rb][u][e], sp[rb][u % NS]);
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) s[rb] = NS == 4 ? (sp[rb][0] + sp[rb][1]) + (sp[rb][2] + sp[rb][3]) : NS == 2 ? sp[rb][0] + sp[rb][1] : sp[rb][0];
-        // V of this tile into the A operands (keys >= L zeroed: the last tile of the cache only), then the next tile's loads
-        VVec va[4][DQ];
-        const bool ragged = key0 + TILE > L;      // wave-uniform
-#pragma unroll
-        for (int w = 0; w < 4; ++w)
-#pragma unroll
-            for (int dq = 0; dq < DQ; ++dq) {
-                va[w][dq] = vr[w][dq];
-                if (ragged && key0 + 4 * g + w >= L) va[w][dq] = VVec(0.f);
-            }
-        if (tile + WAVES < t_end) load_tile(tile + WAVES, page_next);
-        if (PG) page_next = page_of(tile + 2 * WAVES);
-
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb) {
-            // -inf by selection for keys the row does not see; then log2 units
-            float x[4], tmax = -INFINITY;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const bool seen = key0 + 4 * g + w < limit[rb];
-                x[w] = seen ? s[rb][w] : -INFINITY;
-                tmax = fmaxf(tmax, x[w]);
-            }
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 16));
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-            const float m_new = fmaxf(m[rb], tmax);                   // raw
-            const float ref = m_new == -INFINITY ? 0.f : m_new * a.c; // a row with nothing visible yet: exponents stay -inf, not NaN
-            const float alpha = __builtin_amdgcn_exp2f(m[rb] * a.c - ref);   // -inf * c = -inf: 0
-            m[rb] = m_new;
-            float psum = 0.f;
-            f32x4v p;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                p[w] = __builtin_amdgcn_exp2f(fmaf(x[w], a.c, -ref));
-                psum += p[w];
-            }
-            l[rb] = l[rb] * alpha + psum;
-#pragma unroll
-            for (int dq = 0; dq < DQ; ++dq)
-#pragma unroll
-                for (int e = 0; e < VW; ++e) {
-                    f32x4v o = acc[rb][dq][e] * alpha;
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) o = MFMA16(comp<VW>(va[w][dq], e), p[w], o);
-                    acc[rb][dq][e] = o;
-                }
-        }
-    }
-
-    // merge the four waves in wave order, one row block at a time, and store
-    const long slot = ((long)b * a.kv_heads + c) * gridDim.x + split;
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-        float lsum = l[rb];
-        lsum += __shfl_xor(lsum, 16);
-        lsum += __shfl_xor(lsum, 32);
-        if (rb) __syncthreads();
-        if (g == 0) { s_m[wave][n] = m[rb]; s_l[wave][n] = lsum; }
-        __syncthreads();
-        float m_tot = -INFINITY;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) m_tot = fmaxf(m_tot, s_m[w][n]);
-        const float ref = m_tot == -INFINITY ? 0.f : m_tot * a.c;
-        const float weight = __builtin_amdgcn_exp2f(m[rb] * a.c - ref);   // 0 for a wave that saw nothing of this row
-#pragma unroll
-        for (int dq = 0; dq < DQ; ++dq)
-#pragma unroll
-            for (int e = 0; e < VW; ++e)
-#pragma unroll
-                for (int w = 0; w < 4; ++w) s_acc[wave][n][16 * VW * dq + VW * (4 * g + w) + e] = acc[rb][dq][e][w] * weight;
-        __syncthreads();
-        for (int i = threadIdx.x; i < 16 * (D / 4); i += WAVES * 64) {
-            const int row = i / (D / 4), d = (i % (D / 4)) * 4;
-            const int r = rb * 16 + row;
-            float mt = -INFINITY;
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) mt = fmaxf(mt, s_m[w][row]);
-            const float rf = mt == -INFINITY ? 0.f : mt * a.c;
-            float lt = 0.f;
-            f32x4v o{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int w = 0; w < WAVES; ++w) {
-                lt += s_l[w][row] * __builtin_amdgcn_exp2f(s_m[w][row] * a.c - rf);
-                o += *reinterpret_cast<const f32x4v *>(&s_acc[w][row][d]);
-            }
-            if (a.part_acc) {                      // this split's (m, l, acc) of the row, padding rows included (finite: q = 0)
-                const long prow = slot * (RB * 16) + r;
-                *reinterpret_cast<f32x4v *>(a.part_acc + prow * D + d) = o;
-                if (d == 0) { a.part_ml[2 * prow] = mt; a.part_ml[2 * prow + 1] = lt; }
-            } else if (r < R) {
-                const int t = r % T, h = c + (r / T) * a.kv_heads;
-                const bool none = VL && mt == -INFINITY;       // no visible key: 0 and -inf by selection, not 0 / 0
-                *reinterpret_cast<f32x4v *>(a.ctx + ((long)b * T + t) * a.ctx_pitch + (long)h * D + d) =
-                    none ? f32x4v{0.f, 0.f, 0.f, 0.f} : o / lt;
-                if (d == 0 && a.lse)
-                    a.lse[((long)b * a.heads + h) * T + t] =
-                        none ? -INFINITY : fmaf(a.scale, mt, (__builtin_amdgcn_logf(lt) + fmaf(-mt, a.c, rf)) * LN2);
-            }
-        }
-    }
+    constexpr bool WN = false;
+#include "npm_decode_block.h"
 }
 
+// Sliding-window attention (npm_mha_decode_fwd_window): the same body with WN on, for the per-sequence layouts only (VL).  Row t of
+// sequence b sees keys max(0, limit - a.window) <= j < limit; the walk starts at the sequence's first live tile
+// lo = max(0, L - nb + 1 - a.window) / 16 and a.tiles_per_split partitions the tiles FROM THERE (the host sizes it for the most
+// tiles min(a.len, window + T - 1) keys can touch).  A key below a row's floor gets -inf by selection, V rows below the smallest
+// floor of the sequence are zeroed by selection, tiles below lo are not loaded and their table entries not read.  A kernel name
+// of its own: the instances above keep theirs, symbol for symbol.
+template <int D, int RB, bool NT, bool PG, typename KV>
+__global__ void __launch_bounds__(WAVES * 64)
+mha_decode_window_kernel(const DecodeArgs a, const int *__restrict__ kv_lens, const int *__restrict__ new_lens, const PageArgs pg) {
+#pragma clang fp contract(off)
+    constexpr bool VL = true, WN = true;
+#include "npm_decode_block.h"
+}
 
 // One thread per (batch, K / V head, row, four columns): the splits of the row merged in split order.
 // VL: a row none of whose splits saw a key (a padded token, a sequence without keys) is ctx = 0, lse = -inf by selection.
@@ -489,6 +299,24 @@ void launch_decode_rb(const DecodeArgs &a, const int *kv_lens, const int *new_le
     else launch_decode<D, 2, false, false, KV>(a, nullptr, nullptr, pg, grid, nt, s);
 }
 
+template <int D, typename KV>
+void launch_decode_window(const DecodeArgs &a, const int *kv_lens, const int *new_lens, const PageArgs &pg, dim3 grid, int rb, bool nt,
+                          hipStream_t s) {
+    const dim3 block(WAVES * 64);
+#define NPM_WINDOW(RB, NT, PG) hipLaunchKernelGGL((mha_decode_window_kernel<D, RB, NT, PG, KV>), grid, block, 0, s, a, kv_lens, new_lens, pg)
+#define NPM_WINDOW_NT(RB, PG) do { if (nt) NPM_WINDOW(RB, true, PG); else NPM_WINDOW(RB, false, PG); } while (0)
+    if (pg.table) {
+        if (rb == 1) NPM_WINDOW_NT(1, true); else NPM_WINDOW_NT(2, true);
+    } else {
+        if (rb == 1) NPM_WINDOW_NT(1, false); else NPM_WINDOW_NT(2, false);
+    }
+#undef NPM_WINDOW_NT
+#undef NPM_WINDOW
+}
+
+// The keys one sequence of a windowed call can hold live: its T rows see at most window + T - 1 of them, and never more than kv_len
+long window_keys(long kv_len, long tokens, long window) { return std::min(kv_len, window + tokens - 1); }
+
 // page_rows -> log2, or -1 unless it is a power of two >= TILE
 int page_shift(int page_rows) {
     if (page_rows < TILE || (page_rows & (page_rows - 1))) return -1;
@@ -528,15 +356,23 @@ extern "C" int npm_mha_decode_splits(int batch, int kv_heads, int kv_len) {
     return (int)std::max<long>(1, std::min<long>(std::min(want, by_len), NPM_DECODE_MAX_SPLITS));
 }
 
+extern "C" int npm_mha_decode_window_splits(int batch, int kv_heads, int kv_len, int new_tokens, int window) {
+    if (kv_len < 1 || new_tokens < 1 || window < 1) return 1;
+    return npm_mha_decode_splits(batch, kv_heads, (int)window_keys(kv_len, new_tokens, window));
+}
+
 extern "C" const char *npm_last_decode_kernel(void) { return g_last; }
 
 // npm_mha_decode_fwd (kv_lens == nullptr), npm_mha_decode_fwd_varlen and npm_mha_decode_fwd_paged (block_table != nullptr): one
 // host path, so that the split count, the tile partition and the load policy of a varlen or paged call are those of the uniform
 // call at d->kv_len.  KV = _Float16 (npm_mha_decode_fwd_f16): d->k / d->v hold halves and their pitches and strides count halves
 // (multiples of 8: 16 bytes); the same checks, split count and partition, and the load policy on the BYTES of the valid part of K.
+// window > 0 (npm_mha_decode_fwd_window; the entry point has checked it, d->causal and kv_lens): split count, partition, scratch,
+// grid and load policy follow keys_bound = min(kv_len, window + T - 1) -- kv_len itself under a covering window, so that call is
+// the unwindowed one operation for operation.
 template <typename KV = float>
 static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens,
-                      const int32_t *block_table = nullptr, int32_t table_pitch = 0, int32_t page_rows = 0) {
+                      const int32_t *block_table = nullptr, int32_t table_pitch = 0, int32_t page_rows = 0, int32_t window = 0) {
     const bool varlen = kv_lens != nullptr, paged = block_table != nullptr;
     constexpr int KV_ALIGN = 16 / sizeof(KV);                          // elements of the cache in 16 bytes
     NPM_REQUIRE_INIT();
@@ -564,8 +400,11 @@ static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *
     NPM_ARG(d->k_pitch >= (int64_t)d->kv_heads * D && d->v_pitch >= (int64_t)d->kv_heads * D);
     NPM_ARG(d->batch <= 65535 && d->kv_heads <= 65535);
 
-    const int tiles = (d->kv_len + TILE - 1) / TILE;
-    const int splits = npm_mha_decode_splits(d->batch, d->kv_heads, d->kv_len);
+    // window: an interval of keys_bound keys touches at most (keys_bound + 14) / 16 + 1 tiles wherever it starts, and no more than
+    // the cache has
+    const int keys_bound = window > 0 ? (int)window_keys(d->kv_len, d->new_tokens, window) : d->kv_len;
+    const int tiles = window > 0 ? std::min((d->kv_len + TILE - 1) / TILE, (keys_bound + TILE - 2) / TILE + 1) : (d->kv_len + TILE - 1) / TILE;
+    const int splits = npm_mha_decode_splits(d->batch, d->kv_heads, keys_bound);
     const int rb = rows > 16 ? 2 : 1;
     DecodeArgs a{};
     a.q = d->q; a.k = d->k; a.v = d->v;
@@ -576,6 +415,7 @@ static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *
     a.tiles_per_split = (tiles + splits - 1) / splits;
     a.c = d->scale * LOG2E;
     a.scale = d->scale;
+    a.window = window;
 
     hipStream_t s = npm::ctx().stream;
     npm::Scratch ml, acc;
@@ -590,12 +430,21 @@ static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *
     // Each K / V byte is read once by one block.  Measured (tools/decode_bench.py, profiles/r08_decode_bench.log): from 64 MB of
     // K + V up the nontemporal hint is 3 - 13 % faster (the stream does not displace itself in the L2s and the Infinity Cache);
     // below that plain loads are 0 - 3 % faster.  The project's rule for streaming tensors (32 MB each) draws the same line.
-    const bool nt = g_nt == 1 || (g_nt == 0 && npm::stream_nt_enabled(sizeof(KV) * (size_t)d->batch * d->kv_len * d->kv_heads * D));
-    switch (D) {
-        case 16: launch_decode_rb<16, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
-        case 32: launch_decode_rb<32, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
-        case 64: launch_decode_rb<64, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
-        default: launch_decode_rb<128, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+    const bool nt = g_nt == 1 || (g_nt == 0 && npm::stream_nt_enabled(sizeof(KV) * (size_t)d->batch * keys_bound * d->kv_heads * D));
+    if (window > 0) {
+        switch (D) {
+            case 16: launch_decode_window<16, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+            case 32: launch_decode_window<32, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+            case 64: launch_decode_window<64, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+            default: launch_decode_window<128, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+        }
+    } else {
+        switch (D) {
+            case 16: launch_decode_rb<16, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+            case 32: launch_decode_rb<32, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+            case 64: launch_decode_rb<64, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+            default: launch_decode_rb<128, KV>(a, kv_lens, new_lens, pg, grid, rb, nt, s); break;
+        }
     }
     NPM_CHECK_LAUNCH();
     if (splits > 1) {
@@ -618,7 +467,8 @@ static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *
     int at = snprintf(g_last, sizeof g_last, "mha_decode_kernel D=%d rows=%d splits=%d causal=%d%s", D, rows, splits, a.causal,
                       varlen ? " varlen=1" : "");
     if (paged) at += snprintf(g_last + at, sizeof g_last - at, " paged=%d", page_rows);
-    if (sizeof(KV) == 2) snprintf(g_last + at, sizeof g_last - at, " kv=f16");
+    if (sizeof(KV) == 2) at += snprintf(g_last + at, sizeof g_last - at, " kv=f16");
+    if (window > 0) snprintf(g_last + at, sizeof g_last - at, " window=%d", window);
     return NPM_OK;
 }
 
@@ -648,6 +498,24 @@ extern "C" int npm_mha_decode_fwd_f16(const npm_mha_decode *d, const int32_t *kv
             return npm::fail(NPM_E_BAD_ARGUMENT, "npm_mha_decode_fwd_f16: page_rows %d is not a power of two >= %d", page_rows, TILE);
     }
     return decode_fwd<_Float16>("npm_mha_decode_fwd_f16", d, kv_lens, new_lens, block_table, table_pitch, page_rows);
+}
+
+// Sliding-window attention over the per-sequence layouts: NULL block_table is the contiguous cache (npm_mha_decode_fwd_varlen),
+// else the paged one; kv_f16: d->k / d->v hold halves.  The refusals of that entry point, and: window < 1, a call that is not
+// causal (the window is a rule about a growing self-attention cache), NULL kv_lens.  A refused call launches nothing.
+extern "C" int npm_mha_decode_fwd_window(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens,
+                                         const int32_t *block_table, int32_t table_pitch, int32_t page_rows, int32_t window,
+                                         int32_t kv_f16) {
+    const char *name = "npm_mha_decode_fwd_window";
+    NPM_REQUIRE_INIT();
+    if (window < 1) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: window %d is not >= 1", name, window);
+    if (d == nullptr) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: the descriptor is NULL", name);
+    if (d->causal == 0) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: a window needs causal attention", name);
+    if (kv_lens == nullptr) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: kv_lens is NULL", name);
+    if (block_table != nullptr && page_shift(page_rows) < 0)
+        return npm::fail(NPM_E_BAD_ARGUMENT, "%s: page_rows %d is not a power of two >= %d", name, page_rows, TILE);
+    if (kv_f16) return decode_fwd<_Float16>(name, d, kv_lens, new_lens, block_table, table_pitch, page_rows, window);
+    return decode_fwd<float>(name, d, kv_lens, new_lens, block_table, table_pitch, page_rows, window);
 }
 
 // What the five row-copy entry points share, after NPM_REQUIRE_INIT and the preconditions that hold even for an empty call: the

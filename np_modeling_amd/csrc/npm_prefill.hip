@@ -54,7 +54,7 @@ typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
-char g_last[112] = "";
+char g_last[128] = "";
 
 struct PrefillArgs {
     const float *q, *k, *v;       // k, v: the cache in its storage type KV (halves behind a float pointer for KV = _Float16)
@@ -65,6 +65,7 @@ struct PrefillArgs {
     int heads, kv_heads, tokens, len, causal;
     int group, gb, tb, head_chunks;   // Hq / Hkv; heads of the group and tokens per block (gb tb <= ROWS); ceil(group / gb)
     float c, scale;               // scale * log2(e), scale
+    int window;                   // npm_mha_prefill_fwd_window: keys a row sees, itself included (read by the WN instances only)
 };
 
 struct PageArgs {
@@ -96,6 +97,7 @@ __global__ void __launch_bounds__(WAVES * 64)
 mha_prefill_kernel(const PrefillArgs a, const int *__restrict__ kv_lens, const int *__restrict__ new_lens, const PageArgs pg) {
 #pragma clang fp contract(off)
     using KV = float;
+    constexpr bool WN = false;
 #include "npm_prefill_block.h"
 }
 
@@ -104,12 +106,45 @@ __global__ void __launch_bounds__(WAVES * 64)
 mha_prefill_f16_kernel(const PrefillArgs a, const int *__restrict__ kv_lens, const int *__restrict__ new_lens, const PageArgs pg) {
 #pragma clang fp contract(off)
     using KV = _Float16;
+    constexpr bool WN = false;
+#include "npm_prefill_block.h"
+}
+
+// Sliding-window attention (npm_mha_prefill_fwd_window), per-sequence layouts only: row t sees keys max(0, limit - a.window) <= j
+// < limit.  The block's walk starts at the tile of the smallest floor of its live rows, a wave skips the tiles wholly below its
+// own rows' smallest floor as it skips those at and above wlimit; a key below a row's floor gets -inf by selection and V rows
+// below the block's smallest floor are zeroed on their way into LDS.  Kernel names of their own: the instances above keep theirs.
+template <int D, bool PG>
+__global__ void __launch_bounds__(WAVES * 64)
+mha_prefill_window_kernel(const PrefillArgs a, const int *__restrict__ kv_lens, const int *__restrict__ new_lens, const PageArgs pg) {
+#pragma clang fp contract(off)
+    using KV = float;
+    constexpr bool VL = true, WN = true;
+#include "npm_prefill_block.h"
+}
+
+template <int D, bool PG>
+__global__ void __launch_bounds__(WAVES * 64)
+mha_prefill_window_f16_kernel(const PrefillArgs a, const int *__restrict__ kv_lens, const int *__restrict__ new_lens, const PageArgs pg) {
+#pragma clang fp contract(off)
+    using KV = _Float16;
+    constexpr bool VL = true, WN = true;
 #include "npm_prefill_block.h"
 }
 
 template <int D, typename KV>
 void launch_prefill(const PrefillArgs &a, const int *kv_lens, const int *new_lens, const PageArgs &pg, dim3 grid, hipStream_t s) {
     const dim3 block(WAVES * 64);
+    if (a.window > 0) {
+        if constexpr (sizeof(KV) == 2) {
+            if (pg.table) hipLaunchKernelGGL((mha_prefill_window_f16_kernel<D, true>), grid, block, 0, s, a, kv_lens, new_lens, pg);
+            else hipLaunchKernelGGL((mha_prefill_window_f16_kernel<D, false>), grid, block, 0, s, a, kv_lens, new_lens, pg);
+        } else {
+            if (pg.table) hipLaunchKernelGGL((mha_prefill_window_kernel<D, true>), grid, block, 0, s, a, kv_lens, new_lens, pg);
+            else hipLaunchKernelGGL((mha_prefill_window_kernel<D, false>), grid, block, 0, s, a, kv_lens, new_lens, pg);
+        }
+        return;
+    }
     if constexpr (sizeof(KV) == 2) {
         if (pg.table) hipLaunchKernelGGL((mha_prefill_f16_kernel<D, true, true>), grid, block, 0, s, a, kv_lens, new_lens, pg);
         else if (kv_lens) hipLaunchKernelGGL((mha_prefill_f16_kernel<D, true, false>), grid, block, 0, s, a, kv_lens, new_lens, pg);
@@ -139,9 +174,10 @@ extern "C" const char *npm_last_prefill_kernel(void) { return g_last; }
 
 // npm_mha_prefill_fwd and npm_mha_prefill_fwd_f16: one host path.  KV = _Float16: d->k / d->v hold halves and their pitches and
 // strides count halves (multiples of 8: 16 bytes); the same checks, grid and launch.  ``name``: the entry point, for the error texts.
+// window > 0 (npm_mha_prefill_fwd_window; the entry point has checked it, d->causal and kv_lens): the windowed instances, same grid.
 template <typename KV>
 static int prefill_fwd(const char *name, const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens,
-                       const int32_t *block_table, int32_t table_pitch, int32_t page_rows) {
+                       const int32_t *block_table, int32_t table_pitch, int32_t page_rows, int32_t window = 0) {
 #define PREFILL_ARG(cond)                                                                              \
     do {                                                                                               \
         if (!(cond)) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: bad argument: %s", name, #cond);        \
@@ -185,6 +221,7 @@ static int prefill_fwd(const char *name, const npm_mha_decode *d, const int32_t 
     a.head_chunks = (a.group + a.gb - 1) / a.gb;
     a.c = d->scale * LOG2E;
     a.scale = d->scale;
+    a.window = window;
     const int64_t token_tiles = ((int64_t)d->new_tokens + a.tb - 1) / a.tb;
     PREFILL_ARG(token_tiles * a.head_chunks <= 0x7fffffff);
 #undef PREFILL_ARG
@@ -202,7 +239,8 @@ static int prefill_fwd(const char *name, const npm_mha_decode *d, const int32_t 
     int at = snprintf(g_last, sizeof g_last, "mha_prefill_kernel D=%d T=%d rows=%d causal=%d%s", D, d->new_tokens, ROWS, a.causal,
                       varlen ? " varlen=1" : "");
     if (paged) at += snprintf(g_last + at, sizeof g_last - at, " paged=%d", page_rows);
-    if (sizeof(KV) == 2) snprintf(g_last + at, sizeof g_last - at, " kv=f16");
+    if (sizeof(KV) == 2) at += snprintf(g_last + at, sizeof g_last - at, " kv=f16");
+    if (window > 0) snprintf(g_last + at, sizeof g_last - at, " window=%d", window);
     return NPM_OK;
 }
 
@@ -214,4 +252,19 @@ extern "C" int npm_mha_prefill_fwd(const npm_mha_decode *d, const int32_t *kv_le
 extern "C" int npm_mha_prefill_fwd_f16(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens,
                                        const int32_t *block_table, int32_t table_pitch, int32_t page_rows) {
     return prefill_fwd<_Float16>("npm_mha_prefill_fwd_f16", d, kv_lens, new_lens, block_table, table_pitch, page_rows);
+}
+
+// Sliding-window attention over the per-sequence layouts (NULL block_table: the contiguous cache; kv_f16: halves).  The refusals of
+// npm_mha_prefill_fwd[_f16], and: window < 1, a call that is not causal, NULL kv_lens.  A refused call launches nothing.
+extern "C" int npm_mha_prefill_fwd_window(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens,
+                                          const int32_t *block_table, int32_t table_pitch, int32_t page_rows, int32_t window,
+                                          int32_t kv_f16) {
+    const char *name = "npm_mha_prefill_fwd_window";
+    if (!npm::ctx().ready) return npm::fail(NPM_E_NOT_INITIALIZED, "%s: npm_init() has not been called", name);
+    if (window < 1) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: window %d is not >= 1", name, window);
+    if (d == nullptr) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: the descriptor is NULL", name);
+    if (d->causal == 0) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: a window needs causal attention", name);
+    if (kv_lens == nullptr) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: kv_lens is NULL", name);
+    if (kv_f16) return prefill_fwd<_Float16>(name, d, kv_lens, new_lens, block_table, table_pitch, page_rows, window);
+    return prefill_fwd<float>(name, d, kv_lens, new_lens, block_table, table_pitch, page_rows, window);
 }

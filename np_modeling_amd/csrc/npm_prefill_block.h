@@ -1,8 +1,10 @@
-// NOT A HEADER OF ITS OWN: a fragment of two function bodies.  It has no include guard, declares nothing at file scope and compiles
-// nowhere but at its two places in npm_prefill.hip; include it nowhere else.
+// NOT A HEADER OF ITS OWN: a fragment of four function bodies.  It has no include guard, declares nothing at file scope and compiles
+// nowhere but at its four places in npm_prefill.hip; include it nowhere else.
 //
-// The body of mha_prefill_kernel and mha_prefill_f16_kernel (npm_prefill.hip includes this file once inside each, after
-// ``using KV = float`` or ``_Float16``): the storage type of the cache.  Only the base pointers, load_tile and store_tile know it.
+// The body of mha_prefill_kernel, mha_prefill_f16_kernel and their windowed forms mha_prefill_window_kernel /
+// mha_prefill_window_f16_kernel (npm_prefill.hip includes this file once inside each, after ``using KV = float`` or ``_Float16``
+// and ``constexpr bool WN``; the windowed ones fix VL = true): the storage type of the cache, and whether a row sees only the
+// a.window keys below its limit.  Only the base pointers, load_tile and store_tile know it.
 // It is text and not an inlined function template because the fp32 kernels then compile to what they were before the fp16
 // instances existed, register for register (an inlined body costs some instances two scalar registers).
     static_assert(VL || !PG, "a paged cache has per-sequence lengths");
@@ -37,6 +39,7 @@
     const bool exists = r < a.gb * a.tb && gi < a.group && t < T;
     const bool live = exists && t < nb;
     const int limit = live ? max(0, min(a.causal ? L - nb + t + 1 : L, L)) : 0;     // keys this row may see: j < limit
+    const int lowest = WN ? max(0, limit - a.window) : 0;                           // WN: ... and j >= lowest
 
     // the block's walk: key tiles below the largest limit of its rows (its last live token's).  tok0 >= nb: no live row, no tile,
     // no load -- the rows are stored below and the block is done.
@@ -48,6 +51,20 @@
     wlimit = max(wlimit, __shfl_xor(wlimit, 4));
     wlimit = max(wlimit, __shfl_xor(wlimit, 8));
     wlimit = __builtin_amdgcn_readfirstlane(wlimit);
+    // WN: the smallest floor of the block's live rows (its first token's) -- the walk starts at its tile, V rows below it are
+    // zeroed on their way into LDS, no table entry below its page is read -- and of this wave's live rows (wave-uniform): the
+    // wave skips the tiles wholly below it
+    const int bmin = WN && tok0 < nb ? max(0, L - nb + tok0 + 1 - a.window) : 0;
+    const int tile0 = WN ? bmin / TILE : 0;
+    int wlow = 0;
+    if (WN) {
+        wlow = live ? lowest : 0x7fffffff;
+        wlow = min(wlow, __shfl_xor(wlow, 1));
+        wlow = min(wlow, __shfl_xor(wlow, 2));
+        wlow = min(wlow, __shfl_xor(wlow, 4));
+        wlow = min(wlow, __shfl_xor(wlow, 8));
+        wlow = __builtin_amdgcn_readfirstlane(wlow);
+    }
 
     f32x4v q[KU];
     {
@@ -88,7 +105,10 @@
                 const long row = min(key, L - 1) & in_page;
                 kst[i] = *reinterpret_cast<const Piece *>(kbase + koff + row * a.k_pitch + col);
                 vst[i] = *reinterpret_cast<const Piece *>(vbase + voff + row * a.v_pitch + col);
-                if (key >= L) vst[i] = Piece(KV(0));                    // the last tile of the sequence only
+                if (key >= L || (WN && key < bmin)) vst[i] = Piece(KV(0));   // the last tile of the sequence only (WN: and the first of the walk)
+                // (WN: a wave whose rows have a higher floor than bmin multiplies p = 0 by the V rows in bmin .. its floor as they
+                // are.  That is sound only because every row in bmin .. L - 1 is a live row of the sequence -- the cache gives back
+                // nothing at or above the floor of the sequence's first new token.  A reclaim bound above that needs a zero here.)
             }
         }
     };
@@ -112,15 +132,15 @@
         }
     };
 
-    if (tiles > 0) {
-        load_tile(0);
-        store_tile(0);
+    if (tiles > tile0) {
+        load_tile(tile0);
+        store_tile(tile0 & 1);
     }
     __syncthreads();
-    for (int tile = 0; tile < tiles; ++tile) {
+    for (int tile = tile0; tile < tiles; ++tile) {
         const int key0 = tile * TILE, buf = tile & 1;
         if (tile + 1 < tiles) load_tile(tile + 1);                    // in flight during the products below
-        if (key0 < wlimit) {                                          // wave-uniform: some row of this wave sees a key of the tile
+        if (key0 < wlimit && (!WN || key0 + TILE > wlow)) {           // wave-uniform: some row of this wave sees a key of the tile
             // S^T = K Q^T: NS independent accumulation chains, summed pairwise (as in mha_decode_kernel)
             f32x4v sp[NS], s;
 #pragma unroll
@@ -136,7 +156,7 @@
             float x[4], tmax = -INFINITY;
 #pragma unroll
             for (int w = 0; w < 4; ++w) {
-                x[w] = key0 + 4 * g + w < limit ? s[w] : -INFINITY;
+                x[w] = key0 + 4 * g + w < limit && (!WN || key0 + 4 * g + w >= lowest) ? s[w] : -INFINITY;
                 tmax = fmaxf(tmax, x[w]);
             }
             tmax = fmaxf(tmax, __shfl_xor(tmax, 16));

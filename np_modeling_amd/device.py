@@ -1198,6 +1198,16 @@ def _kv_dtype(dtype, kv_heads: int, key_dim: int, value_dim: int) -> str:
     return dtype
 
 
+def _kv_window(window, key_dim: int, value_dim: int) -> Optional[int]:
+    if window is None:
+        return None
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
+        raise ValueError(f'KVCache: window must be None or an integer >= 1, got {window!r}')
+    if key_dim != value_dim:
+        raise ValueError(f'KVCache: a windowed cache is read by the decode and prefill kernels only: head sizes {key_dim} / {value_dim} differ')
+    return int(window)
+
+
 def kv_append(src: Mat, dst: int, layout: KVLayout, batch: int, tokens: int, at: int, lens, rows: int) -> None:
     """Row ``at + t`` of sequence b of the cache tensor at address ``dst`` = src[b * tokens + t]; ``src``: (array, row pitch) of
     [B, T, Hkv * D] rows, e.g. the K part of a packed projection (include/npm_hip.h npm_kv_append).  ``lens`` = (at_lens,
@@ -1269,19 +1279,34 @@ def _decode_desc(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int,
     return c, ctx, lse, kl
 
 
+def _window_call(entry: str, timer: str, c, cache: 'KVCache', layout: KVLayout, heads: int, tokens: int, keys: int, lens, window: int):
+    """``npm_mha_decode_fwd_window`` / ``npm_mha_prefill_fwd_window`` (``entry``) on a filled descriptor: the per-sequence form only."""
+    if lens is None:
+        raise ValueError(f'{entry}: a window needs the per-sequence lengths')
+    b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
+    keys = min(int(keys), b * (int(window) + tokens - 1))                # the keys a windowed call reads at most
+    with _timed(timer, flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens) + 2.0 * cache.itemsize * d * hkv * keys):
+        _C.check(getattr(_C.lib(), entry)(C.byref(c), lens[0], lens[1], layout.table, layout.table_pitch, layout.page_rows, int(window),
+                                          int(cache.dtype == 'f16')), entry)
+
+
 def mha_decode(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, scale: float, causal: bool, want_lse: bool = False,
-               lens=None, keys: Optional[int] = None):
+               lens=None, keys: Optional[int] = None, window: Optional[int] = None):
     """ctx [B, T, Hq, D] (and lse [B, Hq, T] or None) of ``tokens`` query rows per sequence over the first ``kv_len`` rows of
     ``cache`` (include/npm_hip.h npm_mha_decode_fwd).  ``q``: (array, row pitch).
 
     ``lens`` = (kv_lens, new_lens), DEVICE addresses of [B] int32 -- valid rows with the new tokens included; new tokens of the
     padded ``tokens``, or None for all -- makes it the call of a ragged batch (npm_mha_decode_fwd_varlen; through the block table
     of a paged cache npm_mha_decode_fwd_paged, bitwise the same on the same rows): ``kv_len`` is then the host's upper bound of
-    ``kv_lens`` and rows without a visible key come back as ctx 0, lse -inf.  ``keys``: the sum of the lengths, for the timer."""
+    ``kv_lens`` and rows without a visible key come back as ctx 0, lse -inf.  ``keys``: the sum of the lengths, for the timer.
+    ``window`` W: row t sees only the W keys up to its own (npm_mha_decode_fwd_window; per-sequence form, causal)."""
     assert cache.key_dim == cache.value_dim and 0 <= kv_len <= cache.capacity and (lens is not None or tokens <= kv_len)
     c, ctx, lse, layout = _decode_desc(q, cache, heads, tokens, kv_len, scale, causal, want_lse)
     b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
     keys = b * kv_len if keys is None else int(keys)
+    if window is not None:
+        _window_call('npm_mha_decode_fwd_window', 'mha_decode', c, cache, layout, heads, tokens, keys, lens, window)
+        return ctx, lse
     if cache.dtype == 'f16':
         kv_lens, new_lens = (None, None) if lens is None else lens
         with _timed('mha_decode', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + hkv * keys)):
@@ -1319,16 +1344,19 @@ def mha_prefill_supported(head_dim: int, value_dim: Optional[int] = None) -> boo
 
 
 def mha_prefill(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, scale: float, causal: bool, want_lse: bool = False,
-                lens=None, keys: Optional[int] = None):
+                lens=None, keys: Optional[int] = None, window: Optional[int] = None):
     """``mha_decode`` without its limit on the rows (include/npm_hip.h npm_mha_prefill_fwd): ctx [B, T, Hq, D] (and lse
     [B, Hq, T] or None) of ``tokens`` query rows per sequence over ``cache``, read in place -- through the block table of a paged
     cache -- with ``lens`` = (kv_lens, new_lens) as there.  No mask and no gathered copy exist.  An fp16 cache takes
     ``npm_mha_prefill_fwd_f16`` (bitwise the fp32 call on the rounded values); this is the low-level call, whatever
-    ``PREFILL_KERNEL_F16`` says."""
+    ``PREFILL_KERNEL_F16`` says.  ``window`` W: npm_mha_prefill_fwd_window, as in ``mha_decode``."""
     assert cache.key_dim == cache.value_dim and 0 <= kv_len <= cache.capacity and (lens is not None or tokens <= kv_len)
     c, ctx, lse, layout = _decode_desc(q, cache, heads, tokens, kv_len, scale, causal, want_lse)
     b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
     keys = b * kv_len if keys is None else int(keys)
+    if window is not None:
+        _window_call('npm_mha_prefill_fwd_window', 'mha_prefill', c, cache, layout, heads, tokens, keys, lens, window)
+        return ctx, lse
     kv_lens, new_lens = (None, None) if lens is None else lens
     if cache.dtype == 'f16':
         with _timed('mha_prefill', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + hkv * keys)):
@@ -1403,14 +1431,21 @@ class KVCache:
     once, by the append (round to nearest even; |x| >= 65520 becomes inf), and every reader -- the decode kernel, ``gather`` -- sees
     them as stored, converted back exactly (npm_kv_append_f16 / npm_mha_decode_fwd_f16 / npm_kv_gather_f16, and
     npm_mha_prefill_fwd_f16 behind ``PREFILL_KERNEL_F16``).  ``itemsize`` is the bytes per stored element and ``nbytes`` those of
-    K + V."""
+    K + V.
+
+    ``window`` W >= 1 (default None): sliding-window attention -- a token at position p sees keys max(0, p - W + 1) .. p.
+    ``attend(..., causal=True)`` then calls the windowed entry points (npm_mha_decode_fwd_window / npm_mha_prefill_fwd_window),
+    always in their per-sequence form; ``causal=False`` raises.  A contiguous windowed cache gains the speed only: its memory
+    stays B x capacity (``PagedKVCache`` gives pages back)."""
 
     paged = False
 
-    def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None, dtype: str = 'f32'):
+    def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None, dtype: str = 'f32',
+                 window: Optional[int] = None):
         value_dim = key_dim if value_dim is None else value_dim
         if min(batch, capacity, kv_heads, key_dim, value_dim) < 1:
             raise ValueError('KVCache: batch, capacity, kv_heads and the head sizes must be positive')
+        self.window = _kv_window(window, int(key_dim), int(value_dim))
         self.dtype = _kv_dtype(dtype, int(kv_heads), int(key_dim), int(value_dim))
         self.batch, self.capacity, self.kv_heads = int(batch), int(capacity), int(kv_heads)
         self.key_dim, self.value_dim = int(key_dim), int(value_dim)
@@ -1547,6 +1582,16 @@ class KVCache:
         only with ``PREFILL_KERNEL_F16`` on."""
         if kernel not in ('decode', 'prefill'):
             raise ValueError(f"KVCache.attend: kernel must be 'decode' or 'prefill', got {kernel!r}")
+        if self.window is not None:
+            if not causal:
+                raise ValueError('KVCache.attend: a windowed cache is a self-attention cache: causal=False has no window to apply')
+            n = self._counts(tokens, self.new_lengths(tokens, new_lengths))
+            if (n > self.lengths).any():
+                raise ValueError(f'KVCache.attend: {n.tolist()} new tokens are not among the {self.lengths.tolist()} valid rows')
+            _, new_ptr, kv_ptr = self._device_lengths(self.lengths - n, n)
+            return (mha_prefill if kernel == 'prefill' else mha_decode)(
+                q, self, heads, tokens, self.max_length, scale, True, want_lse, lens=(kv_ptr, new_ptr), keys=int(self.lengths.sum()),
+                window=self.window)
         if kernel == 'prefill' and self.dtype != 'f32' and not PREFILL_KERNEL_F16:
             raise ValueError(f"KVCache.attend: the prefill kernel reads an {self.dtype} cache only with PREFILL_KERNEL_F16 on "
                              "(NPM_PREFILL_KERNEL_F16=1); without it the cache takes kernel='decode' or gather()")
@@ -1564,6 +1609,9 @@ class KVCache:
     def gather(self, rows: int):
         """(k, v) [B, rows, Hkv, D]: the valid rows of every sequence made contiguous, zeros behind them (``kv_gather_rows``)."""
         assert rows <= self.capacity
+        if self.paged and self.dropped.any():
+            raise ValueError(f'PagedKVCache.gather: the leading {self.dropped.tolist()} rows were given back (window={self.window}); '
+                             'there is nothing to gather them from')
         lens = self._current_lengths()
         out = []
         for x in (self.k, self.v):
@@ -1587,16 +1635,24 @@ class PagedKVCache(KVCache):
     (``table_uploads`` counts them).  Every call is the paged one (npm_kv_append_paged / npm_mha_decode_fwd_paged /
     npm_kv_gather_paged), uniform lengths included: it is bitwise the uniform entry point.
 
-    Its own: the pool and the table (``layout``), the page accounting ``append`` calls on (``room``, ``_allocate``) and
-    ``release``; ``append``, ``attend`` and ``gather`` are ``KVCache``'s."""
+    ``window`` W: pages come back while a sequence is still alive.  After an append left ``lengths[b]`` rows, keys below
+    ``lengths[b] - W + 1`` can never be seen again; at the start of the next ``append`` every page whose rows all lie below that
+    bound returns to the free list, its table slot becomes -1 and ``dropped[b]`` (host int64 [B], a multiple of ``page_size``)
+    counts the leading rows given up.  ``lengths`` stays the absolute length (rotary positions and ``capacity`` do not change); a
+    sequence holds at most ceil((W - 1 + T) / page_size) + 1 pages between calls of T tokens; ``room`` counts the pages about to
+    come back as free; ``gather`` raises once rows were dropped.
+
+    Its own: the pool and the table (``layout``), the page accounting ``append`` calls on (``room``, ``_reclaim``, ``_allocate``)
+    and ``release``; ``append``, ``attend`` and ``gather`` are ``KVCache``'s."""
 
     paged = True
 
     def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None, *, page_size: int,
-                 pages: Optional[int] = None, dtype: str = 'f32'):
+                 pages: Optional[int] = None, dtype: str = 'f32', window: Optional[int] = None):
         value_dim = key_dim if value_dim is None else value_dim
         if min(batch, capacity, kv_heads, key_dim, value_dim) < 1:
             raise ValueError('PagedKVCache: batch, capacity, kv_heads and the head sizes must be positive')
+        self.window = _kv_window(window, int(key_dim), int(value_dim))
         self.dtype = _kv_dtype(dtype, int(kv_heads), int(key_dim), int(value_dim))
         page_size = int(page_size)
         if page_size < 16 or page_size & (page_size - 1):
@@ -1620,6 +1676,7 @@ class PagedKVCache(KVCache):
     def reset(self) -> None:
         KVCache.reset(self)
         self.block_table = np.full([self.batch, self.pages_per_sequence], -1, dtype=np.int32)
+        self.dropped = np.zeros([self.batch], dtype=np.int64)   # leading rows whose pages were given back (window)
         self._free = list(range(self.pages))          # a heap: the lowest-numbered free page first
         self._table_dev = None                        # ByteBuffer of the table as the device last saw it
         self._table_dirty = True
@@ -1651,11 +1708,32 @@ class PagedKVCache(KVCache):
         KVCache.room(self, tokens, new_lengths)
         n = self._counts(tokens, self.new_lengths(tokens, new_lengths))
         need = int(self._pages_needed(n).sum())
-        if need > self.pages_free:
+        free = self.pages_free + int(self._reclaimable().sum()) // self.page_size
+        if need > free:
             raise ValueError(f'PagedKVCache: {n.tolist()} new rows after {self.lengths.tolist()} need {need} more pages of '
-                             f'{self.page_size} rows, {self.pages_free} of {self.pages} are free; release() a sequence first')
+                             f'{self.page_size} rows, {free} of {self.pages} are free; release() a sequence first')
+
+    def _reclaimable(self) -> np.ndarray:
+        """Rows per sequence, a multiple of ``page_size``, that the next ``append`` gives back: whole pages below
+        ``lengths[b] - window + 1`` that are still held."""
+        if self.window is None:
+            return np.zeros([self.batch], dtype=np.int64)
+        bound = np.maximum(self.lengths - self.window + 1, 0) // self.page_size * self.page_size
+        return np.maximum(bound - self.dropped, 0)
+
+    def _reclaim(self) -> None:
+        """The pages of ``_reclaimable`` back to the free list, their table slots -1, ``dropped`` advanced."""
+        rows = self._reclaimable()
+        for b in np.nonzero(rows)[0]:
+            first = int(self.dropped[b]) // self.page_size
+            for slot in range(first, first + int(rows[b]) // self.page_size):
+                heapq.heappush(self._free, int(self.block_table[b, slot]))
+                self.block_table[b, slot] = -1
+            self.dropped[b] += rows[b]
+            self._table_dirty = True
 
     def _allocate(self, n: np.ndarray) -> None:
+        self._reclaim()
         need = self._pages_needed(n)
         have = -(-self.lengths // self.page_size)
         for b in np.nonzero(need)[0]:
@@ -1682,6 +1760,7 @@ class PagedKVCache(KVCache):
                 heapq.heappush(self._free, int(page))
             self.block_table[i] = -1
             self.lengths[i] = 0
+            self.dropped[i] = 0
             self._table_dirty = True
 
     def write_slot(self, b: int, k: Optional[Mat], v: Optional[Mat], rows: int) -> None:

@@ -110,8 +110,12 @@ def _from(x: D.DeviceArray, offset: int) -> D.DeviceArray:
 
 
 class MultiHeadAttention(layer.StatefulLayer):
-    def __init__(self, num_heads: int, *args, num_kv_heads: Optional[int] = None, rope_base: Optional[float] = None, **kwargs):
+    def __init__(self, num_heads: int, *args, num_kv_heads: Optional[int] = None, rope_base: Optional[float] = None,
+                 window: Optional[int] = None, **kwargs):
         super().__init__(*args, **kwargs)
+        if window is not None and (isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1):
+            raise ValueError(f'window must be None or an integer >= 1, got {window!r}')
+        self._window = None if window is None else int(window)              # None: every cache this layer makes is unwindowed
         self._num_heads = num_heads
         self._num_kv_heads = num_heads if num_kv_heads is None else num_kv_heads
         if rope_base is not None and not rope_base > 0:
@@ -320,7 +324,11 @@ class MultiHeadAttention(layer.StatefulLayer):
         for every sequence to reach ``capacity``) that sequences take as they grow and give back with ``cache.release(b)``.
 
         ``dtype`` 'f16': K / V rows are stored as IEEE fp16 (half the bytes; see ``device.KVCache``) and every attention over the
-        cache sees them as stored.  It needs the head sizes the decode kernel takes."""
+        cache sees them as stored.  It needs the head sizes the decode kernel takes.
+
+        A layer made with ``window=W`` gives the cache that window (``device.KVCache(window=)``): cached forwards run the windowed
+        decode kernel (up to 32 score rows per K / V head) or the windowed prefill kernel, never a gather, a mask or a GEMM
+        composition, so it needs their head sizes too; a paged cache then gives pages back as its sequences move on."""
         if not self._initialized:
             raise RuntimeError('make_cache: the layer has no parameters yet (run one forward, or bind weights, first)')
         if dtype not in D.KV_ITEMSIZE:
@@ -329,16 +337,20 @@ class MultiHeadAttention(layer.StatefulLayer):
         if dtype != 'f32' and not (dk == dv and dk in (16, 32, 64, 128)):
             raise NotImplementedError(f'an {dtype} cache needs head sizes Dk == Dv in {{16, 32, 64, 128}} (the decode kernel and the '
                                       f'fused masked forward on the gathered rows), got {dk} / {dv}')
+        if self._window is not None and not (dk == dv and dk in (16, 32, 64, 128)):
+            raise ValueError(f'a windowed cache needs head sizes Dk == Dv in {{16, 32, 64, 128}} (the windowed decode and prefill '
+                             f'kernels), got {dk} / {dv}')
         if self._rope_base is not None:
             self._rope_table(capacity)                                   # sized once: decoding up to the capacity never grows it
         if page_size is None:
             if pages is not None:
                 raise ValueError('make_cache: pages= sizes the pool of a paged cache: it needs page_size=')
-            return D.KVCache(batch, capacity, self._num_kv_heads, dk, dv, dtype=dtype)
+            return D.KVCache(batch, capacity, self._num_kv_heads, dk, dv, dtype=dtype, window=self._window)
         if not (D.mha_decode_supported(dk, self._num_heads // self._num_kv_heads, dv) or D.mha_core_supported(dk, dv, any_math=True)):
             raise NotImplementedError('a paged cache needs head sizes Dk == Dv in {16, 32, 64, 128} (the decode kernel or '
                                       'the fused masked forward); the GEMM composition has no masked softmax')
-        return D.PagedKVCache(batch, capacity, self._num_kv_heads, dk, dv, page_size=page_size, pages=pages, dtype=dtype)
+        return D.PagedKVCache(batch, capacity, self._num_kv_heads, dk, dv, page_size=page_size, pages=pages, dtype=dtype,
+                              window=self._window)
 
     def fill_cache(self, cache: D.KVCache, key, value=None, lengths=None) -> D.KVCache:
         """Cross-attention: project ``key`` / ``value`` [B, Skv, F] once into ``cache`` and freeze it; ``forward(x, cache=cache)``
@@ -380,7 +392,8 @@ class MultiHeadAttention(layer.StatefulLayer):
         new_lengths = cache.new_lengths(t, new_lengths)                  # None when it says what T says
         # a paged cache has no [B, capacity, Hkv, D] tensor to hand to the uniform paths: it always takes the per-sequence route,
         # whose kernels read through the block table (uniform lengths are bitwise the uniform entry point there)
-        ragged = new_lengths is not None or cache.ragged or cache.paged
+        # (so does a windowed cache: its entry points exist in the per-sequence form only)
+        ragged = new_lengths is not None or cache.ragged or cache.paged or cache.window is not None
         if (ragged or cache.dtype != 'f32') and not (D.mha_decode_supported(dk, h // hkv * t, dv) or D.mha_core_supported(dk, dv, any_math=True)):
             raise NotImplementedError('per-sequence lengths need head sizes Dk == Dv in {16, 32, 64, 128} (the decode kernel or '
                                       'the fused masked forward); the GEMM composition has no masked softmax')
@@ -508,6 +521,17 @@ class MultiHeadAttention(layer.StatefulLayer):
         b, scale = cache.batch, 1.0 / math.sqrt(self._key_dim)
         n = np.full([b], t, dtype=np.int64) if new_lengths is None else new_lengths
         stored = cache.dtype != 'f32'
+        if cache.window is not None:
+            # sliding-window attention: the windowed decode kernel up to its row limit, the windowed prefill kernel above it -- f32
+            # and f16 alike, whatever PREFILL_KERNEL / PREFILL_KERNEL_F16 say, a uniform prefill from empty included.  No gather,
+            # mask or GEMM composition knows the window: a call neither kernel takes is an error.
+            if not causal:
+                raise ValueError('a windowed cache is a self-attention cache: it cannot be frozen for cross-attention')
+            if not D.mha_prefill_supported(dk, dv):
+                raise NotImplementedError('a windowed cache needs the exact-fp32 decode and prefill kernels (head sizes Dk == Dv in '
+                                          '{16, 32, 64, 128}, math mode f32)')
+            self._cached_path = 'decode' if h // hkv * t <= 32 else 'prefill'
+            return cache.attend(q, h, t, scale, True, new_lengths=n, kernel=self._cached_path)[0]
         if decode_ok and D.mha_decode_supported(dk, h // hkv * t, dv):
             self._cached_path = 'decode'
             return cache.attend(q, h, t, scale, causal, new_lengths=n)[0]

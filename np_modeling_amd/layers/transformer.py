@@ -224,13 +224,19 @@ class TransformerDecoder(layer.Layer):
     ``dkv = dkey + dvalue`` of the cross-attention (transformer.py:186)."""
 
     def __init__(self, num_heads: int, hidden_units: int, norm_first: bool, drop_rate: float = 0.0,
-                 *args, num_kv_heads: Optional[int] = None, causal: bool = False, rope_base: Optional[float] = None, **kwargs):
+                 *args, num_kv_heads: Optional[int] = None, causal: bool = False, rope_base: Optional[float] = None,
+                 window: Optional[int] = None, **kwargs):
         super().__init__(*args, **kwargs)
+        if window is not None and not causal:
+            raise ValueError('TransformerDecoder: window= is a rule of causal self-attention: it needs causal=True')
         self._num_heads = num_heads
         self._causal = bool(causal)
         self._causal_masks = {}         # (B, Sq) -> device.AttnMask: bytes and tile summary stay on the device between steps
         self._decoded = False           # decode() ran since the last forward: the saved activations are not that forward's
-        self._self_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads, rope_base=rope_base)
+        # window: token p sees keys max(0, p - W + 1) .. p in the self-attention only -- a band mask in training, windowed caches
+        # in decoding; the cross-attention sees the whole memory
+        self._self_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads, rope_base=rope_base, window=window)
+        self._window = self._self_attention._window
         self._cross_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)   # never rotates: no query position
         self._dense1 = mlp.Dense(units=hidden_units)
         self._norm1 = normalizations.LayerNormalization()
@@ -279,13 +285,16 @@ class TransformerDecoder(layer.Layer):
                                   + _block_segments(self._norm1, sa, pre))
 
     def _self_mask(self, batch: int, seq: int):
-        """None, or (``causal=True``) the lower-triangular mask of the self-attention, made once per (B, Sq): its tile summary
-        lets the fused kernels skip the upper triangle."""
+        """None, or (``causal=True``) the lower-triangular mask of the self-attention -- with ``window=W`` the band
+        ``tril & ~tril(-W)`` -- made once per (B, Sq): its tile summary lets the fused kernels skip the tiles outside it."""
         if not self._causal:
             return None
         key = (int(batch), int(seq))
         if key not in self._causal_masks:
-            self._causal_masks[key] = D.AttnMask(np.tril(np.ones([seq, seq], dtype=bool)), batch, self._num_heads, seq, seq)
+            band = np.tril(np.ones([seq, seq], dtype=bool))
+            if self._window is not None:
+                band &= ~np.tril(np.ones([seq, seq], dtype=bool), -self._window)
+            self._causal_masks[key] = D.AttnMask(band, batch, self._num_heads, seq, seq)
         return self._causal_masks[key]
 
     def forward(self, q, kv):
