@@ -609,6 +609,68 @@ int npm_sgemm_skinny_w16(const npm_gemm *g);
 /* 1 when npm_sgemm_skinny_w16 takes this call, else 0; never sets an error. */
 int npm_sgemm_skinny_w16_supported(const npm_gemm *g);
 
+/* ---- token generation: rows by index, the gradient of that lookup, and sampling on the device ----
+ * npm_take_rows: dst[r, :] = src[idx[r], :] for r < n, both sides with a row pitch in floats (>= cols); idx: device array of n int32.
+ * An index below 0 or >= src_rows gives a row of zeros and the source is not read for it (a finished sequence carries token -1 and
+ * the decoder wants finite padding).  The embedding lookup, and picking the last row of every sequence of a ragged chunk so that
+ * the vocabulary projection runs on B rows.  cols % 4 == 0, pitches % 4 == 0 and 16-byte aligned src and dst move 16 bytes per
+ * access, everything else one float per thread: a copy, the same bits.  n == 0 or cols == 0 returns NPM_OK whatever the pointers
+ * are; a negative size, a pitch below cols or a NULL pointer is NPM_E_BAD_ARGUMENT.
+ *
+ * npm_embedding_bwd: the gradient of the lookup without atomics.  The caller sorts the rows of dy stably by token: order[j] is the
+ * j-th row of dy in that order, segment s = starts[s] .. starts[s + 1] - 1 (starts has distinct + 1 entries, every segment at least
+ * one row) holds the rows of token tokens[s], in ascending row order.  dw[tokens[s], c] = ((dy[order[first], c] + dy[order[first
+ * + 1], c]) + ...) in fp32, in that order: deterministic, bit for bit a NumPy float32 loop.  Rows of dw that no segment names are
+ * not written (the caller zeroes dw first).  One block per segment and chunk of 256 columns.  All arrays are device arrays;
+ * nothing is checked on the device: order must name rows of dy and tokens rows of dw. */
+int npm_take_rows(const float *src, int64_t src_pitch, int64_t src_rows, const int32_t *idx, float *dst, int64_t dst_pitch, int64_t n,
+                  int64_t cols);
+int npm_embedding_bwd(const float *dy, int64_t dy_pitch, const int32_t *order, const int32_t *starts, const int32_t *tokens,
+                      int32_t distinct, float *dw, int64_t dw_pitch, int64_t cols);
+
+/* npm_sample_rows: one launch samples one token per row of a [batch, vocab] fp32 logit matrix; every row has its own parameters
+ * (the sequences of a continuous batch do not share them).  All pointers are device pointers.  One row, with z its logits:
+ *  1. A row that holds a NaN or +inf, or whose every logit is -inf, is invalid: token = -1, kept = 0, prob = 0; it never faults.
+ *     So is a row whose temperature is not >= 0 or whose top_p is not > 0.  -inf logits are otherwise legal (a masked
+ *     vocabulary); such tokens are never kept.
+ *  2. Order: i comes before j when z_i > z_j, or when z_i == z_j and i < j; -0.0 == 0.0.
+ *  3. Greedy: temperature == 0 or top_k == 1 (or a temperature so small that 1 / t is not finite in fp32): the token is the first
+ *     in that order, kept = 1, prob = 1.
+ *  4. Otherwise K1 is the first min(top_k, finite count) tokens in order; top_k <= 0: every finite token.  Exact: logits only.
+ *  5. Weights: w_i = floor(q_i * 2^32) as an unsigned 64-bit integer, q_i = exp((z_i - zmax) * (1 / t)) with the difference, the
+ *     reciprocal, the product and the exponential each in fp32; the largest logit has w = 2^32 exactly.  Every mass after this
+ *     point is an integer sum of w: no result depends on the order in which anything is added.
+ *  6. Top-p: K2 is the shortest prefix of K1 in order whose mass reaches max(1, floor((double)top_p * (double)W1)), W1 the mass
+ *     of K1; top_p >= 1: K2 = K1.  kept = |K2|, Wk its mass.
+ *  7. Draw: u24 = word0 >> 8, word0 the first word of Philox4x32-10 with counter (draw lo, draw hi, 0, 0) and key (seed lo, seed
+ *     hi).  target = floor(Wk * u24 / 2^24), exact in integers.  The token is the first i of K2 IN INDEX ORDER whose running mass
+ *     S_i exceeds target.  prob = (float)((double)w_token / (double)Wk).
+ *  8. Then draw[b] += 1 for every active row: greedy and invalid rows included.  With active != NULL and active[b] == 0 the row is
+ *     left alone: no logit of it is loaded, draw[b] stays, token = -1, kept = 0, prob = 0.
+ * Hence a row's result depends on nothing outside that row, the launch is bitwise reproducible, and row b of a batch is the
+ * batch-1 call on that row with the same seed and counter.
+ * One block per row; a row of at most NPM_SAMPLE_LDS_ROW logits is kept in LDS, a longer one is read again from L2.  A 16-byte
+ * aligned `logits` with pitch % 4 == 0 is loaded 16 bytes per lane, anything else one float per lane, with the same results.
+ * NPM_E_BAD_ARGUMENT before anything is launched: s == NULL, batch < 1, vocab outside 1 .. NPM_SAMPLE_MAX_VOCAB, pitch < vocab, a
+ * NULL logits, temperature, top_k, top_p, seed, draw or token (active, kept and prob may be NULL). */
+#define NPM_SAMPLE_LDS_ROW 32768
+#define NPM_SAMPLE_MAX_VOCAB (1 << 20)
+typedef struct npm_sample {
+    const float *logits; int64_t pitch;          /* row b starts at logits + b * pitch, pitch >= vocab */
+    int32_t batch, vocab;                        /* 1 <= vocab <= 1 << 20 */
+    const float *temperature;                    /* [batch], >= 0; 0 = greedy */
+    const int32_t *top_k;                        /* [batch], <= 0 = off */
+    const float *top_p;                          /* [batch], (0, 1]; >= 1 = off */
+    const uint64_t *seed; uint64_t *draw;        /* [batch]; draw[b] is advanced by 1 for every active row */
+    const int32_t *active;                       /* NULL = all, or [batch]: 0 = leave the row alone */
+    int32_t *token;                              /* [batch] out; -1 for an inactive or invalid row */
+    int32_t *kept; float *prob;                  /* [batch] out, either may be NULL */
+} npm_sample;
+int npm_sample_rows(const npm_sample *s);
+/* What the most recent npm_sample_rows launched: "sample_rows_kernel <vec|scalar> B=<batch> V=<vocab> row=<lds|global>"; ""
+ * before the first call. */
+const char *npm_last_sample_kernel(void);
+
 /* ---- around the path ("next" rows of SURVEY.md section 8f): keeps a Trainer step on the device ---- */
 /* Adam as the reference computes it (optimizer.py:53-67), operation for operation: (1 - beta1) * g and (1 - beta2) * (g * g) are
  * float32 products (the gradient is float32 and the scalars do not widen it), the moments m, v are fp64 (device buffers of n

@@ -92,6 +92,17 @@ class npm_mha_decode(C.Structure):
     ]
 
 
+class npm_sample(C.Structure):
+    _fields_ = [
+        ('logits', C.c_void_p), ('pitch', C.c_int64),
+        ('batch', C.c_int32), ('vocab', C.c_int32),
+        ('temperature', C.c_void_p), ('top_k', C.c_void_p), ('top_p', C.c_void_p),
+        ('seed', C.c_void_p), ('draw', C.c_void_p),
+        ('active', C.c_void_p),
+        ('token', C.c_void_p), ('kept', C.c_void_p), ('prob', C.c_void_p),
+    ]
+
+
 class npm_comm_exchange_stats(C.Structure):
     _fields_ = [('bytes', C.c_ulonglong), ('allreduce_calls', C.c_int), ('waits', C.c_int),
                 ('allreduce_ms', C.c_double), ('exposed_ms', C.c_double), ('last_allreduce_ms', C.c_double),
@@ -174,6 +185,9 @@ SIGNATURES = {
     'npm_mha_prefill_fwd_window': [C.POINTER(npm_mha_decode), _P, _P, _P, _I32, _I32, _I32, _I32],
     'npm_mha_decode_window_splits': [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
     'npm_rope': [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _I32],
+    'npm_take_rows': [_P, _I64, _I64, _P, _P, _I64, _I64, _I64],
+    'npm_embedding_bwd': [_P, _I64, _P, _P, _P, _I32, _P, _I64, _I64],
+    'npm_sample_rows': [C.POINTER(npm_sample)],
     'npm_sgemm_skinny': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_supported': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_splits': [C.c_int, C.c_int, C.c_int],
@@ -198,6 +212,7 @@ _SPECIAL = {
     'npm_last_decode_kernel': (C.c_char_p, []),
     'npm_last_prefill_kernel': (C.c_char_p, []),
     'npm_last_skinny_kernel': (C.c_char_p, []),
+    'npm_last_sample_kernel': (C.c_char_p, []),
 }
 
 COMM_SIGNATURES = {
@@ -446,6 +461,14 @@ SKINNY_MAX_M, SKINNY_MAX_SPLITS = 64, 64        # include/npm_hip.h NPM_SKINNY_M
 def last_skinny_kernel() -> str:
     """What the most recent npm_sgemm_skinny / npm_sgemm_skinny_w16 launched (include/npm_hip.h npm_last_skinny_kernel)."""
     return lib().npm_last_skinny_kernel().decode()
+
+
+SAMPLE_LDS_ROW, SAMPLE_MAX_VOCAB = 32768, 1 << 20      # include/npm_hip.h NPM_SAMPLE_*
+
+
+def last_sample_kernel() -> str:
+    """What the most recent npm_sample_rows launched (include/npm_hip.h npm_last_sample_kernel)."""
+    return lib().npm_last_sample_kernel().decode()
 
 
 def comm_lib():

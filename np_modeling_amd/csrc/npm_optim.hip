@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "npm_internal.h"
+#include "npm_philox.h"
 
 namespace {
 
@@ -33,21 +34,6 @@ adam_kernel(float *__restrict__ var, const float *__restrict__ grad, double *__r
         v[i] = nv;
         const double step = lr * ((nm / corr1) / sqrt(nv / corr2 + eps));
         var[i] = (float)((double)var[i] - step);  // numpy: float32 -= float64 array runs the fp64 loop and rounds ONCE
-    }
-}
-
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter (c0..c3), key (k0, k1).
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const unsigned long long p0 = 0xD2511F53ull * c[0], p1 = 0xCD9E8D57ull * c[2];
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1;
-        c[1] = (unsigned)p1;
-        c[3] = (unsigned)p0;
-        c[0] = n0;
-        c[2] = n2;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
     }
 }
 

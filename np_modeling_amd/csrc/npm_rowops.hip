@@ -771,6 +771,41 @@ int cvt_launch(const void *src, long src_pitch, void *dst, long dst_pitch, long 
     return NPM_OK;
 }
 
+// ---------------------------------------------------------------------------------
+// rows by a device index vector (npm_take_rows) and the gradient of that lookup (npm_embedding_bwd)
+// ---------------------------------------------------------------------------------
+// dst[r, :] = src[idx[r], :], zeros for an index outside 0 .. src_rows - 1 (the source is not read then).  One thread per W
+// columns, W = 4 (16-byte accesses) or 1, grid-stride over (row, column group) with the columns fastest.
+template <int W>
+__global__ void __launch_bounds__(256)
+take_rows_kernel(const float *__restrict__ src, long src_pitch, long src_rows, const int *__restrict__ idx, float *__restrict__ dst,
+                 long dst_pitch, long per_row, long total) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / per_row, col = (i - r * per_row) * W;
+        const long from = idx[r];
+        const bool inside = from >= 0 && from < src_rows;
+        float *to = dst + r * dst_pitch + col;
+        if constexpr (W == 4) {
+            *reinterpret_cast<f32x4v *>(to) = inside ? *reinterpret_cast<const f32x4v *>(src + from * src_pitch + col) : f32x4v{0.f, 0.f, 0.f, 0.f};
+        } else {
+            *to = inside ? src[from * src_pitch + col] : 0.f;
+        }
+    }
+}
+
+// dw[tokens[s], c] = the sum of dy[order[j], c] over j = starts[s] .. starts[s + 1] - 1 in that order, fp32, starting from the
+// first row: block (s, column chunk of 256), one column per thread -- a wave reads 256 contiguous bytes of each row.  No atomics.
+__global__ void __launch_bounds__(256)
+embedding_bwd_kernel(const float *__restrict__ dy, long dy_pitch, const int *__restrict__ order, const int *__restrict__ starts,
+                     const int *__restrict__ tokens, float *__restrict__ dw, long dw_pitch, long cols) {
+    const long c = (long)blockIdx.y * 256 + threadIdx.x;
+    if (c >= cols) return;
+    const int s = blockIdx.x, first = starts[s], last = starts[s + 1];
+    float acc = dy[(long)order[first] * dy_pitch + c];
+    for (int j = first + 1; j < last; ++j) acc += dy[(long)order[j] * dy_pitch + c];
+    dw[(long)tokens[s] * dw_pitch + c] = acc;
+}
+
 }  // namespace
 
 namespace npm {
@@ -842,6 +877,34 @@ int npm_cvt_f16_f32(const void *src, int64_t src_pitch, float *dst, int64_t dst_
     if (rows == 0 || cols == 0) return NPM_OK;
     NPM_ARG(src != nullptr && dst != nullptr);
     return cvt_launch<false>(src, src_pitch, dst, dst_pitch, rows, cols);
+}
+
+int npm_take_rows(const float *src, int64_t src_pitch, int64_t src_rows, const int32_t *idx, float *dst, int64_t dst_pitch, int64_t n,
+                  int64_t cols) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(n >= 0 && cols >= 0 && src_rows >= 0 && src_pitch >= cols && dst_pitch >= cols);
+    if (n == 0 || cols == 0) return NPM_OK;
+    NPM_ARG(idx != nullptr && dst != nullptr && (src != nullptr || src_rows == 0));
+    const bool vec = cols % 4 == 0 && src_pitch % 4 == 0 && dst_pitch % 4 == 0 && aligned16(src) && aligned16(dst);
+    const long per_row = vec ? cols / 4 : cols, total = n * per_row;
+    hipStream_t s = npm::ctx().stream;
+    if (vec) hipLaunchKernelGGL(take_rows_kernel<4>, dim3(grid_for(total)), dim3(256), 0, s, src, (long)src_pitch, (long)src_rows, idx, dst, (long)dst_pitch, per_row, total);
+    else hipLaunchKernelGGL(take_rows_kernel<1>, dim3(grid_for(total)), dim3(256), 0, s, src, (long)src_pitch, (long)src_rows, idx, dst, (long)dst_pitch, per_row, total);
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
+}
+
+int npm_embedding_bwd(const float *dy, int64_t dy_pitch, const int32_t *order, const int32_t *starts, const int32_t *tokens,
+                      int32_t distinct, float *dw, int64_t dw_pitch, int64_t cols) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(distinct >= 0 && cols >= 0 && dy_pitch >= cols && dw_pitch >= cols);
+    if (distinct == 0 || cols == 0) return NPM_OK;
+    NPM_ARG(dy != nullptr && order != nullptr && starts != nullptr && tokens != nullptr && dw != nullptr);
+    NPM_ARG((cols + 255) / 256 <= 65535);
+    hipLaunchKernelGGL(embedding_bwd_kernel, dim3(distinct, (unsigned)((cols + 255) / 256)), dim3(256), 0, npm::ctx().stream, dy,
+                       (long)dy_pitch, order, starts, tokens, dw, (long)dw_pitch, (long)cols);
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
 }
 
 int npm_colsum(const float *x, float *out, int64_t rows, int64_t cols, int64_t ld) {

@@ -572,6 +572,52 @@ class HalfBuffer(ByteBuffer):
         return out
 
 
+class IdBuffer(ByteBuffer):
+    """``shape`` int32 values on the device: token ids, row indices.  What ``sampling.Sampler`` returns as ``.ids`` and what
+    ``take_rows`` / ``layers.embedding.Embedding`` take as indices without a trip through the host."""
+
+    __slots__ = ('shape',)
+
+    def __init__(self, shape: Sequence[int], _buf: Optional[_Buffer] = None, _ptr: Optional[int] = None):
+        self.shape = tuple(int(s) for s in shape)
+        if _buf is None:
+            ByteBuffer.__init__(self, 4 * _prod(self.shape))
+        else:
+            self._buf, self.ptr, self.nbytes = _buf, _ptr, 4 * _prod(self.shape)
+
+    @property
+    def size(self) -> int:
+        return _prod(self.shape)
+
+    def numpy(self) -> np.ndarray:
+        host = np.empty(self.shape, dtype=np.int32)
+        if host.size:
+            _C.check(_C.lib().npm_d2h(host.ctypes.data, self.ptr, host.nbytes), 'npm_d2h')
+        return host
+
+    def __deepcopy__(self, memo):
+        buf = self._buf.__deepcopy__(memo)
+        return IdBuffer(self.shape, buf, buf.ptr + (self.ptr - self._buf.ptr))
+
+
+def ids_from_host(value) -> IdBuffer:
+    """Integers of any shape as int32 on the device (ValueError for anything that is not integral or does not fit)."""
+    host = np.asarray(value)
+    if host.dtype == np.bool_ or not np.issubdtype(host.dtype, np.integer):
+        raise ValueError(f'indices must be integers, got dtype {host.dtype}')
+    if host.size and (host.min() < -2 ** 31 or host.max() >= 2 ** 31):
+        raise ValueError('indices do not fit int32')
+    host = np.ascontiguousarray(host.astype(np.int32))
+    out = IdBuffer(host.shape)
+    if host.size:
+        _C.check(_C.lib().npm_h2d(out.ptr, host.ctypes.data, host.nbytes), 'npm_h2d')
+    return out
+
+
+def as_ids(value) -> IdBuffer:
+    return value if isinstance(value, IdBuffer) else ids_from_host(value)
+
+
 def bytes_from_host(value: np.ndarray) -> ByteBuffer:
     host = np.ascontiguousarray(value).view(np.uint8)
     out = ByteBuffer(host.nbytes)
@@ -1410,6 +1456,45 @@ def rope(x: Mat, batch: int, tokens: int, heads: int, head_dim: int, table: Rope
     with _timed('rope', nbytes=8.0 * rows * heads * head_dim + 4.0 * head_dim * min(rows, table.rows)):
         _C.check(_C.lib().npm_rope(x.ptr, x.ld, batch, tokens, heads, head_dim, table.cos.ptr, table.sin.ptr, table.rows, int(at),
                                    at_lens, int(bool(inverse))), 'npm_rope')
+
+
+def take_rows(x2d: DeviceArray, idx, out: Optional[Mat] = None) -> DeviceArray:
+    """``x2d[idx]`` for a 2-D ``x2d`` [R, F] and integer ``idx`` of any shape (host integers, or an ``IdBuffer`` that never
+    leaves the device): [..., F].  An index outside 0 .. R - 1 gives a row of zeros and reads nothing (include/npm_hip.h
+    npm_take_rows).  ``out``: (array, row pitch) to write the rows into instead of a fresh array."""
+    x2d = as_device(x2d)
+    if x2d.ndim != 2:
+        raise ValueError(f'take_rows: the source must be 2-D, got {x2d.shape}')
+    idx = as_ids(idx)
+    rows, cols = x2d.shape
+    result = empty(tuple(idx.shape) + (cols,)) if out is None else None
+    dst_ptr, dst_ld = (result.ptr, cols) if out is None else (out.ptr, out.ld)
+    with _timed('take_rows', nbytes=8.0 * idx.size * cols):
+        _C.check(_C.lib().npm_take_rows(x2d.ptr, cols, rows, idx.ptr, dst_ptr, dst_ld, idx.size, cols), 'npm_take_rows')
+    return result
+
+
+def embedding_bwd(dy: DeviceArray, ids: np.ndarray, dw: DeviceArray) -> None:
+    """dw[v] = the sum of the rows r of ``dy`` [n, F] with ids[r] == v, added in ascending r in fp32; rows of tokens that do not
+    occur are zero, ids outside the table are skipped (their forward rows were zeros).  The host sorts the ids stably; the
+    kernel sums each token's rows in that order (include/npm_hip.h npm_embedding_bwd): deterministic, no atomics."""
+    vocab, cols = dw.shape
+    ids = np.asarray(ids).reshape(-1).astype(np.int64)
+    assert dy.size == ids.size * cols, (dy.shape, ids.shape, dw.shape)
+    if dw.size:
+        _C.check(_C.lib().npm_fill_f32(dw.ptr, 0.0, dw.size), 'npm_fill_f32')
+    order = np.argsort(ids, kind='stable')
+    order = order[(ids[order] >= 0) & (ids[order] < vocab)]
+    if order.size == 0 or cols == 0:
+        return
+    sorted_ids = ids[order]
+    firsts = np.flatnonzero(np.concatenate([[True], sorted_ids[1:] != sorted_ids[:-1]]))
+    tokens, starts = sorted_ids[firsts], np.concatenate([firsts, [order.size]])
+    packed = bytes_from_host(np.concatenate([order, starts, tokens]).astype(np.int32))
+    p_order, p_starts = packed.ptr, packed.ptr + 4 * order.size
+    with _timed('embedding_bwd', nbytes=4.0 * cols * (order.size + tokens.size)):
+        _C.check(_C.lib().npm_embedding_bwd(dy.ptr, cols, p_order, p_starts, p_starts + 4 * starts.size, int(tokens.size), dw.ptr,
+                                            cols, cols), 'npm_embedding_bwd')
 
 
 class KVCache:
