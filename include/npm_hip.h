@@ -667,9 +667,75 @@ typedef struct npm_sample {
     int32_t *kept; float *prob;                  /* [batch] out, either may be NULL */
 } npm_sample;
 int npm_sample_rows(const npm_sample *s);
-/* What the most recent npm_sample_rows launched: "sample_rows_kernel <vec|scalar> B=<batch> V=<vocab> row=<lds|global>"; ""
+/* What the most recent npm_sample_rows or npm_verify_rows launched: "sample_rows_kernel <vec|scalar> B=<batch> V=<vocab>
+ * row=<lds|global>", or "verify_rows_kernel <vec|scalar> B=<batch> rows=<rows> V=<vocab> row=<lds|global> history=<0|1>"; ""
  * before the first call. */
 const char *npm_last_sample_kernel(void);
+
+/* ---- speculative decoding: drafts by prompt lookup, verified by sampling ----
+ * npm_verify_rows: a speculative step fed every slot b its last token and up to T = rows - 1 drafted tokens, and the model
+ * returned rows = T + 1 logit rows per slot, row (b, r) at logits + (b * rows + r) * pitch.  Row r is what follows the r-th
+ * drafted token, so it counts only while every drafted token before it was the token sampled.  All pointers are device pointers.
+ * Per slot b, with n = n_draft[b] (0 .. rows - 1 drafted tokens; below 0: the slot is inactive; above rows - 1 is read as
+ * rows - 1):
+ *  1. For r = 0 .. n, s[r] is what npm_sample_rows returns for that logit row with slot b's temperature, top_k, top_p and seed
+ *     and the counter draw[b] + r (64 bits: the carry into the high word counts) -- the same device function samples the row in
+ *     both entry points.  Rows r > n are not loaded.
+ *  2. a is the smallest r in 0 .. n with r == n or s[r] != draft[b * draft_pitch + r].  An invalid row has s[r] = -1 and a draft
+ *     entry below 0 never matches, so acceptance stops there.
+ *  3. token[b, 0 .. a] = s[0 .. a] with their kept and prob; token[b, r > a] = -1 with kept 0 and prob 0 (token, kept and prob are
+ *     [batch, rows], dense); accepted[b] = a; draw[b] += a + 1.
+ *  4. With history != NULL: the tokens token[b, 0 .. a] that are >= 0 are written to history[b * history_pitch + history_len[b]
+ *     ...] in order and history_len[b] grows by their number.  Nothing is written at or past history_cap: a token that does not
+ *     fit is dropped and history_len[b] stops at history_cap (the caller checks the room before the launch).
+ *  5. An inactive slot: token -1, kept 0, prob 0 in every column, accepted 0; draw[b] and history_len[b] stay and no logit of
+ *     the slot is read.
+ * Hence the tokens a slot emits over any number of calls are the tokens npm_sample_rows gives it from the same logit rows one
+ * call at a time, seed for seed and counter for counter, whatever was drafted.  Two launches: one block of 1024 threads per
+ * (slot, row), then one thread per slot for steps 2 - 4; integers only between them, so the call is bitwise reproducible and
+ * slot b of a batch is the batch-1 call on that slot.
+ * NPM_E_BAD_ARGUMENT before anything is launched: v == NULL, batch < 1, rows outside 1 .. NPM_VERIFY_MAX_ROWS, vocab outside
+ * 1 .. NPM_SAMPLE_MAX_VOCAB, pitch < vocab, batch * rows >= 2^31, a NULL logits, temperature, top_k, top_p, seed, draw, n_draft,
+ * token or accepted, with rows > 1 a NULL draft or draft_pitch < rows - 1, with a history a NULL history_len, history_cap < 1 or
+ * history_pitch < history_cap (kept, prob and history may be NULL). */
+#define NPM_VERIFY_MAX_ROWS 64
+typedef struct npm_verify {
+    const float *logits; int64_t pitch;          /* row (b, r) starts at logits + (b * rows + r) * pitch, pitch >= vocab */
+    int32_t batch, rows, vocab, history_cap;     /* rows = T + 1 in 1 .. 64 */
+    const float *temperature;                    /* the five per-slot vectors of npm_sample, [batch] each */
+    const int32_t *top_k;
+    const float *top_p;
+    const uint64_t *seed; uint64_t *draw;        /* draw[b] is advanced by accepted[b] + 1 for every active slot */
+    const int32_t *draft; int64_t draft_pitch;   /* [batch, >= rows - 1]: the drafted tokens the rows were computed behind */
+    const int32_t *n_draft;                      /* [batch], -1 .. rows - 1; below 0 = inactive */
+    int32_t *token, *accepted;                   /* out: [batch, rows] and [batch] */
+    int32_t *kept; float *prob;                  /* [batch, rows] out, either may be NULL */
+    int32_t *history; int64_t history_pitch;     /* NULL, or [batch, history_cap] with a row pitch: the tokens of every slot so far */
+    int32_t *history_len;                        /* [batch], advanced by the tokens appended */
+} npm_verify;
+int npm_verify_rows(const npm_verify *v);
+
+/* npm_ngram_draft: the draft of every slot from its own token history h = history[b * history_pitch ...] of L = history_len[b]
+ * tokens (read as min(L, history_cap)), by prompt lookup.  T = max_draft, m_max = min(T, limit[b]) (limit NULL: T); a slot with
+ * L <= 0 or limit[b] < 0 is inactive.  Exact, integers only:
+ *  1. n walks from nmax down to nmin; an n with L < n + 1 is skipped.
+ *  2. Its candidates are the j in 0 .. L - n - 1 with h[j + i] == h[L - n + i] for every i < n: earlier occurrences of the last n
+ *     tokens (they may overlap the last one).  The first n that has a candidate is used.
+ *  3. Among them the LARGEST j with j + n + m_max <= L -- the most recent occurrence followed by a whole draft -- else the
+ *     SMALLEST candidate, which has the longest continuation.  m = min(m_max, L - (j + n)).
+ *  4. No candidate at any n, or m_max <= 0: m = 0.
+ *  5. chunk[b, 0] = h[L - 1], chunk[b, 1 + i] = h[j + n + i] for i < m, -1 behind that (chunk is [batch, T + 1], dense);
+ *     n_new[b] = 1 + m.  An inactive slot gets a row of -1 and n_new[b] = 0.
+ * chunk is what the model is fed; chunk + 1 with pitch T + 1 is npm_verify's draft and n_new[b] - 1 its n_draft[b].  One block
+ * of 256 threads per slot; the history is read once per n.  NPM_E_BAD_ARGUMENT before the launch: batch < 1, max_draft outside
+ * 0 .. NPM_VERIFY_MAX_ROWS - 1, nmin < 1, nmax < nmin, nmax > NPM_DRAFT_MAX_NGRAM, history_cap < 1, history_pitch < history_cap,
+ * a NULL history, history_len, chunk or n_new. */
+#define NPM_DRAFT_MAX_NGRAM 8
+int npm_ngram_draft(const int32_t *history, int64_t history_pitch, int32_t history_cap, const int32_t *history_len,
+                    const int32_t *limit, int32_t batch, int32_t max_draft, int32_t nmax, int32_t nmin, int32_t *chunk,
+                    int32_t *n_new);
+/* What the most recent npm_ngram_draft launched: "ngram_draft_kernel B=<batch> T=<max_draft> ngram=<nmax>..<nmin> cap=<cap>". */
+const char *npm_last_draft_kernel(void);
 
 /* ---- around the path ("next" rows of SURVEY.md section 8f): keeps a Trainer step on the device ---- */
 /* Adam as the reference computes it (optimizer.py:53-67), operation for operation: (1 - beta1) * g and (1 - beta2) * (g * g) are

@@ -103,6 +103,21 @@ class npm_sample(C.Structure):
     ]
 
 
+class npm_verify(C.Structure):
+    _fields_ = [
+        ('logits', C.c_void_p), ('pitch', C.c_int64),
+        ('batch', C.c_int32), ('rows', C.c_int32), ('vocab', C.c_int32), ('history_cap', C.c_int32),
+        ('temperature', C.c_void_p), ('top_k', C.c_void_p), ('top_p', C.c_void_p),
+        ('seed', C.c_void_p), ('draw', C.c_void_p),
+        ('draft', C.c_void_p), ('draft_pitch', C.c_int64),
+        ('n_draft', C.c_void_p),
+        ('token', C.c_void_p), ('accepted', C.c_void_p),
+        ('kept', C.c_void_p), ('prob', C.c_void_p),
+        ('history', C.c_void_p), ('history_pitch', C.c_int64),
+        ('history_len', C.c_void_p),
+    ]
+
+
 class npm_comm_exchange_stats(C.Structure):
     _fields_ = [('bytes', C.c_ulonglong), ('allreduce_calls', C.c_int), ('waits', C.c_int),
                 ('allreduce_ms', C.c_double), ('exposed_ms', C.c_double), ('last_allreduce_ms', C.c_double),
@@ -188,6 +203,8 @@ SIGNATURES = {
     'npm_take_rows': [_P, _I64, _I64, _P, _P, _I64, _I64, _I64],
     'npm_embedding_bwd': [_P, _I64, _P, _P, _P, _I32, _P, _I64, _I64],
     'npm_sample_rows': [C.POINTER(npm_sample)],
+    'npm_verify_rows': [C.POINTER(npm_verify)],
+    'npm_ngram_draft': [_P, _I64, _I32, _P, _P, _I32, _I32, _I32, _I32, _P, _P],
     'npm_sgemm_skinny': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_supported': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_splits': [C.c_int, C.c_int, C.c_int],
@@ -213,6 +230,7 @@ _SPECIAL = {
     'npm_last_prefill_kernel': (C.c_char_p, []),
     'npm_last_skinny_kernel': (C.c_char_p, []),
     'npm_last_sample_kernel': (C.c_char_p, []),
+    'npm_last_draft_kernel': (C.c_char_p, []),
 }
 
 COMM_SIGNATURES = {
@@ -464,11 +482,17 @@ def last_skinny_kernel() -> str:
 
 
 SAMPLE_LDS_ROW, SAMPLE_MAX_VOCAB = 32768, 1 << 20      # include/npm_hip.h NPM_SAMPLE_*
+VERIFY_MAX_ROWS, DRAFT_MAX_NGRAM = 64, 8               # include/npm_hip.h NPM_VERIFY_MAX_ROWS, NPM_DRAFT_MAX_NGRAM
 
 
 def last_sample_kernel() -> str:
-    """What the most recent npm_sample_rows launched (include/npm_hip.h npm_last_sample_kernel)."""
+    """What the most recent npm_sample_rows or npm_verify_rows launched (include/npm_hip.h npm_last_sample_kernel)."""
     return lib().npm_last_sample_kernel().decode()
+
+
+def last_draft_kernel() -> str:
+    """What the most recent npm_ngram_draft launched (include/npm_hip.h npm_last_draft_kernel)."""
+    return lib().npm_last_draft_kernel().decode()
 
 
 def comm_lib():

@@ -1643,6 +1643,25 @@ class KVCache:
             kv_append(src, dst.ptr, self.layout(dst), self.batch, tokens, at, lens, rows)
         self.lengths = self.lengths + n
 
+    def _truncated(self, rows) -> np.ndarray:
+        """The lengths after ``truncate(rows)``, int64 [B]; every refusal of ``truncate`` is raised here, with nothing changed."""
+        if self.frozen:
+            raise ValueError('KVCache.truncate: this cache was filled for cross-attention and is frozen')
+        r = np.asarray(rows)
+        if r.dtype == np.bool_ or not np.issubdtype(r.dtype, np.integer) or r.shape not in ((), (self.batch,)):
+            raise ValueError(f'KVCache.truncate: rows must be an integer or {self.batch} integers, got {rows!r}')
+        r = np.broadcast_to(r, [self.batch]).astype(np.int64)
+        if (r < 0).any() or (r > self.lengths).any():
+            raise ValueError(f'KVCache.truncate: {r.tolist()} rows cannot leave sequences of {self.lengths.tolist()} rows')
+        return self.lengths - r
+
+    def truncate(self, rows) -> None:
+        """The last ``rows`` (an integer, or [B] integers with 0 <= rows[b] <= lengths[b]) rows of every sequence leave the
+        cache: ``lengths[b] -= rows[b]``, which is all -- nothing is launched, and nothing reads a row at or past a length.
+        What a speculative step does with the rows of the drafted tokens that were not accepted.  ValueError, with nothing
+        changed, for anything else and for a frozen cache."""
+        self.lengths = self._truncated(rows)
+
     def write_slot(self, b: int, k: Optional[Mat], v: Optional[Mat], rows: int) -> None:
         """Sequence ``b`` is replaced: its rows 0 .. rows - 1 are the ``rows`` rows of ``k`` / ``v`` ([rows, Hkv * D] with a row
         pitch each) and ``lengths[b] = rows``; the other sequences are not touched (npm_kv_append on slot b alone).  ``k`` or ``v``
@@ -1847,6 +1866,28 @@ class PagedKVCache(KVCache):
             self.lengths[i] = 0
             self.dropped[i] = 0
             self._table_dirty = True
+
+    def truncate(self, rows) -> None:
+        """``KVCache.truncate``, and every page above ceil(new length / page_size) goes back to the free list, its table slot
+        becomes -1 and the table is uploaded again before its next use.  With a ``window`` the new length L' must still have
+        its window -- max(L' - window + 1, 0) >= dropped[b] wherever L' > 0 -- else ValueError with lengths, table and free list
+        as they were; a rollback inside the chunk just appended always has it, since pages are reclaimed at the start of
+        ``append`` from the length before it."""
+        after = self._truncated(rows)
+        if self.window is not None:
+            short = (after > 0) & (np.maximum(after - self.window + 1, 0) < self.dropped)
+            if short.any():
+                raise ValueError(f'PagedKVCache.truncate: lengths {after.tolist()} would reach below the {self.dropped.tolist()} '
+                                 f'leading rows already given back (window={self.window})')
+        keep, have = -(-after // self.page_size), -(-self.lengths // self.page_size)
+        for b in np.nonzero(have > keep)[0]:
+            for slot in range(int(keep[b]), int(have[b])):
+                if self.block_table[b, slot] >= 0:                # below ``dropped`` the window gave the page back already
+                    heapq.heappush(self._free, int(self.block_table[b, slot]))
+                self.block_table[b, slot] = -1
+            self._table_dirty = True
+        self.dropped[after == 0] = 0                              # an emptied sequence starts over, as after release()
+        self.lengths = after
 
     def write_slot(self, b: int, k: Optional[Mat], v: Optional[Mat], rows: int) -> None:
         raise NotImplementedError('PagedKVCache.write_slot: a released slot is filled by the ragged append, which hands out its pages')

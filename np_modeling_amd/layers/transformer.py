@@ -552,6 +552,12 @@ class DecodeState:
         self.self_cache.release(b)
         self.cross_cache.lengths[np.unique(np.atleast_1d(np.asarray(b, dtype=np.int64)))] = 0
 
+    def truncate(self, rows) -> None:
+        """The last ``rows`` (an integer or [B]) tokens leave the self-attention cache (``device.KVCache.truncate``): the drafted
+        tokens of a speculative step that were not accepted.  The cross-attention cache is not touched; rotary positions follow
+        the lengths."""
+        self.self_cache.truncate(rows)
+
     @property
     def position(self) -> int:
         return self.self_cache.length

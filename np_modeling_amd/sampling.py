@@ -11,6 +11,12 @@ device (``result.ids``) for ``layers.embedding.Embedding.forward``, and ``result
 
 A slot's tokens depend on its own logits, parameters, seed and counter only -- never on the batch around it -- and the same
 (seed, counter) gives the same token on every run.  A slot that was never ``set`` samples greedily.
+
+Speculative decoding (include/npm_hip.h npm_verify_rows, npm_ngram_draft; ``speculative.decode_step`` runs the whole step):
+``NgramDrafter`` keeps every slot's tokens so far in HBM and proposes, as the next T tokens, what followed the most recent earlier
+occurrence of the last few; ``Sampler.verify`` samples the T + 1 logit rows the model returned for them, row r at counter
+``draw + r``, and accepts drafted tokens while they are the tokens sampled.  The tokens emitted are those of the one-token loop
+from the same logits, seed for seed and counter for counter: a draft changes when tokens appear, never which.
 """
 
 from __future__ import annotations
@@ -49,6 +55,48 @@ class SampleResult:
     @property
     def prob(self) -> np.ndarray:
         return self._fetch()[8 * self._batch:12 * self._batch].view(np.float32).copy()
+
+
+class VerifyResult:
+    """What one ``Sampler.verify`` produced, for T + 1 = ``rows`` logit rows per slot.  ``ids``: device int32 [B, rows], the
+    tokens sampled up to and including the first that is not the drafted one, -1 behind it (and everywhere for an inactive slot);
+    ``numpy()``: the same on the host; ``accepted``: int32 [B], how many drafted tokens were confirmed -- slot b emitted
+    ``accepted[b] + 1`` tokens; ``kept`` / ``prob``: [B, rows] as in ``SampleResult``.  One host copy serves all four."""
+
+    def __init__(self, out: D.ByteBuffer, batch: int, rows: int):
+        self._out, self._batch, self._rows, self._host = out, batch, rows, None
+        self.ids = D.IdBuffer([batch, rows], out._buf, out.ptr)
+
+    @property
+    def extra(self) -> np.ndarray:
+        """The int32 words behind the four results (``Sampler.verify(..., extra_words=)``): what ``before_fetch`` had written
+        there came to the host in the same copy."""
+        return self._fetch()[3 * self._batch * self._rows + self._batch:].copy()
+
+    def _fetch(self) -> np.ndarray:
+        if self._host is None:
+            self._host = self._out.numpy().view(np.int32)
+        return self._host
+
+    def _rows_of(self, first: int) -> np.ndarray:
+        n = self._batch * self._rows
+        return self._fetch()[first:first + n].reshape(self._batch, self._rows)
+
+    def numpy(self) -> np.ndarray:
+        return self._rows_of(0).copy()
+
+    @property
+    def accepted(self) -> np.ndarray:
+        n = self._batch * self._rows
+        return self._fetch()[n:n + self._batch].copy()
+
+    @property
+    def kept(self) -> np.ndarray:
+        return self._rows_of(self._batch * self._rows + self._batch).copy()
+
+    @property
+    def prob(self) -> np.ndarray:
+        return self._rows_of(2 * self._batch * self._rows + self._batch).view(np.float32).copy()
 
 
 class Sampler:
@@ -123,3 +171,169 @@ class Sampler:
         _C.check(_C.lib().npm_sample_rows(C.byref(desc)), 'npm_sample_rows')
         self.draw += np.uint64(1) if mask is None else mask.astype(np.uint64)
         return SampleResult(out, self.batch)
+
+    def verify(self, logits, draft, n_draft, history: Optional['NgramDrafter'] = None, draft_pitch: Optional[int] = None,
+               extra_words: int = 0, before_fetch=None) -> VerifyResult:
+        """The T + 1 logit rows of every slot of a speculative step, ``logits`` [B * (T + 1), V] with slot b's rows together, in
+        one call of npm_verify_rows: row r is sampled with slot b's parameters at counter ``draw[b] + r``, and drafted tokens are
+        accepted while they equal the token sampled.  ``draft``: [B, >= T] integers or an ``IdBuffer`` (``draft_pitch``: its row
+        pitch when that is not its last dimension -- ``NgramDrafter.propose``'s chunk from its second column on has pitch T + 1);
+        ``n_draft``: [B] integers or an ``IdBuffer``, 0 .. T drafted tokens per slot, below 0 for a slot left alone (an
+        ``IdBuffer`` is copied to the host once: the counters need it).  ``history``: the ``NgramDrafter`` whose histories the
+        emitted tokens are appended to, on the device; ValueError before the launch when one might not fit.
+
+        The host mirror ``draw`` advances by ``accepted + 1``, so the result is copied to the host here.  ``extra_words`` int32
+        words are allocated behind the results and ``before_fetch(address)`` is called between the launch and that copy: what it
+        launches may write them, and they arrive as ``result.extra`` without a copy of their own (``speculative.decode_step``
+        has the next draft's lengths ride along)."""
+        if not isinstance(logits, D.DeviceArray) or logits.ndim != 2 or logits.shape[0] % self.batch or logits.shape[0] == 0:
+            raise ValueError(f'Sampler.verify: logits must be a DeviceArray of shape [{self.batch} * (T + 1), V], got '
+                             f'{getattr(logits, "shape", type(logits).__name__)}')
+        rows, vocab = logits.shape[0] // self.batch, logits.shape[1]
+        if rows > _C.VERIFY_MAX_ROWS:
+            raise ValueError(f'Sampler.verify: at most {_C.VERIFY_MAX_ROWS} rows per slot, got {rows}')
+        if not 1 <= vocab <= _C.SAMPLE_MAX_VOCAB:
+            raise ValueError(f'Sampler.verify: the vocabulary must be 1 .. {_C.SAMPLE_MAX_VOCAB}, got {vocab}')
+        n_host = np.asarray(n_draft.numpy() if isinstance(n_draft, D.IdBuffer) else n_draft)
+        if n_host.shape != (self.batch,) or not np.issubdtype(n_host.dtype, np.integer) or (n_host >= rows).any():
+            raise ValueError(f'Sampler.verify: n_draft must be {self.batch} integers below {rows}, got {n_host.tolist()!r}')
+        n_host = np.maximum(n_host.astype(np.int64), -1)
+        n_dev = n_draft if isinstance(n_draft, D.IdBuffer) else D.ids_from_host(n_host)
+        draft_dev = D.as_ids(draft)
+        if draft_pitch is None:
+            if len(draft_dev.shape) != 2 or draft_dev.shape[0] != self.batch:
+                raise ValueError(f'Sampler.verify: draft must be [{self.batch}, >= {rows - 1}] integers, got {draft_dev.shape}')
+            draft_pitch = draft_dev.shape[1]
+        if draft_pitch < rows - 1:
+            raise ValueError(f'Sampler.verify: the draft holds fewer than {rows - 1} tokens per slot (pitch {draft_pitch})')
+        active = n_host >= 0
+        if history is not None:
+            if not isinstance(history, NgramDrafter) or history.batch != self.batch:
+                raise ValueError(f'Sampler.verify: history must be an NgramDrafter of batch {self.batch}')
+            if (history.lengths + np.where(active, n_host + 1, 0) > history.capacity).any():
+                raise ValueError(f'Sampler.verify: up to {(n_host + 1).tolist()} more tokens after {history.lengths.tolist()} do not fit '
+                                 f'the history capacity {history.capacity}')
+        seed, draw, temperature, top_k, top_p = self._pointers()
+        cells = self.batch * rows
+        out = D.ByteBuffer(4 * (3 * cells + self.batch + int(extra_words)))
+        if history is not None:
+            history._ahead = None                                            # the histories are about to change
+        desc = _C.npm_verify(logits=logits.ptr, pitch=vocab, batch=self.batch, rows=rows, vocab=vocab,
+                             history_cap=0 if history is None else history.capacity, temperature=temperature, top_k=top_k,
+                             top_p=top_p, seed=seed, draw=draw, draft=draft_dev.ptr, draft_pitch=draft_pitch, n_draft=n_dev.ptr,
+                             token=out.ptr, accepted=out.ptr + 4 * cells, kept=out.ptr + 4 * (cells + self.batch),
+                             prob=out.ptr + 4 * (2 * cells + self.batch),
+                             history=None if history is None else history._history.ptr,
+                             history_pitch=0 if history is None else history.capacity,
+                             history_len=None if history is None else history._lengths.ptr)
+        _C.check(_C.lib().npm_verify_rows(C.byref(desc)), 'npm_verify_rows')
+        if before_fetch is not None:
+            before_fetch(out.ptr + 4 * (3 * cells + self.batch))
+        result = VerifyResult(out, self.batch, rows)
+        emitted = np.where(active, result.accepted.astype(np.int64) + 1, 0)
+        self.draw += emitted.astype(np.uint64)
+        if history is not None:
+            history.lengths += ((result.numpy() >= 0) & (np.arange(rows)[None, :] < emitted[:, None])).sum(axis=1)
+        return result
+
+
+class NgramDrafter:
+    """Drafts by prompt lookup (include/npm_hip.h npm_ngram_draft): the tokens of every slot so far live on the device, int32
+    [batch, capacity], with a host mirror ``lengths`` of how many each slot holds.  ``propose`` returns, per slot, its last token
+    followed by up to ``max_draft`` tokens that followed the most recent earlier occurrence of its last n tokens, n from
+    ``ngram[0]`` down to ``ngram[1]``; ``Sampler.verify(..., history=drafter)`` appends what a step emitted without a trip
+    through the host.  Integers only: the same history gives the same draft on every run."""
+
+    def __init__(self, batch: int, capacity: int, max_draft: int, ngram=(3, 1)):
+        if int(batch) < 1 or int(capacity) < 1:
+            raise ValueError(f'NgramDrafter: batch and capacity must be at least 1, got {batch!r}, {capacity!r}')
+        if not 1 <= int(max_draft) <= _C.VERIFY_MAX_ROWS - 1:
+            raise ValueError(f'NgramDrafter: max_draft must be 1 .. {_C.VERIFY_MAX_ROWS - 1}, got {max_draft!r}')
+        nmax, nmin = (int(v) for v in ngram)
+        if not 1 <= nmin <= nmax <= _C.DRAFT_MAX_NGRAM:
+            raise ValueError(f'NgramDrafter: ngram is (nmax, nmin) with 1 <= nmin <= nmax <= {_C.DRAFT_MAX_NGRAM}, got {ngram!r}')
+        self.batch, self.capacity, self.max_draft, self.ngram = int(batch), int(capacity), int(max_draft), (nmax, nmin)
+        self.lengths = np.zeros([self.batch], dtype=np.int64)
+        self._history = D.IdBuffer([self.batch, self.capacity])
+        self._lengths = D.ids_from_host(np.zeros([self.batch], dtype=np.int32))
+        self._ahead = None                # [limits, chunk, n_new] of a proposal launched ahead; n_new None until it reached the host
+
+    def _slot(self, b, what: str) -> int:
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 0 <= b < self.batch:
+            raise ValueError(f'NgramDrafter.{what}: slot must be an integer in 0 .. {self.batch - 1}, got {b!r}')
+        return int(b)
+
+    def _set_length(self, b: int, n: int) -> None:
+        host = np.array([n], dtype=np.int32)
+        _C.check(_C.lib().npm_h2d(self._lengths.ptr + 4 * b, host.ctypes.data, 4), 'npm_h2d')
+        self.lengths[b] = n
+        self._ahead = None
+
+    def admit(self, b: int, ids) -> None:
+        """Slot ``b`` starts over with the tokens ``ids`` (1-D, 0 .. 2^31 - 1 each, at most ``capacity``): a sequence's prompt
+        and whatever it has emitted already.  ValueError before anything changes."""
+        b = self._slot(b, 'admit')
+        host = np.asarray(ids)
+        if host.ndim != 1 or host.dtype == np.bool_ or not (np.issubdtype(host.dtype, np.integer) or host.size == 0):
+            raise ValueError(f'NgramDrafter.admit: ids must be a 1-D integer array, got {host.dtype} {host.shape}')
+        if host.size > self.capacity or (host.size and (host.min() < 0 or host.max() >= 2 ** 31)):
+            raise ValueError(f'NgramDrafter.admit: at most {self.capacity} token ids in 0 .. 2^31 - 1, got {host.size} in '
+                             f'{int(host.min()) if host.size else 0} .. {int(host.max()) if host.size else 0}')
+        host = np.ascontiguousarray(host.astype(np.int32))
+        if host.size:
+            _C.check(_C.lib().npm_h2d(self._history.ptr + 4 * b * self.capacity, host.ctypes.data, host.nbytes), 'npm_h2d')
+        self._set_length(b, host.size)
+
+    def release(self, b: int) -> None:
+        """Slot ``b`` holds no tokens: ``propose`` leaves it alone until the next ``admit``."""
+        self._set_length(self._slot(b, 'release'), 0)
+
+    def propose(self, limit=None):
+        """(chunk, n_new): ``chunk`` an ``IdBuffer`` [batch, max_draft + 1] -- slot b's last token, then its draft, then -1 -- and
+        ``n_new`` host int64 [batch], 1 + the drafted tokens (0: an empty slot, or one with ``limit[b] < 0``).  ``limit``: [batch]
+        integers, the most tokens slot b may be drafted (None: ``max_draft``).  ``chunk`` feeds ``Embedding.forward``, ``n_new``
+        is ``decode``'s ``new_lengths``; one launch and one host copy of 4 bytes per slot."""
+        lim = self._limits(limit)
+        ahead, self._ahead = self._ahead, None
+        if ahead is not None and ahead[2] is not None and np.array_equal(ahead[0], lim):
+            return ahead[1], ahead[2]                                        # launched behind the last verify: nothing to do
+        cells = self.batch * (self.max_draft + 1)
+        out = D.IdBuffer([cells + self.batch])
+        n_new = D.IdBuffer([self.batch], out._buf, out.ptr + 4 * cells)
+        self._launch(lim, out.ptr, n_new.ptr)
+        return D.IdBuffer([self.batch, self.max_draft + 1], out._buf, out.ptr), n_new.numpy().astype(np.int64)
+
+    def _limits(self, limit) -> np.ndarray:
+        if limit is None:
+            return np.full([self.batch], self.max_draft, dtype=np.int32)
+        lim = np.asarray(limit)
+        if lim.shape != (self.batch,) or not np.issubdtype(lim.dtype, np.integer):
+            raise ValueError(f'NgramDrafter.propose: limit must be {self.batch} integers, got {np.asarray(limit).tolist()!r}')
+        return np.clip(lim, -1, self.max_draft).astype(np.int32)
+
+    def _launch(self, lim: np.ndarray, chunk_ptr: int, n_new_ptr: int) -> None:
+        limit_dev = D.ids_from_host(lim)
+        _C.check(_C.lib().npm_ngram_draft(self._history.ptr, self.capacity, self.capacity, self._lengths.ptr, limit_dev.ptr, self.batch,
+                                          self.max_draft, self.ngram[0], self.ngram[1], chunk_ptr, n_new_ptr), 'npm_ngram_draft')
+
+    def propose_ahead(self, limit, n_new_ptr: int) -> None:
+        """``propose(limit)`` launched now, its ``n_new`` written to device address ``n_new_ptr`` instead of copied: the caller
+        brings it to the host with something else (``Sampler.verify(..., before_fetch=)``) and hands it to ``settle_ahead``.  The
+        next ``propose`` with the same limits returns this proposal without a launch or a copy; ``admit``, ``release``, another
+        ``verify`` on these histories or other limits drop it."""
+        lim = self._limits(limit)
+        chunk = D.IdBuffer([self.batch, self.max_draft + 1])
+        self._launch(lim, chunk.ptr, n_new_ptr)
+        self._ahead = [lim, chunk, None]
+
+    def settle_ahead(self, n_new) -> None:
+        if self._ahead is not None:
+            self._ahead[2] = np.asarray(n_new).astype(np.int64)
+
+    def device_lengths(self) -> np.ndarray:
+        """The history lengths as the device holds them, int64 [batch] (equal to ``lengths`` at any time)."""
+        return self._lengths.numpy().astype(np.int64)
+
+    def numpy(self) -> np.ndarray:
+        """The histories on the host, int32 [batch, capacity]; slot b's first ``lengths[b]`` entries are its tokens."""
+        return self._history.numpy()
