@@ -149,6 +149,7 @@ enum {
     NPM_TUNE_DECODE_NT = 21,         /* npm_mha_decode_fwd, the cache hint of the K / V loads (each byte is read once): 0 (default) nontemporal when the valid part of K is at least 32 MB (NPM_TUNE_STREAM_NT's rule), 1 always, 2 never; measured in tools/decode_bench.py */
     NPM_TUNE_SKINNY_SPLITS = 22,     /* npm_sgemm_skinny: blocks the K range of one 64-column strip is split over: 0 (default) automatic (npm_sgemm_skinny_splits), n in 1 .. NPM_SKINNY_MAX_SPLITS forced -- more splits than 16-k chunks leaves empty splits, which is allowed */
     NPM_TUNE_SKINNY_NT = 23,         /* npm_sgemm_skinny, the cache hint of the weight loads (each byte is read once): 0 (default) nontemporal when the weights are at least 32 MB (NPM_TUNE_STREAM_NT's rule), 1 always, 2 never; measured in tools/skinny_gemm_bench.py */
+    NPM_TUNE_PREFIX_SPLITS = 24,     /* npm_mha_prefix_splits: blocks the keys of a shared prefix are split over: 0 (default) automatic, n in 1 .. NPM_PREFIX_MAX_SPLITS forced -- more splits than 16-key tiles leaves empty splits, which is allowed */
     NPM_TUNE_GEMM_ABLATE = 99
 };
 int npm_set_tuning(int knob, int value);
@@ -533,6 +534,51 @@ int npm_mha_decode_fwd_window(const npm_mha_decode *d, const int32_t *kv_lens, c
 int npm_mha_prefill_fwd_window(const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens, const int32_t *block_table,
                                int32_t table_pitch, int32_t page_rows, int32_t window, int32_t kv_f16);
 int npm_mha_decode_window_splits(int batch, int kv_heads, int kv_len, int new_tokens, int window);
+
+/* ---- shared key / value prefixes: pages named by several sequences (opt-in; everything above is unchanged) ----
+ * npm_kv_copy_pages, the copy of copy-on-write: for i < n, rows 0 .. rows[i] - 1 of page dst_pages[i] of the pool become those of
+ * page src_pages[i]; rows at and past rows[i] of the destination are not written.  ONE launch for all pairs.  The pool is bytes
+ * here: page_stride_bytes between pages, the rows of a page back to back at row_bytes each, both multiples of 16 and the pool
+ * 16-byte aligned, so f32 and f16 pools take the same call.  src_pages, dst_pages, rows: device arrays of n int32; the caller
+ * guarantees pages of the pool, src_pages[i] != dst_pages[i], distinct destinations and rows[i] * row_bytes <= page_stride_bytes.
+ * n == 0 or row_bytes == 0: NPM_OK, nothing launched.  NPM_E_BAD_ARGUMENT for a NULL pointer, a negative count or a misaligned size.
+ *
+ * npm_mha_prefix_fwd: the R = d->batch * d->new_tokens query rows of ALL sequences (row b * new_tokens + t of d->q, pitch
+ * d->q_pitch) attend, NOT causally, to the same prefix_rows = P keys: those of the ONE sequence whose block-table row is
+ * prefix_table (device, P / page_rows int32).  d->k / d->v are the page pools with the pitches and page strides of
+ * npm_mha_decode_fwd_paged (kv_f16 != 0: halves, counted in halves, multiples of 8); d->kv_len, d->causal, d->ctx and d->lse are
+ * not read.  P is a positive multiple of page_rows, a power of two >= 16: every 16-key tile is full, so there are no lengths, no
+ * masked score and no redirected load.  A block covers 64 (head of the group, row) pairs of one K / V head, the batch folded into
+ * the row index, and its four waves share every tile through LDS as in npm_mha_prefill_fwd; the KEYS are split over `splits`
+ * blocks in contiguous ranges of ceil(P / 16 / splits) tiles (a split past the last tile is empty, which is allowed).  Every
+ * (split s, row r, head h) with t < new_lens[b] (NULL: every row) writes
+ *   part_ctx[((s * R + r) * heads + h) * head_dim ..]   softmax-weighted V over the split's keys, normalised within the split
+ *   part_lse[(s * R + r) * heads + h]                   log sum exp of the split's scaled scores (-inf and ctx 0 for an empty split)
+ * and other rows read no q and write nothing.  The caller provides splits * R * heads * (head_dim + 1) floats, part_ctx 16-byte
+ * aligned.  Exact fp32 MFMA, no atomics; a row's partials depend on its q, the prefix and `splits` only (bitwise the same at any
+ * batch); the f16 call is bitwise the f32 call on the rounded values.  head_dim in {16, 32, 64, 128}, else NPM_E_UNSUPPORTED.
+ * npm_last_prefix_kernel(): "mha_prefix_kernel D=<head_dim> R=<rows> rows=64 prefix=<P> splits=<splits> paged=<page_rows>", then
+ * " kv=f16"; "" before the first call.
+ * npm_mha_prefix_splits: the split count for this shape (rows = R) under NPM_TUNE_PREFIX_SPLITS: row tiles x kv_heads x splits
+ * of about two blocks per compute unit, no split shorter than 128 keys.  Shape arguments and the knob only.
+ *
+ * npm_attn_combine: for every row with t < new_lens[b] (NULL: every row) and every head, the `splits` partials in split order and
+ * then, LAST, the result the caller's suffix call left in ctx [B, T, heads, head_dim] (pitch ctx_pitch) and lse [B, heads, T]:
+ *   M = max lse_i,  w_i = exp(lse_i - M) (0 by selection for lse_i = -inf, whose ctx is not read),
+ *   ctx = (sum w_i ctx_i) / sum w_i, summed in that order,  lse = M + log sum w_i (stored when store_lse != 0).
+ * The suffix call is the paged entry point of the cache with block_table + P / page_rows, lengths max(kv_lens[b] - P, 0) and
+ * d->kv_len less P: a row's causal limit is the same number in suffix coordinates.  Rows with t >= new_lens[b] are stored as
+ * ctx = 0 (lse = -inf with store_lse), by selection.  lse is required: it carries the suffix weights in. */
+#define NPM_PREFIX_MAX_SPLITS 1024
+int npm_kv_copy_pages(void *pool, int64_t page_stride_bytes, int64_t row_bytes, const int32_t *src_pages, const int32_t *dst_pages,
+                      const int32_t *rows, int32_t n);
+int npm_mha_prefix_supported(int head_dim);
+int npm_mha_prefix_fwd(const npm_mha_decode *d, const int32_t *new_lens, const int32_t *prefix_table, int32_t page_rows,
+                       int32_t prefix_rows, int32_t splits, float *part_ctx, float *part_lse, int32_t kv_f16);
+int npm_mha_prefix_splits(int rows, int heads, int kv_heads, int prefix_rows);
+const char *npm_last_prefix_kernel(void);
+int npm_attn_combine(const float *part_ctx, const float *part_lse, int32_t splits, float *ctx, int64_t ctx_pitch, float *lse,
+                     int32_t batch, int32_t new_tokens, int32_t heads, int32_t head_dim, const int32_t *new_lens, int32_t store_lse);
 
 /* ---- rotary position embedding (RoPE), in place ----
  * Rotates the first `heads` heads of every row b * tokens + t (b < batch, t < tokens) of x: head h of a row is the head_dim floats

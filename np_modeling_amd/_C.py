@@ -199,6 +199,11 @@ SIGNATURES = {
     'npm_mha_decode_fwd_window': [C.POINTER(npm_mha_decode), _P, _P, _P, _I32, _I32, _I32, _I32],
     'npm_mha_prefill_fwd_window': [C.POINTER(npm_mha_decode), _P, _P, _P, _I32, _I32, _I32, _I32],
     'npm_mha_decode_window_splits': [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int],
+    'npm_kv_copy_pages': [_P, _I64, _I64, _P, _P, _P, _I32],
+    'npm_mha_prefix_supported': [C.c_int],
+    'npm_mha_prefix_fwd': [C.POINTER(npm_mha_decode), _P, _P, _I32, _I32, _I32, _P, _P, _I32],
+    'npm_mha_prefix_splits': [C.c_int, C.c_int, C.c_int, C.c_int],
+    'npm_attn_combine': [_P, _P, _I32, _P, _I64, _P, _I32, _I32, _I32, _I32, _P, _I32],
     'npm_rope': [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _I32],
     'npm_take_rows': [_P, _I64, _I64, _P, _P, _I64, _I64, _I64],
     'npm_embedding_bwd': [_P, _I64, _P, _P, _P, _I32, _P, _I64, _I64],
@@ -228,6 +233,7 @@ _SPECIAL = {
     'npm_last_attn_kernel': (C.c_char_p, []),
     'npm_last_decode_kernel': (C.c_char_p, []),
     'npm_last_prefill_kernel': (C.c_char_p, []),
+    'npm_last_prefix_kernel': (C.c_char_p, []),
     'npm_last_skinny_kernel': (C.c_char_p, []),
     'npm_last_sample_kernel': (C.c_char_p, []),
     'npm_last_draft_kernel': (C.c_char_p, []),
@@ -466,6 +472,11 @@ def last_decode_kernel() -> str:
     return lib().npm_last_decode_kernel().decode()
 
 
+def last_prefix_kernel() -> str:
+    """What the most recent npm_mha_prefix_fwd launched (include/npm_hip.h npm_last_prefix_kernel)."""
+    return lib().npm_last_prefix_kernel().decode()
+
+
 def last_prefill_kernel() -> str:
     """What the most recent npm_mha_prefill_fwd / npm_mha_prefill_fwd_f16 launched (include/npm_hip.h npm_last_prefill_kernel)."""
     return lib().npm_last_prefill_kernel().decode()
@@ -473,6 +484,7 @@ def last_prefill_kernel() -> str:
 
 TUNE_DECODE_SPLITS, TUNE_DECODE_NT = 20, 21     # include/npm_hip.h NPM_TUNE_DECODE_*
 TUNE_SKINNY_SPLITS, TUNE_SKINNY_NT = 22, 23     # include/npm_hip.h NPM_TUNE_SKINNY_*
+TUNE_PREFIX_SPLITS, PREFIX_MAX_SPLITS = 24, 1024    # include/npm_hip.h NPM_TUNE_PREFIX_SPLITS, NPM_PREFIX_MAX_SPLITS
 SKINNY_MAX_M, SKINNY_MAX_SPLITS = 64, 64        # include/npm_hip.h NPM_SKINNY_MAX_*
 
 

@@ -279,6 +279,23 @@ kv_gather_kernel(const RowLayout src, float *__restrict__ out, int rows, int row
     }
 }
 
+// Copy-on-write of a paged cache (npm_kv_copy_pages): the first rows[i] rows of page src_pages[i] become those of page
+// dst_pages[i], for all n pairs in one launch.  Bytes, 16 at a time, so one kernel serves f32 and f16 pools: the rows of a page
+// are contiguous, row16 such pieces each, and a page lies page16 pieces from the next.  blockIdx.y walks the pairs, blockIdx.x the
+// rows[i] * row16 pieces of one; pieces at and past that (the rows at and past rows[i] of the destination) are not written.
+typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
+
+__global__ void __launch_bounds__(256)
+kv_copy_pages_kernel(u32x4v *__restrict__ pool, long page16, long row16, const int *__restrict__ src_pages,
+                     const int *__restrict__ dst_pages, const int *__restrict__ rows, int n) {
+    for (int pair = blockIdx.y; pair < n; pair += gridDim.y) {
+        const long pieces = (long)rows[pair] * row16;
+        const u32x4v *from = pool + src_pages[pair] * page16;
+        u32x4v *to = pool + dst_pages[pair] * page16;
+        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < pieces; i += (long)gridDim.x * blockDim.x) to[i] = from[i];
+    }
+}
+
 // VL = false (npm_mha_decode_fwd): the instances that never look at the length arrays; PG: the ones that read through a block table
 template <int D, int RB, bool VL, bool PG, typename KV>
 void launch_decode(const DecodeArgs &a, const int *kv_lens, const int *new_lens, const PageArgs &pg, dim3 grid, bool nt, hipStream_t s) {
@@ -637,4 +654,23 @@ extern "C" int npm_kv_gather_f16(const void *cache, int64_t cache_pitch, int64_t
     }
     return row_copy<_Float16>("npm_kv_gather_f16", true, out, row_len, contiguous(cache, cache_pitch, cache_stride), 0, batch, rows,
                               row_len, true, 0, lens, nullptr);
+}
+
+// Copy-on-write of a paged cache: rows 0 .. rows[i] - 1 of page dst_pages[i] = those of page src_pages[i], i < n, in one launch.
+// The pool is bytes here -- page_stride_bytes between pages, rows of row_bytes back to back inside one -- so f32 and f16 pools
+// take the same call.  src_pages, dst_pages and rows are device arrays; the caller guarantees pages of the pool, src != dst and
+// rows[i] * row_bytes <= page_stride_bytes.  The grid is sized for a full page; n == 0 or row_bytes == 0 is NPM_OK and no launch.
+extern "C" int npm_kv_copy_pages(void *pool, int64_t page_stride_bytes, int64_t row_bytes, const int32_t *src_pages,
+                                 const int32_t *dst_pages, const int32_t *rows, int32_t n) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(n >= 0 && row_bytes >= 0 && page_stride_bytes >= 0);
+    if (n == 0 || row_bytes == 0) return NPM_OK;
+    NPM_ARG(pool != nullptr && src_pages != nullptr && dst_pages != nullptr && rows != nullptr);
+    NPM_ARG(aligned16(pool) && row_bytes % 16 == 0 && page_stride_bytes % 16 == 0 && page_stride_bytes >= row_bytes);
+    const long page16 = page_stride_bytes / 16;
+    const dim3 grid((unsigned)std::min<long>((page16 + 255) / 256, 64), (unsigned)std::min(n, 65535)), block(256);
+    hipLaunchKernelGGL(kv_copy_pages_kernel, grid, block, 0, npm::ctx().stream, static_cast<u32x4v *>(pool), page16, (long)(row_bytes / 16),
+                       src_pages, dst_pages, rows, n);
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
 }

@@ -448,6 +448,7 @@ extern "C" int npm_decode_set_splits(int value);
 extern "C" int npm_decode_set_nt(int value);
 extern "C" int npm_skinny_set_splits(int value);
 extern "C" int npm_skinny_set_nt(int value);
+extern "C" int npm_prefix_set_splits(int value);
 
 extern "C" int npm_set_math(int mode) { return npm_set_tuning(NPM_TUNE_GEMM_MATH, mode); }
 extern "C" int npm_get_math(void) { return g_math; }
@@ -482,6 +483,7 @@ extern "C" int npm_set_tuning(int knob, int value) {
         case NPM_TUNE_DECODE_NT: return npm_decode_set_nt(value);
         case NPM_TUNE_SKINNY_SPLITS: return npm_skinny_set_splits(value);
         case NPM_TUNE_SKINNY_NT: return npm_skinny_set_nt(value);
+        case NPM_TUNE_PREFIX_SPLITS: return npm_prefix_set_splits(value);
         default: return npm::fail(NPM_E_BAD_ARGUMENT, "npm_set_tuning: unknown knob %d", knob);
     }
 }

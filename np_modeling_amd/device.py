@@ -1336,8 +1336,16 @@ def _window_call(entry: str, timer: str, c, cache: 'KVCache', layout: KVLayout, 
                                           int(cache.dtype == 'f16')), entry)
 
 
+def _behind_prefix(layout: KVLayout, prefix: int) -> KVLayout:
+    """``layout`` of a paged cache with every table row starting ``prefix`` rows (whole pages) later; the pitch stays."""
+    if not prefix:
+        return layout
+    assert layout.table is not None and prefix % layout.page_rows == 0, (prefix, layout.page_rows)
+    return layout._replace(table=layout.table + 4 * (prefix // layout.page_rows))
+
+
 def mha_decode(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, scale: float, causal: bool, want_lse: bool = False,
-               lens=None, keys: Optional[int] = None, window: Optional[int] = None):
+               lens=None, keys: Optional[int] = None, window: Optional[int] = None, prefix: int = 0):
     """ctx [B, T, Hq, D] (and lse [B, Hq, T] or None) of ``tokens`` query rows per sequence over the first ``kv_len`` rows of
     ``cache`` (include/npm_hip.h npm_mha_decode_fwd).  ``q``: (array, row pitch).
 
@@ -1345,9 +1353,12 @@ def mha_decode(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, s
     padded ``tokens``, or None for all -- makes it the call of a ragged batch (npm_mha_decode_fwd_varlen; through the block table
     of a paged cache npm_mha_decode_fwd_paged, bitwise the same on the same rows): ``kv_len`` is then the host's upper bound of
     ``kv_lens`` and rows without a visible key come back as ctx 0, lse -inf.  ``keys``: the sum of the lengths, for the timer.
-    ``window`` W: row t sees only the W keys up to its own (npm_mha_decode_fwd_window; per-sequence form, causal)."""
+    ``window`` W: row t sees only the W keys up to its own (npm_mha_decode_fwd_window; per-sequence form, causal).
+    ``prefix`` P (a paged cache, whole pages): the call runs over the rows BEHIND the first P of every sequence -- the table moved
+    on by P / page_size slots, ``kv_len`` and ``lens`` already in those coordinates (``PagedKVCache`` 's shared-prefix path)."""
     assert cache.key_dim == cache.value_dim and 0 <= kv_len <= cache.capacity and (lens is not None or tokens <= kv_len)
     c, ctx, lse, layout = _decode_desc(q, cache, heads, tokens, kv_len, scale, causal, want_lse)
+    layout = _behind_prefix(layout, prefix)
     b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
     keys = b * kv_len if keys is None else int(keys)
     if window is not None:
@@ -1390,14 +1401,15 @@ def mha_prefill_supported(head_dim: int, value_dim: Optional[int] = None) -> boo
 
 
 def mha_prefill(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, scale: float, causal: bool, want_lse: bool = False,
-                lens=None, keys: Optional[int] = None, window: Optional[int] = None):
+                lens=None, keys: Optional[int] = None, window: Optional[int] = None, prefix: int = 0):
     """``mha_decode`` without its limit on the rows (include/npm_hip.h npm_mha_prefill_fwd): ctx [B, T, Hq, D] (and lse
     [B, Hq, T] or None) of ``tokens`` query rows per sequence over ``cache``, read in place -- through the block table of a paged
     cache -- with ``lens`` = (kv_lens, new_lens) as there.  No mask and no gathered copy exist.  An fp16 cache takes
     ``npm_mha_prefill_fwd_f16`` (bitwise the fp32 call on the rounded values); this is the low-level call, whatever
-    ``PREFILL_KERNEL_F16`` says.  ``window`` W: npm_mha_prefill_fwd_window, as in ``mha_decode``."""
+    ``PREFILL_KERNEL_F16`` says.  ``window`` W: npm_mha_prefill_fwd_window, as in ``mha_decode``; ``prefix``: as there."""
     assert cache.key_dim == cache.value_dim and 0 <= kv_len <= cache.capacity and (lens is not None or tokens <= kv_len)
     c, ctx, lse, layout = _decode_desc(q, cache, heads, tokens, kv_len, scale, causal, want_lse)
+    layout = _behind_prefix(layout, prefix)
     b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
     keys = b * kv_len if keys is None else int(keys)
     if window is not None:
@@ -1413,6 +1425,60 @@ def mha_prefill(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, 
         _C.check(_C.lib().npm_mha_prefill_fwd(C.byref(c), kv_lens, new_lens, layout.table, layout.table_pitch, layout.page_rows),
                  'npm_mha_prefill_fwd')
     return ctx, lse
+
+
+# shared prefixes: with the switch on, a causal ``attend`` on a paged cache whose active sequences name the same leading pages
+# (``PagedKVCache.fork``) reads those pages once for all of them -- npm_mha_prefix_fwd, the ordinary paged call over what lies
+# behind them, npm_attn_combine -- from ``SHARED_PREFIX_MIN_ROWS`` shared rows up.  Off by default: every call sequence is then
+# what it was before the entry points existed (tools/shared_prefix_bench.py measures both sides).
+SHARED_PREFIX = os.environ.get('NPM_SHARED_PREFIX', '0') != '0'
+# Measured (tools/shared_prefix_bench.py, profiles/r19_shared_prefix_bench.log; D 128, Hq 8, page 64): at B 8 and Hkv 8 the three
+# launches are not slower than the paged call from P 8192 up (0.96 - 1.12 of it; 1.26 - 1.56 at P 2048), which is the default;
+# at B 64 they win from P 512 (0.85 - 1.05) to P 8192 (0.19 - 0.31).  At Hkv 1 they LOSE at every measured shape but B 64, P 8192,
+# T 4 and f16: leave the switch off for multi-query attention.
+SHARED_PREFIX_MIN_ROWS = int(os.environ.get('NPM_SHARED_PREFIX_MIN_ROWS', '8192'))
+
+
+def mha_prefix_supported(head_dim: int, value_dim: Optional[int] = None) -> bool:
+    """Whether ``npm_mha_prefix_fwd`` takes this head size.  Exact-fp32 MFMA only, like ``mha_decode_supported``."""
+    if not ATTN_CORE or (value_dim is not None and value_dim != head_dim) or _C.current_math() != 'f32':
+        return False
+    return bool(_C.lib().npm_mha_prefix_supported(int(head_dim)))
+
+
+def mha_prefix(q: Mat, cache: 'PagedKVCache', heads: int, tokens: int, scale: float, new_lens: Optional[int], prefix_table: int,
+               prefix: int):
+    """The partial results of all ``cache.batch * tokens`` query rows over the ``prefix`` rows whose pages the device table row at
+    ``prefix_table`` names (include/npm_hip.h npm_mha_prefix_fwd): (splits, part_ctx address, part_lse address, the pooled
+    scratch that holds both -- keep it until the combine is launched)."""
+    b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
+    kl, vl = cache.layout(cache.k), cache.layout(cache.v)
+    rows = b * int(tokens)
+    splits = int(_C.lib().npm_mha_prefix_splits(rows, int(heads), hkv, int(prefix)))
+    part = empty([splits * rows * heads * (d + 1)])
+    part_lse = part.ptr + 4 * splits * rows * heads * d
+    c = _C.npm_mha_decode()
+    c.batch, c.heads, c.kv_heads, c.new_tokens, c.kv_len, c.head_dim = b, int(heads), hkv, int(tokens), int(prefix), d
+    c.causal, c.scale = 0, float(scale)
+    c.q, c.q_pitch = q.ptr, q.ld
+    c.k, c.k_pitch, c.k_stride_b = cache.k.ptr, kl.pitch, kl.stride
+    c.v, c.v_pitch, c.v_stride_b = cache.v.ptr, vl.pitch, vl.stride
+    row_tiles = -(-rows * heads // (hkv * 64))
+    with _timed('mha_prefix', flops=4.0 * heads * rows * prefix * d,
+                nbytes=4.0 * d * heads * rows * (1 + splits) + 2.0 * cache.itemsize * d * hkv * prefix * row_tiles):
+        _C.check(_C.lib().npm_mha_prefix_fwd(C.byref(c), new_lens, prefix_table, cache.page_size, int(prefix), splits, part.ptr, part_lse,
+                                             int(cache.dtype == 'f16')), 'npm_mha_prefix_fwd')
+    return splits, part.ptr, part_lse, part
+
+
+def attn_combine(part_ctx: int, part_lse: int, splits: int, ctx: DeviceArray, lse: DeviceArray, new_lens: Optional[int],
+                 store_lse: bool) -> None:
+    """``ctx`` [B, T, Hq, D] and ``lse`` [B, Hq, T] of a suffix call become the attention over prefix and suffix together: the
+    ``splits`` partials of ``mha_prefix`` merged in split order, the suffix last (include/npm_hip.h npm_attn_combine)."""
+    b, t, h, d = ctx.shape
+    with _timed('attn_combine', nbytes=4.0 * d * b * t * h * (splits + 2)):
+        _C.check(_C.lib().npm_attn_combine(part_ctx, part_lse, int(splits), ctx.ptr, h * d, lse.ptr, b, t, h, d, new_lens,
+                                           int(bool(store_lse))), 'npm_attn_combine')
 
 
 def rope_tables(rows: int, head_dim: int, base: float):
@@ -1677,6 +1743,28 @@ class KVCache:
                 kv_append(src, dst.ptr + self.itemsize * b * layout.stride, layout, 1, rows, 0, None, rows)
         self.lengths[b] = rows
 
+    def _fork_slots(self, src, dst):
+        src, dst = int(src), int(dst)
+        for i in (src, dst):
+            if not 0 <= i < self.batch:
+                raise IndexError(f'{type(self).__name__}.fork: no sequence {i} in a batch of {self.batch}')
+        if src == dst:
+            raise ValueError(f'{type(self).__name__}.fork: sequence {src} cannot be forked onto itself')
+        return src, dst
+
+    def fork(self, src: int, dst: int) -> None:
+        """Slot ``dst`` becomes a copy of sequence ``src``: its ``lengths[src]`` rows of K and V are copied on the device (one
+        copy per tensor) and ``lengths[dst] = lengths[src]``; what ``dst`` held is replaced, as by ``write_slot``.  The API of
+        ``PagedKVCache.fork`` without the sharing; a frozen (cross-attention) cache may be forked.  IndexError / ValueError with
+        nothing changed for a slot outside the batch or ``src == dst``."""
+        src, dst = self._fork_slots(src, dst)
+        rows = int(self.lengths[src])
+        for x in (self.k, self.v):
+            slot = self.itemsize * self.layout(x).stride
+            if rows:
+                _C.check(_C.lib().npm_d2d(x.ptr + dst * slot, x.ptr + src * slot, self.itemsize * rows * self.layout(x).pitch), 'npm_d2d')
+        self.lengths[dst] = rows
+
     def attend(self, q: Mat, heads: int, tokens: int, scale: float, causal: bool, want_lse: bool = False, new_lengths=None,
                kernel: str = 'decode'):
         """``mha_decode`` of ``tokens`` query rows per sequence over the valid rows; with ``new_lengths`` (or a ragged or paged
@@ -1706,9 +1794,27 @@ class KVCache:
         n = self._counts(tokens, n)
         if causal and (n > self.lengths).any():
             raise ValueError(f'KVCache.attend: {n.tolist()} new tokens are not among the {self.lengths.tolist()} valid rows')
+        prefix = self.attend_prefix_rows(n, causal)
+        if prefix:
+            # one upload: the lengths in the coordinates of the rows behind the prefix (a sequence that brings nothing may be shorter)
+            behind = np.maximum(self.lengths - prefix, 0)
+            _, new_ptr, kv_ptr = self._device_lengths(behind - n, n)
+            ctx, lse = attend(q, self, heads, tokens, self.max_length - prefix, scale, True, True, lens=(kv_ptr, new_ptr),
+                              keys=int(behind.sum()), prefix=prefix)
+            first = int(np.nonzero(n)[0][0])
+            table = self.layout(self.k)
+            splits, part_ctx, part_lse, keep = mha_prefix(q, self, heads, tokens, scale, new_ptr, table.table + 4 * first * table.table_pitch,
+                                                          prefix)
+            attn_combine(part_ctx, part_lse, splits, ctx, lse, new_ptr, want_lse)
+            return ctx, (lse if want_lse else None)
         _, new_ptr, kv_ptr = self._device_lengths(self.lengths - n, n)
         return attend(q, self, heads, tokens, self.max_length, scale, causal, want_lse, lens=(kv_ptr, new_ptr),
                       keys=int(self.lengths.sum()))
+
+    def attend_prefix_rows(self, n: np.ndarray, causal: bool) -> int:
+        """The rows of a shared prefix that ``attend`` reads in one pass for all sequences; 0: the ordinary call.  A contiguous
+        cache shares nothing."""
+        return 0
 
     def gather(self, rows: int):
         """(k, v) [B, rows, Hkv, D]: the valid rows of every sequence made contiguous, zeros behind them (``kv_gather_rows``)."""
@@ -1746,8 +1852,16 @@ class PagedKVCache(KVCache):
     sequence holds at most ceil((W - 1 + T) / page_size) + 1 pages between calls of T tokens; ``room`` counts the pages about to
     come back as free; ``gather`` raises once rows were dropped.
 
-    Its own: the pool and the table (``layout``), the page accounting ``append`` calls on (``room``, ``_reclaim``, ``_allocate``)
-    and ``release``; ``append``, ``attend`` and ``gather`` are ``KVCache``'s."""
+    Sharing: ``fork(src, dst)`` makes two sequences name the same pages.  ``refcount`` (host int32 [pages]) counts the sequences
+    naming each page; a page is on the free list exactly when its count is 0, so ``release``, ``truncate`` and the window's
+    reclaim only decrement, and ``pages_in_use`` counts distinct pages.  Copy-on-write sits in ``_allocate``: before an append
+    writes into a partly filled page that another sequence names, the sequence takes a page of its own and the valid rows are
+    copied on the device (npm_kv_copy_pages, one launch per tensor and call; ``page_copies`` counts the pages); ``room`` counts
+    those pages.  With ``SHARED_PREFIX`` on, a causal ``attend`` reads the pages all active sequences share once
+    (``shared_prefix_rows``; npm_mha_prefix_fwd, the paged call over the rest, npm_attn_combine).
+
+    Its own: the pool and the table (``layout``), the page accounting ``append`` calls on (``room``, ``_reclaim``, ``_allocate``),
+    ``release`` and ``fork``; ``append``, ``attend`` and ``gather`` are ``KVCache``'s."""
 
     paged = True
 
@@ -1782,6 +1896,8 @@ class PagedKVCache(KVCache):
         self.block_table = np.full([self.batch, self.pages_per_sequence], -1, dtype=np.int32)
         self.dropped = np.zeros([self.batch], dtype=np.int64)   # leading rows whose pages were given back (window)
         self._free = list(range(self.pages))          # a heap: the lowest-numbered free page first
+        self.refcount = np.zeros([self.pages], dtype=np.int32)   # sequences naming each page; on the free list exactly when 0
+        self.page_copies = 0                          # pages copied by copy-on-write so far
         self._table_dev = None                        # ByteBuffer of the table as the device last saw it
         self._table_dirty = True
 
@@ -1811,8 +1927,8 @@ class PagedKVCache(KVCache):
         lengths, table and free list as they were."""
         KVCache.room(self, tokens, new_lengths)
         n = self._counts(tokens, self.new_lengths(tokens, new_lengths))
-        need = int(self._pages_needed(n).sum())
-        free = self.pages_free + int(self._reclaimable().sum()) // self.page_size
+        need = int(self._pages_needed(n).sum()) + len(self._copy_on_write(n))
+        free = self.pages_free + self._reclaim_frees()
         if need > free:
             raise ValueError(f'PagedKVCache: {n.tolist()} new rows after {self.lengths.tolist()} need {need} more pages of '
                              f'{self.page_size} rows, {free} of {self.pages} are free; release() a sequence first')
@@ -1825,25 +1941,117 @@ class PagedKVCache(KVCache):
         bound = np.maximum(self.lengths - self.window + 1, 0) // self.page_size * self.page_size
         return np.maximum(bound - self.dropped, 0)
 
+    def _reclaim_frees(self) -> int:
+        """Pages that ``_reclaim`` puts on the free list: those of ``_reclaimable`` that no other sequence goes on naming."""
+        rows = self._reclaimable()
+        if not rows.any():
+            return 0
+        left = self.refcount.copy()
+        for b in np.nonzero(rows)[0]:
+            first = int(self.dropped[b]) // self.page_size
+            left[self.block_table[b, first:first + int(rows[b]) // self.page_size]] -= 1
+        return int(((left == 0) & (self.refcount > 0)).sum())
+
+    def _unref(self, page: int) -> None:
+        """One sequence fewer names ``page``; the last one gives it back to the free list."""
+        self.refcount[page] -= 1
+        if self.refcount[page] == 0:
+            heapq.heappush(self._free, int(page))
+
+    def _copy_on_write(self, n: np.ndarray):
+        """[(b, table slot, page, valid rows)] of the appends that must first take a page of their own: sequence b brings rows
+        (n[b] > 0), its next row falls into a partly filled page, and that page is still named by another sequence once the
+        earlier sequences of this call have taken their copies.  The last owner writes in place; a full page is never copied."""
+        out, left = [], {}
+        for b in np.nonzero(n)[0]:
+            rows = int(self.lengths[b]) % self.page_size
+            if not rows:
+                continue
+            slot = int(self.lengths[b]) // self.page_size
+            page = int(self.block_table[b, slot])
+            if left.setdefault(page, int(self.refcount[page])) > 1:
+                left[page] -= 1
+                out.append((int(b), slot, page, rows))
+        return out
+
     def _reclaim(self) -> None:
-        """The pages of ``_reclaimable`` back to the free list, their table slots -1, ``dropped`` advanced."""
+        """The pages of ``_reclaimable`` given up -- back to the free list unless another sequence names them --, their table
+        slots -1, ``dropped`` advanced."""
         rows = self._reclaimable()
         for b in np.nonzero(rows)[0]:
             first = int(self.dropped[b]) // self.page_size
             for slot in range(first, first + int(rows[b]) // self.page_size):
-                heapq.heappush(self._free, int(self.block_table[b, slot]))
+                self._unref(int(self.block_table[b, slot]))
                 self.block_table[b, slot] = -1
             self.dropped[b] += rows[b]
             self._table_dirty = True
 
+    def _take(self) -> int:
+        page = heapq.heappop(self._free)
+        self.refcount[page] = 1
+        return page
+
     def _allocate(self, n: np.ndarray) -> None:
+        """Pages for n[b] more rows.  Copy-on-write lives here and nowhere else: a sequence about to write into a partly filled
+        page that another sequence names takes a fresh page first, and the valid rows of K and of V are copied into it on the
+        device -- one launch per tensor for all sequences of the call (npm_kv_copy_pages)."""
         self._reclaim()
+        copies = self._copy_on_write(n)
+        for b, slot, page, _ in copies:
+            self.block_table[b, slot] = self._take()
+            self.refcount[page] -= 1                  # another sequence still names it: it does not come back
+            self._table_dirty = True
         need = self._pages_needed(n)
         have = -(-self.lengths // self.page_size)
         for b in np.nonzero(need)[0]:
             for slot in range(int(have[b]), int(have[b] + need[b])):
-                self.block_table[b, slot] = heapq.heappop(self._free)
+                self.block_table[b, slot] = self._take()
             self._table_dirty = True
+        if copies:
+            pairs = bytes_from_host(np.array([[page for _, _, page, _ in copies], [self.block_table[b, slot] for b, slot, _, _ in copies],
+                                              [rows for _, _, _, rows in copies]], dtype=np.int32))
+            count = len(copies)
+            for x in (self.k, self.v):
+                row = self.itemsize * self.kv_heads * x.shape[3]
+                with _timed('kv_copy_pages', nbytes=2.0 * row * sum(rows for _, _, _, rows in copies)):
+                    _C.check(_C.lib().npm_kv_copy_pages(x.ptr, self.page_size * row, row, pairs.ptr, pairs.ptr + 4 * count,
+                                                        pairs.ptr + 8 * count, count), 'npm_kv_copy_pages')
+            self.page_copies += count
+
+    def fork(self, src: int, dst: int) -> None:
+        """Slot ``dst`` becomes the sequence of slot ``src`` with nothing launched and no page taken: the same table row,
+        ``lengths`` and ``dropped``, and every named page's ``refcount`` one higher.  The sequences then grow apart through
+        copy-on-write (``_allocate``).  ``dst`` must be empty (``lengths[dst] == 0``: ``release`` it first) and not ``src``:
+        ValueError / IndexError otherwise, with nothing changed.  A windowed cache may be forked."""
+        src, dst = self._fork_slots(src, dst)
+        if self.lengths[dst] != 0:
+            raise ValueError(f'PagedKVCache.fork: slot {dst} still holds {int(self.lengths[dst])} rows; release() it first')
+        self.block_table[dst] = self.block_table[src]
+        self.refcount[self.block_table[dst][self.block_table[dst] >= 0]] += 1
+        self.lengths[dst] = self.lengths[src]
+        self.dropped[dst] = self.dropped[src]
+        self._table_dirty = True
+
+    def shared_prefix_rows(self, n) -> int:
+        """P = ``page_size`` x the number of leading table slots that every sequence with n[b] > 0 fills with the SAME page and
+        that lie wholly below every such sequence's ``lengths[b] - n[b]``: shared pages hold old rows only (copy-on-write keeps
+        the new ones private).  0 with fewer than two such sequences, with a ``window`` and once rows were dropped."""
+        n = np.asarray(n)
+        active = np.nonzero(n > 0)[0]
+        if active.size < 2 or self.window is not None or self.dropped.any():
+            return 0
+        slots = int((self.lengths[active] - n[active]).min()) // self.page_size
+        if slots <= 0:
+            return 0
+        rows = self.block_table[active, :slots]
+        same = ((rows == rows[0]).all(axis=0)) & (rows[0] >= 0)
+        return self.page_size * (slots if same.all() else int(np.argmin(same)))
+
+    def attend_prefix_rows(self, n: np.ndarray, causal: bool) -> int:
+        if not (SHARED_PREFIX and causal and self.window is None and mha_prefix_supported(self.key_dim, self.value_dim)):
+            return 0
+        prefix = self.shared_prefix_rows(n)
+        return prefix if prefix >= max(SHARED_PREFIX_MIN_ROWS, 1) else 0
 
     def _device_table(self) -> int:
         """Device address of the block table, int32 [B, pages_per_sequence]; uploaded only when it changed.  Slots without a page
@@ -1861,7 +2069,7 @@ class PagedKVCache(KVCache):
             if not 0 <= i < self.batch:
                 raise IndexError(f'PagedKVCache.release: no sequence {i} in a batch of {self.batch}')
             for page in self.block_table[i][self.block_table[i] >= 0]:
-                heapq.heappush(self._free, int(page))
+                self._unref(int(page))
             self.block_table[i] = -1
             self.lengths[i] = 0
             self.dropped[i] = 0
@@ -1883,7 +2091,7 @@ class PagedKVCache(KVCache):
         for b in np.nonzero(have > keep)[0]:
             for slot in range(int(keep[b]), int(have[b])):
                 if self.block_table[b, slot] >= 0:                # below ``dropped`` the window gave the page back already
-                    heapq.heappush(self._free, int(self.block_table[b, slot]))
+                    self._unref(int(self.block_table[b, slot]))
                 self.block_table[b, slot] = -1
             self._table_dirty = True
         self.dropped[after == 0] = 0                              # an emptied sequence starts over, as after release()

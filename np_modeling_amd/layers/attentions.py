@@ -124,7 +124,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         self._rope = None                                                   # device.RopeTable, made at the first use
         self._softmax = activations.Softmax()
         self._cached_forward = False    # the last forward ran with a cache: it saved nothing a backward could use
-        self._cached_path = None        # 'decode' | 'prefill' | 'fused_masked' | 'gemm': how the last cached forward attended
+        self._cached_path = None        # 'decode' | 'prefill' | 'fused_masked' | 'gemm' (| 'decode_shared' | 'prefill_shared'): how the last cached forward attended
 
     def initialize(self, query, key=None, value=None, *args, **kwargs) -> None:
         # query [B, Sq, H*Dk]; key [B, Skv, H*Dk]; value [B, Skv, H*Dv]
@@ -532,13 +532,16 @@ class MultiHeadAttention(layer.StatefulLayer):
                                           '{16, 32, 64, 128}, math mode f32)')
             self._cached_path = 'decode' if h // hkv * t <= 32 else 'prefill'
             return cache.attend(q, h, t, scale, True, new_lengths=n, kernel=self._cached_path)[0]
+        # (a paged cache whose active sequences share their leading pages reads those once, with D.SHARED_PREFIX on: the same
+        # call, reported as 'decode_shared' / 'prefill_shared')
+        shared = '_shared' if cache.attend_prefix_rows(n, causal) else ''
         if decode_ok and D.mha_decode_supported(dk, h // hkv * t, dv):
-            self._cached_path = 'decode'
+            self._cached_path = 'decode' + shared
             return cache.attend(q, h, t, scale, causal, new_lengths=n)[0]
         if (D.PREFILL_KERNEL_F16 if stored else D.PREFILL_KERNEL) and D.mha_prefill_supported(dk, dv):
             # a ragged prefill, a chunk of one, a sequence admitted beside decoding ones, a paged or a frozen cache: the prefill
             # kernel over the cache in place, through the block table -- lengths and causality are arithmetic on the device
-            self._cached_path = 'prefill'
+            self._cached_path = 'prefill' + shared
             return cache.attend(q, h, t, scale, causal, new_lengths=n, kernel='prefill')[0]
         # a ragged prefill, mostly: the fused training forward with the lengths as a mask [B, 1, T, keys], whose tile summary
         # skips what lies past them.  K / V: the fresh projection when every sequence started empty (keys = T; the rows of padded

@@ -410,6 +410,11 @@ class TransformerDecoder(layer.Layer):
         cross.write_slot(b, project('_wk', '_bk', cross.key_dim), None, rows)     # K is projected and written, then V
         cross.write_slot(b, None, project('_wv', '_bv', cross.value_dim), rows)
 
+    def fork(self, state: 'DecodeState', src: int, dst: int) -> None:
+        """Slot ``dst`` of a running batch continues sequence ``src`` (n completions of one prompt, n-best sampling):
+        ``DecodeState.fork``."""
+        state.fork(src, dst)
+
     def decode(self, q_new, state: 'DecodeState', new_lengths=None):
         """One incremental step: the T new tokens ``q_new`` [B, T, F] through cached causal self-attention, cross-attention over
         the frozen cache, feed-forward and the three norms -> [B, T, F].  Dropout is the identity (inference: the reference's
@@ -551,6 +556,17 @@ class DecodeState:
             raise ValueError('DecodeState.release: the self-attention cache is not paged (start_decoding(..., page_size=))')
         self.self_cache.release(b)
         self.cross_cache.lengths[np.unique(np.atleast_1d(np.asarray(b, dtype=np.int64)))] = 0
+
+    def fork(self, src: int, dst: int) -> None:
+        """Slot ``dst`` becomes sequence ``src``: the self-attention cache is forked (a paged one shares its pages until the
+        sequences grow apart, ``device.PagedKVCache.fork``; a contiguous one copies the rows) and so is the frozen
+        cross-attention cache (a copy of the memory's projected rows).  ``weights`` is left alone; rotary positions follow the
+        lengths.  ValueError, with nothing changed, while slot ``dst`` still holds rows (``release`` it first), as ``admit``."""
+        src, dst = self.self_cache._fork_slots(src, dst)
+        if self.self_cache.lengths[dst] != 0:
+            raise ValueError(f'fork: slot {dst} still holds {int(self.self_cache.lengths[dst])} rows; release({dst}) it first')
+        self.self_cache.fork(src, dst)
+        self.cross_cache.fork(src, dst)
 
     def truncate(self, rows) -> None:
         """The last ``rows`` (an integer or [B]) tokens leave the self-attention cache (``device.KVCache.truncate``): the drafted
