@@ -783,6 +783,56 @@ int npm_ngram_draft(const int32_t *history, int64_t history_pitch, int32_t histo
 /* What the most recent npm_ngram_draft launched: "ngram_draft_kernel B=<batch> T=<max_draft> ngram=<nmax>..<nmin> cap=<cap>". */
 const char *npm_last_draft_kernel(void);
 
+/* ---- beam search: the best 2 W of W x V continuations per prompt, and the split, on the device ----
+ * npm_beam_step: slots are `groups` groups of `width` beams, slot g W + w, 1 <= W <= NPM_BEAM_MAX_WIDTH, C = 2 W candidates per
+ * group.  logits: fp32 [G W, vocab] with a row pitch; cum: fp32 [G W], the beams' running scores, -inf for a dead beam, updated in
+ * place; eos: the end-of-sequence token, below 0 for none.  All pointers are device pointers.
+ *  1. A dead row (cum == -inf, or NaN) is NOT READ and contributes nothing.
+ *  2. A live row that holds a NaN or +inf, or whose every logit is -inf, is invalid: it contributes nothing and never faults.
+ *     -inf logits are otherwise legal (a masked token) and never candidates.
+ *  3. Row order is npm_sample_rows': i before j when z_i > z_j, or z_i == z_j and i < j; -0.0 == 0.0.
+ *  4. The row normaliser is npm_sample_rows' mass at temperature 1: W1 = sum over the finite tokens of floor(expf(z_i - zmax) *
+ *     2^32), difference and exponential in fp32, as an unsigned 64-bit INTEGER sum: nothing depends on the order in which lanes,
+ *     waves or LDS atomics add.
+ *  5. n = log((double)W1 * 2^-32) in fp64; lse = (float)((double)zmax + n), a zmax of -0.0 read as 0.0.
+ *  6. Candidate (w, i) has score s = (float)((((double)cum_w - (double)zmax_w) - n_w) + (double)z_i): fp64 throughout, in that
+ *     order, ONE rounding to fp32.  Rounding is monotone, so a row's candidates in row order have non-increasing scores.
+ *  7. The candidates of a group are totally ordered: the larger score first, then the smaller beam w, then row order.  Hence only
+ *     the first min(C, finite count) tokens of a row can matter.
+ *  8. cand_slot (g W + w), cand_token and cand_score, [G, C] each, are the first C candidates of every group in that order;
+ *     -1 / -1 / -inf behind the last candidate that exists.
+ *  9. The split: walking the C candidates in order, one whose token is eos is FINISHED when its position is below W and ignored
+ *     otherwise -- either way it never becomes a beam; the others become the next beams 0, 1, ... in order until W are placed.  (A
+ *     row holds eos once, so C = 2 W candidates always hold W others when they exist.)  eos < 0: no candidate is finished.
+ * 10. Per slot g W + j of the NEXT step: parent (the slot beam j continues; -1: dead), ids (its token; -1: dead -- npm_take_rows
+ *     turns that into a row of zeros), cum (written in place: its score; -inf: dead).  lse [G W] belongs to the rows of THIS
+ *     step: the log-sum-exp of row g W + w, NaN for a dead or invalid row; z_i - lse is token i's log-probability.
+ * 11. The caller chooses where the seven results live: np_modeling_amd/beam.py puts them in one allocation, one host copy a step.
+ * 12. Hence a group's results depend on nothing outside its own W rows and cum entries, group g of a batch is the groups = 1 call
+ *     on that group, and a launch is bitwise reproducible.
+ * Two launches: one block of 1024 threads per row (npm_sample_rows' passes -- the row in LDS up to NPM_SAMPLE_LDS_ROW logits,
+ * 16-byte loads for a 16-byte aligned `logits` with pitch % 4 == 0, else one float per lane with the same results -- then the at
+ * most C survivors ranked by one wavefront), which leaves each row's list in `workspace`; then one block per group merges W
+ * lists and splits.  workspace: NPM_BEAM_WORKSPACE_BYTES(groups, width) bytes, 4-byte aligned, contents unspecified before and
+ * after.  NPM_E_BAD_ARGUMENT before anything is launched: s == NULL, groups < 1, width outside 1 .. NPM_BEAM_MAX_WIDTH, vocab
+ * outside 1 .. NPM_SAMPLE_MAX_VOCAB, pitch < vocab, groups * width * C >= 2^31, a NULL pointer, a workspace that is too small or
+ * misaligned. */
+#define NPM_BEAM_MAX_WIDTH 32
+#define NPM_BEAM_WORKSPACE_BYTES(groups, width) ((int64_t)4 * (groups) * (width) * (1 + 4 * (int64_t)(width)))
+typedef struct npm_beam {
+    const float *logits; int64_t pitch;          /* row g W + w starts at logits + (g W + w) * pitch, pitch >= vocab */
+    int32_t groups, width, vocab, eos;
+    float *cum;                                  /* [G W] in and out */
+    int32_t *cand_slot, *cand_token; float *cand_score;   /* [G, 2 W] out */
+    int32_t *parent, *ids;                       /* [G W] out: the next step's slots */
+    float *lse;                                  /* [G W] out: this step's rows */
+    void *workspace; int64_t workspace_bytes;
+} npm_beam;
+int npm_beam_step(const npm_beam *s);
+/* What the most recent npm_beam_step launched: "beam_rows_kernel <vec|scalar> G=<groups> W=<width> V=<vocab> row=<lds|global>";
+ * "" before the first call. */
+const char *npm_last_beam_kernel(void);
+
 /* ---- around the path ("next" rows of SURVEY.md section 8f): keeps a Trainer step on the device ---- */
 /* Adam as the reference computes it (optimizer.py:53-67), operation for operation: (1 - beta1) * g and (1 - beta2) * (g * g) are
  * float32 products (the gradient is float32 and the scalars do not widen it), the moments m, v are fp64 (device buffers of n

@@ -118,6 +118,18 @@ class npm_verify(C.Structure):
     ]
 
 
+class npm_beam(C.Structure):
+    _fields_ = [
+        ('logits', C.c_void_p), ('pitch', C.c_int64),
+        ('groups', C.c_int32), ('width', C.c_int32), ('vocab', C.c_int32), ('eos', C.c_int32),
+        ('cum', C.c_void_p),
+        ('cand_slot', C.c_void_p), ('cand_token', C.c_void_p), ('cand_score', C.c_void_p),
+        ('parent', C.c_void_p), ('ids', C.c_void_p),
+        ('lse', C.c_void_p),
+        ('workspace', C.c_void_p), ('workspace_bytes', C.c_int64),
+    ]
+
+
 class npm_comm_exchange_stats(C.Structure):
     _fields_ = [('bytes', C.c_ulonglong), ('allreduce_calls', C.c_int), ('waits', C.c_int),
                 ('allreduce_ms', C.c_double), ('exposed_ms', C.c_double), ('last_allreduce_ms', C.c_double),
@@ -210,6 +222,7 @@ SIGNATURES = {
     'npm_sample_rows': [C.POINTER(npm_sample)],
     'npm_verify_rows': [C.POINTER(npm_verify)],
     'npm_ngram_draft': [_P, _I64, _I32, _P, _P, _I32, _I32, _I32, _I32, _P, _P],
+    'npm_beam_step': [C.POINTER(npm_beam)],
     'npm_sgemm_skinny': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_supported': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_splits': [C.c_int, C.c_int, C.c_int],
@@ -237,6 +250,7 @@ _SPECIAL = {
     'npm_last_skinny_kernel': (C.c_char_p, []),
     'npm_last_sample_kernel': (C.c_char_p, []),
     'npm_last_draft_kernel': (C.c_char_p, []),
+    'npm_last_beam_kernel': (C.c_char_p, []),
 }
 
 COMM_SIGNATURES = {
@@ -505,6 +519,19 @@ def last_sample_kernel() -> str:
 def last_draft_kernel() -> str:
     """What the most recent npm_ngram_draft launched (include/npm_hip.h npm_last_draft_kernel)."""
     return lib().npm_last_draft_kernel().decode()
+
+
+BEAM_MAX_WIDTH = 32                                    # include/npm_hip.h NPM_BEAM_MAX_WIDTH
+
+
+def beam_workspace_bytes(groups: int, width: int) -> int:
+    """include/npm_hip.h NPM_BEAM_WORKSPACE_BYTES."""
+    return 4 * groups * width * (1 + 4 * width)
+
+
+def last_beam_kernel() -> str:
+    """What the most recent npm_beam_step launched (include/npm_hip.h npm_last_beam_kernel)."""
+    return lib().npm_last_beam_kernel().decode()
 
 
 def comm_lib():

@@ -1765,6 +1765,42 @@ class KVCache:
                 _C.check(_C.lib().npm_d2d(x.ptr + dst * slot, x.ptr + src * slot, self.itemsize * rows * self.layout(x).pitch), 'npm_d2d')
         self.lengths[dst] = rows
 
+    def _parents(self, parents) -> np.ndarray:
+        """``parents`` of ``reorder`` as int64 [B] with every entry in -1 .. B - 1; ValueError / IndexError otherwise."""
+        p = np.asarray(parents)
+        if p.shape != (self.batch,) or p.dtype == np.bool_ or not np.issubdtype(p.dtype, np.integer):
+            raise ValueError(f'{type(self).__name__}.reorder: parents must be {self.batch} integers, got {parents!r}')
+        p = p.astype(np.int64)
+        if (p < -1).any() or (p >= self.batch).any():
+            raise IndexError(f'{type(self).__name__}.reorder: parents name slots -1 (empty) .. {self.batch - 1}, got {p.tolist()}')
+        return p
+
+    def reorder(self, parents) -> None:
+        """Slot b becomes the sequence slot ``parents[b]`` held BEFORE the call (int [B]; -1 empties the slot): what a beam
+        step does to its W sequences.  A slot whose parent is another slot gets that slot's ``lengths[parent]`` rows of K and of
+        V copied on the device -- O(L) per moved slot, where ``PagedKVCache.reorder`` moves a table row.  Swaps and chains are
+        safe: a slot that is both read and overwritten is read from a snapshot taken first (one more copy of its rows), and
+        slots that only move are copied in place.  A frozen (cross-attention) cache may be reordered.  IndexError / ValueError
+        with nothing changed for a vector that is not [B] integers in -1 .. B - 1."""
+        p = self._parents(parents)
+        moved = [b for b in range(self.batch) if p[b] >= 0 and p[b] != b and self.lengths[p[b]] > 0]
+        overwritten = set(moved)
+        sources = sorted({int(p[b]) for b in moved})
+        for x in (self.k, self.v):
+            layout = self.layout(x)
+            slot, row = self.itemsize * layout.stride, self.itemsize * layout.pitch
+            snapshot = {}
+            for s in sources:
+                if s in overwritten:                   # its rows are about to change: keep them as they were
+                    keep = ByteBuffer(int(self.lengths[s]) * row)
+                    _C.check(_C.lib().npm_d2d(keep.ptr, x.ptr + s * slot, keep.nbytes), 'npm_d2d')
+                    snapshot[s] = keep
+            for b in moved:
+                s = int(p[b])
+                src = snapshot[s].ptr if s in snapshot else x.ptr + s * slot
+                _C.check(_C.lib().npm_d2d(x.ptr + b * slot, src, int(self.lengths[s]) * row), 'npm_d2d')
+        self.lengths = np.where(p >= 0, self.lengths[np.maximum(p, 0)], 0)
+
     def attend(self, q: Mat, heads: int, tokens: int, scale: float, causal: bool, want_lse: bool = False, new_lengths=None,
                kernel: str = 'decode'):
         """``mha_decode`` of ``tokens`` query rows per sequence over the valid rows; with ``new_lengths`` (or a ragged or paged
@@ -2031,6 +2067,27 @@ class PagedKVCache(KVCache):
         self.lengths[dst] = self.lengths[src]
         self.dropped[dst] = self.dropped[src]
         self._table_dirty = True
+
+    def reorder(self, parents) -> None:
+        """Slot b becomes the sequence slot ``parents[b]`` held BEFORE the call (int [B]; -1 empties the slot), all slots at
+        once: what a beam step does, where ``release`` / ``fork`` would need a spare slot for a permutation.  Host state only --
+        nothing is launched and no page is taken: the new table, ``lengths`` and ``dropped`` are the old rows indexed by
+        ``parents``, ``refcount`` becomes the number of table entries naming each page, and pages that reach 0 return to the free
+        list.  Children of one parent share its pages and grow apart through copy-on-write (one copied tail page per beam and
+        step at most).  The table is marked for upload only if a row changed: an identity reorder, or a parent that keeps its
+        only child in its own slot, costs nothing.  Windowed and fp16 caches work unchanged.  IndexError / ValueError with nothing
+        changed for a vector that is not [B] integers in -1 .. B - 1."""
+        p = self._parents(parents)
+        live, source = p >= 0, np.maximum(p, 0)
+        table = np.where(live[:, None], self.block_table[source], -1).astype(np.int32)
+        lengths, dropped = np.where(live, self.lengths[source], 0), np.where(live, self.dropped[source], 0)
+        if not np.array_equal(table, self.block_table):
+            refcount = np.bincount(table[table >= 0], minlength=self.pages).astype(np.int32)
+            for page in np.nonzero((self.refcount > 0) & (refcount == 0))[0]:
+                heapq.heappush(self._free, int(page))
+            self.block_table, self.refcount = table, refcount
+            self._table_dirty = True
+        self.lengths, self.dropped = lengths, dropped
 
     def shared_prefix_rows(self, n) -> int:
         """P = ``page_size`` x the number of leading table slots that every sequence with n[b] > 0 fills with the SAME page and

@@ -415,6 +415,11 @@ class TransformerDecoder(layer.Layer):
         ``DecodeState.fork``."""
         state.fork(src, dst)
 
+    def reorder(self, state: 'DecodeState', parents, memory: str = 'shared') -> None:
+        """Slot b of a running batch continues the sequence slot ``parents[b]`` held before the call, -1 ends it (a beam step):
+        ``DecodeState.reorder``."""
+        state.reorder(parents, memory=memory)
+
     def decode(self, q_new, state: 'DecodeState', new_lengths=None):
         """One incremental step: the T new tokens ``q_new`` [B, T, F] through cached causal self-attention, cross-attention over
         the frozen cache, feed-forward and the three norms -> [B, T, F].  Dropout is the identity (inference: the reference's
@@ -567,6 +572,28 @@ class DecodeState:
             raise ValueError(f'fork: slot {dst} still holds {int(self.self_cache.lengths[dst])} rows; release({dst}) it first')
         self.self_cache.fork(src, dst)
         self.cross_cache.fork(src, dst)
+
+    def reorder(self, parents, memory: str = 'shared') -> None:
+        """Slot b becomes the sequence slot ``parents[b]`` held BEFORE the call (int [B]; -1 empties the slot): the
+        self-attention cache is reordered (``device.PagedKVCache.reorder``: table rows, nothing launched; a contiguous cache
+        copies rows).  ``memory`` 'shared' (default): slot b and slot ``parents[b]`` attend the same memory, as the beams of
+        one prompt do, so the cross-attention cache is left alone -- ValueError, with nothing changed, if their cross
+        ``lengths`` differ; a -1 still sets the slot's cross length to 0.  'copy': the cross-attention cache is reordered too
+        (``device.KVCache.reorder``, O(L) per moved slot).  ``weights`` is left alone; rotary positions follow the lengths."""
+        if memory not in ('shared', 'copy'):
+            raise ValueError(f"reorder: memory must be 'shared' or 'copy', got {memory!r}")
+        p = self.self_cache._parents(parents)
+        cross = self.cross_cache
+        if memory == 'shared':
+            live = p >= 0
+            if (cross.lengths[live] != cross.lengths[p[live]]).any():
+                raise ValueError(f"reorder: memory='shared' but the cross-attention lengths {cross.lengths.tolist()} differ between "
+                                 f"a slot and its parent in {p.tolist()}; memory='copy' moves the memory along")
+        self.self_cache.reorder(p)
+        if memory == 'shared':
+            cross.lengths = np.where(p >= 0, cross.lengths, 0)
+        else:
+            cross.reorder(p)
 
     def truncate(self, rows) -> None:
         """The last ``rows`` (an integer or [B]) tokens leave the self-attention cache (``device.KVCache.truncate``): the drafted
