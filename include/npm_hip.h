@@ -829,9 +829,90 @@ typedef struct npm_beam {
     void *workspace; int64_t workspace_bytes;
 } npm_beam;
 int npm_beam_step(const npm_beam *s);
-/* What the most recent npm_beam_step launched: "beam_rows_kernel <vec|scalar> G=<groups> W=<width> V=<vocab> row=<lds|global>";
- * "" before the first call. */
+/* What the most recent npm_beam_step launched: "beam_rows_kernel <vec|scalar> G=<groups> W=<width> V=<vocab> row=<lds|global>"
+ * (npm_logprob_rows: "logprob_rows_kernel <vec|scalar> R=<rows> V=<vocab> top=<top_n> row=<lds|global>"); "" before the first call. */
 const char *npm_last_beam_kernel(void);
+
+/* npm_logprob_rows: clauses 2 - 6 of npm_beam_step with cum = 0, per row and without the beam bookkeeping -- the same kernel,
+ * instantiated without the workspace.  logits: fp32 [rows, vocab] with a row pitch.  Per row r, with zmax, W1 and
+ * n = log((double)W1 * 2^-32) as npm_beam_step defines them:
+ *  1. lse[r] = (float)((double)zmax + n): npm_beam_step's lse of the same row bit for bit.
+ *  2. Token i's log-probability is (float)(((0.0 - (double)zmax) - n) + (double)z_i); that of a -inf token is -inf.
+ *  3. top_token / top_logprob [rows, top_n], top_n in 0 .. 64: the first min(top_n, finite count) tokens in the sampler's order
+ *     with their log-probabilities, -1 / -inf behind them.
+ *  4. With ids != NULL: chosen[r] is the log-probability of ids[r], NaN when that id is >= vocab.  It is the expression of 2, so a
+ *     chosen token among the top n equals that entry bit for bit.
+ *  5. With ids != NULL a row with ids[r] < 0 is NOT LOADED: lse NaN, chosen NaN, top -1 / -inf (the rows a verify step rejected,
+ *     the inactive slots).  An invalid row (a NaN or +inf, or every logit -inf) gives the same outputs and never faults.
+ * One launch, one block of 1024 threads per row; bitwise reproducible; a row depends on nothing outside it.
+ * NPM_E_BAD_ARGUMENT before the launch: p == NULL, rows < 1, vocab outside 1 .. NPM_SAMPLE_MAX_VOCAB, pitch < vocab, top_n outside
+ * 0 .. 64, a NULL logits or lse, ids without chosen, top_n > 0 without top_token or top_logprob. */
+typedef struct npm_logprob {
+    const float *logits; int64_t pitch;          /* row r starts at logits + r * pitch, pitch >= vocab */
+    int32_t rows, vocab, top_n;
+    const int32_t *ids;                          /* NULL, or [rows]: the token whose log-probability chosen reports; < 0: skip the row */
+    float *lse, *chosen;                         /* [rows] out; chosen may be NULL when ids is */
+    int32_t *top_token; float *top_logprob;      /* [rows, top_n] out; may be NULL when top_n == 0 */
+} npm_logprob;
+int npm_logprob_rows(const npm_logprob *p);
+
+/* ---- logit processors: penalties, bias, bans and the minimum length, applied in place before sampling ----
+ * npm_logits_process edits the logit rows npm_sample_rows (rows = 1) or npm_verify_rows (rows = T + 1) is about to read: row (b, r)
+ * starts at logits + (b * rows + r) * pitch.  All pointers are device pointers.  Per slot b:
+ *   L = history_len[b] clipped to 0 .. history_cap (history == NULL: 0); P = prompt_len[b] clipped to 0 .. L (NULL: 0);
+ *   n = 0 with n_draft == NULL (rows must be 1), else min(n_draft[b], rows - 1).
+ * A slot with active != NULL and active[b] == 0, or with n_draft[b] < 0, is inactive: none of its logits is read or written.
+ * Rows r > n of an active slot are not touched.  For an active slot and r in 0 .. n:
+ *   S_r = history[b, 0 .. L) followed by draft[b, 0 .. r); an id outside 0 .. vocab - 1 anywhere in it is ignored;
+ *   seen_i: token i occurs in S_r; c_i: its occurrences at positions >= P of S_r (draft positions always count);
+ *   gen_r = (L - P) + r.
+ * The row's logits z change as follows, every operation rounded to fp32 on its own (no contraction; the division is IEEE):
+ *  1. Repetition: where seen_i and repetition[b] is finite, positive and != 1: z_i = z_i > 0 ? z_i / rep : z_i * rep.
+ *  2. Frequency and presence: where c_i > 0, unless frequency[b] and presence[b] are both zero:
+ *     z_i = z_i - frequency[b] * (float)c_i, then z_i = z_i - presence[b].
+ *  3. Bias: for each of the first min(bias_count[b], bias_cap) entries whose index lies in the vocabulary: z_i = z_i + bias_value.
+ *     -inf bans the token.  An index listed twice takes the entry with the smallest position only.
+ *  4. Minimum length: when 0 <= eos[b] < vocab and gen_r < min_new[b]: z_eos = -inf.
+ * Every other logit, the pitch padding and everything outside the rows are NOT WRITTEN.  NULL parameter vectors: repetition 1,
+ * presence and frequency 0, eos or min_new NULL: no rule 4.  A neutral slot (no rule applies: rep 1, both penalties 0, no bias
+ * entry, no eos rule with gen_0 < min_new) returns before its first load of a logit.
+ * Any int32 content of history, draft, bias_index and eos is legal and leads to no access outside the slot's rows and its
+ * workspace row.  workspace: int32 [batch, vocab], ALL ZERO on entry and all zero again when the call's work has finished.
+ * Hence a row's result is a pure function of the row and the slot's own history, draft and parameters; the launch is bitwise
+ * reproducible (integer atomics only); slot b of a batch is the batch-1 call on that slot; row r of a chunk is the rows = 1 call
+ * on that row with draft[b, 0 .. r) appended to the history.  Calling twice applies the rules twice.
+ * One launch, one block per slot; O(L + distinct tokens * (n + 1) + bias entries) work per slot, nothing O(vocab).
+ * NPM_E_BAD_ARGUMENT before anything is launched: p == NULL, a NULL logits or workspace, batch < 1, rows outside
+ * 1 .. NPM_VERIFY_MAX_ROWS, vocab outside 1 .. NPM_SAMPLE_MAX_VOCAB, pitch < vocab, batch * rows >= 2^31, rows > 1 without draft or
+ * n_draft or with draft_pitch < rows - 1, a history without history_len or with history_cap < 1 or history_pitch < history_cap,
+ * bias_cap outside 0 .. NPM_LOGITS_MAX_BIAS, bias_cap > 0 with a NULL bias_index, bias_value or bias_count. */
+#define NPM_LOGITS_MAX_BIAS 256
+typedef struct npm_logits {
+    float *logits; int64_t pitch;                /* edited in place */
+    int32_t batch, rows, vocab, history_cap;
+    const int32_t *history; int64_t history_pitch;   /* NULL, or [batch, history_cap] with a row pitch (NgramDrafter's layout) */
+    const int32_t *history_len;                  /* [batch] */
+    const int32_t *prompt_len;                   /* NULL = 0, or [batch] */
+    const int32_t *draft; int64_t draft_pitch;   /* as in npm_verify */
+    const int32_t *n_draft;                      /* NULL (rows == 1), or [batch]; below 0 = inactive */
+    const int32_t *active;                       /* NULL = all, or [batch]: 0 = leave the slot alone */
+    const float *repetition, *presence, *frequency;  /* [batch] each, or NULL */
+    const int32_t *eos, *min_new;                /* [batch] each, or NULL */
+    const int32_t *bias_index; const float *bias_value;  /* [batch, bias_cap] */
+    const int32_t *bias_count;                   /* [batch] */
+    int32_t bias_cap;                            /* 0 = no list */
+    int32_t *workspace;                          /* [batch, vocab], zero before and after */
+} npm_logits;
+int npm_logits_process(const npm_logits *p);
+/* One token behind every slot's history: when (active == NULL or active[b] != 0), ids[b] >= 0 and history_len[b] (clipped at 0) is
+ * below history_cap, ids[b] is written to history[b * history_pitch + history_len[b]] and history_len[b] advances -- step 4 of
+ * npm_verify_rows for a plain sampling loop.  One thread per slot.  NPM_E_BAD_ARGUMENT: batch < 1, history_cap < 1, history_pitch <
+ * history_cap, a NULL history, history_len or ids. */
+int npm_history_append(int32_t *history, int64_t history_pitch, int32_t history_cap, int32_t *history_len, const int32_t *ids,
+                       const int32_t *active, int32_t batch);
+/* What the most recent of the two launched: "logits_process_kernel B=<batch> rows=<rows> V=<vocab> history=<0|1> bias=<bias_cap>"
+ * or "history_append_kernel B=<batch> cap=<history_cap>"; "" before the first call. */
+const char *npm_last_logits_kernel(void);
 
 /* ---- around the path ("next" rows of SURVEY.md section 8f): keeps a Trainer step on the device ---- */
 /* Adam as the reference computes it (optimizer.py:53-67), operation for operation: (1 - beta1) * g and (1 - beta2) * (g * g) are

@@ -130,6 +130,35 @@ class npm_beam(C.Structure):
     ]
 
 
+class npm_logprob(C.Structure):
+    _fields_ = [
+        ('logits', C.c_void_p), ('pitch', C.c_int64),
+        ('rows', C.c_int32), ('vocab', C.c_int32), ('top_n', C.c_int32),
+        ('ids', C.c_void_p),
+        ('lse', C.c_void_p), ('chosen', C.c_void_p),
+        ('top_token', C.c_void_p), ('top_logprob', C.c_void_p),
+    ]
+
+
+class npm_logits(C.Structure):
+    _fields_ = [
+        ('logits', C.c_void_p), ('pitch', C.c_int64),
+        ('batch', C.c_int32), ('rows', C.c_int32), ('vocab', C.c_int32), ('history_cap', C.c_int32),
+        ('history', C.c_void_p), ('history_pitch', C.c_int64),
+        ('history_len', C.c_void_p),
+        ('prompt_len', C.c_void_p),
+        ('draft', C.c_void_p), ('draft_pitch', C.c_int64),
+        ('n_draft', C.c_void_p),
+        ('active', C.c_void_p),
+        ('repetition', C.c_void_p), ('presence', C.c_void_p), ('frequency', C.c_void_p),
+        ('eos', C.c_void_p), ('min_new', C.c_void_p),
+        ('bias_index', C.c_void_p), ('bias_value', C.c_void_p),
+        ('bias_count', C.c_void_p),
+        ('bias_cap', C.c_int32),
+        ('workspace', C.c_void_p),
+    ]
+
+
 class npm_comm_exchange_stats(C.Structure):
     _fields_ = [('bytes', C.c_ulonglong), ('allreduce_calls', C.c_int), ('waits', C.c_int),
                 ('allreduce_ms', C.c_double), ('exposed_ms', C.c_double), ('last_allreduce_ms', C.c_double),
@@ -223,6 +252,9 @@ SIGNATURES = {
     'npm_verify_rows': [C.POINTER(npm_verify)],
     'npm_ngram_draft': [_P, _I64, _I32, _P, _P, _I32, _I32, _I32, _I32, _P, _P],
     'npm_beam_step': [C.POINTER(npm_beam)],
+    'npm_logprob_rows': [C.POINTER(npm_logprob)],
+    'npm_logits_process': [C.POINTER(npm_logits)],
+    'npm_history_append': [_P, _I64, _I32, _P, _P, _P, _I32],
     'npm_sgemm_skinny': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_supported': [C.POINTER(npm_gemm)],
     'npm_sgemm_skinny_splits': [C.c_int, C.c_int, C.c_int],
@@ -251,6 +283,7 @@ _SPECIAL = {
     'npm_last_sample_kernel': (C.c_char_p, []),
     'npm_last_draft_kernel': (C.c_char_p, []),
     'npm_last_beam_kernel': (C.c_char_p, []),
+    'npm_last_logits_kernel': (C.c_char_p, []),
 }
 
 COMM_SIGNATURES = {
@@ -532,6 +565,14 @@ def beam_workspace_bytes(groups: int, width: int) -> int:
 def last_beam_kernel() -> str:
     """What the most recent npm_beam_step launched (include/npm_hip.h npm_last_beam_kernel)."""
     return lib().npm_last_beam_kernel().decode()
+
+
+LOGITS_MAX_BIAS, LOGPROB_MAX_TOP = 256, 64             # include/npm_hip.h NPM_LOGITS_MAX_BIAS; npm_logprob top_n
+
+
+def last_logits_kernel() -> str:
+    """What the most recent npm_logits_process or npm_history_append launched (include/npm_hip.h npm_last_logits_kernel)."""
+    return lib().npm_last_logits_kernel().decode()
 
 
 def comm_lib():

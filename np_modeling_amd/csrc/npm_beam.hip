@@ -41,21 +41,37 @@ __device__ __forceinline__ bool row_before(unsigned key_i, int i, unsigned key_j
     return key_i > key_j || (key_i == key_j && i < j);
 }
 
-template <bool VEC>
+// A row that gives nothing.  The beam: an empty list.  LOGPROB: lse and chosen NaN, the top lists -1 / -inf.
+template <bool LOGPROB>
+__device__ __forceinline__ void empty_row(int r, int cands, float *__restrict__ lse, int *__restrict__ ws_count,
+                                          float *__restrict__ ws_score, int *__restrict__ ws_token, float *__restrict__ chosen) {
+    if (threadIdx.x == 0) {
+        if (!LOGPROB) ws_count[r] = 0;
+        lse[r] = __uint_as_float(0x7FC00000u);
+        if (LOGPROB && chosen != nullptr) chosen[r] = __uint_as_float(0x7FC00000u);
+    }
+    if (LOGPROB && (int)threadIdx.x < cands) {
+        ws_score[(long)r * cands + threadIdx.x] = -INFINITY;
+        ws_token[(long)r * cands + threadIdx.x] = -1;
+    }
+}
+
+// LOGPROB (npm_logprob_rows): cum is 0 for every row, a row is skipped when ids[r] < 0, the list goes to the caller's top_logprob /
+// top_token [rows, cands] (padded with -inf / -1, cands may be 0) and chosen[r] is the score of token ids[r].
+template <bool VEC, bool LOGPROB>
 __global__ void __launch_bounds__(NT)
 beam_rows_kernel(const float *__restrict__ logits, long pitch, int vocab, int cands, const float *__restrict__ cum,
-                 float *__restrict__ lse, int *__restrict__ ws_count, float *__restrict__ ws_score, int *__restrict__ ws_token) {
+                 float *__restrict__ lse, int *__restrict__ ws_count, float *__restrict__ ws_score, int *__restrict__ ws_token,
+                 const int *__restrict__ ids, float *__restrict__ chosen) {
     __shared__ float row[LDS_ROW];
     __shared__ Shared sh;
     __shared__ Survivors sv;
     const int r = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const float c = cum[r];
-    if (!(c > -INFINITY)) {                            // dead (-inf or NaN): before any logit is loaded
-        if (threadIdx.x == 0) {
-            ws_count[r] = 0;
-            lse[r] = __uint_as_float(0x7FC00000u);
-        }
+    const float c = LOGPROB ? 0.f : cum[r];
+    const int id = (LOGPROB && ids != nullptr) ? ids[r] : 0;
+    if (LOGPROB ? id < 0 : !(c > -INFINITY)) {         // dead (-inf or NaN), or skipped: before any logit is loaded
+        empty_row<LOGPROB>(r, cands, lse, ws_count, ws_score, ws_token, chosen);
         return;
     }
     const float *__restrict__ g = logits + (long)r * pitch;
@@ -95,10 +111,7 @@ beam_rows_kernel(const float *__restrict__ logits, long pitch, int vocab, int ca
         finite += sh.red_cnt[w];
     }
     if (bad != 0 || finite == 0) {                     // invalid: contributes nothing
-        if (threadIdx.x == 0) {
-            ws_count[r] = 0;
-            lse[r] = __uint_as_float(0x7FC00000u);
-        }
+        empty_row<LOGPROB>(r, cands, lse, ws_count, ws_score, ws_token, chosen);
         return;
     }
     zmax += 0.f;                                       // a maximum of -0.0 enters the arithmetic as 0.0, whichever zero came first
@@ -106,7 +119,7 @@ beam_rows_kernel(const float *__restrict__ logits, long pitch, int vocab, int ca
     // ---- the cut: {key > t1} and the q1 lowest indices of {key == t1} ----
     const unsigned k_eff = (unsigned)cands < finite ? (unsigned)cands : finite;
     unsigned t1 = NEG_INF_KEY, q1 = 0, above = finite;
-    if (k_eff < finite) {
+    if (k_eff > 0 && k_eff < finite) {                 // k_eff == 0: npm_logprob_rows with top_n == 0
         u64 unused_m, rest;
         t1 = radix_select<VEC, false>(sh, g, row, in_lds, vocab, NEG_INF_KEY, 0, 0, zmax, 1.f, k_eff, unused_m, above, rest);
         q1 = (unsigned)rest;
@@ -125,7 +138,7 @@ beam_rows_kernel(const float *__restrict__ logits, long pitch, int vocab, int ca
     const int seg = ((vocab + NW - 1) / NW + 63) / 64 * 64;
     const int begin = wave * seg, end = begin + seg < vocab ? begin + seg : vocab;
     unsigned seg_eq = 0;
-    for (int i = begin + lane; i < end; i += 64) {
+    for (int i = begin + lane; i < end && k_eff > 0; i += 64) {
         const float z = in_lds ? row[i] : g[i];
         const unsigned key = order_key(z);
         if (key > t1) {
@@ -164,10 +177,21 @@ beam_rows_kernel(const float *__restrict__ logits, long pitch, int vocab, int ca
     // ---- one wavefront: rank by (key, index), score in fp64 with one rounding, the list to the workspace ----
     if (wave != 0) return;
     if (lane == 0) {
-        ws_count[r] = (int)k_eff;
+        if (!LOGPROB) ws_count[r] = (int)k_eff;
         lse[r] = (float)((double)zmax + n);
+        if (LOGPROB && chosen != nullptr) {
+            float s_id = __uint_as_float(0x7FC00000u);
+            if (id < vocab) s_id = (float)((((double)c - (double)zmax) - n) + (double)(in_lds ? row[id] : g[id]));
+            chosen[r] = s_id;
+        }
     }
-    if ((unsigned)lane >= k_eff) return;
+    if ((unsigned)lane >= k_eff) {
+        if (LOGPROB && lane < cands) {
+            ws_score[(long)r * cands + lane] = -INFINITY;
+            ws_token[(long)r * cands + lane] = -1;
+        }
+        return;
+    }
     const float z = sv.z[lane];
     const int idx = sv.idx[lane];
     const unsigned key = order_key(z);
@@ -274,15 +298,38 @@ extern "C" int npm_beam_step(const npm_beam *s) {
     int *ws_token = (int *)(ws_score + (long)rows * cands);
     hipStream_t stream = npm::ctx().stream;
     if (vec)
-        hipLaunchKernelGGL(beam_rows_kernel<true>, dim3(rows), dim3(NT), 0, stream, s->logits, (long)s->pitch, (int)s->vocab, cands,
-                           (const float *)s->cum, s->lse, ws_count, ws_score, ws_token);
+        hipLaunchKernelGGL((beam_rows_kernel<true, false>), dim3(rows), dim3(NT), 0, stream, s->logits, (long)s->pitch, (int)s->vocab,
+                           cands, (const float *)s->cum, s->lse, ws_count, ws_score, ws_token, (const int *)nullptr, (float *)nullptr);
     else
-        hipLaunchKernelGGL(beam_rows_kernel<false>, dim3(rows), dim3(NT), 0, stream, s->logits, (long)s->pitch, (int)s->vocab, cands,
-                           (const float *)s->cum, s->lse, ws_count, ws_score, ws_token);
+        hipLaunchKernelGGL((beam_rows_kernel<false, false>), dim3(rows), dim3(NT), 0, stream, s->logits, (long)s->pitch, (int)s->vocab,
+                           cands, (const float *)s->cum, s->lse, ws_count, ws_score, ws_token, (const int *)nullptr, (float *)nullptr);
     NPM_CHECK_LAUNCH();
     hipLaunchKernelGGL(beam_merge_kernel, dim3(s->groups), dim3(NT), 0, stream, (int)s->width, (int)s->eos, (const int *)ws_count,
                        (const float *)ws_score, (const int *)ws_token, s->cum, s->cand_slot, s->cand_token, s->cand_score, s->parent,
                        s->ids);
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
+}
+
+extern "C" int npm_logprob_rows(const npm_logprob *p) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(p != nullptr);
+    NPM_ARG(p->rows >= 1 && p->vocab >= 1 && p->vocab <= NPM_SAMPLE_MAX_VOCAB && p->pitch >= p->vocab);
+    NPM_ARG(p->top_n >= 0 && p->top_n <= MAXC);
+    NPM_ARG(p->logits != nullptr && p->lse != nullptr);
+    NPM_ARG(p->ids == nullptr || p->chosen != nullptr);
+    NPM_ARG(p->top_n == 0 || (p->top_token != nullptr && p->top_logprob != nullptr));
+    const bool vec = aligned16(p->logits) && p->pitch % 4 == 0;
+    snprintf(g_last_beam_kernel, sizeof(g_last_beam_kernel), "logprob_rows_kernel %s R=%d V=%d top=%d row=%s", vec ? "vec" : "scalar",
+             (int)p->rows, (int)p->vocab, (int)p->top_n, p->vocab <= NPM_SAMPLE_LDS_ROW ? "lds" : "global");
+    hipStream_t stream = npm::ctx().stream;
+    float *chosen = p->ids != nullptr ? p->chosen : nullptr;
+    if (vec)
+        hipLaunchKernelGGL((beam_rows_kernel<true, true>), dim3(p->rows), dim3(NT), 0, stream, p->logits, (long)p->pitch, (int)p->vocab,
+                           (int)p->top_n, (const float *)nullptr, p->lse, (int *)nullptr, p->top_logprob, p->top_token, p->ids, chosen);
+    else
+        hipLaunchKernelGGL((beam_rows_kernel<false, true>), dim3(p->rows), dim3(NT), 0, stream, p->logits, (long)p->pitch, (int)p->vocab,
+                           (int)p->top_n, (const float *)nullptr, p->lse, (int *)nullptr, p->top_logprob, p->top_token, p->ids, chosen);
     NPM_CHECK_LAUNCH();
     return NPM_OK;
 }

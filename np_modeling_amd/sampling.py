@@ -17,6 +17,18 @@ Speculative decoding (include/npm_hip.h npm_verify_rows, npm_ngram_draft; ``spec
 occurrence of the last few; ``Sampler.verify`` samples the T + 1 logit rows the model returned for them, row r at counter
 ``draw + r``, and accepts drafted tokens while they are the tokens sampled.  The tokens emitted are those of the one-token loop
 from the same logits, seed for seed and counter for counter: a draft changes when tokens appear, never which.
+
+Logit processors (include/npm_hip.h npm_logits_process, npm_history_append, npm_logprob_rows): ``LogitProcessor`` applies, per slot,
+repetition / presence / frequency penalties over the slot's ``TokenHistory``, a bias list (-inf bans a token) and the minimum
+length before end-of-sequence, IN PLACE on the logits a sampler is about to read -- the few logits those name, one launch,
+nothing copied to the host; ``logprobs`` returns the log-sum-exp of every row, the log-probability of chosen tokens and the top n.
+
+    history = sampling.TokenHistory(batch, capacity)                       # or the NgramDrafter of a speculative loop
+    proc = sampling.LogitProcessor(batch, vocab, max_bias=8)
+    proc.set(b, repetition_penalty=1.2, logit_bias={13: -math.inf}, eos=2, min_new_tokens=16, prompt_length=len(prompt_b))
+    history.admit(b, prompt_b)
+    result = sampler(proc(logits, history))                                # logits are edited in place: calling twice applies twice
+    history.append(result)
 """
 
 from __future__ import annotations
@@ -237,7 +249,92 @@ class Sampler:
         return result
 
 
-class NgramDrafter:
+class TokenHistory:
+    """The tokens of every slot so far on the device, int32 [batch, capacity], with a host mirror ``lengths`` of how many each slot
+    holds: what ``LogitProcessor`` reads its penalties from and ``NgramDrafter`` its drafts.  ``admit`` starts a slot over,
+    ``append`` puts one sampled token behind every slot's history on the device (npm_history_append)."""
+
+    def __init__(self, batch: int, capacity: int):
+        if int(batch) < 1 or int(capacity) < 1:
+            raise ValueError(f'{type(self).__name__}: batch and capacity must be at least 1, got {batch!r}, {capacity!r}')
+        self.batch, self.capacity = int(batch), int(capacity)
+        self.lengths = np.zeros([self.batch], dtype=np.int64)
+        self._history = D.IdBuffer([self.batch, self.capacity])
+        self._lengths = D.ids_from_host(np.zeros([self.batch], dtype=np.int32))
+        self._ahead = None                # NgramDrafter: a proposal launched ahead; anything that changes a history drops it
+
+    def _slot(self, b, what: str) -> int:
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 0 <= b < self.batch:
+            raise ValueError(f'{type(self).__name__}.{what}: slot must be an integer in 0 .. {self.batch - 1}, got {b!r}')
+        return int(b)
+
+    def _set_length(self, b: int, n: int) -> None:
+        host = np.array([n], dtype=np.int32)
+        _C.check(_C.lib().npm_h2d(self._lengths.ptr + 4 * b, host.ctypes.data, 4), 'npm_h2d')
+        self.lengths[b] = n
+        self._ahead = None
+
+    def admit(self, b: int, ids) -> None:
+        """Slot ``b`` starts over with the tokens ``ids`` (1-D, 0 .. 2^31 - 1 each, at most ``capacity``): a sequence's prompt
+        and whatever it has emitted already.  ValueError before anything changes."""
+        name = type(self).__name__
+        b = self._slot(b, 'admit')
+        host = np.asarray(ids)
+        if host.ndim != 1 or host.dtype == np.bool_ or not (np.issubdtype(host.dtype, np.integer) or host.size == 0):
+            raise ValueError(f'{name}.admit: ids must be a 1-D integer array, got {host.dtype} {host.shape}')
+        if host.size > self.capacity or (host.size and (host.min() < 0 or host.max() >= 2 ** 31)):
+            raise ValueError(f'{name}.admit: at most {self.capacity} token ids in 0 .. 2^31 - 1, got {host.size} in '
+                             f'{int(host.min()) if host.size else 0} .. {int(host.max()) if host.size else 0}')
+        host = np.ascontiguousarray(host.astype(np.int32))
+        if host.size:
+            _C.check(_C.lib().npm_h2d(self._history.ptr + 4 * b * self.capacity, host.ctypes.data, host.nbytes), 'npm_h2d')
+        self._set_length(b, host.size)
+
+    def release(self, b: int) -> None:
+        """Slot ``b`` holds no tokens until the next ``admit``."""
+        self._set_length(self._slot(b, 'release'), 0)
+
+    def append(self, result_or_ids, active=None) -> None:
+        """The token every slot just sampled goes behind its history, on the device: ``result_or_ids`` a ``SampleResult`` (its
+        cached ``numpy()``, which the loop fetches anyway, advances the host mirror) or an ``IdBuffer`` [batch] (one copy of 4 bytes
+        per slot).  A token below 0 (an inactive or invalid row) and a slot with ``active[b] <= 0`` append nothing.  ValueError
+        before the launch when a token does not fit the capacity."""
+        name = type(self).__name__
+        if isinstance(result_or_ids, SampleResult):
+            ids, host = result_or_ids.ids, result_or_ids.numpy()
+        elif isinstance(result_or_ids, D.IdBuffer):
+            ids, host = result_or_ids, None
+        else:
+            raise ValueError(f'{name}.append: a SampleResult or an IdBuffer is required, got {type(result_or_ids).__name__}')
+        if ids.size != self.batch:
+            raise ValueError(f'{name}.append: {self.batch} token ids are required, got shape {ids.shape}')
+        mask = None
+        if active is not None:
+            a = np.asarray(active)
+            if a.shape != (self.batch,) or not (np.issubdtype(a.dtype, np.integer) or a.dtype == np.bool_):
+                raise ValueError(f'{name}.append: active must be {self.batch} integers, got {np.asarray(active).tolist()!r}')
+            mask = a > 0
+        if host is None:
+            host = ids.numpy()
+        grows = (host.reshape(-1) >= 0) if mask is None else ((host.reshape(-1) >= 0) & mask)
+        if (self.lengths + grows > self.capacity).any():
+            raise ValueError(f'{name}.append: one more token after {self.lengths.tolist()} does not fit the capacity {self.capacity}')
+        active_dev = None if mask is None else D.ids_from_host(mask.astype(np.int32))
+        self._ahead = None                                                   # the histories are about to change
+        _C.check(_C.lib().npm_history_append(self._history.ptr, self.capacity, self.capacity, self._lengths.ptr, ids.ptr,
+                                             None if active_dev is None else active_dev.ptr, self.batch), 'npm_history_append')
+        self.lengths += grows
+
+    def device_lengths(self) -> np.ndarray:
+        """The history lengths as the device holds them, int64 [batch] (equal to ``lengths`` at any time)."""
+        return self._lengths.numpy().astype(np.int64)
+
+    def numpy(self) -> np.ndarray:
+        """The histories on the host, int32 [batch, capacity]; slot b's first ``lengths[b]`` entries are its tokens."""
+        return self._history.numpy()
+
+
+class NgramDrafter(TokenHistory):
     """Drafts by prompt lookup (include/npm_hip.h npm_ngram_draft): the tokens of every slot so far live on the device, int32
     [batch, capacity], with a host mirror ``lengths`` of how many each slot holds.  ``propose`` returns, per slot, its last token
     followed by up to ``max_draft`` tokens that followed the most recent earlier occurrence of its last n tokens, n from
@@ -252,41 +349,9 @@ class NgramDrafter:
         nmax, nmin = (int(v) for v in ngram)
         if not 1 <= nmin <= nmax <= _C.DRAFT_MAX_NGRAM:
             raise ValueError(f'NgramDrafter: ngram is (nmax, nmin) with 1 <= nmin <= nmax <= {_C.DRAFT_MAX_NGRAM}, got {ngram!r}')
-        self.batch, self.capacity, self.max_draft, self.ngram = int(batch), int(capacity), int(max_draft), (nmax, nmin)
-        self.lengths = np.zeros([self.batch], dtype=np.int64)
-        self._history = D.IdBuffer([self.batch, self.capacity])
-        self._lengths = D.ids_from_host(np.zeros([self.batch], dtype=np.int32))
+        TokenHistory.__init__(self, batch, capacity)
+        self.max_draft, self.ngram = int(max_draft), (nmax, nmin)
         self._ahead = None                # [limits, chunk, n_new] of a proposal launched ahead; n_new None until it reached the host
-
-    def _slot(self, b, what: str) -> int:
-        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 0 <= b < self.batch:
-            raise ValueError(f'NgramDrafter.{what}: slot must be an integer in 0 .. {self.batch - 1}, got {b!r}')
-        return int(b)
-
-    def _set_length(self, b: int, n: int) -> None:
-        host = np.array([n], dtype=np.int32)
-        _C.check(_C.lib().npm_h2d(self._lengths.ptr + 4 * b, host.ctypes.data, 4), 'npm_h2d')
-        self.lengths[b] = n
-        self._ahead = None
-
-    def admit(self, b: int, ids) -> None:
-        """Slot ``b`` starts over with the tokens ``ids`` (1-D, 0 .. 2^31 - 1 each, at most ``capacity``): a sequence's prompt
-        and whatever it has emitted already.  ValueError before anything changes."""
-        b = self._slot(b, 'admit')
-        host = np.asarray(ids)
-        if host.ndim != 1 or host.dtype == np.bool_ or not (np.issubdtype(host.dtype, np.integer) or host.size == 0):
-            raise ValueError(f'NgramDrafter.admit: ids must be a 1-D integer array, got {host.dtype} {host.shape}')
-        if host.size > self.capacity or (host.size and (host.min() < 0 or host.max() >= 2 ** 31)):
-            raise ValueError(f'NgramDrafter.admit: at most {self.capacity} token ids in 0 .. 2^31 - 1, got {host.size} in '
-                             f'{int(host.min()) if host.size else 0} .. {int(host.max()) if host.size else 0}')
-        host = np.ascontiguousarray(host.astype(np.int32))
-        if host.size:
-            _C.check(_C.lib().npm_h2d(self._history.ptr + 4 * b * self.capacity, host.ctypes.data, host.nbytes), 'npm_h2d')
-        self._set_length(b, host.size)
-
-    def release(self, b: int) -> None:
-        """Slot ``b`` holds no tokens: ``propose`` leaves it alone until the next ``admit``."""
-        self._set_length(self._slot(b, 'release'), 0)
 
     def propose(self, limit=None):
         """(chunk, n_new): ``chunk`` an ``IdBuffer`` [batch, max_draft + 1] -- slot b's last token, then its draft, then -1 -- and
@@ -330,10 +395,236 @@ class NgramDrafter:
         if self._ahead is not None:
             self._ahead[2] = np.asarray(n_new).astype(np.int64)
 
-    def device_lengths(self) -> np.ndarray:
-        """The history lengths as the device holds them, int64 [batch] (equal to ``lengths`` at any time)."""
-        return self._lengths.numpy().astype(np.int64)
 
-    def numpy(self) -> np.ndarray:
-        """The histories on the host, int32 [batch, capacity]; slot b's first ``lengths[b]`` entries are its tokens."""
-        return self._history.numpy()
+def _is_real(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def _is_int32(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer)) and -2 ** 31 <= v < 2 ** 31
+
+
+class LogitProcessor:
+    """Per-slot logit processors applied on the device, in place, before sampling (include/npm_hip.h npm_logits_process).
+
+    ``set(b, ...)`` gives slot b its rules; a slot that was never ``set`` is neutral.  ``proc(logits, history)`` edits the [B, V]
+    logits of a one-token step, ``proc(logits, history, draft=, n_draft=, draft_pitch=)`` the [B (T + 1), V] logits of a
+    speculative chunk -- row r as if ``draft[b, :r]`` had been appended to the history, which is what the one-token loop would
+    hold when it samples that token.  It returns ``logits`` (the same array).  Calling it twice on the same logits applies the
+    rules twice.  Only the logits that the history, the draft, the bias list and eos name are touched; one launch, no copy to the
+    host; while every slot is neutral nothing is launched at all."""
+
+    def __init__(self, batch: int, vocab: int, max_bias: int = 0):
+        if int(batch) < 1 or not 1 <= int(vocab) <= _C.SAMPLE_MAX_VOCAB:
+            raise ValueError(f'LogitProcessor: batch >= 1 and a vocabulary of 1 .. {_C.SAMPLE_MAX_VOCAB}, got {batch!r}, {vocab!r}')
+        if not 0 <= int(max_bias) <= _C.LOGITS_MAX_BIAS:
+            raise ValueError(f'LogitProcessor: max_bias must be 0 .. {_C.LOGITS_MAX_BIAS}, got {max_bias!r}')
+        self.batch, self.vocab, self.max_bias = int(batch), int(vocab), int(max_bias)
+        b, m = self.batch, self.max_bias
+        self.repetition = np.ones([b], dtype=np.float32)
+        self.presence = np.zeros([b], dtype=np.float32)
+        self.frequency = np.zeros([b], dtype=np.float32)
+        self.eos = np.full([b], -1, dtype=np.int32)
+        self.min_new = np.zeros([b], dtype=np.int32)
+        self.prompt_len = np.zeros([b], dtype=np.int32)
+        self.bias_count = np.zeros([b], dtype=np.int32)
+        self.bias_index = np.full([b, m], -1, dtype=np.int32)
+        self.bias_value = np.zeros([b, m], dtype=np.float32)
+        self._device: Optional[D.ByteBuffer] = None                          # the nine arrays back to back
+        self._stale = True
+        self._workspace = D.IdBuffer([b, self.vocab])                        # all zero between calls
+        _C.check(_C.lib().npm_fill_f32(self._workspace.ptr, 0.0, b * self.vocab), 'npm_fill_f32')
+
+    def set(self, b: int, repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+            logit_bias=None, eos: Optional[int] = None, min_new_tokens: int = 0, prompt_length: int = 0) -> None:
+        """The rules of slot ``b``.  ``repetition_penalty`` finite and > 0 (1: off); ``presence_penalty`` and
+        ``frequency_penalty`` finite (0: off) -- they count the tokens behind the first ``prompt_length`` of the history, the
+        repetition penalty counts all of it; ``logit_bias`` a mapping or pairs of distinct token ids in 0 .. vocab - 1 to a finite
+        number or -inf (a ban), at most ``max_bias``; ``eos`` (None: no rule) gets -inf while fewer than ``min_new_tokens``
+        tokens stand behind the prompt.  ValueError before anything changes."""
+        if isinstance(b, bool) or not isinstance(b, (int, np.integer)) or not 0 <= b < self.batch:
+            raise ValueError(f'LogitProcessor.set: slot must be an integer in 0 .. {self.batch - 1}, got {b!r}')
+        with np.errstate(over='ignore'):                                     # a value that overflows fp32 is refused, not warned about
+            pairs = self._check(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, eos, min_new_tokens, prompt_length)
+        self.repetition[b], self.presence[b], self.frequency[b] = repetition_penalty, presence_penalty, frequency_penalty
+        self.eos[b], self.min_new[b], self.prompt_len[b] = -1 if eos is None else eos, min_new_tokens, prompt_length
+        self.bias_count[b] = len(pairs)
+        self.bias_index[b], self.bias_value[b] = -1, 0
+        for j, (k, v) in enumerate(pairs):
+            self.bias_index[b, j], self.bias_value[b, j] = k, v
+        self._stale = True
+
+    def _check(self, repetition_penalty, presence_penalty, frequency_penalty, logit_bias, eos, min_new_tokens, prompt_length) -> list:
+        """ValueError for anything ``set`` refuses; the bias list as pairs."""
+        if not _is_real(repetition_penalty) or not (math.isfinite(repetition_penalty) and np.float32(repetition_penalty) > 0
+                                                    and math.isfinite(np.float32(repetition_penalty))):
+            raise ValueError(f'LogitProcessor.set: repetition_penalty must be a finite number > 0, got {repetition_penalty!r}')
+        for name, v in (('presence_penalty', presence_penalty), ('frequency_penalty', frequency_penalty)):
+            if not _is_real(v) or not math.isfinite(v) or not math.isfinite(np.float32(v)):
+                raise ValueError(f'LogitProcessor.set: {name} must be a finite number, got {v!r}')
+        for name, v in (('min_new_tokens', min_new_tokens), ('prompt_length', prompt_length)) + ((('eos', eos),) if eos is not None else ()):
+            if not _is_int32(v):
+                raise ValueError(f'LogitProcessor.set: {name} must be an int32 integer, got {v!r}')
+        try:
+            pairs = [] if logit_bias is None else [(k, v) for k, v in (logit_bias.items() if hasattr(logit_bias, 'items') else logit_bias)]
+        except (TypeError, ValueError):
+            raise ValueError(f'LogitProcessor.set: logit_bias must be a mapping or pairs (token id, value), got {logit_bias!r}') from None
+        if len(pairs) > self.max_bias:
+            raise ValueError(f'LogitProcessor.set: at most max_bias = {self.max_bias} bias entries, got {len(pairs)}')
+        for k, v in pairs:
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < self.vocab:
+                raise ValueError(f'LogitProcessor.set: a bias token id must be an integer in 0 .. {self.vocab - 1}, got {k!r}')
+            if not _is_real(v) or math.isnan(v) or v == math.inf or np.float32(v) == np.inf:
+                raise ValueError(f'LogitProcessor.set: a bias value must be a finite number or -inf, got {v!r}')
+        if len({int(k) for k, _ in pairs}) != len(pairs):
+            raise ValueError(f'LogitProcessor.set: a token id occurs twice in logit_bias: {[int(k) for k, _ in pairs]}')
+        return pairs
+
+    def neutral(self) -> bool:
+        """Whether no rule of any slot can change a logit, whatever the histories hold."""
+        return bool(((self.repetition == 1) & (self.presence == 0) & (self.frequency == 0) & (self.bias_count == 0)
+                     & ((self.eos < 0) | (self.eos >= self.vocab) | (self.min_new <= 0))).all())
+
+    def _pointers(self) -> dict:
+        """Device addresses of the per-slot arrays; one upload after a ``set``."""
+        arrays = [('repetition', self.repetition), ('presence', self.presence), ('frequency', self.frequency), ('eos', self.eos),
+                  ('min_new', self.min_new), ('prompt_len', self.prompt_len), ('bias_count', self.bias_count),
+                  ('bias_index', self.bias_index), ('bias_value', self.bias_value)]
+        if self._stale or self._device is None:
+            host = np.concatenate([a.reshape(-1).view(np.uint8) for _, a in arrays])
+            if self._device is None:
+                self._device = D.ByteBuffer(host.nbytes)
+            _C.check(_C.lib().npm_h2d(self._device.ptr, host.ctypes.data, host.nbytes), 'npm_h2d')
+            self._stale = False
+        out, at = {}, self._device.ptr
+        for name, a in arrays:
+            out[name] = at
+            at += a.nbytes
+        if self.max_bias == 0:
+            out['bias_index'] = out['bias_value'] = out['bias_count'] = None
+        return out
+
+    def __call__(self, logits, history: Optional[TokenHistory] = None, active=None, draft=None, n_draft=None,
+                 draft_pitch: Optional[int] = None):
+        """``logits`` [B, V], or with ``draft`` / ``n_draft`` (what ``Sampler.verify`` takes: [B, >= T] integers or an ``IdBuffer``
+        with an optional ``draft_pitch``; [B] integers or an ``IdBuffer``, below 0 for a slot left alone) [B (T + 1), V] with slot
+        b's rows together.  ``history``: the ``TokenHistory`` (or ``NgramDrafter``) of the batch, None for empty histories;
+        ``active``: [B] integers, a slot with ``active[b] <= 0`` is left alone.  ValueError before anything is launched."""
+        if not isinstance(logits, D.DeviceArray) or logits.ndim != 2 or logits.shape[0] % self.batch or logits.shape[0] == 0 \
+                or logits.shape[1] != self.vocab:
+            raise ValueError(f'LogitProcessor: logits must be a DeviceArray of shape [{self.batch} * rows, {self.vocab}], got '
+                             f'{getattr(logits, "shape", type(logits).__name__)}')
+        rows = logits.shape[0] // self.batch
+        if rows > _C.VERIFY_MAX_ROWS:
+            raise ValueError(f'LogitProcessor: at most {_C.VERIFY_MAX_ROWS} rows per slot, got {rows}')
+        if history is not None and (not isinstance(history, TokenHistory) or history.batch != self.batch):
+            raise ValueError(f'LogitProcessor: history must be a TokenHistory of batch {self.batch}')
+        if (draft is None or n_draft is None) and rows != 1:
+            raise ValueError(f'LogitProcessor: {rows} rows per slot need draft and n_draft')
+        mask = None
+        if active is not None:
+            a = np.asarray(active)
+            if a.shape != (self.batch,) or not (np.issubdtype(a.dtype, np.integer) or a.dtype == np.bool_):
+                raise ValueError(f'LogitProcessor: active must be {self.batch} integers, got {np.asarray(active).tolist()!r}')
+            mask = a > 0
+        n_host = None
+        if n_draft is not None and not isinstance(n_draft, D.IdBuffer):
+            n_host = np.asarray(n_draft)
+            if n_host.shape != (self.batch,) or not np.issubdtype(n_host.dtype, np.integer) or (n_host >= rows).any():
+                raise ValueError(f'LogitProcessor: n_draft must be {self.batch} integers below {rows}, got {n_host.tolist()!r}')
+            n_host = np.maximum(n_host.astype(np.int64), -1)
+        elif n_draft is not None and n_draft.size != self.batch:
+            raise ValueError(f'LogitProcessor: n_draft must hold {self.batch} integers, got shape {n_draft.shape}')
+        draft_dev = None
+        if draft is not None:
+            if not isinstance(draft, D.IdBuffer):
+                host = np.asarray(draft)
+                if host.dtype == np.bool_ or not np.issubdtype(host.dtype, np.integer) or (host.size and (host.min() < -2 ** 31
+                                                                                                          or host.max() >= 2 ** 31)):
+                    raise ValueError(f'LogitProcessor: draft must be int32 integers, got dtype {host.dtype}')
+            shape = draft.shape if isinstance(draft, D.IdBuffer) else np.asarray(draft).shape
+            if draft_pitch is None:
+                if len(shape) != 2 or shape[0] != self.batch:
+                    raise ValueError(f'LogitProcessor: draft must be [{self.batch}, >= {rows - 1}] integers, got {tuple(shape)}')
+                draft_pitch = shape[1]
+            if draft_pitch < rows - 1:
+                raise ValueError(f'LogitProcessor: the draft holds fewer than {rows - 1} tokens per slot (pitch {draft_pitch})')
+        if self.neutral():
+            return logits                                                    # nothing can change: nothing is launched
+        if draft is not None and rows > 1:
+            draft_dev = D.as_ids(draft)
+        n_dev = None if n_draft is None else (n_draft if isinstance(n_draft, D.IdBuffer) else D.ids_from_host(n_host))
+        active_dev = None if mask is None else D.ids_from_host(mask.astype(np.int32))
+        p = self._pointers()
+        desc = _C.npm_logits(logits=logits.ptr, pitch=self.vocab, batch=self.batch, rows=rows, vocab=self.vocab,
+                             history_cap=0 if history is None else history.capacity,
+                             history=None if history is None else history._history.ptr,
+                             history_pitch=0 if history is None else history.capacity,
+                             history_len=None if history is None else history._lengths.ptr, prompt_len=p['prompt_len'],
+                             draft=None if draft_dev is None else draft_dev.ptr, draft_pitch=0 if draft_dev is None else draft_pitch,
+                             n_draft=None if n_dev is None else n_dev.ptr, active=None if active_dev is None else active_dev.ptr,
+                             repetition=p['repetition'], presence=p['presence'], frequency=p['frequency'], eos=p['eos'],
+                             min_new=p['min_new'], bias_index=p['bias_index'], bias_value=p['bias_value'], bias_count=p['bias_count'],
+                             bias_cap=self.max_bias, workspace=self._workspace.ptr)
+        _C.check(_C.lib().npm_logits_process(C.byref(desc)), 'npm_logits_process')
+        return logits
+
+
+class LogProbs:
+    """What ``logprobs`` produced for R logit rows.  ``lse``: float32 [R], the log-sum-exp (NaN for a skipped or invalid row);
+    ``chosen``: float32 [R], the log-probability of ``ids[r]`` (None without ``ids``); ``top_tokens`` int32 and ``top_logprobs``
+    float32 [R, top_n]: the most probable tokens in the sampler's order, -1 / -inf behind the last that exists.  The host copies
+    are made on first use, one copy for all four."""
+
+    def __init__(self, out: D.ByteBuffer, rows: int, top_n: int, with_ids: bool):
+        self._out, self._rows, self._top, self._with_ids, self._host = out, rows, top_n, with_ids, None
+
+    def _fetch(self) -> np.ndarray:
+        if self._host is None:
+            self._host = self._out.numpy().view(np.uint32)
+        return self._host
+
+    @property
+    def lse(self) -> np.ndarray:
+        return self._fetch()[:self._rows].view(np.float32).copy()
+
+    @property
+    def chosen(self) -> Optional[np.ndarray]:
+        return self._fetch()[self._rows:2 * self._rows].view(np.float32).copy() if self._with_ids else None
+
+    @property
+    def top_tokens(self) -> np.ndarray:
+        n = self._rows * self._top
+        return self._fetch()[2 * self._rows:2 * self._rows + n].view(np.int32).reshape(self._rows, self._top).copy()
+
+    @property
+    def top_logprobs(self) -> np.ndarray:
+        n = self._rows * self._top
+        return self._fetch()[2 * self._rows + n:2 * self._rows + 2 * n].view(np.float32).reshape(self._rows, self._top).copy()
+
+
+def logprobs(logits, ids=None, top_n: int = 0) -> LogProbs:
+    """Log-probabilities of the rows of ``logits`` [R, V] in one launch (include/npm_hip.h npm_logprob_rows): the normaliser is the
+    sampler's integer mass at temperature 1, so the call is bitwise reproducible.  ``ids``: [R] integers or an ``IdBuffer`` of R
+    entries (``result.ids`` of a ``Sampler`` call, a ``VerifyResult``'s); a row with ``ids[r] < 0`` is not read.  ``top_n``:
+    0 .. 64 most probable tokens per row.  Apply a ``LogitProcessor`` first for the log-probabilities the sampler saw."""
+    if not isinstance(logits, D.DeviceArray) or logits.ndim != 2 or logits.shape[0] < 1:
+        raise ValueError(f'logprobs: logits must be a DeviceArray of shape [R, V], got {getattr(logits, "shape", type(logits).__name__)}')
+    rows, vocab = logits.shape
+    if not 1 <= vocab <= _C.SAMPLE_MAX_VOCAB:
+        raise ValueError(f'logprobs: the vocabulary must be 1 .. {_C.SAMPLE_MAX_VOCAB}, got {vocab}')
+    if isinstance(top_n, bool) or not isinstance(top_n, (int, np.integer)) or not 0 <= top_n <= _C.LOGPROB_MAX_TOP:
+        raise ValueError(f'logprobs: top_n must be an integer in 0 .. {_C.LOGPROB_MAX_TOP}, got {top_n!r}')
+    ids_dev = None
+    if ids is not None:
+        ids_dev = D.as_ids(ids)
+        if ids_dev.size != rows:
+            raise ValueError(f'logprobs: ids must hold {rows} integers, got shape {ids_dev.shape}')
+    top_n = int(top_n)
+    out = D.ByteBuffer(4 * (2 * rows + 2 * rows * top_n))
+    desc = _C.npm_logprob(logits=logits.ptr, pitch=vocab, rows=rows, vocab=vocab, top_n=top_n,
+                          ids=None if ids_dev is None else ids_dev.ptr, lse=out.ptr, chosen=out.ptr + 4 * rows,
+                          top_token=out.ptr + 8 * rows if top_n else None,
+                          top_logprob=out.ptr + 4 * (2 * rows + rows * top_n) if top_n else None)
+    _C.check(_C.lib().npm_logprob_rows(C.byref(desc)), 'npm_logprob_rows')
+    return LogProbs(out, rows, top_n, ids_dev is not None)

@@ -24,7 +24,7 @@ import numpy as np
 from np_modeling_amd import device as D
 
 
-def decode_step(dec, state, emb, head, sampler, drafter, active=None) -> List[List[int]]:
+def decode_step(dec, state, emb, head, sampler, drafter, active=None, processor=None) -> List[List[int]]:
     """One speculative step for the sequences of ``state``; the tokens each slot emitted (an empty list for a slot that is not
     ``active``, holds no history or has no room left).  ``dec`` a ``TransformerDecoder``, ``state`` its ``DecodeState``, ``emb`` an
     ``Embedding``, ``head`` the layer that turns [rows, F] into logits, ``sampler`` a ``Sampler`` and ``drafter`` an
@@ -33,6 +33,11 @@ def decode_step(dec, state, emb, head, sampler, drafter, active=None) -> List[Li
     Propose (``limit[b] = min(T, capacity - lengths[b] - 1)``, so that the chunk always fits the cache) -> ``emb.forward(chunk)``
     -> ``dec.decode(x, state, new_lengths=n_new)`` -> ``head`` on all B (T + 1) rows -> ``sampler.verify(..., history=drafter)`` ->
     ``state.truncate(n_new - 1 - accepted)``.
+
+    ``processor``: a ``sampling.LogitProcessor`` applied to the logits between ``head`` and the verify, with the drafter as its
+    history and the chunk as its draft: one more launch, no copy to the host.  Row r is processed as if the r drafted tokens
+    before it stood in the history already, and it counts only when they were the tokens sampled -- so the step emits the tokens of
+    the loop ``processor(logits, history) -> sampler(logits) -> history.append(result)``, seed for seed and counter for counter.
 
     One copy to the host per step in the steady state: right behind the verify the NEXT step's proposal is launched, with the
     limits the next step will ask for if the same slots stay active and none comes within 2 T + 2 rows of its capacity, and its
@@ -53,6 +58,8 @@ def decode_step(dec, state, emb, head, sampler, drafter, active=None) -> List[Li
     hidden = dec.decode(x, state, new_lengths=n_new)
     logits = head(hidden.reshape(batch * (t + 1), hidden.shape[2]))
     draft = D.IdBuffer([batch, t], chunk._buf, chunk.ptr + 4)            # the chunk behind its first column
+    if processor is not None:
+        processor(logits, drafter, draft=draft, n_draft=n_new - 1, draft_pitch=t + 1)
     # the limits of the next step when every drafted token is accepted: they are the next step's own wherever both are T
     ahead = np.where(limit >= 0, np.minimum(t, cache.capacity - cache.lengths - 1), -1)
     result = sampler.verify(logits, draft, n_new - 1, history=drafter, draft_pitch=t + 1, extra_words=batch,
