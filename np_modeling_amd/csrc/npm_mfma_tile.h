@@ -400,9 +400,9 @@ __device__ __forceinline__ void write_tile_buf(const f32x16 (&acc)[2][2], const 
         a.m0 = m0; a.n0 = n0; a.N = N; a.wn = wn; a.l32 = l32; a.half = half; a.cptr = cptr;
         const bool cs = WITH_COLSUM && want_cs;
         const int key = flags | (alpha == 1.f ? 64 : 0);
-        if (key == (NPM_EPI_BIAS | NPM_EPI_RESIDUAL | 64)) rmw_epilogue<NPM_EPI_BIAS | NPM_EPI_RESIDUAL | 64, false>(acc, e, a, csum);
+        if (key == (NPM_EPI_BIAS | NPM_EPI_RESIDUAL | 64) && !cs) rmw_epilogue<NPM_EPI_BIAS | NPM_EPI_RESIDUAL | 64, false>(acc, e, a, csum);
         else if (key == (NPM_EPI_RESIDUAL | 64) && !cs) rmw_epilogue<NPM_EPI_RESIDUAL | 64, false>(acc, e, a, csum);
-        else if (key == (NPM_EPI_BIAS | NPM_EPI_RELU_SAVE | 64)) rmw_epilogue<NPM_EPI_BIAS | NPM_EPI_RELU_SAVE | 64, false>(acc, e, a, csum);
+        else if (key == (NPM_EPI_BIAS | NPM_EPI_RELU_SAVE | 64) && !cs) rmw_epilogue<NPM_EPI_BIAS | NPM_EPI_RELU_SAVE | 64, false>(acc, e, a, csum);
         else if (key == (NPM_EPI_RELU_SAVE | 64) && !cs) rmw_epilogue<NPM_EPI_RELU_SAVE | 64, false>(acc, e, a, csum);
         else if (key == (NPM_EPI_RELU_MASK | 64)) { if (cs) rmw_epilogue<NPM_EPI_RELU_MASK | 64, WITH_COLSUM>(acc, e, a, csum);
                                                     else rmw_epilogue<NPM_EPI_RELU_MASK | 64, false>(acc, e, a, csum); }
