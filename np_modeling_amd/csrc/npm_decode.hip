@@ -69,20 +69,11 @@
 #include <cmath>
 #include <cstring>
 
-#include "npm_internal.h"
+#include "npm_kvattn.h"
 
 namespace {
 
-constexpr float LOG2E = 1.44269504088896340736f;
-constexpr float LN2 = 0.69314718055994530942f;
-constexpr int WAVES = 4;          // per block
-constexpr int TILE = 16;          // keys per wave tile
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
+constexpr int WAVES = 4;          // per block; TILE (npm_kvattn.h): keys per wave tile
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
@@ -103,17 +94,6 @@ struct DecodeArgs {
     int window;                   // npm_mha_decode_fwd_window: keys a row sees, itself included (read by the WN instances only)
 };
 
-// npm_*_paged: row j of sequence b is row (j & (rows - 1)) of page table[b * pitch + (j >> shift)]; rows = 1 << shift
-struct PageArgs {
-    const int *table;
-    int pitch, shift;
-};
-
-template <int VW> struct VecOf;
-template <> struct VecOf<4> { using type = f32x4v; };
-template <> struct VecOf<2> { using type = f32x2v; };
-template <> struct VecOf<1> { using type = float; };
-
 template <bool NT, typename V>
 __device__ __forceinline__ V ld_kv(const float *p) {
     if (NT) return __builtin_nontemporal_load(reinterpret_cast<const V *>(p));
@@ -121,11 +101,6 @@ __device__ __forceinline__ V ld_kv(const float *p) {
 }
 
 // The same elements out of an fp16 cache: one load of as many halves, converted exactly (v_cvt_f32_f16; subnormals are kept)
-template <int VW> struct HalfVecOf;
-template <> struct HalfVecOf<4> { using type = f16x4v; };
-template <> struct HalfVecOf<2> { using type = f16x2v; };
-template <> struct HalfVecOf<1> { using type = _Float16; };
-
 template <bool NT, typename V>
 __device__ __forceinline__ V ld_kv(const _Float16 *p) {
     constexpr int VW = sizeof(V) / sizeof(float);
@@ -136,9 +111,6 @@ __device__ __forceinline__ V ld_kv(const _Float16 *p) {
     if constexpr (VW == 1) return (float)h;
     else return __builtin_convertvector(h, V);
 }
-
-template <int VW> __device__ __forceinline__ float comp(const typename VecOf<VW>::type &x, int e) { return x[e]; }
-template <> __device__ __forceinline__ float comp<1>(const float &x, int) { return x; }
 
 // D: head size; RB: 16-row blocks of the score tile (rows = (Hq / Hkv) T <= 16 RB); NT: nontemporal K / V loads.
 // VL (npm_mha_decode_fwd_varlen): the sequence has L = kv_lens[b] <= a.len valid keys and nb = new_lens[b] <= a.tokens new tokens.
@@ -334,13 +306,14 @@ void launch_decode_window(const DecodeArgs &a, const int *kv_lens, const int *ne
 // The keys one sequence of a windowed call can hold live: its T rows see at most window + T - 1 of them, and never more than kv_len
 long window_keys(long kv_len, long tokens, long window) { return std::min(kv_len, window + tokens - 1); }
 
-// page_rows -> log2, or -1 unless it is a power of two >= TILE
-int page_shift(int page_rows) {
-    if (page_rows < TILE || (page_rows & (page_rows - 1))) return -1;
-    return __builtin_ctz((unsigned)page_rows);
+// The decode kernel's own rule: the head size and the rows of a score tile
+int decode_head_ok(const char *name, const npm_mha_decode *d) {
+    const int rows = d->heads / d->kv_heads * d->new_tokens;
+    if (!npm_mha_decode_supported(d->head_dim, rows))
+        return npm::fail(NPM_E_UNSUPPORTED, "%s: head_dim %d with %d rows per K / V head is not supported "
+                         "(head_dim in {16, 32, 64, 128}, rows <= %d)", name, d->head_dim, rows, NPM_DECODE_MAX_ROWS);
+    return NPM_OK;
 }
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -391,31 +364,11 @@ template <typename KV = float>
 static int decode_fwd(const char *name, const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens,
                       const int32_t *block_table = nullptr, int32_t table_pitch = 0, int32_t page_rows = 0, int32_t window = 0) {
     const bool varlen = kv_lens != nullptr, paged = block_table != nullptr;
-    constexpr int KV_ALIGN = 16 / sizeof(KV);                          // elements of the cache in 16 bytes
-    NPM_REQUIRE_INIT();
-    NPM_ARG(d != nullptr);
     PageArgs pg{};
-    if (paged) {
-        NPM_ARG(varlen && page_shift(page_rows) >= 0);
-        NPM_ARG(d->kv_len >= 0 && (int64_t)table_pitch * page_rows >= d->kv_len);       // a table row names every page of kv_len rows
-        NPM_ARG(d->k_stride_b >= (int64_t)page_rows * d->k_pitch && d->v_stride_b >= (int64_t)page_rows * d->v_pitch);
-        pg.table = block_table; pg.pitch = table_pitch; pg.shift = page_shift(page_rows);
-    }
-    NPM_ARG(d->batch >= 1 && d->heads >= 1 && d->kv_heads >= 1 && d->new_tokens >= 1 && d->head_dim >= 1);
-    NPM_ARG(d->heads % d->kv_heads == 0);
-    NPM_ARG(varlen ? d->kv_len >= 0 : d->kv_len >= d->new_tokens);     // varlen: new_lens[b] <= kv_lens[b] <= kv_len is the caller's
-    NPM_ARG(d->scale > 0.f);
-    NPM_ARG(d->q != nullptr && d->k != nullptr && d->v != nullptr && d->ctx != nullptr);
+    if (int rc = check_kv_attn(name, d, varlen, block_table, table_pitch, page_rows, 16 / sizeof(KV), decode_head_ok, &pg)) return rc;
+    if (d->batch > 65535 || d->kv_heads > 65535)
+        return npm::fail(NPM_E_BAD_ARGUMENT, "%s: bad argument: d->batch <= 65535 && d->kv_heads <= 65535", name);
     const int D = d->head_dim, rows = d->heads / d->kv_heads * d->new_tokens;
-    if (!npm_mha_decode_supported(D, rows))
-        return npm::fail(NPM_E_UNSUPPORTED, "%s: head_dim %d with %d rows per K / V head is not supported "
-                         "(head_dim in {16, 32, 64, 128}, rows <= %d)", name, D, rows, NPM_DECODE_MAX_ROWS);
-    NPM_ARG(aligned16(d->q) && aligned16(d->k) && aligned16(d->v) && aligned16(d->ctx));
-    NPM_ARG(d->q_pitch % 4 == 0 && d->k_pitch % KV_ALIGN == 0 && d->v_pitch % KV_ALIGN == 0 && d->ctx_pitch % 4 == 0);
-    NPM_ARG(d->k_stride_b % KV_ALIGN == 0 && d->v_stride_b % KV_ALIGN == 0);
-    NPM_ARG(d->q_pitch >= (int64_t)d->heads * D && d->ctx_pitch >= (int64_t)d->heads * D);
-    NPM_ARG(d->k_pitch >= (int64_t)d->kv_heads * D && d->v_pitch >= (int64_t)d->kv_heads * D);
-    NPM_ARG(d->batch <= 65535 && d->kv_heads <= 65535);
 
     // window: an interval of keys_bound keys touches at most (keys_bound + 14) / 16 + 1 tiles wherever it starts, and no more than
     // the cache has

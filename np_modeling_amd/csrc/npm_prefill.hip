@@ -38,19 +38,12 @@
 #include <cmath>
 #include <cstring>
 
-#include "npm_internal.h"
+#include "npm_kvattn.h"
 
 namespace {
 
-constexpr float LOG2E = 1.44269504088896340736f;
-constexpr float LN2 = 0.69314718055994530942f;
 constexpr int WAVES = 4;          // per block
-constexpr int TILE = 16;          // keys per tile
 constexpr int ROWS = WAVES * 16;  // query rows per block
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
@@ -67,26 +60,6 @@ struct PrefillArgs {
     float c, scale;               // scale * log2(e), scale
     int window;                   // npm_mha_prefill_fwd_window: keys a row sees, itself included (read by the WN instances only)
 };
-
-struct PageArgs {
-    const int *table;
-    int pitch, shift;
-};
-
-template <int VW> struct VecOf;
-template <> struct VecOf<4> { using type = f32x4v; };
-template <> struct VecOf<2> { using type = f32x2v; };
-template <> struct VecOf<1> { using type = float; };
-
-template <int VW> __device__ __forceinline__ float comp(const typename VecOf<VW>::type &x, int e) { return x[e]; }
-template <> __device__ __forceinline__ float comp<1>(const float &x, int) { return x; }
-template <int VW> __device__ __forceinline__ void put(typename VecOf<VW>::type &x, int e, float y) { x[e] = y; }
-template <> __device__ __forceinline__ void put<1>(float &x, int, float y) { x = y; }
-
-// A 16-byte piece of a cache row: 4 floats or 8 halves
-template <typename KV> struct PieceOf;
-template <> struct PieceOf<float> { using type = f32x4v; };
-template <> struct PieceOf<_Float16> { using type = f16x8v; };
 
 // D: head size.  VL: the sequence has L = kv_lens[b] valid keys and nb = new_lens[b] (NULL: a.tokens) new tokens; VL = false reads
 // neither array (L = a.len, nb = a.tokens) and is otherwise the same code.  PG (implies VL): a.k / a.v are page pools, a.k_sb /
@@ -156,13 +129,11 @@ void launch_prefill(const PrefillArgs &a, const int *kv_lens, const int *new_len
     }
 }
 
-// page_rows -> log2, or -1 unless it is a power of two >= TILE
-int page_shift(int page_rows) {
-    if (page_rows < TILE || (page_rows & (page_rows - 1))) return -1;
-    return __builtin_ctz((unsigned)page_rows);
+int prefill_head_ok(const char *name, const npm_mha_decode *d) {
+    if (!npm_mha_prefill_supported(d->head_dim))
+        return npm::fail(NPM_E_UNSUPPORTED, "%s: head_dim %d is not supported (head_dim in {16, 32, 64, 128})", name, d->head_dim);
+    return NPM_OK;
 }
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -178,37 +149,12 @@ extern "C" const char *npm_last_prefill_kernel(void) { return g_last; }
 template <typename KV>
 static int prefill_fwd(const char *name, const npm_mha_decode *d, const int32_t *kv_lens, const int32_t *new_lens,
                        const int32_t *block_table, int32_t table_pitch, int32_t page_rows, int32_t window = 0) {
-#define PREFILL_ARG(cond)                                                                              \
-    do {                                                                                               \
-        if (!(cond)) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: bad argument: %s", name, #cond);        \
-    } while (0)
     const bool varlen = kv_lens != nullptr, paged = block_table != nullptr;
-    constexpr int KV_ALIGN = 16 / sizeof(KV);                          // elements of the cache in 16 bytes
-    if (!npm::ctx().ready) return npm::fail(NPM_E_NOT_INITIALIZED, "%s: npm_init() has not been called", name);
-    PREFILL_ARG(d != nullptr);
     PageArgs pg{};
-    if (paged) {
-        if (!varlen) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: a block table needs kv_lens", name);
-        if (page_shift(page_rows) < 0)
-            return npm::fail(NPM_E_BAD_ARGUMENT, "%s: page_rows %d is not a power of two >= %d", name, page_rows, TILE);
-        PREFILL_ARG(d->kv_len >= 0 && (int64_t)table_pitch * page_rows >= d->kv_len);   // a table row names every page of kv_len rows
-        PREFILL_ARG(d->k_stride_b >= (int64_t)page_rows * d->k_pitch && d->v_stride_b >= (int64_t)page_rows * d->v_pitch);
-        pg.table = block_table; pg.pitch = table_pitch; pg.shift = page_shift(page_rows);
-    }
-    PREFILL_ARG(d->batch >= 1 && d->heads >= 1 && d->kv_heads >= 1 && d->new_tokens >= 1 && d->head_dim >= 1);
-    PREFILL_ARG(d->heads % d->kv_heads == 0);
-    PREFILL_ARG(varlen ? d->kv_len >= 0 : d->kv_len >= d->new_tokens); // varlen: new_lens[b] <= kv_lens[b] <= kv_len is the caller's
-    PREFILL_ARG(d->scale > 0.f);
-    PREFILL_ARG(d->q != nullptr && d->k != nullptr && d->v != nullptr && d->ctx != nullptr);
+    if (int rc = check_kv_attn(name, d, varlen, block_table, table_pitch, page_rows, 16 / sizeof(KV), prefill_head_ok, &pg)) return rc;
+    if (d->batch > 65535 || d->kv_heads > 65535)
+        return npm::fail(NPM_E_BAD_ARGUMENT, "%s: bad argument: d->batch <= 65535 && d->kv_heads <= 65535", name);
     const int D = d->head_dim;
-    if (!npm_mha_prefill_supported(D))
-        return npm::fail(NPM_E_UNSUPPORTED, "%s: head_dim %d is not supported (head_dim in {16, 32, 64, 128})", name, D);
-    PREFILL_ARG(aligned16(d->q) && aligned16(d->k) && aligned16(d->v) && aligned16(d->ctx));
-    PREFILL_ARG(d->q_pitch % 4 == 0 && d->k_pitch % KV_ALIGN == 0 && d->v_pitch % KV_ALIGN == 0 && d->ctx_pitch % 4 == 0);
-    PREFILL_ARG(d->k_stride_b % KV_ALIGN == 0 && d->v_stride_b % KV_ALIGN == 0);
-    PREFILL_ARG(d->q_pitch >= (int64_t)d->heads * D && d->ctx_pitch >= (int64_t)d->heads * D);
-    PREFILL_ARG(d->k_pitch >= (int64_t)d->kv_heads * D && d->v_pitch >= (int64_t)d->kv_heads * D);
-    PREFILL_ARG(d->batch <= 65535 && d->kv_heads <= 65535);
 
     PrefillArgs a{};
     a.q = d->q; a.k = d->k; a.v = d->v;
@@ -223,8 +169,8 @@ static int prefill_fwd(const char *name, const npm_mha_decode *d, const int32_t 
     a.scale = d->scale;
     a.window = window;
     const int64_t token_tiles = ((int64_t)d->new_tokens + a.tb - 1) / a.tb;
-    PREFILL_ARG(token_tiles * a.head_chunks <= 0x7fffffff);
-#undef PREFILL_ARG
+    if (token_tiles * a.head_chunks > 0x7fffffff)
+        return npm::fail(NPM_E_BAD_ARGUMENT, "%s: bad argument: token_tiles * a.head_chunks <= 0x7fffffff", name);
 
     const dim3 grid((unsigned)(token_tiles * a.head_chunks), d->kv_heads, d->batch);
     hipStream_t s = npm::ctx().stream;

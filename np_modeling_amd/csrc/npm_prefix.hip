@@ -26,20 +26,13 @@
 #include <cmath>
 #include <cstring>
 
-#include "npm_internal.h"
+#include "npm_kvattn.h"
 
 namespace {
 
-constexpr float LOG2E = 1.44269504088896340736f;
-constexpr float LN2 = 0.69314718055994530942f;
 constexpr int WAVES = 4;          // per block
-constexpr int TILE = 16;          // keys per tile
 constexpr int ROWS = WAVES * 16;  // (head, row) pairs per block
 constexpr int MIN_TILES = 8;      // the automatic rule keeps at least this many tiles (128 keys) in a split
-
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8v __attribute__((ext_vector_type(8)));
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
@@ -58,21 +51,6 @@ struct PrefixArgs {
     int tiles, tiles_per_split;
     float c, scale;               // scale * log2(e), scale
 };
-
-template <int VW> struct VecOf;
-template <> struct VecOf<4> { using type = f32x4v; };
-template <> struct VecOf<2> { using type = f32x2v; };
-template <> struct VecOf<1> { using type = float; };
-
-template <int VW> __device__ __forceinline__ float comp(const typename VecOf<VW>::type &x, int e) { return x[e]; }
-template <> __device__ __forceinline__ float comp<1>(const float &x, int) { return x; }
-template <int VW> __device__ __forceinline__ void put(typename VecOf<VW>::type &x, int e, float y) { x[e] = y; }
-template <> __device__ __forceinline__ void put<1>(float &x, int, float y) { x = y; }
-
-// A 16-byte piece of a pool row: 4 floats or 8 halves
-template <typename KV> struct PieceOf;
-template <> struct PieceOf<float> { using type = f32x4v; };
-template <> struct PieceOf<_Float16> { using type = f16x8v; };
 
 template <int D, typename KV>
 __global__ void __launch_bounds__(WAVES * 64)
@@ -293,12 +271,11 @@ attn_combine_kernel(const float *__restrict__ part_ctx, const float *__restrict_
     if (d == 0 && store_lse) *out_lse = mt + __builtin_amdgcn_logf(sum) * LN2;
 }
 
-int page_shift(int page_rows) {
-    if (page_rows < TILE || (page_rows & (page_rows - 1))) return -1;
-    return __builtin_ctz((unsigned)page_rows);
+int prefix_head_ok(const char *name, const npm_mha_decode *d) {
+    if (!npm_mha_prefix_supported(d->head_dim))
+        return npm::fail(NPM_E_UNSUPPORTED, "%s: head_dim %d is not supported (head_dim in {16, 32, 64, 128})", name, d->head_dim);
+    return NPM_OK;
 }
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // the row tiles of `rows` folded rows: heads of the group and rows per block, head chunks, tiles
 struct RowTiles {
@@ -358,18 +335,14 @@ extern "C" int npm_mha_prefix_fwd(const npm_mha_decode *d, const int32_t *new_le
     NPM_ARG(prefix_table != nullptr && page_shift(page_rows) >= 0);
     NPM_ARG(prefix_rows >= page_rows && prefix_rows % page_rows == 0);
     NPM_ARG(splits >= 1 && splits <= NPM_PREFIX_MAX_SPLITS && part_ctx != nullptr && part_lse != nullptr);
-    NPM_ARG(d->batch >= 1 && d->heads >= 1 && d->kv_heads >= 1 && d->new_tokens >= 1 && d->head_dim >= 1);
-    NPM_ARG(d->heads % d->kv_heads == 0 && (int64_t)d->batch * d->new_tokens <= 0x7fffffff);
-    NPM_ARG(d->scale > 0.f);
-    NPM_ARG(d->q != nullptr && d->k != nullptr && d->v != nullptr);
-    const int D = d->head_dim, kv_align = kv_f16 ? 8 : 4;              // elements of the pool in 16 bytes
-    if (!npm_mha_prefix_supported(D))
-        return npm::fail(NPM_E_UNSUPPORTED, "npm_mha_prefix_fwd: head_dim %d is not supported (head_dim in {16, 32, 64, 128})", D);
-    NPM_ARG(aligned16(d->q) && aligned16(d->k) && aligned16(d->v) && aligned16(part_ctx));
-    NPM_ARG(d->q_pitch % 4 == 0 && d->k_pitch % kv_align == 0 && d->v_pitch % kv_align == 0);
-    NPM_ARG(d->k_stride_b % kv_align == 0 && d->v_stride_b % kv_align == 0);
-    NPM_ARG(d->q_pitch >= (int64_t)d->heads * D);
-    NPM_ARG(d->k_pitch >= (int64_t)d->kv_heads * D && d->v_pitch >= (int64_t)d->kv_heads * D);
+    NPM_ARG((int64_t)d->batch * d->new_tokens <= 0x7fffffff);
+    // To the shared check this is the per-sequence call over prefix_rows keys that writes part_ctx: d->kv_len, d->causal, d->ctx and
+    // d->lse are not read.  The table is one row and has been checked above, so the check sees none.
+    npm_mha_decode p = *d;
+    p.kv_len = prefix_rows; p.ctx = part_ctx; p.ctx_pitch = (int64_t)d->heads * d->head_dim;
+    PageArgs none{};
+    if (int rc = check_kv_attn("npm_mha_prefix_fwd", &p, true, nullptr, 0, 0, kv_f16 ? 8 : 4, prefix_head_ok, &none)) return rc;
+    const int D = d->head_dim;
     NPM_ARG(d->k_stride_b >= (int64_t)page_rows * d->k_pitch && d->v_stride_b >= (int64_t)page_rows * d->v_pitch);
     NPM_ARG(d->kv_heads <= 65535);
 

@@ -1307,33 +1307,25 @@ def kv_gather(cache: DeviceArray, out: DeviceArray, length: int) -> None:
                  'npm_d2d')
 
 
-def _decode_desc(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, scale: float, causal: bool, want_lse: bool):
+def _decode_desc(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, scale: float, causal: bool, want_lse: bool,
+                 out: bool = True):
     """The ``npm_mha_decode`` of ``tokens`` query rows per sequence over ``cache`` -- the only place that fills one -- with fresh
-    ctx [B, T, Hq, D] and lse [B, Hq, T] (or None), and the layout of ``cache.k`` (its table is that of ``cache.v`` too)."""
+    ctx [B, T, Hq, D] and lse [B, Hq, T] (or None), and the layout of ``cache.k`` (its table is that of ``cache.v`` too).
+    ``out`` False: ctx and lse are left out (a call that writes elsewhere: ``mha_prefix``)."""
     b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
     kl, vl = cache.layout(cache.k), cache.layout(cache.v)
-    ctx = empty([b, tokens, heads, d])
-    lse = empty([b, heads, tokens]) if want_lse else None
+    ctx = empty([b, tokens, heads, d]) if out else None
+    lse = empty([b, heads, tokens]) if out and want_lse else None
     c = _C.npm_mha_decode()
     c.batch, c.heads, c.kv_heads, c.new_tokens, c.kv_len, c.head_dim = b, int(heads), hkv, int(tokens), int(kv_len), d
     c.causal, c.scale = int(bool(causal)), float(scale)
     c.q, c.q_pitch = q.ptr, q.ld
     c.k, c.k_pitch, c.k_stride_b = cache.k.ptr, kl.pitch, kl.stride
     c.v, c.v_pitch, c.v_stride_b = cache.v.ptr, vl.pitch, vl.stride
-    c.ctx, c.ctx_pitch = ctx.ptr, heads * d
-    c.lse = None if lse is None else lse.ptr
+    if out:
+        c.ctx, c.ctx_pitch = ctx.ptr, heads * d
+        c.lse = None if lse is None else lse.ptr
     return c, ctx, lse, kl
-
-
-def _window_call(entry: str, timer: str, c, cache: 'KVCache', layout: KVLayout, heads: int, tokens: int, keys: int, lens, window: int):
-    """``npm_mha_decode_fwd_window`` / ``npm_mha_prefill_fwd_window`` (``entry``) on a filled descriptor: the per-sequence form only."""
-    if lens is None:
-        raise ValueError(f'{entry}: a window needs the per-sequence lengths')
-    b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
-    keys = min(int(keys), b * (int(window) + tokens - 1))                # the keys a windowed call reads at most
-    with _timed(timer, flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens) + 2.0 * cache.itemsize * d * hkv * keys):
-        _C.check(getattr(_C.lib(), entry)(C.byref(c), lens[0], lens[1], layout.table, layout.table_pitch, layout.page_rows, int(window),
-                                          int(cache.dtype == 'f16')), entry)
 
 
 def _behind_prefix(layout: KVLayout, prefix: int) -> KVLayout:
@@ -1342,6 +1334,53 @@ def _behind_prefix(layout: KVLayout, prefix: int) -> KVLayout:
         return layout
     assert layout.table is not None and prefix % layout.page_rows == 0, (prefix, layout.page_rows)
     return layout._replace(table=layout.table + 4 * (prefix // layout.page_rows))
+
+
+def _attend_entry(kernel: str, cache: 'KVCache', layout: KVLayout, lens, window: Optional[int]):
+    """The entry point that runs ``kernel`` ('decode' | 'prefill') over ``cache`` and its arguments behind the descriptor, by
+
+    ==========  ======  =================  =============================  ================================================
+    window      dtype   layout             entry point                    arguments
+    ==========  ======  =================  =============================  ================================================
+    W           any     per-sequence       npm_mha_<kernel>_fwd_window    kv_lens, new_lens, table, W, dtype == 'f16'
+    None        f16     any                npm_mha_<kernel>_fwd_f16       kv_lens, new_lens, table
+    None        f32     any (prefill)      npm_mha_prefill_fwd            kv_lens, new_lens, table
+    None        f32     paged (decode)     npm_mha_decode_fwd_paged       kv_lens, new_lens, table
+    None        f32     ragged (decode)    npm_mha_decode_fwd_varlen      kv_lens, new_lens
+    None        f32     uniform (decode)   npm_mha_decode_fwd             --
+    ==========  ======  =================  =============================  ================================================
+
+    ``table``: (block table, its pitch, rows per page), NULL and zeros for a contiguous cache; the lengths are NULL in the
+    uniform call."""
+    kv_lens, new_lens = (None, None) if lens is None else lens
+    table = (layout.table, layout.table_pitch, layout.page_rows)
+    if window is not None:
+        if lens is None:
+            raise ValueError(f'npm_mha_{kernel}_fwd_window: a window needs the per-sequence lengths')
+        return f'npm_mha_{kernel}_fwd_window', (kv_lens, new_lens, *table, int(window), int(cache.dtype == 'f16'))
+    if cache.dtype == 'f16':
+        return f'npm_mha_{kernel}_fwd_f16', (kv_lens, new_lens, *table)
+    if kernel == 'prefill':
+        return 'npm_mha_prefill_fwd', (kv_lens, new_lens, *table)
+    if layout.table is not None:
+        return 'npm_mha_decode_fwd_paged', (kv_lens, new_lens, *table)
+    return ('npm_mha_decode_fwd_varlen', (kv_lens, new_lens)) if lens is not None else ('npm_mha_decode_fwd', ())
+
+
+def _mha_cached(kernel: str, q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, scale: float, causal: bool, want_lse: bool,
+                lens, keys: Optional[int], window: Optional[int], prefix: int):
+    """``mha_decode`` / ``mha_prefill`` (``kernel``): one descriptor, one entry point out of ``_attend_entry``, one timer."""
+    assert cache.key_dim == cache.value_dim and 0 <= kv_len <= cache.capacity and (lens is not None or tokens <= kv_len)
+    c, ctx, lse, layout = _decode_desc(q, cache, heads, tokens, kv_len, scale, causal, want_lse)
+    entry, args = _attend_entry(kernel, cache, _behind_prefix(layout, prefix), lens, window)
+    b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
+    keys = b * kv_len if keys is None else int(keys)
+    if window is not None:
+        keys = min(keys, b * (int(window) + tokens - 1))                 # the keys a windowed call reads at most
+    # q and ctx in fp32, K and V once in the cache's type
+    with _timed('mha_' + kernel, flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens) + 2.0 * cache.itemsize * d * hkv * keys):
+        _C.check(getattr(_C.lib(), entry)(C.byref(c), *args), entry)
+    return ctx, lse
 
 
 def mha_decode(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, scale: float, causal: bool, want_lse: bool = False,
@@ -1356,29 +1395,7 @@ def mha_decode(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, s
     ``window`` W: row t sees only the W keys up to its own (npm_mha_decode_fwd_window; per-sequence form, causal).
     ``prefix`` P (a paged cache, whole pages): the call runs over the rows BEHIND the first P of every sequence -- the table moved
     on by P / page_size slots, ``kv_len`` and ``lens`` already in those coordinates (``PagedKVCache`` 's shared-prefix path)."""
-    assert cache.key_dim == cache.value_dim and 0 <= kv_len <= cache.capacity and (lens is not None or tokens <= kv_len)
-    c, ctx, lse, layout = _decode_desc(q, cache, heads, tokens, kv_len, scale, causal, want_lse)
-    layout = _behind_prefix(layout, prefix)
-    b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
-    keys = b * kv_len if keys is None else int(keys)
-    if window is not None:
-        _window_call('npm_mha_decode_fwd_window', 'mha_decode', c, cache, layout, heads, tokens, keys, lens, window)
-        return ctx, lse
-    if cache.dtype == 'f16':
-        kv_lens, new_lens = (None, None) if lens is None else lens
-        with _timed('mha_decode', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + hkv * keys)):
-            _C.check(_C.lib().npm_mha_decode_fwd_f16(C.byref(c), kv_lens, new_lens, layout.table, layout.table_pitch, layout.page_rows),
-                     'npm_mha_decode_fwd_f16')
-        return ctx, lse
-    with _timed('mha_decode', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + 2 * hkv * keys)):
-        if layout.table is not None:
-            _C.check(_C.lib().npm_mha_decode_fwd_paged(C.byref(c), lens[0], lens[1], layout.table, layout.table_pitch, layout.page_rows),
-                     'npm_mha_decode_fwd_paged')
-        elif lens is not None:
-            _C.check(_C.lib().npm_mha_decode_fwd_varlen(C.byref(c), lens[0], lens[1]), 'npm_mha_decode_fwd_varlen')
-        else:
-            _C.check(_C.lib().npm_mha_decode_fwd(C.byref(c)), 'npm_mha_decode_fwd')
-    return ctx, lse
+    return _mha_cached('decode', q, cache, heads, tokens, kv_len, scale, causal, want_lse, lens, keys, window, prefix)
 
 
 # prefill: cached forwards with more rows than the decode kernel takes (a prompt chunk on top of cached rows, a ragged or paged
@@ -1407,24 +1424,7 @@ def mha_prefill(q: Mat, cache: 'KVCache', heads: int, tokens: int, kv_len: int, 
     cache -- with ``lens`` = (kv_lens, new_lens) as there.  No mask and no gathered copy exist.  An fp16 cache takes
     ``npm_mha_prefill_fwd_f16`` (bitwise the fp32 call on the rounded values); this is the low-level call, whatever
     ``PREFILL_KERNEL_F16`` says.  ``window`` W: npm_mha_prefill_fwd_window, as in ``mha_decode``; ``prefix``: as there."""
-    assert cache.key_dim == cache.value_dim and 0 <= kv_len <= cache.capacity and (lens is not None or tokens <= kv_len)
-    c, ctx, lse, layout = _decode_desc(q, cache, heads, tokens, kv_len, scale, causal, want_lse)
-    layout = _behind_prefix(layout, prefix)
-    b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
-    keys = b * kv_len if keys is None else int(keys)
-    if window is not None:
-        _window_call('npm_mha_prefill_fwd_window', 'mha_prefill', c, cache, layout, heads, tokens, keys, lens, window)
-        return ctx, lse
-    kv_lens, new_lens = (None, None) if lens is None else lens
-    if cache.dtype == 'f16':
-        with _timed('mha_prefill', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + hkv * keys)):
-            _C.check(_C.lib().npm_mha_prefill_fwd_f16(C.byref(c), kv_lens, new_lens, layout.table, layout.table_pitch, layout.page_rows),
-                     'npm_mha_prefill_fwd_f16')
-        return ctx, lse
-    with _timed('mha_prefill', flops=4.0 * heads * tokens * keys * d, nbytes=4.0 * d * (2 * b * heads * tokens + 2 * hkv * keys)):
-        _C.check(_C.lib().npm_mha_prefill_fwd(C.byref(c), kv_lens, new_lens, layout.table, layout.table_pitch, layout.page_rows),
-                 'npm_mha_prefill_fwd')
-    return ctx, lse
+    return _mha_cached('prefill', q, cache, heads, tokens, kv_len, scale, causal, want_lse, lens, keys, window, prefix)
 
 
 # shared prefixes: with the switch on, a causal ``attend`` on a paged cache whose active sequences name the same leading pages
@@ -1451,18 +1451,12 @@ def mha_prefix(q: Mat, cache: 'PagedKVCache', heads: int, tokens: int, scale: fl
     """The partial results of all ``cache.batch * tokens`` query rows over the ``prefix`` rows whose pages the device table row at
     ``prefix_table`` names (include/npm_hip.h npm_mha_prefix_fwd): (splits, part_ctx address, part_lse address, the pooled
     scratch that holds both -- keep it until the combine is launched)."""
+    c, _, _, _ = _decode_desc(q, cache, heads, tokens, prefix, scale, False, False, out=False)
     b, hkv, d = cache.batch, cache.kv_heads, cache.key_dim
-    kl, vl = cache.layout(cache.k), cache.layout(cache.v)
     rows = b * int(tokens)
     splits = int(_C.lib().npm_mha_prefix_splits(rows, int(heads), hkv, int(prefix)))
     part = empty([splits * rows * heads * (d + 1)])
     part_lse = part.ptr + 4 * splits * rows * heads * d
-    c = _C.npm_mha_decode()
-    c.batch, c.heads, c.kv_heads, c.new_tokens, c.kv_len, c.head_dim = b, int(heads), hkv, int(tokens), int(prefix), d
-    c.causal, c.scale = 0, float(scale)
-    c.q, c.q_pitch = q.ptr, q.ld
-    c.k, c.k_pitch, c.k_stride_b = cache.k.ptr, kl.pitch, kl.stride
-    c.v, c.v_pitch, c.v_stride_b = cache.v.ptr, vl.pitch, vl.stride
     row_tiles = -(-rows * heads // (hkv * 64))
     with _timed('mha_prefix', flops=4.0 * heads * rows * prefix * d,
                 nbytes=4.0 * d * heads * rows * (1 + splits) + 2.0 * cache.itemsize * d * hkv * prefix * row_tiles):
@@ -1810,22 +1804,15 @@ class KVCache:
         only with ``PREFILL_KERNEL_F16`` on."""
         if kernel not in ('decode', 'prefill'):
             raise ValueError(f"KVCache.attend: kernel must be 'decode' or 'prefill', got {kernel!r}")
-        if self.window is not None:
-            if not causal:
-                raise ValueError('KVCache.attend: a windowed cache is a self-attention cache: causal=False has no window to apply')
-            n = self._counts(tokens, self.new_lengths(tokens, new_lengths))
-            if (n > self.lengths).any():
-                raise ValueError(f'KVCache.attend: {n.tolist()} new tokens are not among the {self.lengths.tolist()} valid rows')
-            _, new_ptr, kv_ptr = self._device_lengths(self.lengths - n, n)
-            return (mha_prefill if kernel == 'prefill' else mha_decode)(
-                q, self, heads, tokens, self.max_length, scale, True, want_lse, lens=(kv_ptr, new_ptr), keys=int(self.lengths.sum()),
-                window=self.window)
-        if kernel == 'prefill' and self.dtype != 'f32' and not PREFILL_KERNEL_F16:
+        windowed = self.window is not None                               # always the per-sequence call, whatever the switch says
+        if windowed and not causal:
+            raise ValueError('KVCache.attend: a windowed cache is a self-attention cache: causal=False has no window to apply')
+        if kernel == 'prefill' and self.dtype != 'f32' and not (PREFILL_KERNEL_F16 or windowed):
             raise ValueError(f"KVCache.attend: the prefill kernel reads an {self.dtype} cache only with PREFILL_KERNEL_F16 on "
                              "(NPM_PREFILL_KERNEL_F16=1); without it the cache takes kernel='decode' or gather()")
         attend = mha_prefill if kernel == 'prefill' else mha_decode
         n = self.new_lengths(tokens, new_lengths)
-        if self._scalar_call(n) and (kernel == 'decode' or tokens <= int(self.lengths[0])):
+        if not windowed and self._scalar_call(n) and (kernel == 'decode' or tokens <= int(self.lengths[0])):
             return attend(q, self, heads, tokens, int(self.lengths[0]), scale, causal, want_lse)
         n = self._counts(tokens, n)
         if causal and (n > self.lengths).any():
@@ -1845,7 +1832,7 @@ class KVCache:
             return ctx, (lse if want_lse else None)
         _, new_ptr, kv_ptr = self._device_lengths(self.lengths - n, n)
         return attend(q, self, heads, tokens, self.max_length, scale, causal, want_lse, lens=(kv_ptr, new_ptr),
-                      keys=int(self.lengths.sum()))
+                      keys=int(self.lengths.sum()), window=self.window)
 
     def attend_prefix_rows(self, n: np.ndarray, causal: bool) -> int:
         """The rows of a shared prefix that ``attend`` reads in one pass for all sequences; 0: the ordinary call.  A contiguous

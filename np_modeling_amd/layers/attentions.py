@@ -43,30 +43,57 @@ Incremental decoding (inference; the reference has none: ``# TODO: support cache
 ``make_cache(batch, capacity)`` returns a ``device.KVCache`` with Hkv heads; ``forward(x, cache=cache)`` projects the T new
 tokens (one packed GEMM where the parameters allow), appends their K / V rows behind the ``cache.length`` valid ones and attends
 causally over all of them -- T is the whole prompt or 1.  Cross-attention projects K / V once with ``fill_cache(cache, key,
-value)`` and then ``forward(x, cache=cache)`` attends to the whole frozen cache.  The attention itself is ``npm_mha_decode_fwd``
-(csrc/npm_decode.hip: one block per K / V head serves its whole group of query heads, keys split over blocks) where it takes the
-shape; otherwise the fused forward with a causal ``AttnMask`` over the valid rows (a long prefill), or the GEMM composition on the
-valid rows (other head sizes, split math modes): ``_cached_path`` names which ran.  Nothing is saved for a backward.
+value)`` and then ``forward(x, cache=cache)`` attends to the whole frozen cache.  Nothing is saved for a backward.
 
 Ragged batches.  ``forward(x, cache=cache, new_lengths=n)``: ``x`` [B, T, F] is padded on the right and sequence b brings n[b] <= T
 tokens (0: it rides along); their K / V go behind the sequence's own ``cache.lengths[b]`` rows and row t < n[b] sees keys
 j <= lengths[b] + t.  ``fill_cache(cache, key, value, lengths=...)`` does the same for a padded cross-attention memory.  Valid rows
 equal what the sequence gives alone at batch 1; padded rows are unspecified but finite; nothing at or past a sequence's length
-enters a result.  ``'decode'`` is then ``npm_mha_decode_fwd_varlen``, ``'fused_masked'`` (a ragged prefill) builds its mask from the
-lengths and takes K / V from the fresh projection or ``npm_kv_gather_varlen``; the GEMM composition has no masked softmax and
-raises NotImplementedError.  Lengths that are all equal take exactly the calls they took without the keyword.
+enters a result.  Lengths that are all equal take exactly the calls they took without the keyword.
 
-Prefill kernel (``device.PREFILL_KERNEL``, environment ``NPM_PREFILL_KERNEL=1``; off by default).  With the switch on, a cached
-forward that the decode kernel does not take runs ``npm_mha_prefill_fwd`` (csrc/npm_prefill.hip; ``_cached_path == 'prefill'``)
-straight over the cache under ``f32`` math and a supported head size: everything ``'fused_masked'`` served for ragged, paged and
-frozen caches, and the uniform contiguous cache with rows already in it or frozen -- no gathered K / V, no mask, no copy per
-sequence.  One case stays on ``'fused_masked'``: a uniform contiguous prefill from empty, where the fused forward reads the fresh
-projection in place.  With the switch off every call sequence is what it was.
+Which kernel attends (``cached_route``; ``_cached_path`` names the path of the last cached forward).  A call is in the
+*per-sequence form* when ``new_lengths`` is given or the cache is ragged, paged or windowed -- its entry points read the lengths
+(and the block table) on the device -- else in the *uniform form*.  R = (Hq / Hkv) T is the number of score rows per K / V head;
+the first row of the table that applies decides:
 
-Half-precision caches have a switch of their own (``device.PREFILL_KERNEL_F16``, environment ``NPM_PREFILL_KERNEL_F16=1``; off by
-default, independent of the one above): a cached forward over an ``f16`` cache that the decode kernel does not take then runs
-``npm_mha_prefill_fwd_f16`` over the stored halves in place -- a prefill from empty included, since such a cache is attended to as
-stored -- instead of the fused forward on ``cache.gather``'s fp32 copies.  Under a split math mode the gathered path stays.
+====  ====================================================  ==================  ====================================================
+rule  when                                                  path                runs
+====  ====================================================  ==================  ====================================================
+1     the cache has a ``window`` (never frozen: ValueError;  ``decode`` where    the windowed entry points, f32 and f16 alike,
+      exact-fp32 kernels only: NotImplementedError)         rule 2's predicate  whatever the switches say, a prefill from empty
+                                                            holds, else         included: nothing else knows the window
+                                                            ``prefill``
+2     ``mha_decode_supported(Dk, R, Dv)``; the uniform      ``decode``          ``npm_mha_decode_fwd`` (csrc/npm_decode.hip: one
+      form also needs T <= length (the kernel's contract)                       block per K / V head serves its group of query
+                                                                                heads, keys split over blocks), ``_varlen``,
+                                                                                ``_paged`` or ``_f16`` by the cache
+3     the switch of the cache's type is on                  ``prefill``         ``npm_mha_prefill_fwd[_f16]`` (csrc/npm_prefill.hip)
+      (``device.PREFILL_KERNEL``, NPM_PREFILL_KERNEL=1,                         over the cache in place, through the block table:
+      for f32; ``device.PREFILL_KERNEL_F16``,                                   no gathered K / V, no mask, no copy per sequence.
+      NPM_PREFILL_KERNEL_F16=1, for f16; both off by                            A half-precision cache is attended to as stored,
+      default) and ``mha_prefill_supported(Dk, Dv)`` --                         a prefill from empty included
+      except a uniform f32 call whose fresh projection is
+      the whole cache (a prefill from empty)
+4     per-sequence form, an f16 cache, or                   ``fused_masked``    the fused training forward with a mask.  Uniform
+      ``mha_core_supported(Dk, Dv)`` in any math mode                           f32: K / V are the fresh projection (from empty),
+                                                                                the cache itself (full, or batch 1) or a copy of
+                                                                                the valid rows, and the mask is the causal rule
+                                                                                (none at T = 1).  Otherwise: the fresh projection
+                                                                                only for an f32 cache empty in every sequence,
+                                                                                else ``cache.gather``; the mask is built from the
+                                                                                lengths and its tile summary skips what lies past
+                                                                                them
+5     otherwise (uniform f32, other head sizes)             ``gemm``            the GEMM composition on the valid rows; no masked
+                                                                                softmax, so a causal chunk runs row by row
+6     rule 2 or 3 in the per-sequence form and              ``decode_shared``   the same call over the rows behind the prefix,
+      ``cache.attend_prefix_rows(n, causal)`` is not 0      ``prefill_shared``  ``npm_mha_prefix_fwd`` and ``npm_attn_combine``
+      (a forked paged cache, ``device.SHARED_PREFIX``)                          (``KVCache.attend``)
+====  ====================================================  ==================  ====================================================
+
+The kernels of rules 1 - 3 run the exact-fp32 MFMA only, so under a split math mode the ``*_supported`` predicates are false and
+the call falls to rule 4 or 5, which honour the mode.  Before anything is launched ``forward`` refuses what no rule serves: a
+per-sequence or f16 call whose head sizes neither the decode kernel nor the fused forward takes (NotImplementedError: the GEMM
+composition has no masked softmax).  With every switch off each call sequence is what it was before the switch existed.
 
 Rotary position embeddings (``rope_base``, default None: the reference has no positional encoding and neither has this layer).
 With a positive ``rope_base`` the projected q and k are rotated in place by their positions -- element i < Dk / 2 of a head pairs
@@ -107,6 +134,34 @@ _PARAMS = ('_wq', '_wk', '_wv', '_wo', '_bq', '_bk', '_bv', '_bo')
 def _from(x: D.DeviceArray, offset: int) -> D.DeviceArray:
     """``x`` entered ``offset`` elements later (a head-slice operand of the grouped composition), spanning to its end."""
     return x if offset == 0 else x.flat_view(offset, [x.size - offset])
+
+
+def cached_route(cache, heads: int, tokens: int, causal: bool, fresh_whole: bool, per_sequence: bool, n=None) -> str:
+    """The path of a cached forward (the table in the module docstring), decided without effects: ``'decode'``, ``'prefill'``,
+    ``'fused_masked'`` or ``'gemm'``, the first two with ``'_shared'`` behind them when ``cache`` reads a shared prefix once.
+    ``tokens`` query rows per sequence of ``heads`` heads; ``causal`` False: ``cache`` is frozen; ``fresh_whole``: the fresh
+    projection is the whole cache (every sequence was empty); ``per_sequence``: the call has per-sequence lengths -- ``n`` [B]
+    new tokens each -- because ``new_lengths`` was given or the cache is ragged, paged or windowed.  A windowed cache that
+    neither kernel can serve raises here, before anything is launched."""
+    dk, dv, rows = cache.key_dim, cache.value_dim, heads // cache.kv_heads * tokens
+    if cache.window is not None:
+        # no gather, mask or GEMM composition knows the window: the two windowed kernels, whatever the switches say
+        if not causal:
+            raise ValueError('a windowed cache is a self-attention cache: it cannot be frozen for cross-attention')
+        if not D.mha_prefill_supported(dk, dv):
+            raise NotImplementedError('a windowed cache needs the exact-fp32 decode and prefill kernels (head sizes Dk == Dv in '
+                                      '{16, 32, 64, 128}, math mode f32)')
+        return 'decode' if D.mha_decode_supported(dk, rows, dv) else 'prefill'
+    f16 = cache.dtype != 'f32'
+    shared = '_shared' if per_sequence and cache.attend_prefix_rows(n, causal) else ''
+    if D.mha_decode_supported(dk, rows, dv) and (per_sequence or tokens <= cache.length):    # (the uniform kernel's contract: L >= T)
+        return 'decode' + shared
+    if (D.PREFILL_KERNEL_F16 if f16 else D.PREFILL_KERNEL) and D.mha_prefill_supported(dk, dv) \
+            and not (fresh_whole and not per_sequence and not f16):      # there the fused forward reads the projection in place
+        return 'prefill' + shared
+    if per_sequence or f16 or D.mha_core_supported(dk, dv, any_math=True):
+        return 'fused_masked'            # (_forward_cached has refused the head sizes it does not take)
+    return 'gemm'
 
 
 class MultiHeadAttention(layer.StatefulLayer):
@@ -327,7 +382,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         cache sees them as stored.  It needs the head sizes the decode kernel takes.
 
         A layer made with ``window=W`` gives the cache that window (``device.KVCache(window=)``): cached forwards run the windowed
-        decode kernel (up to 32 score rows per K / V head) or the windowed prefill kernel, never a gather, a mask or a GEMM
+        decode kernel (up to its row limit, ``device.mha_decode_supported``) or the windowed prefill kernel, never a gather, a mask or a GEMM
         composition, so it needs their head sizes too; a paged cache then gives pages back as its sequences move on."""
         if not self._initialized:
             raise RuntimeError('make_cache: the layer has no parameters yet (run one forward, or bind weights, first)')
@@ -448,54 +503,68 @@ class MultiHeadAttention(layer.StatefulLayer):
                     D.rope(q, b, t, h, dk, table, at, at_lens)
                     D.rope(fresh[0], b, t, hkv, dk, table, at, at_lens)
             cache.append(fresh[0], fresh[1], t, new_lengths)
-        if ragged:
-            ctx = self._attend_ragged(q, cache, t, not cross, fresh, before, new_lengths)
-        else:
-            ctx = self._attend_cached(q, cache, t, causal=not cross, fresh=fresh)
+        ctx = self._attend(q, cache, t, not cross, fresh, before, new_lengths, ragged)
         out = D.empty([b, t, f])
         D.gemm(b * t, f, h * dv, Mat(ctx, h * dv), Mat(wo, h * dv, half=half('_wo')), Mat(out, f), trans_b=True, bias=bo,
                residual=None if residual is None else Mat(residual, f), skinny_ok=True)
         return out
 
-    def _attend_cached(self, q: Mat, cache: D.KVCache, t: int, causal: bool, fresh) -> D.DeviceArray:
-        """ctx [B, T, Hq, Dv] of the T query rows ``q`` over the valid rows of ``cache``; sets ``_cached_path``."""
-        h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
-        b, length, scale = cache.batch, cache.length, 1.0 / math.sqrt(self._key_dim)
-        if t <= length and D.mha_decode_supported(dk, h // hkv * t, dv):     # (the kernel's contract: L >= T, causal or not)
-            self._cached_path = 'decode'
-            return cache.attend(q, h, t, scale, causal)[0]
-        if cache.dtype != 'f32':
-            # a half-precision cache is attended to AS STORED, the new tokens' own rows included: whatever the decode kernel
-            # does not take is the prefill kernel over the stored halves in place (PREFILL_KERNEL_F16; a prefill from empty
-            # too: the fresh projection is not what later steps will see), else the fused masked forward on the gathered fp32
-            # copies of the stored rows -- never the fresh projection or the cache tensors themselves
-            if D.PREFILL_KERNEL_F16 and D.mha_prefill_supported(dk, dv):
-                self._cached_path = 'prefill'
-                return cache.attend(q, h, t, scale, causal, kernel='prefill')[0]
-            before = cache.lengths - t if causal else cache.lengths
-            return self._attend_ragged(q, cache, t, causal, None, before, None, decode_ok=False)
-        if D.PREFILL_KERNEL and D.mha_prefill_supported(dk, dv) and not (fresh is not None and length == t):
-            # more rows than the decode kernel takes on top of cached rows, or over a frozen cache: the prefill kernel reads the
-            # cache in place (no copy of the valid rows, no mask).  A prefill from empty stays below: the fused forward reads
-            # the projection in place there.
-            self._cached_path = 'prefill'
-            return cache.attend(q, h, t, scale, causal, kernel='prefill')[0]
-        if D.mha_core_supported(dk, dv, any_math=True):
-            # more rows than the decode kernel takes (a long prefill), or a split math mode: the fused training forward, with the
-            # causal rule as a mask over the valid rows.  It addresses K / V as [B, L, Hkv, D]: the new tokens' own projection
-            # when they are the whole cache (prefill from empty), the cache itself when it is full, else a copy of the valid rows.
-            self._cached_path = 'fused_masked'
-            if fresh is not None and length == t:
+    def _attend(self, q: Mat, cache: D.KVCache, t: int, causal: bool, fresh, before: np.ndarray, new_lengths,
+                per_sequence: bool) -> D.DeviceArray:
+        """ctx [B, T, Hq, Dv] of the T query rows ``q`` over the valid rows of ``cache``, by the path ``cached_route`` names; sets
+        ``_cached_path``.  ``before`` [B] rows were valid before this call; ``fresh``: the new tokens' own (k, v), or None over
+        a frozen cache.  ``per_sequence``: sequence b brings ``new_lengths[b]`` (None: T) of the T padded rows, and row
+        t < n[b] sees keys j <= before[b] + t (causal) or j < lengths[b] (frozen)."""
+        h, scale = self._num_heads, 1.0 / math.sqrt(self._key_dim)
+        n = cache._counts(t, new_lengths) if per_sequence else None
+        fresh_whole = fresh is not None and not before.any()
+        path = cached_route(cache, h, t, causal, fresh_whole, per_sequence, n)
+        self._cached_path = path
+        if path == 'fused_masked':
+            return self._fused_masked(q, cache, t, causal, fresh if fresh_whole else None, before, n)
+        if path == 'gemm':
+            return self._gemm_rows(q, cache, t, causal)
+        return cache.attend(q, h, t, scale, causal, new_lengths=n, kernel=path.partition('_')[0])[0]
+
+    def _fused_masked(self, q: Mat, cache: D.KVCache, t: int, causal: bool, fresh, before: np.ndarray, n) -> D.DeviceArray:
+        """The fused training forward with the causal rule (or the lengths) as a mask.  It addresses K / V as [B, L, Hkv, D];
+        ``fresh``: the new tokens' own projection when they are the whole cache, ``n``: None in the uniform form."""
+        h, hkv, dk = self._num_heads, self._num_kv_heads, self._key_dim
+        b, scale = cache.batch, 1.0 / math.sqrt(dk)
+        if n is None and cache.dtype == 'f32':
+            # uniform fp32: the projection in place (a prefill from empty), the cache itself when it is full or holds one
+            # sequence, else a copy of the valid rows; the mask is the causal rule, which one query row does not need
+            keys = cache.length
+            if fresh is not None:
                 k, v = fresh
-            elif length == cache.capacity or b == 1:
-                k, v = Mat(cache.k, hkv * dk), Mat(cache.v, hkv * dv)
+            elif keys == cache.capacity or b == 1:
+                k, v = Mat(cache.k, hkv * dk), Mat(cache.v, hkv * self._value_dim)
             else:
-                k, v = (Mat(self._valid_rows(x, length), hkv * dk) for x in (cache.k, cache.v))
-            mask = D.AttnMask(np.arange(length)[None, :] <= (length - t + np.arange(t))[:, None], b, h, t, length) if causal and t > 1 else None
-            return D.mha_core_fwd(q, k, v, (b, h, t, length, dk), scale, mask, kv_heads=hkv if hkv != h else None)[0]
-        # other head sizes: the GEMM composition on the valid rows, batched over (B, Hkv) per group as in _forward_impl.  It has
-        # no masked softmax, so a causal chunk runs one query row at a time, each over the keys it sees.
-        self._cached_path = 'gemm'
+                k, v = (Mat(self._valid_rows(x, keys), hkv * dk) for x in (cache.k, cache.v))
+            mask = D.AttnMask(np.arange(keys)[None, :] <= (keys - t + np.arange(t))[:, None], b, h, t, keys) if causal and t > 1 else None
+        else:
+            # per-sequence lengths, or a half-precision cache (attended to AS STORED: never the fresh projection): the lengths
+            # as a mask [B, 1, T, keys], whose tile summary skips what lies past them.  K / V: the fresh projection when every
+            # sequence started empty (keys = T; the rows of padded tokens are masked), else the valid rows gathered with zeros
+            # behind them (P = 0 times stale memory could be NaN).
+            n = cache._counts(t, n)
+            if fresh is not None and cache.dtype == 'f32':
+                keys, (k, v) = t, fresh
+            else:
+                keys = cache.max_length
+                k, v = (Mat(x, hkv * dk) for x in cache.gather(keys))
+            limit = (before[:, None] + np.arange(t)[None, :] + 1) if causal else np.broadcast_to(cache.lengths[:, None], (b, t))
+            limit = np.where(np.arange(t)[None, :] < n[:, None], limit, 0)
+            visible = np.arange(keys)[None, None, :] < limit[:, :, None]                      # [B, T, keys]
+            visible[:, :, 0] |= ~visible.any(axis=2)                     # a row without a key is given key 0: finite, unspecified
+            mask = D.AttnMask(visible[:, None], b, h, t, keys)
+        return D.mha_core_fwd(q, k, v, (b, h, t, keys, dk), scale, mask, kv_heads=hkv if hkv != h else None)[0]
+
+    def _gemm_rows(self, q: Mat, cache: D.KVCache, t: int, causal: bool) -> D.DeviceArray:
+        """Other head sizes, uniform fp32: the GEMM composition on the valid rows, batched over (B, Hkv) per group as in
+        ``_forward_impl``.  It has no masked softmax, so a causal chunk runs one query row at a time, each over the keys it sees."""
+        h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
+        b, length, scale = cache.batch, cache.length, 1.0 / math.sqrt(dk)
         ctx = D.empty([b, t, h, dv])
         pk, pv, cap = hkv * dk, hkv * dv, cache.capacity
         for first, rows, keys in ([(i, 1, length - t + i + 1) for i in range(t)] if causal and t > 1 else [(0, t, length)]):
@@ -509,55 +578,6 @@ class MultiHeadAttention(layer.StatefulLayer):
                        Mat(cache.v, pv, cap * pv, dv),
                        Mat(ctx.ptr + 4 * (first * h * dv + g * pv), h * dv, t * h * dv, dv), batch=(b, hkv))
         return ctx
-
-    def _attend_ragged(self, q: Mat, cache: D.KVCache, t: int, causal: bool, fresh, before: np.ndarray, new_lengths,
-                       decode_ok: bool = True) -> D.DeviceArray:
-        """``_attend_cached`` when the sequences differ: ``before`` [B] rows were valid before this call, sequence b brings
-        ``new_lengths[b]`` (None: T) of the T padded query rows.  Row t < n[b] sees keys j <= before[b] + t (causal) or
-        j < lengths[b] (frozen cache).  A half-precision cache is attended to as stored: the decode kernel, the prefill kernel
-        (``PREFILL_KERNEL_F16``), or the fused masked forward on ``cache.gather`` -- not ``fresh``.  ``decode_ok`` False: the
-        caller (a uniform half-precision cache) has found that neither kernel takes the call."""
-        h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
-        b, scale = cache.batch, 1.0 / math.sqrt(self._key_dim)
-        n = np.full([b], t, dtype=np.int64) if new_lengths is None else new_lengths
-        stored = cache.dtype != 'f32'
-        if cache.window is not None:
-            # sliding-window attention: the windowed decode kernel up to its row limit, the windowed prefill kernel above it -- f32
-            # and f16 alike, whatever PREFILL_KERNEL / PREFILL_KERNEL_F16 say, a uniform prefill from empty included.  No gather,
-            # mask or GEMM composition knows the window: a call neither kernel takes is an error.
-            if not causal:
-                raise ValueError('a windowed cache is a self-attention cache: it cannot be frozen for cross-attention')
-            if not D.mha_prefill_supported(dk, dv):
-                raise NotImplementedError('a windowed cache needs the exact-fp32 decode and prefill kernels (head sizes Dk == Dv in '
-                                          '{16, 32, 64, 128}, math mode f32)')
-            self._cached_path = 'decode' if h // hkv * t <= 32 else 'prefill'
-            return cache.attend(q, h, t, scale, True, new_lengths=n, kernel=self._cached_path)[0]
-        # (a paged cache whose active sequences share their leading pages reads those once, with D.SHARED_PREFIX on: the same
-        # call, reported as 'decode_shared' / 'prefill_shared')
-        shared = '_shared' if cache.attend_prefix_rows(n, causal) else ''
-        if decode_ok and D.mha_decode_supported(dk, h // hkv * t, dv):
-            self._cached_path = 'decode' + shared
-            return cache.attend(q, h, t, scale, causal, new_lengths=n)[0]
-        if (D.PREFILL_KERNEL_F16 if stored else D.PREFILL_KERNEL) and D.mha_prefill_supported(dk, dv):
-            # a ragged prefill, a chunk of one, a sequence admitted beside decoding ones, a paged or a frozen cache: the prefill
-            # kernel over the cache in place, through the block table -- lengths and causality are arithmetic on the device
-            self._cached_path = 'prefill' + shared
-            return cache.attend(q, h, t, scale, causal, new_lengths=n, kernel='prefill')[0]
-        # a ragged prefill, mostly: the fused training forward with the lengths as a mask [B, 1, T, keys], whose tile summary
-        # skips what lies past them.  K / V: the fresh projection when every sequence started empty (keys = T; the rows of padded
-        # tokens are masked), else the valid rows gathered with zeros behind them (P = 0 times stale memory could be NaN).
-        self._cached_path = 'fused_masked'
-        if fresh is not None and not stored and not before.any():
-            keys, (k, v) = t, fresh
-        else:
-            keys = cache.max_length
-            k, v = (Mat(x, hkv * dk) for x in cache.gather(keys))
-        limit = (before[:, None] + np.arange(t)[None, :] + 1) if causal else np.broadcast_to(cache.lengths[:, None], (b, t))
-        limit = np.where(np.arange(t)[None, :] < n[:, None], limit, 0)
-        visible = np.arange(keys)[None, None, :] < limit[:, :, None]                      # [B, T, keys]
-        visible[:, :, 0] |= ~visible.any(axis=2)                         # a row without a key is given key 0: finite, unspecified
-        mask = D.AttnMask(visible[:, None], b, h, t, keys)
-        return D.mha_core_fwd(q, k, v, (b, h, t, keys, dk), scale, mask, kv_heads=hkv if hkv != h else None)[0]
 
     @staticmethod
     def _valid_rows(x: D.DeviceArray, length: int) -> D.DeviceArray:

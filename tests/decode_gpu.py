@@ -110,14 +110,18 @@ def run(q, k, v, lmax, scale, causal, kv_lens=None, new_lens=None, packed=False,
         table, page_rows = paged
         assert table.min() >= 0 and table.max() < k.shape[0], 'every table entry must name a page of the pool'
         table_dev = ints(table)
+        entry = 'npm_mha_decode_fwd_paged'
         rc = _C.lib().npm_mha_decode_fwd_paged(C.byref(c), lens_ptr, new_ptr, None if null_table else table_dev.ptr, table.shape[1],
                                                page_rows)
     elif kv_lens is None and not null_lens:
+        entry = 'npm_mha_decode_fwd'
         rc = _C.lib().npm_mha_decode_fwd(C.byref(c))
     else:
+        entry = 'npm_mha_decode_fwd_varlen'
         rc = _C.lib().npm_mha_decode_fwd_varlen(C.byref(c), lens_ptr, new_ptr)
     if expect:
         assert rc == expect, (rc, _C.lib().npm_last_error())
+        assert (entry + ':').encode() in _C.lib().npm_last_error(), 'the error names the entry point that was called'
         np.testing.assert_array_equal(ctx.numpy(), SENTINEL)              # nothing was launched
         return None
     _C.check(rc, 'npm_mha_decode_fwd[_varlen|_paged]')

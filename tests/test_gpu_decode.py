@@ -88,6 +88,7 @@ def _run(q, k, v, length, scale, causal, packed=False, want_lse=True, expect=0):
     rc = _C.lib().npm_mha_decode_fwd(C.byref(c))
     if expect:
         assert rc == expect, (rc, _C.lib().npm_last_error())
+        assert b'npm_mha_decode_fwd:' in _C.lib().npm_last_error(), 'the error names the entry point that was called'
         return None
     _C.check(rc, 'npm_mha_decode_fwd')
     out_ctx = _guarded(ctx, b * t * hq * d).reshape(b, t, hq, d)

@@ -118,6 +118,7 @@ def _decode16(q, kbuf, vbuf, pitch, stride, hkv, lmax, scale, causal, kv_lens=No
                                        None if table is None else table.ptr, table_pitch, page_rows)
     if expect:
         assert rc == expect, (rc, _lib().npm_last_error())
+        assert b'npm_mha_decode_fwd_f16:' in _lib().npm_last_error(), 'the error names the entry point that was called'
         np.testing.assert_array_equal(ctx.numpy(), SENTINEL)
         np.testing.assert_array_equal(lse.numpy(), SENTINEL)
         return None

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What the prefill attention kernel (npm_mha_prefill_fwd, csrc/npm_prefill.hip) buys the cached forwards that the decode kernel
 does not take, at D 128, Hq 8, Hkv in {8, 1}, page size 64.  Timed is the ATTENTION PART of ``att(x, cache=cache, ...)`` -- the
-layer's own ``_attend_ragged`` / ``_attend_cached`` on a cache that already holds this call's rows -- end to end by WALL CLOCK
+layer's own ``_attend`` on a cache that already holds this call's rows -- end to end by WALL CLOCK
 around a device synchronisation, so the switch-off path pays what it really pays per call: gathering K / V, building the mask with
 NumPy, uploading it, its tile summary, and the fused forward.  Both settings of ``device.PREFILL_KERNEL`` run in the same process on
 the same cache, interleaved (off, on, off, on, ...), after one untimed call each; min / median / max over the repetitions.
@@ -115,7 +115,7 @@ def main() -> None:
             fill(cache, lengths, hkv, rng)
             q = D.from_host(rng.standard_normal([b, t, h, d]).astype(np.float32))
             before = cache.lengths - n
-            fn = lambda: att._attend_ragged(Mat(q, f), cache, t, True, None, before, n)
+            fn = lambda: att._attend(Mat(q, f), cache, t, True, None, before, n, True)
             held = 2 * cache.pages * page * hkv * d * 4 / 2 ** 20
             print(f'(a) lengths sum {int(lengths.sum())} = {lengths.sum() / (b * lmax):.3f} B Lmax, max {int(lengths.max())}; the cache holds {held:.0f} MB of pages; '
                   f'mask [B, 1, T, keys] = {b * t * int(lengths.max()) / 2 ** 20:.0f} MB', flush=True)
@@ -131,12 +131,12 @@ def main() -> None:
             q = D.from_host(rng.standard_normal([b, t, h, d]).astype(np.float32))
             cache = D.PagedKVCache(b, have + t, hkv, d, page_size=page)
             fill(cache, rows, hkv, rng)
-            fn = lambda: att._attend_ragged(Mat(q, f), cache, t, True, None, rows - n, None)
+            fn = lambda: att._attend(Mat(q, f), cache, t, True, None, rows - n, None, True)
             compare(f'(b) chunk B {b} T {t} on {have} paged', setting(False, fn), setting(True, fn), 'gather + mask + fused forward', 'npm_mha_prefill_fwd paged')
             del cache
             cache = D.KVCache(b, have + t + 64, hkv, d)                   # not full: the fused path copies the valid rows
             fill(cache, rows, hkv, rng)
-            fn = lambda: att._attend_cached(Mat(q, f), cache, t, True, None)
+            fn = lambda: att._attend(Mat(q, f), cache, t, True, None, cache.lengths - t, None, False)
             compare(f'(b) chunk B {b} T {t} on {have} contig.', setting(False, fn), setting(True, fn), 'copy + mask + fused forward', 'npm_mha_prefill_fwd')
             assert att._cached_path == 'prefill'
             del cache, q
@@ -148,7 +148,7 @@ def main() -> None:
             fresh = D.from_host(rng.standard_normal([b, t, hkv * d]).astype(np.float32))
             cache = D.KVCache(b, t, hkv, d)
             cache.append(Mat(fresh, hkv * d), Mat(fresh, hkv * d), t)
-            off = lambda: att._attend_cached(Mat(q, f), cache, t, True, (Mat(fresh, hkv * d), Mat(fresh, hkv * d)))
+            off = lambda: att._attend(Mat(q, f), cache, t, True, (Mat(fresh, hkv * d), Mat(fresh, hkv * d)), cache.lengths - t, None, False)
             on = lambda: cache.attend(Mat(q, f), h, t, scale, True, kernel='prefill')[0]
             compare(f'(c) from empty B {b} T {t} Hkv {hkv}', setting(False, off), on, 'fused forward on the projection', 'npm_mha_prefill_fwd (forced)')
             del cache, q, fresh

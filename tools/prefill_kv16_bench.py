@@ -1,9 +1,8 @@
 #!/usr/bin/env python3
 """What the fp16 instance of the prefill attention kernel (npm_mha_prefill_fwd_f16, csrc/npm_prefill.hip) buys the cached forwards
 over a half-precision cache that the decode kernel does not take, on the cases of tools/prefill_bench.py: D 128, Hq 8, Hkv in
-{8, 1}, page size 64.  Timed is the ATTENTION PART of ``att(x, cache=cache, ...)`` -- the layer's own ``_attend_ragged`` /
-``_attend_cached`` on a cache that already holds this call's rows -- end to end by WALL CLOCK around a device synchronisation, so
-the switch-off path pays what it really pays per call: gathering K / V into fp32 copies, building the mask with NumPy, uploading
+{8, 1}, page size 64.  Timed is the ATTENTION PART of ``att(x, cache=cache, ...)`` -- the layer's own ``_attend`` on a cache that
+already holds this call's rows -- end to end by WALL CLOCK around a device synchronisation, so the switch-off path pays what it really pays per call: gathering K / V into fp32 copies, building the mask with NumPy, uploading
 it, its tile summary, and the fused forward.  The arms of a case run in one process, interleaved, after one untimed call each:
 the switch-off arm first and the kernel arms behind it in rotating order, so that each of them follows the switch-off arm (and the
 frees of its gathered copies) equally often.  K / V are cold (512 MB are written between two timed calls, twice the Infinity
@@ -155,7 +154,7 @@ def main() -> None:
             fill((half, full), lengths, hkv, rng)
             q = D.from_host(rng.standard_normal([b, t, h, d]).astype(np.float32))
             before = half.lengths - n
-            call = lambda cache: lambda: att._attend_ragged(Mat(q, f), cache, t, True, None, before, n)
+            call = lambda cache: lambda: att._attend(Mat(q, f), cache, t, True, None, before, n, True)
             print(f'(a) lengths sum {int(lengths.sum())} = {lengths.sum() / (b * lmax):.3f} B Lmax, max {int(lengths.max())}; the caches hold '
                   f'{half.nbytes / 2 ** 20:.0f} MB (fp16) and {full.nbytes / 2 ** 20:.0f} MB (fp32) of pages; one gathered fp32 K + V = '
                   f'{2 * b * int(lengths.max()) * hkv * d * 4 / 2 ** 20:.0f} MB', flush=True)
@@ -173,7 +172,7 @@ def main() -> None:
             half = D.PagedKVCache(b, have + t, hkv, d, page_size=page, dtype='f16')
             full = D.PagedKVCache(b, have + t, hkv, d, page_size=page)
             fill((half, full), rows, hkv, rng)
-            call = lambda cache: lambda: att._attend_ragged(Mat(q, f), cache, t, True, None, rows - n, None)
+            call = lambda cache: lambda: att._attend(Mat(q, f), cache, t, True, None, rows - n, None, True)
             compare(f'(b) chunk B {b} T {t} on {have} paged', arms(call, half, full, 'gather_f16 + mask + fused forward',
                                                                    'npm_mha_prefill_fwd_f16 paged', 'npm_mha_prefill_fwd paged'))
             assert att._cached_path == 'prefill'
@@ -185,7 +184,7 @@ def main() -> None:
             q = D.from_host(rng.standard_normal([b, t, h, d]).astype(np.float32))
             half, full = D.KVCache(b, t, hkv, d, dtype='f16'), D.KVCache(b, t, hkv, d)
             fill((half, full), np.full(b, t), hkv, rng)
-            through_layer = lambda cache: lambda: att._attend_cached(Mat(q, f), cache, t, True, None)
+            through_layer = lambda cache: lambda: att._attend(Mat(q, f), cache, t, True, None, cache.lengths - t, None, False)
             forced = lambda cache: lambda: cache.attend(Mat(q, f), h, t, scale, True, kernel='prefill')[0]
             compare(f'(c) from empty B {b} T {t} Hkv {hkv}',
                     [('f16 off', 'gather_f16 + mask + fused forward', setting('PREFILL_KERNEL_F16', False, through_layer(half))),
