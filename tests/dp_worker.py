@@ -104,7 +104,7 @@ def run_decoder(norm_first, q, kv, dy, comm, scale):
 def main():
     dist.init_process_group('gloo', init_method=f'tcp://127.0.0.1:{os.environ["MASTER_PORT"]}',
                             rank=int(os.environ['RANK']), world_size=int(os.environ['WORLD_SIZE']))
-    hostsim.install()
+    hostsim.install('training')
     rank, world = dist.get_rank(), dist.get_world_size()
     failures = []
     for kind in ('mlp', 'encoder_pre', 'encoder_post'):

@@ -38,7 +38,7 @@ def main():
     from conftest import assert_close, load_golden
     from oracle import np_oracle as O
 
-    hostsim.install()
+    hostsim.install('training')
     if REFERENCE:
         assert os.path.isfile(os.path.join(REFERENCE, 'train.py')), f'NPM_REFERENCE={REFERENCE} is not a reference checkout'
         npm.install()                           # `layers` now resolves to the device layers

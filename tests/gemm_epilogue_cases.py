@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY -- the fixed case lists of the GEMM epilogue tests, the harness that launches them through
-``device.gemm`` and the references they are held to.  tests/test_gemm_epilogue_host.py proves on the CPU (tests/hostsim.py) that
+``device.gemm`` and the references they are held to.  tests/test_gemm_epilogue_host.py proves on the CPU (tests/hostsim/) that
 every case meets the LDS-DMA predicate of ``npm_sgemm``, that every family reaches the ``write_tile_buf`` instance its name says,
 and that harness and references are right; tests/test_gpu_gemm_epilogue.py then runs the same lists on the device.
 

@@ -1,124 +1,28 @@
-"""TEST INFRASTRUCTURE ONLY -- a host-memory simulator of the libnpm_hip.so C ABI.
-
-It lets the CPU test-suite exercise the *host-side* logic of the product (Layer protocol,
-DeviceArray/optimizer contract, gradient bucketing, the data-parallel exchange over gloo)
-in a container without a GPU.  "Device pointers" are addresses of NumPy buffers; every
-entry point is restated with NumPy / the oracle.  The product never loads this: tests
-install it explicitly with ``hostsim.install()`` (which sets ``np_modeling_amd._C._LIB``).
-Numerical parity of the real kernels is established on the GPU (tests marked ``gpu``).
-"""
-
-from __future__ import annotations
+"""TEST INFRASTRUCTURE ONLY -- the entry points of training, restated with NumPy / the oracle: GEMM with its epilogues, elementwise
+and row kernels, the fused attention core (grouped and not), convolution, Adam, losses and dropout."""
 
 import ctypes as C
 
 import numpy as np
 
+import rope_reference as RR
 from oracle import np_oracle as O
 
-
-def _deref(arg):
-    return arg._obj if hasattr(arg, '_obj') else arg
+from .memory import BAD, UNSUPPORTED, _addr, _deref, _heads, _ints, _mat, _vec
 
 
-def _addr(p):
-    if p is None:
-        return 0
-    if isinstance(p, int):
-        return p
-    v = getattr(p, 'value', None)
-    return int(v) if v else 0
-
-
-def _vec(ptr, n):
-    n = int(n)
-    if n == 0:
-        return np.zeros(0, dtype=np.float32)
-    return np.ctypeslib.as_array((C.c_float * n).from_address(_addr(ptr)))
-
-
-def _mat(ptr, rows, cols, ld):
-    rows, cols, ld = int(rows), int(cols), int(ld)
-    if rows == 0 or cols == 0:
-        return np.zeros((rows, cols), dtype=np.float32)
-    flat = _vec(ptr, (rows - 1) * ld + cols)
-    return np.lib.stride_tricks.as_strided(flat, shape=(rows, cols), strides=(4 * ld, 4))
-
-
-class HostSim:
+class Training:
     def __init__(self):
-        self._blocks = {}
-        self._err = b''
-        self.calls = []
-
-    # ---- runtime ---------------------------------------------------------------------
-    def npm_abi_version(self):
-        return 2
-
-    def npm_last_error(self):
-        return self._err
-
-    def npm_init(self, device):
-        return 0
-
-    def npm_shutdown(self):
-        return 0
-
-    def npm_sync(self):
-        return 0
-
-    def npm_stream(self):
-        return 0
-
-    def npm_malloc(self, out, nbytes):
-        buf = np.empty(max(int(nbytes), 4) // 4 + 4, dtype=np.float32)
-        buf.fill(np.nan)                                   # poison: catches reads of unwritten memory
-        addr = buf.ctypes.data
-        addr_aligned = (addr + 15) // 16 * 16
-        self._blocks[addr_aligned] = buf
-        _deref(out).value = addr_aligned
-        return 0
-
-    def npm_free(self, ptr):
-        self._blocks.pop(_addr(ptr), None)
-        return 0
-
-    def npm_pool_stats(self, a, b):
-        _deref(a).value = sum(v.nbytes for v in self._blocks.values())
-        _deref(b).value = _deref(a).value
-        return 0
-
-    def npm_pool_trim(self):
-        return 0
-
-    def npm_h2d(self, dst, src, nbytes):
-        C.memmove(_addr(dst), _addr(src), int(nbytes))
-        return 0
-
-    npm_d2h = npm_h2d
-    npm_d2d = npm_h2d
-
-    def npm_fill_f32(self, dst, value, n):
-        _vec(dst, n)[:] = value
-        return 0
-
-    def npm_event_create(self, out):
-        _deref(out).value = 1
-        return 0
-
-    def npm_event_destroy(self, ev):
-        return 0
-
-    npm_event_record = npm_event_sync = npm_event_destroy
-
-    def npm_event_elapsed_ms(self, a, b, out):
-        _deref(out).value = 0.0
-        return 0
+        super().__init__()
+        self.ropes = []                   # the arguments of every npm_rope
 
     # ---- GEMM ----------------------------------------------------------------------------
     def npm_sgemm(self, gref):
-        g = _deref(gref)
         self.calls.append('npm_sgemm')
+        return self._sgemm(_deref(gref))
+
+    def _sgemm(self, g):
+        """The float64 restatement of every GEMM entry point; the caller records the call."""
         sums = np.zeros((g.batch1, g.n), dtype=np.float64)
         for z0 in range(g.batch0):
             for z1 in range(g.batch1):
@@ -146,7 +50,7 @@ class HostSim:
                 _mat(g.c + oc, g.m, g.n, g.ldc)[:] = v
                 if g.epilogue & 128:                     # NPM_EPI_ROWDOT: per block of 128 columns, row dots of C with aux, added to zeros
                     if g.epilogue != 128 or g.trans_a or g.trans_b or g.n % 128 or g.k % 16 or g.batch0 * g.batch1 != 1:
-                        return 10003
+                        return UNSUPPORTED
                     prod = _mat(g.c + oc, g.m, g.n, g.ldc).astype(np.float64) * _mat(g.aux + oc, g.m, g.n, g.ldaux).astype(np.float64)
                     out = _vec(g.rowdot, (g.n // 128) * g.m).reshape(g.n // 128, g.m)
                     assert not np.isnan(out).any() and (out == 0).all(), 'NPM_EPI_ROWDOT: rowdot must be zero on entry'
@@ -286,12 +190,6 @@ class HostSim:
     def npm_mha_core_supported(self, head_dim):
         return int(head_dim in (16, 32, 64, 128))
 
-    @staticmethod
-    def _heads(ptr, pitch, b, s, h, d):
-        """[B, S, H, D] view of a pitched operand."""
-        flat = _vec(ptr, ((b * s - 1) * pitch + h * d) if b * s else 0)
-        return np.lib.stride_tricks.as_strided(flat, shape=(b, s, h, d), strides=(4 * s * pitch, 4 * pitch, 4 * d, 4))
-
     def _core_mask(self, c):
         if not c.mask:
             return None
@@ -305,14 +203,14 @@ class HostSim:
         c = _deref(cref)
         self.calls.append('npm_mha_core_fwd')
         if c.head_dim not in (16, 32, 64, 128):
-            return 10003
+            return UNSUPPORTED
         b, h, sq, skv, d = c.batch, c.heads, c.seq_q, c.seq_kv, c.head_dim
-        q, k, v = (self._heads(ptr, pitch, b, s, h, d).astype(np.float64)
+        q, k, v = (_heads(ptr, pitch, b, s, h, d).astype(np.float64)
                    for ptr, pitch, s in ((c.q, c.q_pitch, sq), (c.k, c.k_pitch, skv), (c.v, c.v_pitch, skv)))
         mask = self._core_mask(c)
         with np.errstate(invalid='ignore'):
             ctx, lse, _ = O.attention_core_fwd(q, k, v, float(c.scale), mask)
-        self._heads(c.ctx, c.ctx_pitch, b, sq, h, d)[:] = ctx
+        _heads(c.ctx, c.ctx_pitch, b, sq, h, d)[:] = ctx
         _vec(c.lse, b * h * sq)[:] = lse.ravel()
         if c.scores:
             raw = np.einsum('bqhd,bkhd->bhqk', q, k)
@@ -323,9 +221,9 @@ class HostSim:
         c = _deref(cref)
         self.calls.append('npm_mha_core_bwd')
         b, h, sq, skv, d = c.batch, c.heads, c.seq_q, c.seq_kv, c.head_dim
-        q, k, v = (self._heads(ptr, pitch, b, s, h, d).astype(np.float64)
+        q, k, v = (_heads(ptr, pitch, b, s, h, d).astype(np.float64)
                    for ptr, pitch, s in ((c.q, c.q_pitch, sq), (c.k, c.k_pitch, skv), (c.v, c.v_pitch, skv)))
-        dctx = self._heads(c.dctx, c.dctx_pitch, b, sq, h, d).astype(np.float64)
+        dctx = _heads(c.dctx, c.dctx_pitch, b, sq, h, d).astype(np.float64)
         lse = _vec(c.lse, b * h * sq).astype(np.float64).reshape(b, h, sq)
         scaled = float(c.scale) * np.einsum('bqhd,bkhd->bhqk', q, k)
         mask = self._core_mask(c)
@@ -333,16 +231,72 @@ class HostSim:
             scaled = np.where(mask, scaled, -np.inf)
         probs = np.exp(scaled - lse[..., None])             # from the saved log-sum-exp, as the kernel does
         if c.neg_delta:                                     # the caller's row terms: what the kernel would have computed itself
-            ctx = self._heads(c.ctx, c.ctx_pitch, b, sq, h, d).astype(np.float64)
+            ctx = _heads(c.ctx, c.ctx_pitch, b, sq, h, d).astype(np.float64)
             want = -float(c.scale) * np.einsum('bqhd,bqhd->bhq', dctx, ctx)
             extent = (b - 1) * c.neg_delta_stride_b + (h - 1) * c.neg_delta_stride_h + sq
             got = np.lib.stride_tricks.as_strided(_vec(c.neg_delta, extent), shape=(b, h, sq),
                                                   strides=(4 * c.neg_delta_stride_b, 4 * c.neg_delta_stride_h, 4))
             np.testing.assert_allclose(got, want, rtol=2e-5, atol=2e-5 * (np.abs(want).max() + 1e-30), err_msg='neg_delta')
         dq, dk, dv = O.attention_core_bwd(q, k, v, probs, dctx, float(c.scale))
-        self._heads(c.dq, c.dq_pitch, b, sq, h, d)[:] = dq
-        self._heads(c.dk, c.dk_pitch, b, skv, h, d)[:] = dk
-        self._heads(c.dv, c.dv_pitch, b, skv, h, d)[:] = dv
+        _heads(c.dq, c.dq_pitch, b, sq, h, d)[:] = dq
+        _heads(c.dk, c.dk_pitch, b, skv, h, d)[:] = dk
+        _heads(c.dv, c.dv_pitch, b, skv, h, d)[:] = dv
+        return 0
+
+    @staticmethod
+    def _widened(c, kv_heads):
+        """K and V expanded to one head per query head: query head h reads K / V head h % kv_heads."""
+        return [np.ascontiguousarray(_heads(ptr, pitch, c.batch, c.seq_kv, kv_heads, c.head_dim)[:, :, np.arange(c.heads) % kv_heads])
+                for ptr, pitch in ((c.k, c.k_pitch), (c.v, c.v_pitch))]
+
+    def npm_mha_core_fwd_grouped(self, cref, kv_heads):
+        """The ungrouped restatement on expanded K / V."""
+        c = _deref(cref)
+        self.calls.append('npm_mha_core_fwd_grouped')
+        wide = self._widened(c, kv_heads)
+        saved = (c.k, c.k_pitch, c.v, c.v_pitch)
+        c.k, c.k_pitch, c.v, c.v_pitch = wide[0].ctypes.data, c.heads * c.head_dim, wide[1].ctypes.data, c.heads * c.head_dim
+        try:
+            return self.npm_mha_core_fwd(cref)
+        finally:
+            c.k, c.k_pitch, c.v, c.v_pitch = saved
+
+    def npm_mha_core_bwd_grouped(self, cref, kv_heads):
+        """The ungrouped restatement on expanded K / V; dK / dV of a K / V head are the sums over its query heads."""
+        c = _deref(cref)
+        b, h, skv, d = c.batch, c.heads, c.seq_kv, c.head_dim
+        wide = self._widened(c, kv_heads)
+        grads = [np.zeros([b, skv, h, d], dtype=np.float32) for _ in range(2)]
+        saved = (c.k, c.k_pitch, c.v, c.v_pitch, c.dk, c.dk_pitch, c.dv, c.dv_pitch)
+        c.k, c.k_pitch, c.v, c.v_pitch = wide[0].ctypes.data, h * d, wide[1].ctypes.data, h * d
+        c.dk, c.dk_pitch, c.dv, c.dv_pitch = grads[0].ctypes.data, h * d, grads[1].ctypes.data, h * d
+        try:
+            rc = self.npm_mha_core_bwd(cref)
+        finally:
+            c.k, c.k_pitch, c.v, c.v_pitch, c.dk, c.dk_pitch, c.dv, c.dv_pitch = saved
+        for grad, ptr, pitch in ((grads[0], c.dk, c.dk_pitch), (grads[1], c.dv, c.dv_pitch)):
+            _heads(ptr, pitch, b, skv, kv_heads, d)[:] = grad.astype(np.float64).reshape(b, skv, h // kv_heads, kv_heads, d).sum(axis=2)
+        return rc
+
+    def npm_rope(self, x, pitch, batch, tokens, heads, head_dim, cos, sin, table_rows, at, at_lens, inverse):
+        """tests/rope_reference.py ``rotate``, the bitwise model of the kernel; rows outside the table are left untouched."""
+        self.calls.append('npm_rope')
+        self.ropes.append(dict(x=_addr(x), pitch=int(pitch), batch=batch, tokens=tokens, heads=heads, head_dim=head_dim,
+                               table_rows=table_rows, at=at, at_lens=_addr(at_lens), inverse=int(inverse)))
+        if not (_addr(x) and _addr(cos) and _addr(sin)):
+            return BAD
+        if min(batch, tokens, heads, table_rows) < 1 or head_dim < 2 or head_dim % 2 or pitch < heads * head_dim:
+            return BAD
+        if not _addr(at_lens) and (at < 0 or at + tokens > table_rows):
+            return BAD
+        half = head_dim // 2
+        c, s = (_vec(t, table_rows * half).reshape(table_rows, half) for t in (cos, sin))
+        rows = _heads(x, pitch, batch, tokens, heads, head_dim)
+        start = _ints(at_lens, batch) if _addr(at_lens) else np.full(batch, at, dtype=np.int64)
+        positions = start[:, None] + np.arange(tokens)[None, :]
+        inside = (positions >= 0) & (positions < table_rows)
+        rotated = RR.rotate(np.ascontiguousarray(rows), np.where(inside, positions, 0), c, s, inverse=bool(inverse))
+        rows[inside] = rotated[inside]
         return 0
 
     # ---- conv -----------------------------------------------------------------------------------
@@ -380,26 +334,16 @@ class HostSim:
         return self.npm_conv2d_bwd_w(g, x, dw, n, h, w, c0, c1, k)
 
     # ---- around the path -------------------------------------------------------------------------
-    def npm_fill_f64(self, dst, value, n):
-        if int(n) == 0:
-            return 0
-        if not _addr(dst):
-            return 10002
-        if value != 0.0:
-            return 10003                                    # only 0.0 is supported
-        np.ctypeslib.as_array((C.c_double * int(n)).from_address(_addr(dst)))[:] = value
-        return 0
-
     def npm_adam_step(self, var, grad, m, v, n, lr, beta1, beta2, eps, step):
         """csrc/npm_optim.hip adam_kernel = reference optimizer.py:58-63: the two gradient products in float32, the rest in float64."""
         self.calls.append('npm_adam_step')
         n = int(n)
         if step < 1:
-            return 10002
+            return BAD
         if n == 0:
             return 0
         if not (_addr(var) and _addr(grad) and _addr(m) and _addr(v)):
-            return 10002
+            return BAD
         mm = np.ctypeslib.as_array((C.c_double * n).from_address(_addr(m)))
         vv = np.ctypeslib.as_array((C.c_double * n).from_address(_addr(v)))
         g = _vec(grad, n)                                   # float32: the two products below stay float32
@@ -413,7 +357,7 @@ class HostSim:
 
     def npm_mse_fwd(self, y, t, n, out):
         if int(n) == 0 or not (_addr(y) and _addr(t)):
-            return 10002
+            return BAD
         d = _vec(y, n).astype(np.float64) - _vec(t, n)
         _deref(out).value = float((d * d).sum() / int(n))
         return 0
@@ -426,7 +370,7 @@ class HostSim:
 
     def npm_xent_fwd(self, y, t, n, out):
         if int(n) == 0 or not (_addr(y) and _addr(t)):
-            return 10002
+            return BAD
         with np.errstate(all='ignore'):
             _deref(out).value = float(-(_vec(t, n).astype(np.float64) * np.log(_vec(y, n).astype(np.float64))).sum())
         return 0
@@ -443,7 +387,7 @@ class HostSim:
         if int(n) == 0:
             return 0
         if not (_addr(x) and _addr(mask) and _addr(y) and keep > 0):
-            return 10002
+            return BAD
         mk = np.ctypeslib.as_array((C.c_ubyte * int(n)).from_address(_addr(mask)))
         _vec(y, n)[:] = np.where(mk != 0, _vec(x, n) / np.float32(keep), 0)
         return 0
@@ -453,41 +397,13 @@ class HostSim:
         if int(n) == 0:
             return 0
         if not _addr(mask) or bool(_addr(x)) != bool(_addr(y)) or not 0.0 < keep <= 1.0:
-            return 10002
+            return BAD
         keep_mask = O.dropout_philox_mask(int(n), float(keep), int(seed), int(offset))
         np.ctypeslib.as_array((C.c_ubyte * int(n)).from_address(_addr(mask)))[:] = keep_mask
         if _addr(y):                               # x = y = NULL: the mask only
             _vec(y, n)[:] = np.where(keep_mask, _vec(x, n) / np.float32(keep), 0)
         return 0
 
-    def npm_set_math(self, mode):
-        self.math = int(mode)
-        return 0
-
-    def npm_get_math(self):
-        return getattr(self, 'math', 0)
-
-    def npm_last_math(self):
-        return 0
-
-    def npm_set_tuning(self, knob, value):
-        return 0
-
     def npm_last_attn_kernel(self):
         last = [c for c in self.calls if c.startswith('npm_mha_core_')]
         return (('hostsim ' + last[-1]) if last else '').encode()
-
-
-def install():
-    """Install a fresh simulator as the product's library handle; returns it."""
-    from np_modeling_amd import _C
-    sim = HostSim()
-    _C._LIB = sim
-    _C._DEVICE = 0
-    return sim
-
-
-def uninstall():
-    from np_modeling_amd import _C
-    _C._LIB = None
-    _C._DEVICE = None

@@ -1,5 +1,5 @@
 """References shared by the tests of the half-precision key / value cache (tests/test_kv16_host.py on the simulator of
-tests/hostsim_kv16.py, tests/test_gpu_kv16.py on the MI355X): NumPy's own float16 rounding as the definition of what an append
+tests/hostsim/ (profile 'kv16'), tests/test_gpu_kv16.py on the MI355X): NumPy's own float16 rounding as the definition of what an append
 stores, the derived worst-case distance between attention over an fp16 cache and over the fp32 one, the row of edge values, fp16
 buffers with guard regions, and the thinned case grid of the bitwise comparison."""
 

@@ -6,6 +6,7 @@ import os
 import re
 
 import pytest
+from hostsim.fixtures import built
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -14,15 +15,6 @@ def declared(header):
     text = open(os.path.join(ROOT, 'include', header)).read()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     return sorted(set(re.findall(r'\b(npm_\w+)\s*\(', text)))
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as entry
-    from np_modeling_amd import _C
-    if not (os.path.exists(_C.LIB_PATH) and os.path.exists(_C.RCCL_LIB_PATH)):
-        entry.build()
-    return _C
 
 
 def test_every_declared_symbol_is_exported_and_bound(built):

@@ -1,4 +1,4 @@
-"""CPU: beam search without a GPU, on the simulator of tests/hostsim_beam.py.
+"""CPU: beam search without a GPU, on the simulator of tests/hostsim/ (profile 'beam').
 
 * the reference alone: at most 5 % of the general family is ambiguous (a gap among the model's first 2 W + 1 scores within
   2 eps), the exact family passes its filter, and the contract restated in tests/beam_reference.py meets its own fp64 model;
@@ -20,22 +20,13 @@ import pytest
 
 import beam_cases as BC
 import beam_reference as BR
-import hostsim_beam
+from hostsim.fixtures import npm_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST_GENERAL = [c for c in BC.GENERAL if c[0] <= 4099 or (c[0], c[1], c[2]) in ((32768, 3, 1), (32769, 2, 3), (65537, 8, 1))]
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_beam.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_beam.uninstall()
+npm = npm_fixture('beam')
 
 
 # ---- the reference alone --------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""CPU: what the key / value caches ASK of the library, call for call, on the simulator of tests/hostsim_paged.py.
+"""CPU: what the key / value caches ASK of the library, call for call, on the simulator of tests/hostsim/ (profile 'paged').
 
 One scripted scenario runs through ``MultiHeadAttention`` with a ``KVCache`` and again with a ``PagedKVCache`` (pages of 16 rows,
 a pool smaller than batch x pages per sequence), and a ``TransformerDecoder`` goes through release and admit.  After every step
@@ -11,22 +11,13 @@ import numpy as np
 import pytest
 
 import decode_cases as DC
-import hostsim_paged
+from hostsim.fixtures import npm_fixture
 
 F, HEADS, KV_HEADS, BATCH, CAPACITY = 64, 4, 2, 3, 48
 PAGE, POOL = 16, 7                                                        # 3 sequences x 3 pages would be 9
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_paged.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_paged.uninstall()
+npm = npm_fixture('paged')
 
 
 class _Trace:

@@ -4,7 +4,7 @@
   decoding in chunks with a cache equals the full causal forward, for multi-head and grouped-query attention;
 * a float32 model of the kernel's split / combine rule against float64 at every (L, D, splits) tests/test_gpu_decode.py uses:
   its error stays under HALF of the bound the GPU test applies there, so the bound is one the method can meet;
-* the product's host logic on the simulator (tests/hostsim_decode.py): cache bookkeeping, capacity overflow raised before any
+* the product's host logic on the simulator (tests/hostsim/ (profile 'decode')): cache bookkeeping, capacity overflow raised before any
   call, reset, backward after a cached forward, the frozen cross-attention cache, which path a cached forward selects, the
   causal decoder and ``decode`` against the restatements;
 * the new struct's layout and the new entry points against the header.
@@ -23,7 +23,7 @@ import attn_range_data as R
 import decode_cases as DC
 import decode_reference as DR
 import gqa_reference as G
-import hostsim_decode
+from hostsim.fixtures import built, npm_fixture
 from oracle import np_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -131,16 +131,7 @@ def test_split_model_gives_empty_splits_weight_zero():
 
 
 # ---- host logic on the simulator -------------------------------------------------------------------------------------------
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_decode.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_decode.uninstall()
+npm = npm_fixture('decode')
 
 
 def test_cache_bookkeeping_overflow_and_reset(npm):
@@ -313,15 +304,6 @@ def test_default_decoder_passes_no_mask(npm):
 
 
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as entry
-    from np_modeling_amd import _C
-    if not (os.path.exists(_C.LIB_PATH) and os.path.exists(_C.RCCL_LIB_PATH)):
-        entry.build()
-    return _C
-
-
 def test_decode_struct_layout_matches_header(built):
     """npm_mha_decode: field order of the ctypes mirror equals the C declaration; size and offsets as a C compiler sees them."""
     _C = built

@@ -1,4 +1,4 @@
-"""CPU: shared key / value prefixes without a GPU, on the simulator of tests/hostsim_prefix.py.
+"""CPU: shared key / value prefixes without a GPU, on the simulator of tests/hostsim/kvcache.py.
 
 * ``device.PagedKVCache.fork``: reference counts, free list and table after fork / append / truncate / release; copy-on-write of a
   partly filled shared page exactly once per appender but the last owner; a full shared page never copied; ``room`` refusing with
@@ -19,23 +19,15 @@ import numpy as np
 import pytest
 
 import decode_cases as DC
-import hostsim_prefix
+import hostsim
+from hostsim.fixtures import npm_fixture
 import varlen_reference as VR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROW = 32                                   # Hkv * D of the bare caches below: 2 heads of 16
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_prefix.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_prefix.uninstall()
+npm = npm_fixture('prefix')
 
 
 def _rows(seed, count):
@@ -345,7 +337,7 @@ def test_the_entry_points_called_with_the_switch_on_and_off(npm, monkeypatch, dt
         for call in seen:
             assert call['prefix'] == 64 and call['rows'] == 4 * tokens and call['f16'] == (dtype == 'f16')
             assert call['pages'] == cache.block_table[0, :4].tolist()
-            assert call['splits'] == hostsim_prefix.auto_splits(4 * tokens, 8, 1, 64) == 1
+            assert call['splits'] == hostsim.kvcache.auto_splits(4 * tokens, 8, 1, 64) == 1
         if dtype == 'f32':
             for step in range(3):
                 for b in range(3):
@@ -381,7 +373,7 @@ def test_the_split_knob_reaches_the_prefix_pass(npm, monkeypatch):
     out, want, _ = _forked_layer_run(npm, 'f32', 1, steps=1)
     assert [c['splits'] for c in npm.sim.prefix_calls] == [3]
     assert np.abs(out[0][0][0] - want[0]).max() <= 2e-5 * (1 + np.abs(want[0]).max())
-    assert hostsim_prefix.split_ranges(64, 3) == [(0, 32), (32, 64), (64, 64)]        # an empty split is allowed
+    assert hostsim.kvcache.split_ranges(64, 3) == [(0, 32), (32, 64), (64, 64)]        # an empty split is allowed
 
 
 # ---- the contiguous cache and the decoder ----------------------------------------------------------------------------------------------
@@ -459,7 +451,7 @@ def test_prefix_entry_points_are_declared_bound_exported_and_refuse_without_a_de
     text = open(os.path.join(ROOT, 'include', 'npm_hip.h')).read()
     assert re.search(r'#define\s+NPM_ABI_VERSION\s+2\b', text)              # additions: the version stays
     assert int(re.search(r'NPM_TUNE_PREFIX_SPLITS\s*=\s*(\d+)', text).group(1)) == _C.TUNE_PREFIX_SPLITS
-    assert int(re.search(r'#define\s+NPM_PREFIX_MAX_SPLITS\s+(\d+)', text).group(1)) == _C.PREFIX_MAX_SPLITS == hostsim_prefix.MAX_SPLITS
+    assert int(re.search(r'#define\s+NPM_PREFIX_MAX_SPLITS\s+(\d+)', text).group(1)) == _C.PREFIX_MAX_SPLITS == hostsim.kvcache.MAX_SPLITS
     ctype = {'const npm_mha_decode *': ctypes.POINTER(_C.npm_mha_decode), 'const int32_t *': ctypes.c_void_p, 'int32_t': ctypes.c_int32,
              'int64_t': ctypes.c_int64, 'int': ctypes.c_int, 'float *': ctypes.c_void_p, 'const float *': ctypes.c_void_p,
              'void *': ctypes.c_void_p}
@@ -476,9 +468,9 @@ def test_prefix_entry_points_are_declared_bound_exported_and_refuse_without_a_de
     bound = _C.load_library()
     assert bound.npm_last_prefix_kernel() == b''
     assert [bound.npm_mha_prefix_supported(d) for d in (16, 32, 64, 128, 24, 256)] == [1, 1, 1, 1, 0, 0]
-    # the split rule: a function of the shape only, restated in tests/hostsim_prefix.py
+    # the split rule: a function of the shape only, restated in tests/hostsim/kvcache.py
     for shape in ((64, 64, 8, 8192), (8, 64, 8, 2048), (1, 8, 8, 512), (256, 8, 1, 8192), (4, 6, 3, 2112), (2, 8, 8, 16), (64, 128, 1, 8192)):
-        assert bound.npm_mha_prefix_splits(*shape) == hostsim_prefix.auto_splits(*shape), shape
+        assert bound.npm_mha_prefix_splits(*shape) == hostsim.kvcache.auto_splits(*shape), shape
     assert bound.npm_mha_prefix_splits(64, 64, 8, 8192) == 8 and bound.npm_mha_prefix_splits(1, 8, 8, 512) == 4
     assert bound.npm_mha_prefix_splits(0, 8, 8, 512) == 1 and bound.npm_mha_prefix_splits(4, 6, 4, 512) == 1
     count = ctypes.c_int(0)

@@ -4,7 +4,7 @@
   ``write_tile_buf`` (csrc/npm_mfma_tile.h:354-411) are restated in Python in the cases module (each line cited there); every case
   of every list must meet the LDS-DMA predicate -- the share left out is zero, as a condition --, every family must reach the
   instance it is named after, and every (family, layout) list must cover all M, N and K classes.
-* The harness: the whole grid runs through tests/hostsim.py's ``npm_sgemm`` with the GPU test's own harness -- guards, padding
+* The harness: the whole grid runs through tests/hostsim/'s ``npm_sgemm`` with the GPU test's own harness -- guards, padding
   sentinels and untouched inputs checked, results held to float64 at 3e-6 (the simulator computes in float64, so the equality arm
   is off here).
 * The float32 reference expressions against a per-element Python loop.
@@ -20,7 +20,7 @@ import hostsim
 @pytest.fixture
 def D():
     from np_modeling_amd import device, parallel
-    hostsim.install()
+    hostsim.install('training')
     parallel.set_communicator(None)
     yield device
     parallel.set_communicator(None)

@@ -11,18 +11,10 @@ import pytest
 
 import gqa_reference as G
 from oracle import np_oracle as O
+from hostsim.fixtures import built
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GROUPED = ('npm_mha_core_fwd_grouped', 'npm_mha_core_bwd_grouped')
-
-
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as entry
-    from np_modeling_amd import _C
-    if not (os.path.exists(_C.LIB_PATH) and os.path.exists(_C.RCCL_LIB_PATH)):
-        entry.build()
-    return _C
 
 
 def test_grouped_entry_points_are_declared_exported_and_bound(built):

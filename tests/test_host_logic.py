@@ -1,4 +1,4 @@
-"""CPU: host-side logic of the product on the host simulator of the C ABI (tests/hostsim.py):
+"""CPU: host-side logic of the product on the host simulator of the C ABI (tests/hostsim/):
 Layer protocol, weight layouts / GEMM descriptors against the reference's golden outputs,
 gradient bucketing, and the data-parallel exchange over gloo with world_size 2.
 
@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def npm():
     import np_modeling_amd
     from np_modeling_amd import parallel
-    hostsim.install()
+    hostsim.install('training')
     parallel.set_communicator(None)
     yield np_modeling_amd
     parallel.set_communicator(None)

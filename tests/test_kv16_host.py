@@ -1,4 +1,4 @@
-"""CPU: the half-precision key / value cache without a GPU, on the simulator of tests/hostsim_kv16.py.
+"""CPU: the half-precision key / value cache without a GPU, on the simulator of tests/hostsim/ (profile 'kv16').
 
 * what an append stores is NumPy's ``astype(np.float16)``: the row of edge values of tests/kv16_reference.py against bit patterns
   worked out by hand (IEEE round to nearest even, overflow to inf at 65520, subnormal results kept);
@@ -22,8 +22,7 @@ import pytest
 
 import decode_cases as DC
 import decode_reference as DR
-import hostsim_kv16
-import hostsim_prefill
+from hostsim.fixtures import activate, built, deactivate, npm_fixture
 import kv16_reference as K16
 import varlen_reference as VR
 
@@ -32,21 +31,7 @@ F32_CACHE_CALLS = ('npm_kv_append', 'npm_kv_append_varlen', 'npm_kv_append_paged
                    'npm_mha_decode_fwd', 'npm_mha_decode_fwd_varlen', 'npm_mha_decode_fwd_paged', 'npm_mha_prefill_fwd')
 
 
-def _npm(module):
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = module.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    return np_modeling_amd
-
-
-@pytest.fixture
-def npm():
-    from np_modeling_amd import parallel
-    yield _npm(hostsim_kv16)
-    parallel.set_communicator(None)
-    hostsim_kv16.uninstall()
+npm = npm_fixture('kv16')
 
 
 # ---- the references themselves ------------------------------------------------------------------------------------------------------
@@ -342,31 +327,20 @@ def _fp32_schedule(npm):
 def test_an_fp32_cache_makes_exactly_the_calls_it_made_before():
     """The same schedule on the simulator WITHOUT the new entry points and, with the keyword left at its default, on the one with
     them: the recorded call lists and the results are identical."""
-    from np_modeling_amd import parallel
     records = []
-    for module in (hostsim_prefill, hostsim_kv16):
-        npm = _npm(module)
+    for profile in ('prefill', 'kv16'):
+        npm = activate(profile)
         try:
-            assert hasattr(npm.sim, 'npm_kv_append_f16') == (module is hostsim_kv16)
+            assert hasattr(npm.sim, 'npm_kv_append_f16') == (profile == 'kv16')
             records.append(_fp32_schedule(npm))
         finally:
-            parallel.set_communicator(None)
-            module.uninstall()
+            deactivate()
     assert records[0][0] == records[1][0] and len(records[0][0]) > 50 and not any(c.endswith('_f16') for c in records[1][0])
     for a, b in zip(records[0][1], records[1][1]):
         assert np.array_equal(a, b, equal_nan=True)
 
 
 # ---- the C ABI ------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as entry
-    from np_modeling_amd import _C
-    if not (os.path.exists(_C.LIB_PATH) and os.path.exists(_C.RCCL_LIB_PATH)):
-        entry.build()
-    return _C
-
-
 def test_f16_entry_points_header_against_bindings(built):
     _C = built
     text = open(os.path.join(ROOT, 'include', 'npm_hip.h')).read()

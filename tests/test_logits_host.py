@@ -1,4 +1,4 @@
-"""CPU: the logit processors on the host simulator (tests/hostsim_logits.py) and their reference (tests/logits_reference.py).
+"""CPU: the logit processors on the host simulator (tests/hostsim/ (profile 'logits')) and their reference (tests/logits_reference.py).
 
 * the reference on hand-worked rows; the case lists of tests/logits_cases.py through the C-ABI runner on the simulator;
 * row r of a chunk equals the rows = 1 call with the draft prefix appended; slot b of a batch equals the batch-1 call;
@@ -19,22 +19,13 @@ import numpy as np
 import pytest
 
 import controls_cases as GC
-import hostsim_logits
+from hostsim.fixtures import npm_fixture
 import logits_cases as LC
 import logits_reference as LR
 import spec_cases as XC
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_logits.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_logits.uninstall()
+npm = npm_fixture('logits')
 
 
 # ---- the reference ---------------------------------------------------------------------------------------------------------------------

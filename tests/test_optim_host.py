@@ -1,6 +1,6 @@
 """CPU: the optimizer, loss and dropout entry points (csrc/npm_optim.hip) without a GPU.
 
-* the cases of tests/optim_cases.py on the simulator of tests/hostsim.py, so that every check of tests/test_gpu_optim.py has run
+* the cases of tests/optim_cases.py on the simulator of tests/hostsim/, so that every check of tests/test_gpu_optim.py has run
   (and its near-tie count has been asserted for every Adam case) before a GPU sees it;
 * the Adam model of tests/optim_reference.py against the reference's own ``AdamOptimizer`` (where a checkout of the reference is at
   hand) and against the arrays recorded from it (tests/golden/adam_steps.npz);
@@ -17,23 +17,14 @@ import weakref
 import numpy as np
 import pytest
 
-import hostsim
+from hostsim.fixtures import npm_fixture
 import optim_cases as OC
 import optim_reference as R
 from conftest import load_golden
 from oracle import np_oracle as O
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim.uninstall()
+npm = npm_fixture('training')
 
 
 # ---- the same cases as on the GPU ---------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""CPU: the paged key / value cache without a GPU, on the simulator of tests/hostsim_paged.py.
+"""CPU: the paged key / value cache without a GPU, on the simulator of tests/hostsim/ (profile 'paged').
 
 * ``device.PagedKVCache``: page sizes it takes, the pool (not batch x capacity) as the limit -- an append that needs more pages
   than are free raises before any call is recorded and leaves lengths, table and free list as they were; ``release`` gives the
@@ -22,23 +22,14 @@ import numpy as np
 import pytest
 
 import decode_cases as DC
-import hostsim_paged
+from hostsim.fixtures import built, npm_fixture
 import paged_cases as PC
 import varlen_reference as VR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_paged.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_paged.uninstall()
+npm = npm_fixture('paged')
 
 
 def _owned(cache):
@@ -357,15 +348,6 @@ def test_decoder_release_and_admit_with_a_longer_memory(npm, norm_first):
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as entry
-    from np_modeling_amd import _C
-    if not (os.path.exists(_C.LIB_PATH) and os.path.exists(_C.RCCL_LIB_PATH)):
-        entry.build()
-    return _C
-
-
 def test_paged_entry_points_header_against_bindings(built):
     _C = built
     text = open(os.path.join(ROOT, 'include', 'npm_hip.h')).read()

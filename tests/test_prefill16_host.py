@@ -1,4 +1,4 @@
-"""CPU: the prefill attention kernel over half-precision caches without a GPU, on the simulator of tests/hostsim_prefill16.py.
+"""CPU: the prefill attention kernel over half-precision caches without a GPU, on the simulator of tests/hostsim/ (profile 'prefill16').
 
 * routing with ``device.PREFILL_KERNEL_F16`` on: whatever the decode kernel does not take over an fp16 cache -- a prefill from
   empty, a chunk on cached rows, a ragged or paged prefill, a frozen cross cache, the prompt of ``dec.admit`` -- has
@@ -26,8 +26,7 @@ import pytest
 
 import decode_cases as DC
 import decode_reference as DR
-import hostsim_kv16
-import hostsim_prefill16
+from hostsim.fixtures import activate, built, deactivate, npm_fixture
 import kv16_reference as K16
 import varlen_reference as VR
 
@@ -38,21 +37,7 @@ OLD_PATH = ('npm_kv_gather_f16', 'npm_mha_mask_summary', 'npm_mha_core_fwd', 'np
 ENTRY = 'npm_mha_prefill_fwd_f16'
 
 
-def _npm(module):
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = module.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    return np_modeling_amd
-
-
-@pytest.fixture
-def npm():
-    from np_modeling_amd import parallel
-    yield _npm(hostsim_prefill16)
-    parallel.set_communicator(None)
-    hostsim_prefill16.uninstall()
+npm = npm_fixture('prefill16')
 
 
 @pytest.fixture
@@ -186,7 +171,7 @@ def _switch_off_record(npm):
     """What tests/golden/kv16_calls_before_prefill16.json holds: the library calls and ``_cached_path`` of fp16 caches through the
     chunks 40, 1, 3, 40, 1 of tests/test_kv16_host.py's test_layer_attends_to_the_rows_as_stored at its three head groupings (a
     list of calls per chunk), and of ``_f16_schedule``.  The file was recorded by this function on the commit before
-    npm_mha_prefill_fwd_f16 existed, on the simulator of tests/hostsim_kv16.py."""
+    npm_mha_prefill_fwd_f16 existed, on the simulator of tests/hostsim/ (profile 'kv16')."""
     record = {}
     for heads, kv_heads, f in ((8, 8, 128), (8, 2, 128), (4, 1, 256)):
         att, _ = DC.make_mha(npm, f, heads, kv_heads, seed=3)
@@ -204,7 +189,7 @@ def test_switch_off_makes_the_recorded_calls_of_before_npm_mha_prefill_fwd_f16(m
     calls and paths of fp16 caches are, name for name, the list recorded on the commit before the entry point existed
     (tests/golden/kv16_calls_before_prefill16.json), and the outputs of the runs are equal bit for bit."""
     import json
-    from np_modeling_amd import device as D, parallel
+    from np_modeling_amd import device as D
     assert D.PREFILL_KERNEL_F16 == (os.environ.get('NPM_PREFILL_KERNEL_F16', '0') != '0')
     monkeypatch.setattr(D, 'PREFILL_KERNEL_F16', False)
     with open(RECORDED) as fh:
@@ -214,16 +199,15 @@ def test_switch_off_makes_the_recorded_calls_of_before_npm_mha_prefill_fwd_f16(m
     assert recorded['schedule']['paths'].count('fused_masked') == 2 * 3 and recorded['schedule']['copies'] == 0
     assert recorded['chunks H8/2']['paths'] == ['fused_masked', 'decode', 'decode', 'fused_masked', 'decode']
     outs = []
-    for module, fp32_switch in ((hostsim_kv16, False), (hostsim_prefill16, False), (hostsim_prefill16, True)):
+    for profile, fp32_switch in (('kv16', False), ('prefill16', False), ('prefill16', True)):
         monkeypatch.setattr(D, 'PREFILL_KERNEL', fp32_switch)
-        npm = _npm(module)
+        npm = activate(profile)
         try:
-            assert hasattr(npm.sim, ENTRY) == (module is hostsim_prefill16)
-            assert _switch_off_record(npm) == recorded, (module.__name__, fp32_switch)
+            assert hasattr(npm.sim, ENTRY) == (profile == 'prefill16')
+            assert _switch_off_record(npm) == recorded, (profile, fp32_switch)
             outs.append(_f16_schedule(npm)[2])
         finally:
-            parallel.set_communicator(None)
-            module.uninstall()
+            deactivate()
     for other in outs[1:]:
         for a, b in zip(outs[0], other):
             assert np.array_equal(a, b)
@@ -469,15 +453,6 @@ def test_decoder_admit_of_a_prompt_over_f16_caches_runs_npm_mha_prefill_fwd_f16(
 
 
 # ---- the C ABI ------------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as entry
-    from np_modeling_amd import _C
-    if not (os.path.exists(_C.LIB_PATH) and os.path.exists(_C.RCCL_LIB_PATH)):
-        entry.build()
-    return _C
-
-
 def test_npm_mha_prefill_fwd_f16_header_against_bindings(built):
     _C = built
     text = open(os.path.join(ROOT, 'include', 'npm_hip.h')).read()

@@ -5,12 +5,12 @@
   (partly filled tiles, a second head chunk) and the shifted and saturated scores of ``range_cases`` -- every sequence against
   float64 alone.  Float64 itself is the reference, so it stays inside the GPU bound with room to spare.
 * the three entry points: header against bindings and exports.
-* dispatch on the simulator of tests/hostsim_prefill.py.  With ``device.PREFILL_KERNEL`` on, every cached forward the decode kernel
+* dispatch on the simulator of tests/hostsim/ (profile 'prefill').  With ``device.PREFILL_KERNEL`` on, every cached forward the decode kernel
   does not take -- a ragged or paged prefill, a chunk on top of cached rows (uniform contiguous included), a frozen cross cache,
   ``dec.admit`` of a prompt among decoding sequences -- has ``_cached_path == 'prefill'``, records no ``npm_kv_gather_*`` or
   ``npm_mha_mask_summary`` call and no ``npm_d2d`` copy, and uploads nothing but the [3, B] lengths mirror and the block table; a uniform
   contiguous prefill from empty stays on ``'fused_masked'``.  With the switch off the recorded call list is what the simulator
-  WITHOUT the new entry points (tests/hostsim_paged.py) records for the same schedule; under a split math mode the old path runs.
+  WITHOUT the new entry points (tests/hostsim/ (profile 'paged')) records for the same schedule; under a split math mode the old path runs.
 
 Every test names npm_mha_prefill_*, ``PREFILL_KERNEL``, ``mha_prefill`` or the path 'prefill': none exists without this feature.
 """
@@ -23,8 +23,7 @@ import numpy as np
 import pytest
 
 import decode_cases as DC
-import hostsim_paged
-import hostsim_prefill
+from hostsim.fixtures import activate, built, deactivate, npm_fixture
 import paged_cases as PC
 import prefill_reference as PR
 import varlen_reference as VR
@@ -33,21 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OLD_PATH = ('npm_kv_gather_varlen', 'npm_kv_gather_paged', 'npm_mha_mask_summary', 'npm_mha_core_fwd', 'npm_mha_core_fwd_grouped')
 
 
-def _npm(module):
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = module.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    return np_modeling_amd
-
-
-@pytest.fixture
-def npm():
-    from np_modeling_amd import parallel
-    yield _npm(hostsim_prefill)
-    parallel.set_communicator(None)
-    hostsim_prefill.uninstall()
+npm = npm_fixture('prefill')
 
 
 @pytest.fixture
@@ -160,15 +145,6 @@ def test_float32_tile_model_stays_within_half_the_gpu_bound(case):
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as entry
-    from np_modeling_amd import _C
-    if not (os.path.exists(_C.LIB_PATH) and os.path.exists(_C.RCCL_LIB_PATH)):
-        entry.build()
-    return _C
-
-
 def test_prefill_entry_points_header_against_bindings(built):
     _C = built
     text = open(os.path.join(ROOT, 'include', 'npm_hip.h')).read()
@@ -369,18 +345,17 @@ def _schedule_calls(npm, seed=2):
 
 def test_switch_off_records_the_calls_of_the_simulator_without_the_entry_points(monkeypatch):
     """The switch off (its default) against the simulator WITHOUT npm_mha_prefill_*: the same calls, uploads and outputs."""
-    from np_modeling_amd import device as D, parallel
+    from np_modeling_amd import device as D
     assert D.PREFILL_KERNEL == (os.environ.get('NPM_PREFILL_KERNEL', '0') != '0')
     monkeypatch.setattr(D, 'PREFILL_KERNEL', False)
     runs = []
-    for module in (hostsim_paged, hostsim_prefill):
-        npm = _npm(module)
+    for profile in ('paged', 'prefill'):
+        npm = activate(profile)
         try:
-            assert hasattr(npm.sim, 'npm_mha_prefill_fwd') == (module is hostsim_prefill)
+            assert hasattr(npm.sim, 'npm_mha_prefill_fwd') == (profile == 'prefill')
             runs.append(_schedule_calls(npm))
         finally:
-            parallel.set_communicator(None)
-            module.uninstall()
+            deactivate()
     (outs_a, paths_a, calls_a, uploads_a, _), (outs_b, paths_b, calls_b, uploads_b, copies) = runs
     assert calls_a == calls_b and uploads_a == uploads_b and paths_a == paths_b
     assert 'prefill' not in paths_b and 'npm_mha_prefill_fwd' not in calls_b and 'npm_mha_prefill_supported' not in calls_b

@@ -1,4 +1,4 @@
-"""CPU: rotary position embeddings without a GPU, on the simulator of tests/hostsim_rope.py.
+"""CPU: rotary position embeddings without a GPU, on the simulator of tests/hostsim/ (profile 'rope').
 
 * the reference itself (tests/rope_reference.py): float32 ``rotate`` against float64 with exact angles at the bound the number
   formats give, inverse after forward, and the relative-position property;
@@ -21,7 +21,7 @@ import pytest
 
 import decode_cases as DC
 import decode_reference as DR
-import hostsim_rope
+from hostsim.fixtures import built, npm_fixture
 import rope_cases as RC
 import rope_reference as RR
 from conftest import assert_close
@@ -31,16 +31,7 @@ BASE = 1e4
 U = 2.0 ** -24                    # unit roundoff of float32
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_rope.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_rope.uninstall()
+npm = npm_fixture('rope')
 
 
 make_mha = RC.make_mha
@@ -324,15 +315,6 @@ def test_kernel_comparison_runs_on_the_restated_entry_point(npm):
 
 
 # ---- the C ABI --------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as entry
-    from np_modeling_amd import _C
-    if not (os.path.exists(_C.LIB_PATH) and os.path.exists(_C.RCCL_LIB_PATH)):
-        entry.build()
-    return _C
-
-
 def test_npm_rope_header_against_bindings(built):
     _C = built
     text = open(os.path.join(ROOT, 'include', 'npm_hip.h')).read()

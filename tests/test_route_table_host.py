@@ -1,5 +1,5 @@
 """CPU: which kernel attends over a key / value cache, and how it is called -- the route table of a cached forward, replayed on
-the simulator of tests/hostsim_beam.py (that of tests/hostsim_prefix.py plus npm_rope) against tests/golden/cached_attention_routes.json.
+the 'beam' profile of the simulator (tests/hostsim/) against tests/golden/cached_attention_routes.json.
 
 The fixture was recorded BEFORE the attention side of incremental decoding was consolidated into one route decision and one
 device call, from the code that still had a ladder per call form.  It is not regenerated: a change of what this file expects is
@@ -19,7 +19,7 @@ import os
 import numpy as np
 import pytest
 
-import hostsim_beam
+from hostsim.fixtures import npm_fixture
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'cached_attention_routes.json')
 BATCH, CAPACITY, PAGE = 3, 64, 16
@@ -27,16 +27,7 @@ SHAPES = ((64, 4, 2), (48, 4, 4))
 PATHS = ('decode', 'prefill', 'fused_masked', 'gemm', 'decode_shared', 'prefill_shared')
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_beam.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_beam.uninstall()
+npm = npm_fixture('beam')
 
 
 def _layer(npm, features, heads, kv_heads, batch, **kwargs):

@@ -1,4 +1,4 @@
-"""CPU: token generation without a GPU, on the simulator of tests/hostsim_sample.py.
+"""CPU: token generation without a GPU, on the simulator of tests/hostsim/ (profile 'sample').
 
 * ``sampling.Sampler`` bookkeeping: counters advance for active rows only, ``set`` restarts a slot, the host mirror equals the
   device vector, the argument checks raise;
@@ -17,21 +17,12 @@ import ctypes
 import numpy as np
 import pytest
 
-import hostsim_sample
+from hostsim.fixtures import npm_fixture
 import sample_cases as SC
 import sample_reference as SR
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_sample.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_sample.uninstall()
+npm = npm_fixture('sample')
 
 
 # ---- Sampler -------------------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""CPU: the dispatch of the skinny-M GEMM without a GPU, on the simulator of tests/hostsim_skinny.py.
+"""CPU: the dispatch of the skinny-M GEMM without a GPU, on the simulator of tests/hostsim/ (profile 'skinny').
 
 * a decode step with B T <= ``device.SKINNY_MAX_M`` rows records exactly the six (unpacked: eight) ``npm_sgemm_skinny`` calls of
   tests/skinny_cases.py ``decode_products`` and no ``npm_sgemm``; above the threshold it records ``npm_sgemm`` only;
@@ -18,23 +18,14 @@ import numpy as np
 import pytest
 
 import decode_cases as DC
-import hostsim_paged
-import hostsim_skinny
+import hostsim
+from hostsim.fixtures import built, npm_fixture
 import skinny_cases as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_skinny.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_skinny.uninstall()
+npm = npm_fixture('skinny')
 
 
 def _gemms(calls):
@@ -125,11 +116,11 @@ def test_switch_math_mode_old_handle_and_shape_fall_back_with_equal_outputs(npm,
     npm.set_math('bf16x3')
     fallen_back()
     npm.set_math('f32')
-    old = hostsim_paged.install()                                         # a handle of the earlier ABI: no entry points
+    old = hostsim.install('paged')                                        # a handle of the earlier ABI: no entry points
     assert not hasattr(old, 'npm_sgemm_skinny')
     npm.sim = old
     fallen_back()
-    npm.sim = hostsim_skinny.install()
+    npm.sim = hostsim.install('skinny')
     got, calls = _decode_run(npm, dec, q, kv, [4, 1, 1])
     assert _gemms(calls) == ['npm_sgemm_skinny'] * 18 and all(np.array_equal(a, b) for a, b in zip(got, want))
 
@@ -204,20 +195,11 @@ def test_the_simulator_restates_the_split_rule_and_the_support_rule(npm):
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as entry
-    from np_modeling_amd import _C
-    if not (os.path.exists(_C.LIB_PATH) and os.path.exists(_C.RCCL_LIB_PATH)):
-        entry.build()
-    return _C
-
-
 def test_skinny_entry_points_header_against_bindings(built):
     _C = built
     text = open(os.path.join(ROOT, 'include', 'npm_hip.h')).read()
-    assert int(re.search(r'#define\s+NPM_SKINNY_MAX_M\s+(\d+)', text).group(1)) == _C.SKINNY_MAX_M == hostsim_skinny.MAX_M == 64
-    assert int(re.search(r'#define\s+NPM_SKINNY_MAX_SPLITS\s+(\d+)', text).group(1)) == _C.SKINNY_MAX_SPLITS == hostsim_skinny.MAX_SPLITS
+    assert int(re.search(r'#define\s+NPM_SKINNY_MAX_M\s+(\d+)', text).group(1)) == _C.SKINNY_MAX_M == hostsim.gemm.MAX_M == 64
+    assert int(re.search(r'#define\s+NPM_SKINNY_MAX_SPLITS\s+(\d+)', text).group(1)) == _C.SKINNY_MAX_SPLITS == hostsim.gemm.MAX_SPLITS
     assert int(re.search(r'NPM_TUNE_SKINNY_SPLITS\s*=\s*(\d+)', text).group(1)) == _C.TUNE_SKINNY_SPLITS == 22
     assert int(re.search(r'NPM_TUNE_SKINNY_NT\s*=\s*(\d+)', text).group(1)) == _C.TUNE_SKINNY_NT == 23
     assert int(re.search(r'#define\s+NPM_ABI_VERSION\s+(\d+)', text).group(1)) == 2
@@ -237,7 +219,7 @@ def test_skinny_entry_points_header_against_bindings(built):
     bound = _C.load_library()
     assert bound.npm_abi_version() == 2 and bound.npm_last_skinny_kernel() == b''
     assert [bound.npm_sgemm_skinny_splits(n, k, t) for n, k in SC.SHAPES for t in (0, 1)] == \
-        [hostsim_skinny.auto_splits(n, k) for n, k in SC.SHAPES for _ in (0, 1)]
+        [hostsim.gemm.auto_splits(n, k) for n, k in SC.SHAPES for _ in (0, 1)]
     assert bound.npm_sgemm_skinny_supported(None) == 0 and bound.npm_sgemm_skinny_supported(ctypes.byref(_C.npm_gemm())) == 0
     count = ctypes.c_int(-1)
     bound.npm_device_count(ctypes.byref(count))

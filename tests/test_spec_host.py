@@ -1,4 +1,4 @@
-"""CPU: speculative decoding on the host simulator (tests/hostsim_spec.py) and its references (tests/spec_reference.py).
+"""CPU: speculative decoding on the host simulator (tests/hostsim/ (profile 'spec')) and its references (tests/spec_reference.py).
 
 * the draft rule on hand-worked histories (tests/spec_cases.py HAND: the expected n, j and m are written out there);
 * ``KVCache.truncate`` / ``PagedKVCache.truncate`` / ``DecodeState.truncate``: lengths, page accounting, windows, refusals;
@@ -17,21 +17,12 @@ import re
 import numpy as np
 import pytest
 
-import hostsim_spec
+from hostsim.fixtures import npm_fixture
 import spec_cases as XC
 import spec_reference as XR
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_spec.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_spec.uninstall()
+npm = npm_fixture('spec')
 
 
 # ---- the draft rule --------------------------------------------------------------------------------------------------------------------

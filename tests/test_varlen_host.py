@@ -4,7 +4,7 @@
 * a float32 model of the split / combine rule with the partition taken from Lmax and per-sequence early exit stays under HALF of
   the bound tests/test_gpu_varlen.py applies (tests/test_gpu_decode.py's: ctx 2e-6 (1 + |ref|), lse 3e-6, grown by
   attn_range_data.exponent_tol) at every (lengths, D, splits) of that test's grid;
-* the product's host logic on the simulator (tests/hostsim_varlen.py): ``KVCache.lengths`` over ragged calls, overflow of one
+* the product's host logic on the simulator (tests/hostsim/ (profile 'varlen')): ``KVCache.lengths`` over ragged calls, overflow of one
   sequence raised before any call, ``length`` raising once ragged, ``reset``, a frozen cache with ``lengths``, the path each shape
   selects, uniform input recording exactly the scalar calls, NotImplementedError where only the GEMM composition is left, and
   ``TransformerDecoder.decode`` with ragged prompts followed by single-token steps;
@@ -23,7 +23,7 @@ import pytest
 import attn_range_data as R
 import decode_cases as DC
 import decode_reference as DR
-import hostsim_varlen
+from hostsim.fixtures import built, npm_fixture
 import varlen_reference as VR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -114,16 +114,7 @@ def test_kernel_case_grid_covers_what_it_must():
 
 
 # ---- host logic on the simulator -----------------------------------------------------------------------------------------------
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_varlen.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_varlen.uninstall()
+npm = npm_fixture('varlen')
 
 
 def test_cache_lengths_bookkeeping_overflow_and_reset(npm):
@@ -293,15 +284,6 @@ def test_decoder_decode_with_ragged_prompts_then_single_tokens(npm, norm_first, 
 
 
 # ---- the C ABI -----------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as entry
-    from np_modeling_amd import _C
-    if not (os.path.exists(_C.LIB_PATH) and os.path.exists(_C.RCCL_LIB_PATH)):
-        entry.build()
-    return _C
-
-
 def test_varlen_entry_points_header_against_bindings(built):
     _C = built
     text = open(os.path.join(ROOT, 'include', 'npm_hip.h')).read()

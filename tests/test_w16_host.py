@@ -1,5 +1,5 @@
 """CPU: the half-precision weight copies (device.HalfWeights, npm_sgemm_skinny_w16) without a GPU, on the simulator of
-tests/hostsim_w16.py.
+tests/hostsim/ (profile 'w16').
 
 * the ABI version is still 2; header, exports, ``_C.SIGNATURES`` and the simulator's support rule agree;
 * a snapshot keeps adjacent sources adjacent: the packed q / k / v projection is ONE ``npm_sgemm_skinny_w16`` call over one half
@@ -8,7 +8,7 @@ tests/hostsim_w16.py.
   with array_equal outputs: the model with the rounded matrices at every M;
 * a rebound parameter raises RuntimeError and ``refresh()`` repairs it; ``weights='bf16'`` and ``weights=`` without ``cache=``
   raise ValueError;
-* without the keyword the call trace is, call for call, the trace on tests/hostsim_skinny.py;
+* without the keyword the call trace is, call for call, the trace on tests/hostsim/ (profile 'skinny');
 * ``state.release`` / ``dec.admit`` leave the snapshot alone.
 """
 
@@ -20,8 +20,8 @@ import numpy as np
 import pytest
 
 import decode_cases as DC
-import hostsim_skinny
-import hostsim_w16
+import hostsim
+from hostsim.fixtures import built, npm_fixture
 import skinny_cases as SC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,16 +29,7 @@ SIX = (('_self_attention', '_wq'), ('_self_attention', '_wk'), ('_self_attention
        ('_cross_attention', '_wq'), ('_cross_attention', '_wo'), ('_dense1._linear', '_w'), ('_dense2', '_w'))
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_w16.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_w16.uninstall()
+npm = npm_fixture('w16')
 
 
 def _gemms(calls):
@@ -216,8 +207,8 @@ def test_bad_keywords_raise_before_anything_is_launched(npm):
 
 
 def test_without_the_keyword_the_trace_is_the_one_of_the_skinny_simulator(npm):
-    def trace(sim_module, **kwargs):
-        sim = sim_module.install()
+    def trace(profile, **kwargs):
+        sim = hostsim.install(profile)
         npm.sim = sim
         dec, _ = DC.make_decoder(npm, 64, 4, 2, 96, True, True, seed=7, batch=3)
         q, kv = _inputs(3, 9, 64, seed=4)
@@ -230,9 +221,9 @@ def test_without_the_keyword_the_trace_is_the_one_of_the_skinny_simulator(npm):
         outs.append(np.asarray(att(q[:, 4:5], cache=cache)))
         return sim.calls[first:], outs
 
-    old_calls, old_outs = trace(hostsim_skinny)
-    new_calls, new_outs = trace(hostsim_w16)
-    none_calls, none_outs = trace(hostsim_w16, weights=None)
+    old_calls, old_outs = trace('skinny')
+    new_calls, new_outs = trace('w16')
+    none_calls, none_outs = trace('w16', weights=None)
     assert new_calls == old_calls == none_calls and not any('w16' in c or 'cvt' in c for c in new_calls)
     assert all(np.array_equal(a, b) and np.array_equal(a, c) for a, b, c in zip(old_outs, new_outs, none_outs))
     assert npm.sim.w16 == [] and npm.sim.cvt == []
@@ -292,15 +283,6 @@ def test_a_snapshot_is_converted_with_the_pitched_conversions(npm):
 
 
 # ---- the C ABI -------------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope='module')
-def built():
-    import __graft_entry__ as entry
-    from np_modeling_amd import _C
-    if not (os.path.exists(_C.LIB_PATH) and os.path.exists(_C.RCCL_LIB_PATH)):
-        entry.build()
-    return _C
-
-
 def test_w16_entry_points_header_against_bindings(built):
     _C = built
     text = open(os.path.join(ROOT, 'include', 'npm_hip.h')).read()
@@ -320,13 +302,13 @@ def test_w16_entry_points_header_against_bindings(built):
     lib = ctypes.CDLL(_C.LIB_PATH)
     for name in ('npm_sgemm_skinny_w16', 'npm_sgemm_skinny_w16_supported', 'npm_cvt_f32_f16', 'npm_cvt_f16_f32'):
         assert hasattr(lib, name), f'{name} not exported'
-        assert hasattr(hostsim_w16.W16HostSim, name) and not hasattr(hostsim_skinny.SkinnyHostSim, name)
+        assert name in hostsim.PROFILES['w16'] and name not in hostsim.PROFILES['skinny']
     bound = _C.load_library()
     assert bound.npm_abi_version() == 2
     assert bound.npm_sgemm_skinny_w16_supported(None) == 0 and bound.npm_sgemm_skinny_w16_supported(ctypes.byref(_C.npm_gemm())) == 0
     # the rule itself needs no device: the library and the simulator's restatement agree on every field the rule reads, one field
     # changed at a time from a call both take, for both layouts
-    sim = hostsim_w16.W16HostSim()
+    sim = hostsim.HostSim('w16')
     spare = 32768
 
     def base(trans_b):

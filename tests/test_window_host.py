@@ -1,4 +1,4 @@
-"""CPU: sliding-window attention for decoding without a GPU, on the simulator of tests/hostsim_window.py.
+"""CPU: sliding-window attention for decoding without a GPU, on the simulator of tests/hostsim/ (profile 'window').
 
 * the page reclaim of ``PagedKVCache(window=W)`` is exact: after every call the table slots in use are the pages that hold a row
   the window can still reach or a row of the call, ``dropped`` is a multiple of the page size, the free list stays a heap and the
@@ -21,7 +21,7 @@ import pytest
 
 import decode_cases as DC
 import decode_reference as DR
-import hostsim_window
+from hostsim.fixtures import npm_fixture
 import window_cases as WC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,16 +31,7 @@ OTHER_ATTENTION = ('npm_mha_decode_fwd', 'npm_mha_decode_fwd_varlen', 'npm_mha_d
                    'npm_kv_gather_varlen', 'npm_kv_gather_paged', 'npm_kv_gather_f16', 'npm_softmax_fwd')
 
 
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    sim = hostsim_window.install()
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = sim
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim_window.uninstall()
+npm = npm_fixture('window')
 
 
 # ---- page reclaim ---------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""Sliding-window attention over a key / value cache, restated: shared by tests/hostsim_window.py, tests/test_window_host.py
+"""Sliding-window attention over a key / value cache, restated: shared by tests/hostsim/ (profile 'window'), tests/test_window_host.py
 (CPU) and tests/test_gpu_window.py (MI355X).
 
 The rule (include/npm_hip.h npm_mha_decode_fwd_window).  Row t < n[b] of sequence b has the causal upper limit
