@@ -930,6 +930,63 @@ int npm_mse_bwd(const float *y, const float *targets, float *dy, size_t n);
 /* CrossEntropyLoss (loss.py:33-39): loss = -sum(t log y); dy = -t / y */
 int npm_xent_fwd(const float *y, const float *targets, size_t n, double *loss);
 int npm_xent_bwd(const float *y, const float *targets, float *dy, size_t n);
+/* ---- softmax cross-entropy from logits and token ids: what training a language model needs ----
+ * npm_softmax_xent_rows replaces CrossEntropyLoss (loss.py:33-39) composed with Softmax (activations.py:26-45) over a dense
+ * one-hot [rows, vocab] float tensor -- five passes over [rows, vocab] and log(0) = -inf for an underflowed probability -- by one
+ * launch that reads every logit once and, with a gradient, writes every gradient once.  logits: fp32 [rows, vocab], row r at
+ * logits + r * ld; targets: int32 [rows]; dlogits: NULL (no gradient) or fp32 [rows, vocab] with the pitch ldd; row_loss, row_lse:
+ * fp32 [rows], row_lse may be NULL; all of these device pointers.  loss_sum: HOST pointer.  e = smoothing in [0, 1), V = vocab.
+ * Per row r with t = targets[r]:
+ *  1. t < 0: the row is ignored (the padding convention of npm_take_rows): its logits are NOT READ, row_loss = 0, the gradient
+ *     row is all zeros, row_lse is NaN.
+ *  2. t >= V: row_loss, row_lse and the whole gradient row are NaN; nothing outside the row is touched.
+ *  3. Otherwise, with m = max_j z_j, s = sum_j exp(z_j - m), lse = m + log(s):
+ *       row_lse  = lse
+ *       row_loss = lse - (1 - e) z_t - (e / V) sum_j z_j           (the last term only when e != 0)
+ *       dlogits[r, j] = grad_scale * (exp(z_j - lse) - (1 - e) [j == t] - e / V)
+ *  4. A -inf logit is a masked token: it adds 0 to s and its gradient is 0, the target included.  With e != 0 a -inf logit makes
+ *     row_loss +inf, as the formula says; a -inf target logit makes it +inf for every e.
+ *  5. A row that holds a NaN or +inf, or whose every logit is -inf, gives NaN row_loss, row_lse and gradient row; it never faults.
+ *  6. dlogits may be exactly logits with ldd == ld: the gradient then overwrites the logits.  Any other overlap of the two
+ *     [rows, vocab] extents is NPM_E_BAD_ARGUMENT.
+ *  7. *loss_sum = the fp64 sum of row_loss[0 .. rows) in a fixed order (a second launch of one block, no atomics; one 8-byte copy
+ *     to the host, as npm_mse_fwd).  rows == 0 is legal: *loss_sum = 0 and nothing is launched.
+ *  8. Every reduction has a fixed thread-to-token mapping and a fixed tree, the same on the 16-byte and the scalar path: a launch is
+ *     bitwise reproducible, and a row's results depend neither on rows, on the row's position, on the pitches nor on the alignment.
+ * Instances, by vocab alone: "xent_wave" (V <= 1024: one wavefront per row), "xent_block256" (V <= 8192) and "xent_block1024"
+ * (V <= 32768 = NPM_SAMPLE_LDS_ROW): one block per row; these three read the row once and keep it in registers;
+ * "xent_block1024_global" (larger: the second and third pass re-read the row).  16-byte loads and stores when logits (and dlogits) are 16-byte
+ * aligned with ld % 4 == 0 (ldd % 4 == 0), else 4-byte ones.  A [rows, vocab] of at least 32 MB moves with the nontemporal hint
+ * (NPM_TUNE_STREAM_NT): the gradient stores and every load that is the last use of a logit.
+ * Arithmetic: m exact; z_j - m and expf in fp32; s and sum_j z_j accumulated in fp64, the target's own term joining s after the
+ * tree, so that the target's gradient is grad_scale * (float)(e (1 - 1 / V) - s_excl / s) in fp64 -- a quotient of sums, accurate
+ * relative to 1 - p_t however close p_t is to 1; lse and row_loss in fp64 with fp64 log, ONE rounding to fp32 each; the other
+ * gradients are grad_scale * (expf(z_j - m) * (float)(1 / s) - (float)(e / V)), each operation rounded to fp32, no contraction
+ * (the same expf value that entered s: the register instances keep it, the re-reading one computes it again).
+ * Error bound against exact arithmetic on the same fp32 inputs, for a row of clause 3 with finite results.  u = 2^-24; expf is
+ * within 1 ulp <= 2 u (the documented accuracy of the device library's expf), the fp64 log within 2^-52; d_j = m - z_j;
+ * p_j = exp(z_j - lse); A = sum_j p_j d_j (the mean distance below the maximum under the row's own distribution; A <= ln V):
+ *   - a term of s: u d_j from the subtraction, 2 u from expf, so |ds| / s <= (A + 2) u to first order, 1.01 covering the rest;
+ *   - the fp64 sums run through chains of at most 32 + V / 1024 tokens per thread, then the log2(64) = 6 butterfly levels of a
+ *     wavefront, the at most 16 wave partials in order and the target's term, 23 more additions: gamma = (55 + V / 1024) 2^-53
+ *     relative to the sum of magnitudes -- the summation term; it is below u / 512 for every legal V;
+ *   |row_lse  - lse|  <= u (|lse|  + 1.01 (A + 2)) + gamma (1 + |m|)
+ *   |row_loss - loss| <= u (|loss| + 1.01 (A + 2)) + gamma (1 + |m| + |z_t| + e mean_j |z_j|)
+ *   |dlogits[r, j] - g_j| <= 1.01 u |grad_scale| (q_j + e / V + 2 |g_j / grad_scale|) + 2^-125 |grad_scale|
+ *     j != t: q_j = p_j (d_j + 1.01 A + 6.1)       (subtraction, expf, s, the rounding of 1 / s, the product: then the
+ *                                                   subtraction of e / V and the scaling round once each)
+ *     j == t: q_t = (A - p_t d_t) + 2 (1 - p_t) + 1.01 (1 - p_t) (A + 2)        (the error of s_excl and of s in s_excl / s)
+ *   2^-125: a probability below the smallest normal number may be flushed to zero.
+ * tests/test_gpu_xent.py asserts these three bounds on every case of tests/xent_cases.py; DESIGN.md 4.5k records the worst
+ * observed fraction of each.
+ * NPM_E_BAD_ARGUMENT before anything is launched: loss_sum == NULL, rows outside 0 .. 2^31 - 1, vocab outside 1 .. 2^30,
+ * ld < vocab, smoothing outside [0, 1), and for rows > 0 a NULL logits, targets or row_loss, dlogits with ldd < vocab, dlogits ==
+ * logits with ldd != ld, a partial overlap. */
+int npm_softmax_xent_rows(const float *logits, int64_t ld, const int32_t *targets, int64_t rows, int64_t vocab, float smoothing,
+                          float grad_scale, float *dlogits, int64_t ldd, float *row_loss, float *row_lse, double *loss_sum);
+/* What the most recent npm_softmax_xent_rows launched: "<instance> V=<vocab> grad=<0|1> inplace=<0|1> vec=<0|1> nt=<0|1>" with the
+ * instance names above, "xent_none rows=0" for an empty call; "" before the first call. */
+const char *npm_last_xent_kernel(void);
 /* DropOut (normalizations.py:14-30): y = mask ? x / keep_prob : 0 with a host-drawn byte mask */
 int npm_mask_scale(const float *x, const unsigned char *mask, float *y, size_t n, float keep_prob);
 /* The same with the mask drawn ON THE DEVICE: element i keeps its value when word (i & 3) of

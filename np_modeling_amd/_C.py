@@ -284,6 +284,10 @@ _SPECIAL = {
     'npm_last_draft_kernel': (C.c_char_p, []),
     'npm_last_beam_kernel': (C.c_char_p, []),
     'npm_last_logits_kernel': (C.c_char_p, []),
+    # Returns int like everything in SIGNATURES, but lives here: the host simulator's profiles record SIGNATURES entry by entry, and
+    # this call is restated by the tests that need it (tests/hostsim_xent.py) instead of joining the simulator.
+    'npm_softmax_xent_rows': (C.c_int, [_P, _I64, _P, _I64, _I64, _F, _F, _P, _I64, _P, _P, C.POINTER(C.c_double)]),
+    'npm_last_xent_kernel': (C.c_char_p, []),
 }
 
 COMM_SIGNATURES = {
@@ -573,6 +577,11 @@ LOGITS_MAX_BIAS, LOGPROB_MAX_TOP = 256, 64             # include/npm_hip.h NPM_L
 def last_logits_kernel() -> str:
     """What the most recent npm_logits_process or npm_history_append launched (include/npm_hip.h npm_last_logits_kernel)."""
     return lib().npm_last_logits_kernel().decode()
+
+
+def last_xent_kernel() -> str:
+    """What the most recent npm_softmax_xent_rows launched (include/npm_hip.h npm_last_xent_kernel)."""
+    return lib().npm_last_xent_kernel().decode()
 
 
 def comm_lib():

@@ -29,6 +29,8 @@ class Embedding(layer.StatefulLayer):
         self._w = self._new_param([self._vocab, self._features])
         self._pack_parameters([[(self, '_w')]])
 
+    resident_inputs = staticmethod(D.as_ids)     # Trainer.train: integer inputs stay integers, uploaded once
+
     def forward(self, ids):
         self._ids = D.as_ids(ids)
         return D.take_rows(self._param('_w'), self._ids)

@@ -4,6 +4,7 @@ first layer to the loss and back; only the scalar loss comes to the host."""
 
 from __future__ import annotations
 
+import inspect
 import logging
 from typing import Optional, Sequence
 
@@ -31,7 +32,10 @@ class Trainer:
             grad = stage(grad, backprop=True, optimizer_=optimizer_)
 
     def train(self, inputs, targets, steps: int, optimizer_) -> None:
-        inputs, targets = self._resident(inputs), self._resident(targets)     # one upload for the whole loop
+        # one upload for the whole loop; a first layer or a loss that takes something else than floats (token ids) says how
+        first = self._layers[0] if len(self._layers) else None
+        inputs = first.resident_inputs(inputs) if hasattr(first, 'resident_inputs') else self._resident(inputs)
+        targets = self._loss.resident_targets(targets) if hasattr(self._loss, 'resident_targets') else self._resident(targets)
         for index in range(steps):
             print('Step: ', index)
             print('Loss: ', self._loss(self._predict(inputs), targets))
@@ -44,4 +48,5 @@ class Trainer:
         return D.as_device(array)
 
     def eval(self, inputs, targets) -> None:
-        print('Loss: ', self._loss(self._predict(inputs), targets))
+        no_grad = {'need_grad': False} if 'need_grad' in inspect.signature(self._loss.forward).parameters else {}
+        print('Loss: ', self._loss(self._predict(inputs), targets, **no_grad))
