@@ -129,11 +129,30 @@ from np_modeling_amd.device import Mat
 from np_modeling_amd.layers import activations, layer
 
 _PARAMS = ('_wq', '_wk', '_wv', '_wo', '_bq', '_bk', '_bv', '_bo')
+_IN_PROJECTIONS = (('_wq', '_bq'), ('_wk', '_bk'), ('_wv', '_bv'))
 
 
 def _from(x: D.DeviceArray, offset: int) -> D.DeviceArray:
     """``x`` entered ``offset`` elements later (a head-slice operand of the grouped composition), spanning to its end."""
     return x if offset == 0 else x.flat_view(offset, [x.size - offset])
+
+
+def _gemm_attention(q: Mat, k: Mat, v: Mat, ctx: Mat, dims, scale: float) -> D.DeviceArray:
+    """ctx = softmax(scale q k^T) v out of GEMMs: attention[b, h] = q_h k_h^T, scores = softmax(attention / sqrt(dk)) in place,
+    context[b, :, h, :] = scores[b, h] v_h; returns the scores [B, H, rows, keys].  One GEMM batched over (B, Hkv) per group g:
+    query heads g Hkv .. g Hkv + Hkv - 1 with K / V heads 0 .. Hkv - 1 (one group when not grouped).  ``q`` / ``ctx``
+    [B, rows, H, D] and ``k`` / ``v`` [B, keys, Hkv, D] are named by first element, row pitch and batch stride."""
+    b, h, hkv, rows, keys, dk, dv = dims
+    plane = rows * keys
+    scores = D.empty([b, h, rows, keys])
+    groups = [Mat(_from(scores, g * hkv * plane), keys, h * plane, plane) for g in range(h // hkv)]
+    for g, s_g in enumerate(groups):
+        D.gemm(rows, keys, dk, Mat(q.ptr + 4 * g * hkv * dk, q.ld, q.s0, dk), Mat(k.ptr, k.ld, k.s0, dk), s_g, trans_b=True,
+               batch=(b, hkv))
+    D.softmax_fwd(scores, scale, out=scores)
+    for g, s_g in enumerate(groups):
+        D.gemm(rows, dv, keys, s_g, Mat(v.ptr, v.ld, v.s0, dv), Mat(ctx.ptr + 4 * g * hkv * dv, ctx.ld, ctx.s0, dv), batch=(b, hkv))
+    return scores
 
 
 def cached_route(cache, heads: int, tokens: int, causal: bool, fresh_whole: bool, per_sequence: bool, n=None) -> str:
@@ -273,6 +292,37 @@ class MultiHeadAttention(layer.StatefulLayer):
             raise RuntimeError('half_weights: the layer has no parameters yet (run one forward, or bind weights, first)')
         return D.HalfWeights([(self, p) for p in ('_wq', '_wk', '_wv', '_wo')])
 
+    def _project_in(self, query, key, value, rows: Optional[int] = None, weights: Optional[D.HalfWeights] = None,
+                    skinny_ok: bool = False):
+        """The in-projections [rows, F] x w[H*D, F]^T + b of those of ``query`` / ``key`` / ``value`` [B, S, F] that are not None:
+        ``(Mats, arrays, packed)`` with q [B, S, H, Dk], k [B, S, Hkv, Dk], v [B, S, Hkv, Dv] (None where not asked for) as GEMM
+        operands and as the arrays behind them.  ``packed``: ONE GEMM made all three as parts of one [B, S, H + 2 Hkv, D] buffer
+        (``_packed_qkv``) -- k and v are that buffer entered F and F + Hkv*Dk elements later, spanning to its end, with its row
+        pitch; otherwise one GEMM each.  ``rows``: only the first ``rows`` rows of a batch of one.  ``weights``: the fp16 copies
+        to read (RuntimeError if a parameter was rebound since the snapshot); ``skinny_ok``: a decode step (``device.gemm``)."""
+        h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
+        inputs = (query, key, value)
+        halves = [None if weights is None or x is None else weights.view(self, w) for x, (w, _) in zip(inputs, _IN_PROJECTIONS)]
+        if query is not None and self._packed_qkv(query, key, value):
+            b, s, f = query.shape
+            width = f + 2 * hkv * dk
+            qkv = D.empty([b, s, h + 2 * hkv, dk])
+            # (adjacent parameters at unchanged addresses were adjacent when the snapshot was taken: so are their halves)
+            D.gemm(b * s, width, f, Mat(query, f), Mat(self._param('_wq'), f, half=halves[0]), Mat(qkv, width), trans_b=True,
+                   bias=self._param('_bq'), skinny_ok=skinny_ok)
+            arrays = [qkv, _from(qkv, f), _from(qkv, f + hkv * dk)]
+            return [Mat(a, width) for a in arrays], arrays, True
+        mats, arrays = [None, None, None], [None, None, None]
+        for i, (x, (heads, d), (w, bias)) in enumerate(zip(inputs, ((h, dk), (hkv, dk), (hkv, dv)), _IN_PROJECTIONS)):
+            if x is not None:
+                b, s, f = x.shape
+                s = s if rows is None else rows
+                arrays[i] = D.empty([b, s, heads, d])
+                mats[i] = Mat(arrays[i], heads * d)
+                D.gemm(b * s, heads * d, f, Mat(x, f), Mat(self._param(w), f, half=halves[i]), mats[i], trans_b=True,
+                       bias=self._param(bias), skinny_ok=skinny_ok)
+        return mats, arrays, False
+
     def forward(self, query, key=None, value=None, mask=None, cache=None, new_lengths=None, weights=None):
         if weights is not None and cache is None:
             raise ValueError('weights= (half-precision weight copies) serves the cached forward of incremental decoding: it needs cache=')
@@ -296,8 +346,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         skv = key.shape[1]
         fv = value.shape[2]
         assert f == h * dk and key.shape == (b, skv, f) and value.shape[:2] == (b, skv) and fv == h * dv
-        wq, wk, wv, wo = (self._param(p) for p in ('_wq', '_wk', '_wv', '_wo'))
-        bq, bk, bv, bo = (self._param(p) for p in ('_bq', '_bk', '_bv', '_bo'))
+        wo, bo = self._param('_wo'), self._param('_bo')
         self._query, self._key, self._value = query, key, value
         self._cached_forward = False
         if mask is not None and not isinstance(mask, D.AttnMask) and np.ndim(mask) == 0 and not mask:   # `if mask:` false (attentions.py:84,106)
@@ -312,55 +361,25 @@ class MultiHeadAttention(layer.StatefulLayer):
             raise NotImplementedError('masked attention needs head sizes Dk == Dv in {16, 32, 64, 128} (fused kernels)')
         self._core = core
 
-        # in-projections: [rows, F] x w[H*D, F]^T + b.  q/k/v are [B, S, H, D] head slices addressed through
-        # (array, element offset, row pitch): separate tensors, or parts of one packed [B, S, H + 2 Hkv, D].
-        packed = self._packed_qkv(query, key, value)
+        (mq, mk, mv), (q, k, v), packed = self._project_in(query, key, value)
         self._packed = packed
-        fkv, fvkv = hkv * dk, hkv * dv                                   # row widths of k and v
-        if packed:
-            width = f + 2 * fkv
-            qkv = D.empty([b, sq, h + 2 * hkv, dk])
-            D.gemm(b * sq, width, f, Mat(query, f), Mat(wq, f), Mat(qkv, width), trans_b=True, bias=bq)
-            pitch = width
-            # k and v are the same buffer entered f and f + Hkv*Dk elements later (row pitch H*Dk + 2 Hkv*Dk); the views
-            # span to the end
-            q, k, v = qkv, qkv.flat_view(f, [qkv.size - f]), qkv.flat_view(f + fkv, [qkv.size - f - fkv])
-        else:
-            pitch = None
-            q = D.empty([b, sq, h, dk])
-            k = D.empty([b, skv, hkv, dk])
-            v = D.empty([b, skv, hkv, dv])
-            D.gemm(b * sq, h * dk, f, Mat(query, f), Mat(wq, f), Mat(q, h * dk), trans_b=True, bias=bq)
-            D.gemm(b * skv, fkv, f, Mat(key, f), Mat(wk, f), Mat(k, fkv), trans_b=True, bias=bk)
-            D.gemm(b * skv, fvkv, fv, Mat(value, fv), Mat(wv, fv), Mat(v, fvkv), trans_b=True, bias=bv)
         if self._rope_base is not None:                                 # q and k are saved rotated: what the backward needs
             self._rotate(packed, q, k, b, sq, skv)
         self._q, self._k, self._v = q, k, v
-        pq, pk, pv = pitch or h * dk, pitch or fkv, pitch or fvkv       # row pitches of q, k, v
-        self._pitches = (pq, pk, pv)
+        pq, pk, pv = self._pitches = (mq.ld, mk.ld, mv.ld)              # row pitches of q, k, v
 
         self._scale = 1.0 / math.sqrt(dk)
         if core:
             # scores, softmax and context in one kernel; what the backward needs is the log-sum-exp per row
             ctx, self._lse, self._raw_scores = D.mha_core_fwd(
-                Mat(q, pq), Mat(k, pk), Mat(v, pv), (b, h, sq, skv, dk), self._scale, self._mask,
+                mq, mk, mv, (b, h, sq, skv, dk), self._scale, self._mask,
                 save_scores=D.attn_save_scores(dk), kv_heads=hkv if grouped else None)
             self._softmax._y = self._attention_scores = None
         else:
-            # attention[b, h] = q_h k_h^T ; scores = softmax(attention / sqrt(dk)).  One GEMM batched over (B, Hkv) per
-            # group g: query heads g Hkv .. g Hkv + Hkv - 1 with K / V heads 0 .. Hkv - 1 (one group when not grouped)
-            scores = D.empty([b, h, sq, skv])
-            for g in range(h // hkv):
-                D.gemm(sq, skv, dk, Mat(_from(q, g * fkv), pq, sq * pq, dk), Mat(k, pk, skv * pk, dk),
-                       Mat(_from(scores, g * hkv * sq * skv), skv, h * sq * skv, sq * skv), trans_b=True, batch=(b, hkv))
-            D.softmax_fwd(scores, self._scale, out=scores)
-            self._softmax._y = scores
-            self._attention_scores = scores
-            # context[b, :, h, :] = scores[b, h] v_h      -> [B, Sq, H, Dv]
-            ctx = D.empty([b, sq, h, dv])
-            for g in range(h // hkv):
-                D.gemm(sq, dv, skv, Mat(_from(scores, g * hkv * sq * skv), skv, h * sq * skv, sq * skv), Mat(v, pv, skv * pv, dv),
-                       Mat(_from(ctx, g * fvkv), h * dv, sq * h * dv, dv), batch=(b, hkv))
+            ctx = D.empty([b, sq, h, dv])                                # [B, Sq, H, Dv]
+            scores = _gemm_attention(Mat(q, pq, sq * pq), Mat(k, pk, skv * pk), Mat(v, pv, skv * pv), Mat(ctx, h * dv, sq * h * dv),
+                                     (b, h, hkv, sq, skv, dk, dv), self._scale)
+            self._softmax._y = self._attention_scores = scores
         self._context = ctx
 
         # output projection: [B*Sq, H*Dv] x wo[F, H*Dv]^T + bo (+ skip connection)
@@ -416,18 +435,22 @@ class MultiHeadAttention(layer.StatefulLayer):
                                       'frozen cache; rotary position embedding is for self-attention caches')
         key = D.as_device(key)
         value = key if value is None else D.as_device(value)
-        h, hkv, dk, dv = self._num_heads, self._num_kv_heads, self._key_dim, self._value_dim
+        h, dk, dv = self._num_heads, self._key_dim, self._value_dim
         b, skv, f = key.shape
         fv = value.shape[2]
         assert f == h * dk and value.shape[:2] == (b, skv) and fv == h * dv
         cache.reset()
         cache.room(skv, lengths)                                         # ValueError before anything is launched
-        k, v = D.empty([b, skv, hkv, dk]), D.empty([b, skv, hkv, dv])
-        D.gemm(b * skv, hkv * dk, f, Mat(key, f), Mat(self._param('_wk'), f), Mat(k, hkv * dk), trans_b=True, bias=self._param('_bk'))
-        D.gemm(b * skv, hkv * dv, fv, Mat(value, fv), Mat(self._param('_wv'), fv), Mat(v, hkv * dv), trans_b=True, bias=self._param('_bv'))
-        cache.append(Mat(k, hkv * dk), Mat(v, hkv * dv), skv, lengths)
+        (_, k, v), _, _ = self._project_in(None, key, value)
+        cache.append(k, v, skv, lengths)
         cache.frozen = True
         return cache
+
+    def fill_slot(self, cache: D.KVCache, b: int, key, rows: int) -> None:
+        """Cross-attention: sequence ``b`` of a filled cache is replaced by the first ``rows`` rows of the memory ``key`` [1, Skv, F]
+        (``TransformerDecoder.admit``).  K is projected and written, then V: one projection is live at a time."""
+        cache.write_slot(b, self._project_in(None, key, None, rows=rows)[0][1], None, rows)
+        cache.write_slot(b, None, self._project_in(None, None, key, rows=rows)[0][2], rows)
 
     def _forward_cached(self, query: D.DeviceArray, cache: D.KVCache, residual: Optional[D.DeviceArray] = None, new_lengths=None,
                         weights: Optional[D.HalfWeights] = None):
@@ -458,36 +481,13 @@ class MultiHeadAttention(layer.StatefulLayer):
             raise ValueError('the frozen cache is empty: fill_cache(cache, key, value) first')
         before = cache.lengths.copy()
         self._cached_forward = True
-        wq, wk, wv, wo = (self._param(p) for p in ('_wq', '_wk', '_wv', '_wo'))
-        bq, bk, bv, bo = (self._param(p) for p in ('_bq', '_bk', '_bv', '_bo'))
-        fkv, fvkv = hkv * dk, hkv * dv
         fresh = None                                                     # the new tokens' own (k, v) Mats, self-attention only
-
-        def half(attribute):                                             # RuntimeError if the parameter was rebound since the snapshot
-            return None if weights is None else weights.view(self, attribute)
-
         if cross:
-            q = D.empty([b, t, h, dk])
-            D.gemm(b * t, f, f, Mat(query, f), Mat(wq, f, half=half('_wq')), Mat(q, f), trans_b=True, bias=bq, skinny_ok=True)
-            q = Mat(q, f)
+            (q, _, _), _, _ = self._project_in(query, None, None, weights=weights, skinny_ok=True)
         else:
             # ONE GEMM over M = B T rows makes q, k and v where the parameters are adjacent; K and V rows then go into the cache
             # straight out of the packed buffer (npm_kv_append reads with its row pitch)
-            packed = dk == dv and D.PACK_QKV and self._params_adjacent()
-            if packed:
-                width = f + 2 * fkv
-                qkv = D.empty([b, t, h + 2 * hkv, dk])
-                # (adjacent parameters at unchanged addresses were adjacent when the snapshot was taken: so are their halves)
-                wq_half, _, _ = half('_wq'), half('_wk'), half('_wv')
-                D.gemm(b * t, width, f, Mat(query, f), Mat(wq, f, half=wq_half), Mat(qkv, width), trans_b=True, bias=bq, skinny_ok=True)
-                q = Mat(qkv, width)
-                fresh = (Mat(qkv.flat_view(f, [qkv.size - f]), width), Mat(qkv.flat_view(f + fkv, [qkv.size - f - fkv]), width))
-            else:
-                qa, ka, va = D.empty([b, t, h, dk]), D.empty([b, t, hkv, dk]), D.empty([b, t, hkv, dv])
-                D.gemm(b * t, f, f, Mat(query, f), Mat(wq, f, half=half('_wq')), Mat(qa, f), trans_b=True, bias=bq, skinny_ok=True)
-                D.gemm(b * t, fkv, f, Mat(query, f), Mat(wk, f, half=half('_wk')), Mat(ka, fkv), trans_b=True, bias=bk, skinny_ok=True)
-                D.gemm(b * t, fvkv, f, Mat(query, f), Mat(wv, f, half=half('_wv')), Mat(va, fvkv), trans_b=True, bias=bv, skinny_ok=True)
-                q, fresh = Mat(qa, f), (Mat(ka, fkv), Mat(va, fvkv))
+            (q, *fresh), _, packed = self._project_in(query, query, query, weights=weights, skinny_ok=True)
             if rope:
                 # q and the fresh k rows at positions lengths[b] + t, BEFORE they are stored: the cache, its kernels and the
                 # fp16 rounding see rotated rows and need nothing of their own.  Per-sequence positions are the `before` row of
@@ -505,8 +505,8 @@ class MultiHeadAttention(layer.StatefulLayer):
             cache.append(fresh[0], fresh[1], t, new_lengths)
         ctx = self._attend(q, cache, t, not cross, fresh, before, new_lengths, ragged)
         out = D.empty([b, t, f])
-        D.gemm(b * t, f, h * dv, Mat(ctx, h * dv), Mat(wo, h * dv, half=half('_wo')), Mat(out, f), trans_b=True, bias=bo,
-               residual=None if residual is None else Mat(residual, f), skinny_ok=True)
+        D.gemm(b * t, f, h * dv, Mat(ctx, h * dv), Mat(self._param('_wo'), h * dv, half=None if weights is None else weights.view(self, '_wo')),
+               Mat(out, f), trans_b=True, bias=self._param('_bo'), residual=None if residual is None else Mat(residual, f), skinny_ok=True)
         return out
 
     def _attend(self, q: Mat, cache: D.KVCache, t: int, causal: bool, fresh, before: np.ndarray, new_lengths,
@@ -568,15 +568,8 @@ class MultiHeadAttention(layer.StatefulLayer):
         ctx = D.empty([b, t, h, dv])
         pk, pv, cap = hkv * dk, hkv * dv, cache.capacity
         for first, rows, keys in ([(i, 1, length - t + i + 1) for i in range(t)] if causal and t > 1 else [(0, t, length)]):
-            scores = D.empty([b, h, rows, keys])
-            for g in range(h // hkv):
-                D.gemm(rows, keys, dk, Mat(q.ptr + 4 * (first * q.ld + g * pk), q.ld, t * q.ld, dk), Mat(cache.k, pk, cap * pk, dk),
-                       Mat(_from(scores, g * hkv * rows * keys), keys, h * rows * keys, rows * keys), trans_b=True, batch=(b, hkv))
-            D.softmax_fwd(scores, scale, out=scores)
-            for g in range(h // hkv):
-                D.gemm(rows, dv, keys, Mat(_from(scores, g * hkv * rows * keys), keys, h * rows * keys, rows * keys),
-                       Mat(cache.v, pv, cap * pv, dv),
-                       Mat(ctx.ptr + 4 * (first * h * dv + g * pv), h * dv, t * h * dv, dv), batch=(b, hkv))
+            _gemm_attention(Mat(q.ptr + 4 * first * q.ld, q.ld, t * q.ld), Mat(cache.k, pk, cap * pk), Mat(cache.v, pv, cap * pv),
+                            Mat(ctx.ptr + 4 * first * h * dv, h * dv, t * h * dv), (b, h, hkv, rows, keys, dk, dv), scale)
         return ctx
 
     @staticmethod

@@ -26,7 +26,7 @@ dropout, feeding a sequence to ``decode`` in chunks of any sizes gives, row for 
 
 from __future__ import annotations
 
-from typing import Optional
+from typing import Callable, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -61,28 +61,198 @@ def _block_segments(norm, body, norm_first: bool):
 
 # A transformer layer is a chain of residual blocks around a body (attention or the feed-forward pair):
 #     pre-norm :  y = x + body(norm(drop(x)))          post-norm:  y = norm(drop(x + body(x)))
-# The two helpers below are that block and its mirror image, built from standalone device adds -- the literal
-# (unfused) composition, used when dropout is active, by the decoder, and as the reference the fused encoder is
-# tested against.
-def _block_forward(x, norm, dropout, norm_first: bool, body):
+# A layer lists its blocks (``_blocks``) and everything it does is a walk over that list.  The norm order is looked at by the
+# four functions below and by ``_block_segments``, nowhere else.
+class _Block(NamedTuple):
+    norm: normalizations.LayerNormalization
+    dropout: Optional[normalizations.DropOut]   # directly in front of the norm; None: inference
+    forward: Callable                           # fused body, (h, residual=skip) -> body(h) + skip: the addition rides a GEMM epilogue
+    backward: Optional[Callable] = None         # its mirror, (dy, optimizer_, scope, residual=) -> gradient of h (+ residual)
+    body: Optional[Callable] = None             # the literal body, x -> body(x)
+    body_backward: Optional[Callable] = None    # (dy, optimizer_, scope) -> gradient of the body's (first) input
+    segments: Sequence = ()                     # the body's parameters in the order its backward produces their gradients
+    numel: Optional[Callable] = None            # floats those gradients need
+    flat: bool = False                          # works on the [rows, F] view
+    flush: bool = False                         # a scope.flush() closes the block's backward (attention flushes by itself)
+
+
+def _fused_forward(x, block: _Block, norm_first: bool):
+    """The block with its residual addition inside the body's last GEMM and its dropout inside the norm's kernels."""
+    if norm_first:
+        return block.forward(block.norm._forward_impl(x, block.dropout), residual=x)
+    return block.norm._forward_impl(block.forward(x, residual=x), block.dropout)
+
+
+def _fused_backward(dy, block: _Block, norm_first: bool, optimizer_, scope):
+    """Mirror of ``_fused_forward``: the skip path's gradient rides the LayerNorm backward (pre-norm) or the body's
+    input-gradient GEMM (post-norm)."""
+    if norm_first:
+        dx = block.norm._backward_impl(block.backward(dy, optimizer_, scope), optimizer_, scope, residual=dy)
+    else:
+        dy = block.norm._backward_impl(dy, optimizer_, scope)
+        dx = block.backward(dy, optimizer_, scope, residual=dy)
+    if block.flush:
+        scope.flush()
+    return dx
+
+
+# The same block and its mirror image built from standalone device adds -- the literal (unfused) composition, used when
+# the dropout cannot ride the norm's kernels or the activation is not a ReLU, and as the reference the fused one is tested against.
+def _block_forward(x, block: _Block, norm_first: bool):
     x = D.as_device(x)
     if norm_first:
-        return D.add(D.as_device(body(norm(dropout(x)))), x)
-    return D.as_device(norm(dropout(D.add(D.as_device(body(x)), x))))
+        return D.add(D.as_device(block.body(block.norm(block.dropout(x)))), x)
+    return D.as_device(block.norm(block.dropout(D.add(D.as_device(block.body(x)), x))))
 
 
-def _block_backward(dy, norm, dropout, norm_first: bool, body_backward, optimizer_, scope):
-    """``body_backward(dy)`` returns the gradient w.r.t. the body's (first) input; the skip path adds ``dy``."""
+def _block_backward(dy, block: _Block, norm_first: bool, optimizer_, scope):
+    """``body_backward`` returns the gradient w.r.t. the body's (first) input; the skip path adds ``dy``."""
     if not norm_first:
-        dy = dropout.backward(norm._backward_impl(D.as_device(dy), optimizer_, scope))
+        dy = block.dropout.backward(block.norm._backward_impl(D.as_device(dy), optimizer_, scope))
     through_skip = D.as_device(dy)
-    through_body = D.as_device(body_backward(through_skip))
+    through_body = D.as_device(block.body_backward(through_skip, optimizer_, scope))
     if norm_first:
-        through_body = D.as_device(dropout.backward(norm._backward_impl(through_body, optimizer_, scope)))
+        through_body = D.as_device(block.dropout.backward(block.norm._backward_impl(through_body, optimizer_, scope)))
     return D.add(through_body, through_skip)
 
 
-class TransformerEncoder(layer.Layer):
+def _shaped(x, flat: bool, shape):
+    """``x`` as [rows, F] (``flat``) or as ``shape`` [B, S, F]."""
+    if flat == (len(x.shape) == 2):
+        return x
+    return x.reshape(-1, shape[-1]) if flat else x.reshape(shape)
+
+
+# Sub-layers initialise lazily at their first call, in call order, exactly as in the
+# reference (layer.py:33-35) -- that fixes the global-RNG draw order of the parameters.
+def _ensure(sub, *args):
+    if not sub._initialized:
+        sub.initialize(*args)
+        sub._initialized = True
+
+
+class _ResidualBlocks(layer.Layer):
+    """What TransformerEncoder and TransformerDecoder share: a list of residual blocks, walked forward and backward in the
+    fused or the literal composition."""
+
+    _SLACK = 0          # floats of the gradient bucket beyond the parameters' own
+
+    def initialize(self, x, *memory):
+        self._dense2 = mlp.Linear(units=x.shape[-1])  # no activation (transformer.py:25-27)
+
+    def _self_mask(self, batch: int, seq: int):
+        return None
+
+    def _blocks(self, kv=None, kv_grad=None) -> List[_Block]:
+        raise NotImplementedError
+
+    def _self_attention_block(self, norm, dropout) -> _Block:
+        att = self._self_attention
+
+        def forward(h, residual):
+            _ensure(att, h)
+            return att._forward_impl(h, h, h, residual=residual, mask=self._self_mask(*h.shape[:2]))     # ... + skip (transformer.py:39)
+
+        return _Block(norm, dropout, forward,
+                      lambda dy, optimizer_, scope, residual=None:                                     # dq + dk + dv (+ skip)
+                      att._backward_impl(dy, optimizer_, scope, sum_inputs=True, residual=residual),
+                      lambda x: att(x, mask=self._self_mask(*x.shape[:2])),
+                      lambda dy, optimizer_, scope: D.add3(*att._backward_impl(dy, optimizer_, scope)),
+                      att._segments(), att._numel)
+
+    def _feed_forward_block(self, norm, dropout) -> _Block:
+        dense1, dense2 = self._dense1, self._dense2
+        lin1 = dense1._linear
+
+        def forward(h, residual):
+            h = dense1(h)
+            _ensure(dense2, h)
+            return dense2._forward_impl(h, residual=residual)                                           # ... + skip (transformer.py:53)
+
+        def backward(dy, optimizer_, scope, residual=None):
+            # dense2: dx masked by dense1's ReLU (activations.py:19) in the GEMM epilogue; dense1's bias gradient
+            # (the column sums of that masked dx, mlp.py:34) comes out of dense1's weight-gradient GEMM
+            dh = dense2._backward_impl(dy, optimizer_, scope, relu_mask_pre=dense1._activation._x)
+            scope.flush()
+            return lin1._backward_impl(dh, optimizer_, scope, residual=residual)
+
+        def body_backward(dy, optimizer_, scope):
+            dy = dense2._backward_impl(D.as_device(dy), optimizer_, scope)
+            dy = dense1._activation.backward(dy)
+            return lin1._backward_impl(D.as_device(dy), optimizer_, scope)
+
+        return _Block(norm, dropout, forward, backward, lambda x: dense2(dense1(x)), body_backward,
+                      _linear_segments(dense2) + _linear_segments(lin1),
+                      lambda: lin1._w.size + lin1._b.size + dense2._w.size + dense2._b.size, flat=True, flush=True)
+
+    def _walk(self, run, x, blocks, *args):
+        shape = x.shape
+        for block in blocks:
+            x = run(_shaped(x, block.flat, shape), block, self._norm_first, *args)
+        return _shaped(x, False, shape)
+
+    def _fusable(self, features: int = 0) -> bool:
+        """The fused composition: always without dropout; with dropout when the LayerNorm kernels can apply it (row
+        length: device.layernorm_dropout_supported)."""
+        return _dropout_folds(features, *(block.dropout for block in self._blocks())) and self._dense1._fused_relu()
+
+    def _numel(self) -> int:
+        """Floats the gradients of one backward need: ONE bucket for the exchange (opened without a size, every gradient
+        would be a collective of its own at N > 1)."""
+        return sum(block.numel() + 2 * block.norm._param('_gamma').size for block in self._blocks()) + self._SLACK
+
+    def _pack(self) -> None:
+        """After the first forward (every sub-layer has drawn its parameters, in the reference's order): all parameters
+        into ONE arena, ordered as ``backward`` produces their gradients -- last block first -- so that gradient bucket,
+        exchange and the deferred updates walk one range (one optimizer launch per step)."""
+        if self._arena is None:
+            self._pack_parameters([segment for block in reversed(self._blocks())
+                                   for segment in _block_segments(block.norm, list(block.segments), self._norm_first)])
+
+    def _forward(self, x, *memory):
+        self._fused = self._fusable(x.shape[-1])
+        if not self._fused:
+            return self._forward_unfused(x, *memory)
+        # each DropOut sits directly in front of a LayerNormalization (transformer.py:35-36,40-41,49-50,55-56; the decoder's
+        # 125-126,131-132,137-138,142-143,149-150,154-155) and is applied inside that norm's kernels
+        out = self._walk(_fused_forward, x, self._blocks(*memory))
+        self._pack()
+        return out
+
+    def _forward_unfused(self, x, *memory):
+        """The reference's composition (transformer.py:29-59, 120-157) out of standalone kernels."""
+        self._self_mask(*x.shape[:2])                   # made in front of the first block
+        out = self._walk(_block_forward, x, self._blocks(*memory))
+        self._pack()
+        return out
+
+    def backward(self, dy, optimizer_):
+        dy = D.as_device(dy)
+        with parallel.grad_scope(self._numel(), self._arena) as scope:
+            if self._fused and self._dense1._fused_relu():           # the composition the forward ran
+                return self._backward_fused(dy, optimizer_, scope)
+            return self._backward_unfused(dy, optimizer_, scope)
+
+    def _walk_back(self, run, dy, optimizer_, scope):
+        kv_grad = []
+        dx = self._walk(run, dy, self._blocks(None, kv_grad)[::-1], optimizer_, scope)
+        return (dx, kv_grad[0]) if kv_grad else dx
+
+    def _backward_fused(self, dy, optimizer_, scope):
+        """Mirror of the fused forward: skip-connection gradients ride the LayerNorm backward (pre-norm) or the
+        input-gradient GEMMs (post-norm); dense1's ReLU backward is the mask epilogue of dense2's dx GEMM; the
+        cross-attention's dkey + dvalue and the self-attention's dq + dk + dv accumulate in GEMM epilogues."""
+        return self._walk_back(_fused_backward, dy, optimizer_, scope)
+
+    def _backward_unfused(self, dy, optimizer_, scope):
+        """Mirror of ``_forward_unfused`` (transformer.py:61-92, 159-203); the attention blocks sum their input gradients
+        with standalone adds."""
+        return self._walk_back(_block_backward, dy, optimizer_, scope)
+
+
+class TransformerEncoder(_ResidualBlocks):
+    _SLACK = 64
+
     def __init__(self, num_heads: int, hidden_units: int, norm_first: bool, drop_rate: float = 0.0,
                  *args, num_kv_heads: Optional[int] = None, rope_base: Optional[float] = None, **kwargs):
         super().__init__(*args, **kwargs)
@@ -95,133 +265,20 @@ class TransformerEncoder(layer.Layer):
         self._dropout2 = normalizations.DropOut(drop_rate)
         self._fused = True      # which composition the last forward ran (the backward mirrors it)
 
-    def initialize(self, qkv):
-        features = qkv.shape[-1]
-        self._dense2 = mlp.Linear(units=features)  # no activation (transformer.py:25-27)
-
-    def _numel(self) -> int:
-        att = self._self_attention._numel()
-        lin1, lin2 = self._dense1._linear, self._dense2
-        norms = 2 * (self._norm1._param('_gamma').size + self._norm2._param('_gamma').size)
-        return att + lin1._w.size + lin1._b.size + lin2._w.size + lin2._b.size + norms + 64
-
-    def _pack(self) -> None:
-        """After the first forward (every sub-layer has drawn its parameters, in the reference's order): all 16 parameters
-        into ONE arena, ordered as ``backward`` produces their gradients -- feed-forward block, then attention block --
-        so that gradient bucket, exchange and the deferred updates walk one range (one optimizer launch per step)."""
-        if self._arena is None:
-            pre = self._norm_first
-            ffn = _linear_segments(self._dense2) + _linear_segments(self._dense1._linear)
-            if pre:     # dense2 | dense1, norm2 | attention | norm1 -- the four flushes of _backward_fused
-                segments = ffn + _norm_segments(self._norm2) + self._self_attention._segments() + _norm_segments(self._norm1)
-            else:       # norm2, dense2 | dense1 | norm1, attention
-                segments = (_norm_segments(self._norm2) + ffn + _norm_segments(self._norm1)
-                            + self._self_attention._segments())
-            self._pack_parameters(segments)
-
-    # Sub-layers initialise lazily at their first call, in call order, exactly as in the
-    # reference (layer.py:33-35) -- that fixes the global-RNG draw order of the parameters.
-    @staticmethod
-    def _ensure(sub, *args):
-        if not sub._initialized:
-            sub.initialize(*args)
-            sub._initialized = True
+    def _blocks(self, kv=None, kv_grad=None) -> List[_Block]:
+        """Self-attention, feed-forward (transformer.py:29-59): 16 parameters."""
+        return [self._self_attention_block(self._norm1, self._dropout1), self._feed_forward_block(self._norm2, self._dropout2)]
 
     def forward(self, qkv):
-        qkv = D.as_device(qkv)
-        batch, seq_len_q, features = qkv.shape
-        self._fused = _dropout_folds(features, self._dropout1, self._dropout2) and self._dense1._fused_relu()
-        if not self._fused:
-            return self._forward_unfused(qkv)
-        att, dense1, dense2 = self._self_attention, self._dense1, self._dense2
-        norm1, norm2 = self._norm1, self._norm2
-        skip = qkv
-        h = qkv
-        if self._norm_first:
-            h = norm1._forward_impl(h, self._dropout1)                   # dropout1 inside the norm (transformer.py:35-36)
-        self._ensure(att, h)
-        out = att._forward_impl(h, h, h, residual=skip)                  # ... + skip (transformer.py:39)
-        if not self._norm_first:
-            out = norm1._forward_impl(out, self._dropout1)               # transformer.py:40-41
-        out = out.reshape(-1, features)
-        skip = out
-        if self._norm_first:
-            out = norm2._forward_impl(out, self._dropout2)               # transformer.py:49-50
-        out = dense1(out)
-        self._ensure(dense2, out)
-        out = dense2._forward_impl(out, residual=skip)                   # ... + skip (transformer.py:53)
-        if not self._norm_first:
-            out = norm2._forward_impl(out, self._dropout2)               # transformer.py:55-56
-        self._pack()
-        return out.reshape(batch, seq_len_q, features)
-
-    def _feed_forward(self, x):
-        return self._dense2(self._dense1(x))
-
-    def _feed_forward_backward(self, dy, optimizer_, scope):
-        dy = self._dense2._backward_impl(D.as_device(dy), optimizer_, scope)
-        dy = self._dense1._activation.backward(dy)
-        return self._dense1._linear._backward_impl(D.as_device(dy), optimizer_, scope)
-
-    def _forward_unfused(self, qkv):
-        """The reference's composition (transformer.py:29-59) out of standalone kernels: two residual blocks."""
-        batch, seq_len_q, features = qkv.shape
-        out = _block_forward(qkv, self._norm1, self._dropout1, self._norm_first, self._self_attention)
-        out = _block_forward(out.reshape(-1, features), self._norm2, self._dropout2, self._norm_first,
-                             self._feed_forward)
-        self._pack()
-        return out.reshape(batch, seq_len_q, features)
-
-    def backward(self, dy, optimizer_):
-        dy = D.as_device(dy)
-        with parallel.grad_scope(self._numel(), self._arena) as scope:
-            if self._fused and self._dense1._fused_relu():           # the composition the forward ran
-                return self._backward_fused(dy, optimizer_, scope)
-            return self._backward_unfused(dy, optimizer_, scope)
-
-    def _backward_fused(self, dy, optimizer_, scope):
-        batch, seq_len_q, features = dy.shape
-        att, lin1, lin2 = self._self_attention, self._dense1._linear, self._dense2
-        pre1 = self._dense1._activation._x
-        dy = dy.reshape(-1, features)
-        if not self._norm_first:
-            dy = self._norm2._backward_impl(dy, optimizer_, scope)
-        dskip = dy
-        # dense2: dx masked by dense1's ReLU (activations.py:19) in the GEMM epilogue; dense1's bias gradient
-        # (the column sums of that masked dx, mlp.py:34) comes out of dense1's weight-gradient GEMM
-        dh = lin2._backward_impl(dy, optimizer_, scope, relu_mask_pre=pre1)
-        scope.flush()
-        if self._norm_first:
-            dy = lin1._backward_impl(dh, optimizer_, scope)
-            dy = self._norm2._backward_impl(dy, optimizer_, scope, residual=dskip)     # dy += dskip
-        else:
-            dy = lin1._backward_impl(dh, optimizer_, scope, residual=dskip)            # dy += dskip
-        scope.flush()
-        dy = dy.reshape(batch, seq_len_q, features)
-        if not self._norm_first:
-            dy = self._norm1._backward_impl(dy, optimizer_, scope)
-        dskip = dy
-        if self._norm_first:
-            dy = att._backward_impl(dy, optimizer_, scope, sum_inputs=True)            # dq + dk + dv
-            dy = self._norm1._backward_impl(dy, optimizer_, scope, residual=dskip)     # dy += dskip
-        else:
-            dy = att._backward_impl(dy, optimizer_, scope, sum_inputs=True, residual=dskip)
-        return dy
-
-    def _backward_unfused(self, dy, optimizer_, scope):
-        """Mirror of ``_forward_unfused`` (transformer.py:61-92); the attention block sums dquery + dkey + dvalue."""
-        batch, seq_len_q, features = dy.shape
-        dy = _block_backward(dy.reshape(-1, features), self._norm2, self._dropout2, self._norm_first,
-                             lambda g: self._feed_forward_backward(g, optimizer_, scope), optimizer_, scope)
-        return _block_backward(dy.reshape(batch, seq_len_q, features), self._norm1, self._dropout1, self._norm_first,
-                               lambda g: D.add3(*self._self_attention._backward_impl(g, optimizer_, scope)),
-                               optimizer_, scope)
+        return self._forward(D.as_device(qkv))
 
 
-class TransformerDecoder(layer.Layer):
+class TransformerDecoder(_ResidualBlocks):
     """Self-attention, cross-attention over ``kv``, feed-forward; three LayerNorms
     (transformer.py:95-203).  ``backward`` returns ``(dq, dkv)`` with
     ``dkv = dkey + dvalue`` of the cross-attention (transformer.py:186)."""
+
+    _SLACK = 128
 
     def __init__(self, num_heads: int, hidden_units: int, norm_first: bool, drop_rate: float = 0.0,
                  *args, num_kv_heads: Optional[int] = None, causal: bool = False, rope_base: Optional[float] = None,
@@ -246,43 +303,30 @@ class TransformerDecoder(layer.Layer):
         self._dropout1 = normalizations.DropOut(drop_rate)
         self._dropout2 = normalizations.DropOut(drop_rate)
         self._dropout3 = normalizations.DropOut(drop_rate)
+        self._fused = True      # which composition the last forward ran (the backward mirrors it)
 
-    def initialize(self, q, kv):
-        features = q.shape[-1]
-        self._dense2 = mlp.Linear(units=features)  # no activation
+    def _blocks(self, kv=None, kv_grad=None) -> List[_Block]:
+        """Self-attention, cross-attention over ``kv``, feed-forward (transformer.py:120-157): 26 parameters.  ``kv_grad``: the
+        list a backward leaves the cross-attention's dkey + dvalue in (transformer.py:186)."""
+        ca = self._cross_attention
 
-    def _feed_forward(self, x):
-        return self._dense2(self._dense1(x))
+        def forward(h, residual):
+            _ensure(ca, h, kv)
+            return ca._forward_impl(h, kv, kv, residual=residual)                                       # ... + skip (transformer.py:141)
 
-    @staticmethod
-    def _ensure(sub, *args):
-        if not sub._initialized:
-            sub.initialize(*args)
-            sub._initialized = True
+        def backward(dy, optimizer_, scope, residual=None):      # dkey + dvalue accumulate in their GEMMs' epilogues
+            dquery, dkv = ca._backward_impl(dy, optimizer_, scope, sum_kv=True, residual=residual)
+            kv_grad.append(dkv)
+            return dquery
 
-    _fused = True          # which composition the last forward ran (the backward mirrors it)
+        def body_backward(dy, optimizer_, scope):
+            dquery, dkey, dvalue = ca._backward_impl(dy, optimizer_, scope)
+            kv_grad.append(D.add(dkey, dvalue))
+            return dquery
 
-    def _fusable(self, features: int = 0) -> bool:
-        """The fused composition: always without dropout; with dropout when the LayerNorm kernels can apply it (row
-        length: device.layernorm_dropout_supported)."""
-        return _dropout_folds(features, self._dropout1, self._dropout2, self._dropout3) and self._dense1._fused_relu()
-
-    def _numel(self) -> int:
-        """Floats the gradients of one backward need (26 parameter tensors): ONE bucket for the exchange, like the
-        encoder's (round 4 opened the scope without a size: every gradient was a collective of its own at N > 1)."""
-        lin1, lin2 = self._dense1._linear, self._dense2
-        norms = sum(2 * n._param('_gamma').size for n in (self._norm1, self._norm2, self._norm3))
-        return (self._self_attention._numel() + self._cross_attention._numel() + lin1._w.size + lin1._b.size
-                + lin2._w.size + lin2._b.size + norms + 128)
-
-    def _pack(self) -> None:
-        """See TransformerEncoder._pack: feed-forward block, cross-attention block, self-attention block."""
-        if self._arena is None:
-            pre = self._norm_first
-            ffn = _linear_segments(self._dense2) + _linear_segments(self._dense1._linear)
-            ca, sa = self._cross_attention._segments(), self._self_attention._segments()
-            self._pack_parameters(_block_segments(self._norm3, ffn, pre) + _block_segments(self._norm2, ca, pre)
-                                  + _block_segments(self._norm1, sa, pre))
+        return [self._self_attention_block(self._norm1, self._dropout1),
+                _Block(self._norm2, self._dropout2, forward, backward, lambda x: ca(x, kv), body_backward, ca._segments(), ca._numel),
+                self._feed_forward_block(self._norm3, self._dropout3)]
 
     def _self_mask(self, batch: int, seq: int):
         """None, or (``causal=True``) the lower-triangular mask of the self-attention -- with ``window=W`` the band
@@ -301,37 +345,9 @@ class TransformerDecoder(layer.Layer):
         """Three residual blocks: self-attention, cross-attention over ``kv``, feed-forward (transformer.py:120-157).
         The residual additions ride the producing GEMMs' epilogues and the dropouts the LayerNorm kernels, as in the encoder."""
         q, kv = D.as_device(q), D.as_device(kv)
-        batch, seq_len_q, features = q.shape
         self._decoded = False
-        self._fused = self._fusable(features)
-        if not self._fused:
-            return self._forward_unfused(q, kv)
-        pre = self._norm_first
-        sa, ca, dense1, dense2 = self._self_attention, self._cross_attention, self._dense1, self._dense2
         self._kv = kv
-        # each DropOut sits directly in front of a LayerNormalization (transformer.py:125-126,131-132,137-138,142-143,
-        # 149-150,154-155) and is applied inside that norm's kernels
-        h = self._norm1._forward_impl(q, self._dropout1) if pre else q
-        self._ensure(sa, h)
-        out = sa._forward_impl(h, h, h, residual=q, mask=self._self_mask(batch, seq_len_q))   # ... + skip (transformer.py:130)
-        if not pre:
-            out = self._norm1._forward_impl(out, self._dropout1)
-        skip = out
-        h = self._norm2._forward_impl(out, self._dropout2) if pre else out
-        self._ensure(ca, h, kv)
-        out = ca._forward_impl(h, kv, kv, residual=skip)                  # ... + skip (transformer.py:141)
-        if not pre:
-            out = self._norm2._forward_impl(out, self._dropout2)
-        out = out.reshape(-1, features)
-        skip = out
-        h = self._norm3._forward_impl(out, self._dropout3) if pre else out
-        h = dense1(h)
-        self._ensure(dense2, h)
-        out = dense2._forward_impl(h, residual=skip)                      # ... + skip (transformer.py:152)
-        if not pre:
-            out = self._norm3._forward_impl(out, self._dropout3)
-        self._pack()
-        return out.reshape(batch, seq_len_q, features)
+        return self._forward(q, kv)
 
     # -- incremental decoding (inference) ------------------------------------------------------------------------------
     def start_decoding(self, kv, capacity: int, kv_lengths=None, *, page_size: Optional[int] = None, pages: Optional[int] = None,
@@ -400,15 +416,7 @@ class TransformerDecoder(layer.Layer):
         if rows > cross.capacity:
             raise ValueError(f'admit: {rows} memory rows do not fit the cross-attention cache of {cross.capacity} rows '
                              '(start_decoding(..., memory_capacity=))')
-        hkv = cross.kv_heads
-
-        def project(w, bias, dim):
-            proj = D.empty([1, rows, hkv, dim])
-            D.gemm(rows, hkv * dim, f, D.Mat(kv_b, f), D.Mat(ca._param(w), f), D.Mat(proj, hkv * dim), trans_b=True, bias=ca._param(bias))
-            return D.Mat(proj, hkv * dim)
-
-        cross.write_slot(b, project('_wk', '_bk', cross.key_dim), None, rows)     # K is projected and written, then V
-        cross.write_slot(b, None, project('_wv', '_bv', cross.value_dim), rows)
+        ca.fill_slot(cross, b, kv_b, rows)
 
     def fork(self, state: 'DecodeState', src: int, dst: int) -> None:
         """Slot ``dst`` of a running batch continues sequence ``src`` (n completions of one prompt, n-best sampling):
@@ -431,116 +439,31 @@ class TransformerDecoder(layer.Layer):
         passes through them without touching a valid row or being touched by one.  Output rows t >= n[b] are unspecified but
         finite; rows t < n[b] are what sequence b gives when decoded alone."""
         q = D.as_device(q_new)
-        batch, tokens, features = q.shape
-        state.self_cache.room(tokens, new_lengths)                        # ValueError before anything is launched
+        state.self_cache.room(q.shape[1], new_lengths)                    # ValueError before anything is launched
         self._decoded = True
-        pre = self._norm_first
-        sa, ca = self._self_attention, self._cross_attention
+        sa, ca, dense1, dense2 = self._self_attention, self._cross_attention, self._dense1, self._dense2
         hw = state.weights                                                # None, or the fp16 copies of the six matrices below
-        h = self._norm1._forward_impl(q) if pre else q
-        out = sa._forward_cached(h, state.self_cache, residual=q, new_lengths=new_lengths, weights=hw)
-        if not pre:
-            out = self._norm1._forward_impl(out)
-        skip = out
-        h = self._norm2._forward_impl(out) if pre else out
-        out = ca._forward_cached(h, state.cross_cache, residual=skip, new_lengths=new_lengths, weights=hw)
-        if not pre:
-            out = self._norm2._forward_impl(out)
-        out = out.reshape(-1, features)
-        skip = out
-        h = self._norm3._forward_impl(out) if pre else out
-        self._ensure(self._dense1, h)
-        half1 = None if hw is None else hw.view(self._dense1._linear, '_w')
-        half2 = None if hw is None else hw.view(self._dense2, '_w')
-        out = self._dense2._forward_impl(self._dense1.forward(h, decode=True, half=half1), residual=skip, decode=True, half=half2)
-        if not pre:
-            out = self._norm3._forward_impl(out)
-        return out.reshape(batch, tokens, features)
 
-    def _forward_unfused(self, q, kv):
-        batch, seq_len_q, features = q.shape
-        mask = self._self_mask(batch, seq_len_q)
-        out = _block_forward(q, self._norm1, self._dropout1, self._norm_first,
-                             self._self_attention if mask is None else lambda x: self._self_attention(x, mask=mask))
-        out = _block_forward(out, self._norm2, self._dropout2, self._norm_first,
-                             lambda x: self._cross_attention(x, kv))
-        out = _block_forward(out.reshape(-1, features), self._norm3, self._dropout3, self._norm_first,
-                             self._feed_forward)
-        self._pack()
-        return out.reshape(batch, seq_len_q, features)
+        def feed_forward(h, residual):
+            _ensure(dense1, h)
+            half1 = None if hw is None else hw.view(dense1._linear, '_w')
+            half2 = None if hw is None else hw.view(dense2, '_w')
+            return dense2._forward_impl(dense1.forward(h, decode=True, half=half1), residual=residual, decode=True, half=half2)
+
+        # the blocks of ``forward`` over the caches; no dropout, whatever drop_rate is
+        return self._walk(_fused_forward, q, (
+            _Block(self._norm1, None, lambda h, residual: sa._forward_cached(h, state.self_cache, residual=residual,
+                                                                             new_lengths=new_lengths, weights=hw)),
+            _Block(self._norm2, None, lambda h, residual: ca._forward_cached(h, state.cross_cache, residual=residual,
+                                                                             new_lengths=new_lengths, weights=hw)),
+            _Block(self._norm3, None, feed_forward, flat=True)))
 
     def backward(self, dy, optimizer_):
         """Returns ``(dq, dkv)``; ``dkv`` is the cross-attention's dkey + dvalue (transformer.py:159-203)."""
         if self._decoded:
             raise RuntimeError('backward after decode(): incremental decoding is inference only and overwrote what the last '
                                'forward saved -- run forward again first')
-        dy = D.as_device(dy)
-        with parallel.grad_scope(self._numel(), self._arena) as scope:
-            if self._fused and self._dense1._fused_relu():           # the composition the forward ran
-                return self._backward_fused(dy, optimizer_, scope)
-            return self._backward_unfused(dy, optimizer_, scope)
-
-    def _backward_fused(self, dy, optimizer_, scope):
-        """Mirror of the fused forward: skip-connection gradients ride the LayerNorm backward (pre-norm) or the
-        input-gradient GEMMs (post-norm); dense1's ReLU backward is the mask epilogue of dense2's dx GEMM; the
-        cross-attention's dkey + dvalue and the self-attention's dq + dk + dv accumulate in GEMM epilogues."""
-        batch, seq_len_q, features = dy.shape
-        pre = self._norm_first
-        sa, ca, lin1, lin2 = self._self_attention, self._cross_attention, self._dense1._linear, self._dense2
-        dy = dy.reshape(-1, features)
-        if not pre:
-            dy = self._norm3._backward_impl(dy, optimizer_, scope)
-        dskip = dy
-        dh = lin2._backward_impl(dy, optimizer_, scope, relu_mask_pre=self._dense1._activation._x)
-        scope.flush()
-        if pre:
-            dy = self._norm3._backward_impl(lin1._backward_impl(dh, optimizer_, scope), optimizer_, scope, residual=dskip)
-        else:
-            dy = lin1._backward_impl(dh, optimizer_, scope, residual=dskip)
-        scope.flush()
-        dy = dy.reshape(batch, seq_len_q, features)
-        if not pre:
-            dy = self._norm2._backward_impl(dy, optimizer_, scope)
-        dskip = dy
-        if pre:
-            dquery, dkv = ca._backward_impl(dy, optimizer_, scope, sum_kv=True)
-            dy = self._norm2._backward_impl(dquery, optimizer_, scope, residual=dskip)
-        else:
-            dy, dkv = ca._backward_impl(dy, optimizer_, scope, sum_kv=True, residual=dskip)
-        if not pre:
-            dy = self._norm1._backward_impl(dy, optimizer_, scope)
-        dskip = dy
-        if pre:
-            dy = sa._backward_impl(dy, optimizer_, scope, sum_inputs=True)
-            dy = self._norm1._backward_impl(dy, optimizer_, scope, residual=dskip)
-        else:
-            dy = sa._backward_impl(dy, optimizer_, scope, sum_inputs=True, residual=dskip)
-        return dy, dkv
-
-    def _backward_unfused(self, dy, optimizer_, scope):
-        batch, seq_len_q, features = dy.shape
-        kv_grad = []
-
-        def feed_forward_backward(g):
-            g = self._dense2._backward_impl(D.as_device(g), optimizer_, scope)
-            g = self._dense1._activation.backward(g)
-            return self._dense1._linear._backward_impl(D.as_device(g), optimizer_, scope)
-
-        def cross_attention_backward(g):
-            dquery, dkey, dvalue = self._cross_attention._backward_impl(g, optimizer_, scope)
-            kv_grad.append(D.add(dkey, dvalue))
-            return dquery
-
-        def self_attention_backward(g):
-            return D.add3(*self._self_attention._backward_impl(g, optimizer_, scope))
-
-        dy = _block_backward(dy.reshape(-1, features), self._norm3, self._dropout3, self._norm_first,
-                             feed_forward_backward, optimizer_, scope)
-        dy = _block_backward(dy.reshape(batch, seq_len_q, features), self._norm2, self._dropout2,
-                             self._norm_first, cross_attention_backward, optimizer_, scope)
-        dy = _block_backward(dy, self._norm1, self._dropout1, self._norm_first, self_attention_backward,
-                             optimizer_, scope)
-        return dy, kv_grad[0]
+        return super().backward(dy, optimizer_)
 
 
 class DecodeState:
