@@ -245,6 +245,41 @@ int npm_layernorm_dropout_fwd(const float *x, const unsigned char *mask, float k
 int npm_layernorm_dropout_bwd(const float *dz, const float *x, const unsigned char *mask, float keep_prob, const float *mean,
                               const float *rstd, const float *gamma, const float *residual, int64_t rows, int64_t d,
                               float *dx, float *dgamma, float *dbeta);
+/* RMSNorm over the last axis: LayerNorm without the mean and without beta, as kernels of their own in the same width grid (a row
+ * in registers with 1 / 2 / 4 / 8 / 16 float4 per lane for d % 4 == 0, d <= 4096 and 16-byte aligned x, z / dz, dx, residual and
+ * gamma; a generic kernel takes every other d or alignment).
+ *   forward   ms = sum(x^2) / d, rstd = 1 / sqrtf(ms + eps), z = gamma * (x * rstd); rstd [rows] is saved.  The sum is a plain
+ *             fp32 sum of the squares as they are: no rescaling by the row's largest element, so an |x| above about 1.8e19
+ *             overflows it (ms = inf, rstd = 0, z = 0) -- activations are far from that, and the rescaling costs a second pass.
+ *   backward  xh = x * rstd, g = dz * gamma, m2 = sum(g * xh) / d, dx = rstd * (g - xh * m2) [+ residual] (residual may be
+ *             NULL), dgamma = sum over rows of dz * xh.
+ * dgamma is reproducible, as npm_layernorm_bwd's: waves walk rows grid-stride (NPM_TUNE_LN_BWD_BLOCKS blocks per CU), one partial
+ * row per block added in wave order, one fixed-order column sum over the block partials; no float atomics.  A row's z and dx do
+ * not depend on the other rows nor on the row's position.  Tensors of >= 32 MB move with the nontemporal hint (NPM_TUNE_STREAM_NT);
+ * at d in (512, 1024] the hint is on the loads only, npm_layernorm's placement (NPM_TUNE_LN_NT_SPLIT) for npm_layernorm's reason:
+ * a GEMM reads z and dx at once.  rows == 0: the forward is a no-op, the backward writes dgamma = 0. */
+int npm_rmsnorm_fwd(const float *x, const float *gamma, float eps, int64_t rows, int64_t d, float *z, float *rstd);
+int npm_rmsnorm_bwd(const float *dz, const float *x, const float *rstd, const float *gamma, const float *residual /* may be NULL */,
+                    int64_t rows, int64_t d, float *dx, float *dgamma);
+/* The gate of a gated-SiLU ("SwiGLU") feed-forward.  pre [rows, 2 units] with a pitch of ld floats is the output of the packed
+ * gate | up projection: gate columns [0, units), up columns [units, 2 units).
+ *   forward   h[r, c] = (gate * sigma(gate)) * up                                                  h [rows, units], pitch ldh
+ *   backward  dgate = dh * up * sigma(gate) * (1 + gate * (1 - sigma(gate))),  dup = dh * (gate * sigma(gate))
+ *             dpre [rows, 2 units], pitch lddpre, laid out as pre; sigma is recomputed from pre: nothing else is stored.
+ * sigma in the overflow-free two-branch form: t = expf(-|gate|), sigma = gate >= 0 ? 1 / (1 + t) : t / (1 + t); 1 - sigma is the
+ * other branch, so neither cancels.  16-byte loads and stores when units % 4 == 0, every pitch is a multiple of 4 and every base is
+ * 16-byte aligned; one element per thread otherwise.  Grid-stride under NPM_TUNE_EW_GRID_CAP; nontemporal instances when pre has
+ * at least 32 MB (8 rows units bytes; NPM_TUNE_STREAM_NT).  An inf or NaN in an element of pre or dh reaches that element's
+ * outputs only; nothing faults on any value.  The outputs may not overlap the inputs.  Error against exact arithmetic on the
+ * fp32 inputs (u = 2^-24; expf within 1 ulp, correctly rounded division): forward 6 u |h|; backward 8 u T1 + 13 u T2 for dgate
+ * with T1 = |dh up sigma| and T2 = |dh up gate sigma (1 - sigma)| -- relative to the terms, not to their sum, which has a root near
+ * gate = -1.2785 -- and 6 u |dup|; plus absolute terms of a few 2^-126 (|gate| + 1) times the other factors where sigma or 1 - sigma
+ * is below the smallest normal number (|gate| above about 87.3).  tests/test_gpu_swiglu.py derives and asserts them.
+ * NPM_E_BAD_ARGUMENT: units < 1, a pitch below its row, rows outside 0 .. 2^31 - 1, a NULL pointer with rows > 0.  rows == 0 is a
+ * no-op. */
+int npm_swiglu_fwd(const float *pre, int64_t ld, int64_t rows, int64_t units, float *h, int64_t ldh);
+int npm_swiglu_bwd(const float *pre, int64_t ld, const float *dh, int64_t lddh, int64_t rows, int64_t units, float *dpre,
+                   int64_t lddpre);
 
 /* ---- Conv2D: NHWC x HWIO, SAME, stride 1, odd k (layers/conv.py:74-194) ----
  * Implicit-im2col GEMM on the fp32 MFMA; the im2col matrix is never materialised. */

@@ -288,6 +288,11 @@ _SPECIAL = {
     # this call is restated by the tests that need it (tests/hostsim_xent.py) instead of joining the simulator.
     'npm_softmax_xent_rows': (C.c_int, [_P, _I64, _P, _I64, _I64, _F, _F, _P, _I64, _P, _P, C.POINTER(C.c_double)]),
     'npm_last_xent_kernel': (C.c_char_p, []),
+    # Likewise: restated by tests/hostsim_llama.py
+    'npm_rmsnorm_fwd': (C.c_int, [_P, _P, _F, _I64, _I64, _P, _P]),
+    'npm_rmsnorm_bwd': (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
+    'npm_swiglu_fwd': (C.c_int, [_P, _I64, _I64, _I64, _P, _I64]),
+    'npm_swiglu_bwd': (C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _I64]),
 }
 
 COMM_SIGNATURES = {

@@ -719,6 +719,146 @@ layernorm_bwd_dx_generic(const float *__restrict__ dz, const float *__restrict__
     }
 }
 
+// ---- RMSNorm -----------------------------------------------------------------------
+// z = gamma (x rstd), rstd = 1 / sqrt(sum(x^2) / d + eps): LayerNorm without the mean and without beta, as kernels of their own
+// (npm_rmsnorm_fwd / _bwd).  Products and sums are not contracted into fused multiply-adds in the row-in-registers kernels: left to
+// the compiler, instances of one template contracted differently and the nontemporal ones gave other last bits than the plain ones.
+// The sum of squares is a plain fp32 sum of the squares as they are -- no rescaling by the row's
+// largest element: |x| above about 1.8e19 overflows it (rstd = 0, z = 0), as the header says.
+template <int VPL, bool NT, bool NTS = NT>
+__global__ void __launch_bounds__(256)
+rmsnorm_fwd_kernel(const float *__restrict__ x, const float *__restrict__ gamma, float eps, long rows, int d,
+                   float *__restrict__ z, float *__restrict__ rstd_out) {
+#pragma clang fp contract(off)      // every instance (width, hint placement) rounds alike: the hint never changes a bit
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int nvec = d >> 2;
+    float4 v[VPL];
+    load_row<VPL, NT>(x + row * d, nvec, lane, v, 0.f);
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) ss += (v[j].x * v[j].x + v[j].y * v[j].y) + (v[j].z * v[j].z + v[j].w * v[j].w);   // padding is 0
+    const float ms = wave_sum(ss) / (float)d;
+    const float rstd = 1.0f / sqrtf(ms + eps);
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        const int c = lane + WAVE * j;
+        if (c < nvec) {
+            const float4 gm = reinterpret_cast<const float4 *>(gamma)[c];
+            v[j].x = gm.x * (v[j].x * rstd); v[j].y = gm.y * (v[j].y * rstd);
+            v[j].z = gm.z * (v[j].z * rstd); v[j].w = gm.w * (v[j].w * rstd);
+        }
+    }
+    store_row<VPL, NTS>(z + row * d, nvec, lane, v);
+    if (lane == 0) rstd_out[row] = rstd;
+}
+
+__global__ void __launch_bounds__(256)
+rmsnorm_fwd_generic(const float *__restrict__ x, const float *__restrict__ gamma, float eps, long rows, long d,
+                    float *__restrict__ z, float *__restrict__ rstd_out) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float *xr = x + row * d;
+    float ss = 0.f;
+    for (long c = lane; c < d; c += WAVE) ss += xr[c] * xr[c];
+    const float ms = wave_sum(ss) / (float)d;
+    const float rstd = 1.0f / sqrtf(ms + eps);
+    for (long c = lane; c < d; c += WAVE) z[row * d + c] = gamma[c] * (xr[c] * rstd);
+    if (lane == 0) rstd_out[row] = rstd;
+}
+
+// Backward, in the LayerNorm backward's scheme: waves walk rows grid-stride with their dgamma partials in registers, one
+// partial row per BLOCK ([blocks][d]) added in wave order through LDS, one fixed-order column sum over the block partials.
+template <int VPL, bool NT, bool NTS = NT>
+__global__ void __launch_bounds__(256)
+rmsnorm_bwd_kernel(const float *__restrict__ dz, const float *__restrict__ x, const float *__restrict__ rstd,
+                   const float *__restrict__ gamma, const float *__restrict__ residual, long rows, int d,
+                   float *__restrict__ dx, float *__restrict__ part) {
+#pragma clang fp contract(off)      // as the forward: the nontemporal instances give the plain ones' bits
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nvec = d >> 2;
+    float4 gm[VPL], dg[VPL];
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        const int c = lane + WAVE * j;
+        gm[j] = (c < nvec) ? reinterpret_cast<const float4 *>(gamma)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+        dg[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const float inv_d = 1.0f / (float)d;
+    for (long row = (long)blockIdx.x * ROWS_PER_BLOCK + wave; row < rows; row += (long)gridDim.x * ROWS_PER_BLOCK) {
+        float4 g[VPL], xh[VPL], res[VPL];
+        load_row<VPL, NT>(dz + row * d, nvec, lane, g, 0.f);
+        load_row<VPL, NT>(x + row * d, nvec, lane, xh, 0.f);
+        if (residual) load_row<VPL, NT>(residual + row * d, nvec, lane, res, 0.f);
+        const float rs = rstd[row];
+        float s2 = 0.f;
+#pragma unroll
+        for (int j = 0; j < VPL; ++j) {
+            xh[j].x *= rs; xh[j].y *= rs; xh[j].z *= rs; xh[j].w *= rs;                       // padding stays 0
+            dg[j].x += g[j].x * xh[j].x; dg[j].y += g[j].y * xh[j].y;
+            dg[j].z += g[j].z * xh[j].z; dg[j].w += g[j].w * xh[j].w;
+            g[j].x *= gm[j].x; g[j].y *= gm[j].y; g[j].z *= gm[j].z; g[j].w *= gm[j].w;
+            s2 += (g[j].x * xh[j].x + g[j].y * xh[j].y) + (g[j].z * xh[j].z + g[j].w * xh[j].w);
+        }
+        const float m2 = wave_sum(s2) * inv_d;
+#pragma unroll
+        for (int j = 0; j < VPL; ++j) {
+            const int c = lane + WAVE * j;
+            float4 o;
+            o.x = rs * (g[j].x - xh[j].x * m2); o.y = rs * (g[j].y - xh[j].y * m2);
+            o.z = rs * (g[j].z - xh[j].z * m2); o.w = rs * (g[j].w - xh[j].w * m2);
+            if (c < nvec) {
+                if (residual) { o.x += res[j].x; o.y += res[j].y; o.z += res[j].z; o.w += res[j].w; }
+                stg4<NTS>(dx + row * d + 4 * c, o);
+            }
+        }
+    }
+    __shared__ float4 red[3][VPL * WAVE];
+    float4 *prow = reinterpret_cast<float4 *>(part + (long)blockIdx.x * d);
+    if (wave > 0) {
+#pragma unroll
+        for (int j = 0; j < VPL; ++j) red[wave - 1][lane + WAVE * j] = dg[j];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int j = 0; j < VPL; ++j) {
+            const int c = lane + WAVE * j;
+            float4 t = dg[j];
+#pragma unroll
+            for (int w = 0; w < 3; ++w) {
+                const float4 o = red[w][c];
+                t.x += o.x; t.y += o.y; t.z += o.z; t.w += o.w;
+            }
+            if (c < nvec) prow[c] = t;
+        }
+    }
+}
+
+// generic RMSNorm backward: dx only (any d); dgamma then comes from one column sum over dz * xh
+__global__ void __launch_bounds__(256)
+rmsnorm_bwd_dx_generic(const float *__restrict__ dz, const float *__restrict__ x, const float *__restrict__ rstd,
+                       const float *__restrict__ gamma, const float *__restrict__ residual, long rows, long d,
+                       float *__restrict__ dx, float *__restrict__ dz_xhat) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float rs = rstd[row];
+    const float *gr = dz + row * d, *xr = x + row * d;
+    float s2 = 0.f;
+    for (long c = lane; c < d; c += WAVE) s2 += (gr[c] * gamma[c]) * (xr[c] * rs);
+    const float m2 = wave_sum(s2) / (float)d;
+    for (long c = lane; c < d; c += WAVE) {
+        const float xh = xr[c] * rs, g = gr[c] * gamma[c];
+        float o = rs * (g - xh * m2);
+        if (residual) o += residual[row * d + c];
+        dx[row * d + c] = o;
+        dz_xhat[row * d + c] = gr[c] * xh;
+    }
+}
+
 // ---------------------------------------------------------------------------------
 // fp32 <-> IEEE fp16 over a pitched 2-D array (npm_cvt_f32_f16 / npm_cvt_f16_f32): the weight copies of npm_sgemm_skinny_w16
 // ---------------------------------------------------------------------------------
@@ -1126,6 +1266,71 @@ int npm_layernorm_bwd(const float *dz, const float *x, const float *mean, const 
     rc = colsum_impl((const float *)tmp.ptr, dgamma, rows, d, d);
     if (rc) return rc;
     return colsum_impl(dz, dbeta, rows, d, d);
+}
+
+// RMSNorm: the LayerNorm width grid and, at d in (512, 1024], its hint placement (NPM_TUNE_LN_NT_SPLIT, default: loads only).
+int npm_rmsnorm_fwd(const float *x, const float *gamma, float eps, int64_t rows, int64_t d, float *z, float *rstd) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(rows >= 0 && d >= 1);
+    if (rows == 0) return NPM_OK;
+    NPM_ARG(x && gamma && z && rstd);
+    NPM_ARG((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK < (1L << 31));
+    hipStream_t s = npm::ctx().stream;
+    const bool fast = d % 4 == 0 && d <= 4096 && aligned16(x) && aligned16(z) && aligned16(gamma);
+    const int fwd_mode = g_ln_nt_split >> 2;
+    if (fast && fwd_mode && d > 512 && d <= 1024 && stream_nt(sizeof(float) * (size_t)rows * (size_t)d)) {
+        const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
+        if (fwd_mode == 1) hipLaunchKernelGGL((rmsnorm_fwd_kernel<4, true, false>), dim3(grid), dim3(256), 0, s, x, gamma, eps, (long)rows, (int)d, z, rstd);
+        else hipLaunchKernelGGL((rmsnorm_fwd_kernel<4, false, true>), dim3(grid), dim3(256), 0, s, x, gamma, eps, (long)rows, (int)d, z, rstd);
+    } else if (fast) {
+        NPM_ROW_DISPATCH(rmsnorm_fwd_kernel, d, x, gamma, eps, (long)rows, (int)d, z, rstd);
+    } else {
+        const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
+        hipLaunchKernelGGL(rmsnorm_fwd_generic, dim3(grid), dim3(256), 0, s, x, gamma, eps, (long)rows, (long)d, z, rstd);
+    }
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
+}
+
+int npm_rmsnorm_bwd(const float *dz, const float *x, const float *rstd, const float *gamma, const float *residual,
+                    int64_t rows, int64_t d, float *dx, float *dgamma) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(rows >= 0 && d >= 1);
+    NPM_ARG(dgamma != nullptr);
+    if (rows == 0) return npm_fill_f32(dgamma, 0.f, (size_t)d);
+    NPM_ARG(dz && x && rstd && gamma && dx);
+    hipStream_t s = npm::ctx().stream;
+    const bool fast = d % 4 == 0 && d <= 4096 && aligned16(dz) && aligned16(x) && aligned16(dx) &&
+                      aligned16(gamma) && (residual == nullptr || aligned16(residual));
+    if (fast) {
+        const bool nt_rows = stream_nt(sizeof(float) * (size_t)rows * (size_t)d);
+        const long row_blocks = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
+        const int grid = (int)std::min<long>(row_blocks, (long)g_ln_bwd_blocks_per_cu * npm::ctx().num_cus);
+        npm::Scratch part;
+        int rc = part.alloc(sizeof(float) * (size_t)grid * d);
+        if (rc) return rc;
+        float *pp = (float *)part.ptr;                     // [grid][d]: dgamma partials
+        const int bwd_mode = g_ln_nt_split & 3;
+        if (nt_rows && bwd_mode == 1 && d > 512 && d <= 1024)
+            hipLaunchKernelGGL((rmsnorm_bwd_kernel<4, true, false>), dim3(grid), dim3(256), 0, s, dz, x, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
+        else if (nt_rows && bwd_mode == 2 && d > 512 && d <= 1024)
+            hipLaunchKernelGGL((rmsnorm_bwd_kernel<4, false, true>), dim3(grid), dim3(256), 0, s, dz, x, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
+        else if (nt_rows)
+            NPM_ROW_DISPATCH_NT(rmsnorm_bwd_kernel, true, d, dz, x, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
+        else
+            NPM_ROW_DISPATCH_NT(rmsnorm_bwd_kernel, false, d, dz, x, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
+        NPM_CHECK_LAUNCH();
+        return colsum_impl(pp, dgamma, grid, d, d);
+    }
+    NPM_ARG((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK < (1L << 31));
+    npm::Scratch tmp;
+    int rc = tmp.alloc(sizeof(float) * (size_t)rows * d);
+    if (rc) return rc;
+    const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
+    hipLaunchKernelGGL(rmsnorm_bwd_dx_generic, dim3(grid), dim3(256), 0, s, dz, x, rstd, gamma, residual,
+                       (long)rows, (long)d, dx, (float *)tmp.ptr);
+    NPM_CHECK_LAUNCH();
+    return colsum_impl((const float *)tmp.ptr, dgamma, rows, d, d);
 }
 
 }  // extern "C"

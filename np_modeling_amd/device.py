@@ -1101,6 +1101,62 @@ def layernorm_bwd(dz: DeviceArray, x: DeviceArray, mean: DeviceArray, rstd: Devi
     return dx
 
 
+def _entry_point(name: str):
+    """``name`` of the loaded library; NpmError naming it when the library is older than the entry point."""
+    fn = getattr(_C.lib(), name, None)
+    if fn is None:
+        raise _C.NpmError(f'this operation needs {name}, which the loaded library does not have')
+    return fn
+
+
+def rmsnorm_fwd(x: DeviceArray, gamma: DeviceArray, eps: float):
+    """Returns (z, rstd) with z = gamma * x * rstd, rstd = 1 / sqrt(mean(x^2) + eps) of x's shape with the last axis reduced to 1."""
+    fn = _entry_point('npm_rmsnorm_fwd')
+    d = x.shape[-1]
+    rows = x.size // d
+    z, rstd = empty(x.shape), empty(tuple(x.shape[:-1]) + (1,))
+    with _timed('rmsnorm_fwd', nbytes=8.0 * x.size + 4.0 * rows):
+        _C.check(fn(x.ptr, gamma.ptr, float(eps), rows, d, z.ptr, rstd.ptr), 'npm_rmsnorm_fwd')
+    return z, rstd
+
+
+def rmsnorm_bwd(dz: DeviceArray, x: DeviceArray, rstd: DeviceArray, gamma: DeviceArray, dgamma: DeviceArray,
+                residual: Optional[DeviceArray] = None) -> DeviceArray:
+    """dx (+ residual); dgamma is written."""
+    fn = _entry_point('npm_rmsnorm_bwd')
+    d = x.shape[-1]
+    rows = x.size // d
+    dx = empty(dz.shape)
+    with _timed('rmsnorm_bwd', nbytes=(16.0 if residual is not None else 12.0) * x.size + 4.0 * rows):
+        _C.check(fn(dz.ptr, x.ptr, rstd.ptr, gamma.ptr, None if residual is None else residual.ptr, rows, d, dx.ptr, dgamma.ptr),
+                 'npm_rmsnorm_bwd')
+    return dx
+
+
+def swiglu_fwd(pre: DeviceArray) -> DeviceArray:
+    """pre [..., 2 U] = gate | up  ->  h [..., U] = silu(gate) * up."""
+    fn = _entry_point('npm_swiglu_fwd')
+    units = pre.shape[-1] // 2
+    assert 2 * units == pre.shape[-1], pre.shape
+    rows = pre.size // (2 * units) if units else 0
+    h = empty(tuple(pre.shape[:-1]) + (units,))
+    with _timed('swiglu_fwd', nbytes=12.0 * rows * units):
+        _C.check(fn(pre.ptr, 2 * units, rows, units, h.ptr, units), 'npm_swiglu_fwd')
+    return h
+
+
+def swiglu_bwd(pre: DeviceArray, dh: DeviceArray) -> DeviceArray:
+    """dpre [..., 2 U] = dgate | dup from pre and the gradient of ``swiglu_fwd``'s result."""
+    fn = _entry_point('npm_swiglu_bwd')
+    units = pre.shape[-1] // 2
+    rows = pre.size // (2 * units) if units else 0
+    assert dh.size == rows * units, f'{dh.shape} vs {pre.shape}'
+    dpre = empty(pre.shape)
+    with _timed('swiglu_bwd', nbytes=20.0 * rows * units):
+        _C.check(fn(pre.ptr, 2 * units, dh.ptr, units, rows, units, dpre.ptr, 2 * units), 'npm_swiglu_bwd')
+    return dpre
+
+
 # ---- fused attention core ----------------------------------------------------------------------------
 def mha_core_supported(head_dim: int, value_dim: Optional[int] = None, *, any_math: bool = False) -> bool:
     """Whether the fused attention kernels take this head size.  They run the exact-fp32 MFMA only, so under a

@@ -4,6 +4,7 @@
 GEMMs (dw = x^T dy with split-K, dx = dy w^T) plus a column sum for db.
 ``Dense`` with the default ReLU fuses the activation into the forward epilogue (the
 pre-activation is kept for the ``x >= 0`` test of the backward, activations.py:19).
+``GatedDense``: the gate | up half of a gated-SiLU ("SwiGLU") feed-forward, one packed Linear and the gate kernel.
 """
 
 from __future__ import annotations
@@ -131,6 +132,47 @@ class Dense(layer.StatefulLayer):
                 g = D.relu_bwd_colsum(self._activation._x, dy, lin._output_units, db)
                 return lin._backward_impl(g, optimizer_, scope, db=db)
             return lin._backward_impl(self._activation.backward(dy), optimizer_, scope)
+
+    @property
+    def linear(self) -> Linear:
+        assert self._initialized
+        return self._linear
+
+
+class GatedDense(layer.StatefulLayer):
+    """h = silu(x @ w_gate + b_gate) * (x @ w_up + b_up), silu(g) = g * sigmoid(g): the first half of the gated-SiLU feed-forward
+    of LLaMA-style blocks (Shazeer 2020, "GLU Variants Improve Transformer").  ``units`` is the gated width U.
+
+    Both projections are ONE ``Linear`` of 2 U units, ``_linear`` -- one GEMM with the bias epilogue -- whose output ``pre`` is kept
+    for the backward; the gate is ``device.swiglu_fwd`` / ``swiglu_bwd`` (include/npm_hip.h npm_swiglu_fwd / _bwd).
+
+    Binding foreign weights: ``_linear._w`` is [F, 2 U] with ``w[:, :U]`` the gate matrix and ``w[:, U:]`` the up matrix (each the
+    transpose of a checkpoint's [U, F] ``gate_proj`` / ``up_proj`` weight), ``_linear._b`` [2 U] likewise.  Biases bound to 0 -- and,
+    in a transformer block, every RMSNorm gamma to the checkpoint's and the other biases to 0 -- give the bias-free published form."""
+
+    def __init__(self, units: int, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._units = units
+        self._linear = Linear(units=2 * units)
+        self._pre = None
+
+    def initialize(self, x, *args, **kwargs) -> None:
+        self._linear.initialize(x)
+        self._linear._initialized = True
+
+    def forward(self, x, decode: bool = False, half: Optional[D.HalfView] = None):
+        self._pre = self._linear._forward_impl(D.as_device(x), decode=decode, half=half)
+        return D.swiglu_fwd(self._pre)
+
+    def _gate_backward(self, dh: D.DeviceArray) -> D.DeviceArray:
+        """The gradient of ``pre`` (dgate | dup) from the gradient of the last forward's result."""
+        return D.swiglu_bwd(self._pre, dh)
+
+    def backward(self, dy, optimizer_):
+        lin = self._linear
+        with parallel.grad_scope(lin._w.size + lin._b.size + 8, lin._arena) as scope:
+            # the bias gradient (the column sums of dpre) comes out of the weight-gradient GEMM, as for any Linear
+            return lin._backward_impl(self._gate_backward(D.as_device(dy)), optimizer_, scope)
 
     @property
     def linear(self) -> Linear:

@@ -1,4 +1,4 @@
-"""LayerNormalization and DropOut (reference layers/normalizations.py:9-75)."""
+"""LayerNormalization and DropOut (reference layers/normalizations.py:9-75), and RMSNormalization."""
 
 from __future__ import annotations
 
@@ -126,6 +126,14 @@ class LayerNormalization(layer.StatefulLayer):
         self._beta = self._new_param([self._col])
         self._pack_parameters([[(self, '_gamma')], [(self, '_beta')]])
 
+    def _segments(self):
+        """The parameters in the order ``_backward_impl`` produces their gradients (a composite's arena)."""
+        return [[(self, '_gamma')], [(self, '_beta')]]
+
+    def _grad_floats(self) -> int:
+        """Floats those gradients need."""
+        return 2 * self._param('_gamma').size
+
     def forward(self, x):
         return self._forward_impl(x)
 
@@ -162,4 +170,58 @@ class LayerNormalization(layer.StatefulLayer):
         dx = D.layernorm_bwd(dz, x, self._mean, self._rstd, gamma, dgamma, dbeta, residual=residual, drop=self._drop)
         scope.defer(optimizer_, self, '_gamma', dgamma)
         scope.defer(optimizer_, self, '_beta', dbeta)
+        return dx
+
+
+class RMSNormalization(layer.StatefulLayer):
+    """z = gamma * x / sqrt(mean(x^2) + epsilon) over the last axis: no mean, no beta (Zhang & Sennrich 2019; the norm of
+    LLaMA-style blocks).  One parameter, ``_gamma`` [d], drawn by the layer's initializer as every parameter here is -- bind ones
+    for a published checkpoint's starting point.  One wavefront per row (include/npm_hip.h npm_rmsnorm_fwd / _bwd).
+    ``_forward_impl`` / ``_backward_impl`` have the shapes of ``LayerNormalization``'s, so a transformer block holds either."""
+
+    def __init__(self, epsilon: float = 1e-6, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._epsilon = epsilon
+
+    def initialize(self, x):
+        self._col = x.shape[-1]
+        self._gamma = self._new_param([self._col])
+        self._pack_parameters(self._segments())
+
+    def _segments(self):
+        return [[(self, '_gamma')]]
+
+    def _grad_floats(self) -> int:
+        return self._param('_gamma').size
+
+    def forward(self, x):
+        return self._forward_impl(x)
+
+    def _forward_impl(self, x, dropout: Optional[DropOut] = None):
+        """``dropout`` must be None or the identity: the RMSNorm kernels apply no mask (a composite with a real dropout in front
+        of this norm runs it as a layer of its own)."""
+        if dropout is not None and dropout._drop_prob != 0.0:
+            raise ValueError('RMSNormalization: a dropout cannot ride inside the RMSNorm kernels; apply the DropOut layer in front')
+        x = D.as_device(x)
+        if not self._initialized:
+            self.initialize(x)
+            self._initialized = True
+        gamma = self._param('_gamma')
+        assert gamma.shape == (x.shape[-1],), f'{gamma.shape} vs {x.shape[-1]}'
+        self._x = x
+        z, self._rstd = D.rmsnorm_fwd(x, gamma, self._epsilon)
+        return z
+
+    def backward(self, dl_dz, optimizer_):
+        with parallel.grad_scope(self._grad_floats() + 8, self._arena) as scope:
+            return self._backward_impl(D.as_device(dl_dz), optimizer_, scope)
+
+    def _backward_impl(self, dz: D.DeviceArray, optimizer_, scope,
+                       residual: Optional[D.DeviceArray] = None) -> D.DeviceArray:
+        """dx (+ residual), and the deferred update of gamma."""
+        x = self._x
+        assert dz.size == x.size, f'{dz.shape} vs {x.shape}'
+        dgamma = scope.take([x.shape[-1]], owner=(self, '_gamma'))
+        dx = D.rmsnorm_bwd(dz, x, self._rstd, self._param('_gamma'), dgamma, residual=residual)
+        scope.defer(optimizer_, self, '_gamma', dgamma)
         return dx

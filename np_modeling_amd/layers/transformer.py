@@ -18,6 +18,14 @@ self-attention (attentions.py): q and k are rotated by their positions, counted 
 decoding -- where a sequence's position is its row count in the cache, so one admitted into a freed slot starts at 0 again.  The
 decoder's cross-attention never rotates.
 
+``norm`` ('layer', the default, or 'rms') and ``ffn`` ('relu', the default, or 'swiglu') choose the other half of the block:
+``normalizations.RMSNormalization`` in every norm's place, and ``mlp.GatedDense`` -- the packed gate | up projection [F, 2 U] and the
+gate kernel, ``hidden_units`` being the gated width U -- in ``dense1``'s place in front of ``dense2`` [U, F].  ``norm_epsilon``
+(None: 1e-3 for 'layer', 1e-6 for 'rms') is the norms' epsilon.  Both have the fused composition; the RMSNorm kernels apply no
+dropout mask, so ``norm='rms'`` with ``drop_rate > 0`` runs the literal composition with the standalone DropOut in front of the
+norm.  With the defaults not one launch, upload or result differs from the reference's block.  ``decode`` and ``weights='f16'``
+use the same two layers: the packed matrix is the one ``dense1`` holds.
+
 ``TransformerDecoder(causal=True)`` gives the self-attention a lower-triangular mask (the decoder everybody means by the word;
 the reference's passes none, transformer.py:127), and ``start_decoding`` / ``decode`` run it incrementally over key / value
 caches (inference; the reference marks the gap: ``# TODO: support cache``, transformer.py:120).  With ``causal=True`` and no
@@ -49,14 +57,31 @@ def _linear_segments(lin):
     return [[(lin, '_b')], [(lin, '_w')]]              # Linear._backward_impl takes db, then dw
 
 
-def _norm_segments(norm):
-    return [[(norm, '_gamma')], [(norm, '_beta')]]
-
-
 def _block_segments(norm, body, norm_first: bool):
     """A residual block's parameters in the order its backward produces their gradients: the norm's come after the
     body's with pre-norm, before them with post-norm."""
-    return body + _norm_segments(norm) if norm_first else _norm_segments(norm) + body
+    return body + norm._segments() if norm_first else norm._segments() + body
+
+
+NORMS = {'layer': normalizations.LayerNormalization, 'rms': normalizations.RMSNormalization}
+FFNS = ('relu', 'swiglu')
+
+
+def _check_kinds(who: str, norm: str, ffn: str) -> None:
+    if norm not in NORMS:
+        raise ValueError(f"{who}: norm must be one of {sorted(NORMS)}, got {norm!r}")
+    if ffn not in FFNS:
+        raise ValueError(f"{who}: ffn must be one of {sorted(FFNS)}, got {ffn!r}")
+
+
+def _make_norm(norm: str, epsilon: Optional[float]):
+    """A norm layer of that kind; ``epsilon`` None: the kind's own default (1e-3 'layer', 1e-6 'rms')."""
+    return NORMS[norm]() if epsilon is None else NORMS[norm](epsilon)
+
+
+def _make_dense1(ffn: str, hidden_units: int):
+    """The first half of the feed-forward: Dense with a ReLU, or the packed gate | up projection of the gated-SiLU form."""
+    return mlp.GatedDense(units=hidden_units) if ffn == 'swiglu' else mlp.Dense(units=hidden_units)
 
 
 # A transformer layer is a chain of residual blocks around a body (attention or the feed-forward pair):
@@ -64,7 +89,7 @@ def _block_segments(norm, body, norm_first: bool):
 # A layer lists its blocks (``_blocks``) and everything it does is a walk over that list.  The norm order is looked at by the
 # four functions below and by ``_block_segments``, nowhere else.
 class _Block(NamedTuple):
-    norm: normalizations.LayerNormalization
+    norm: layer.StatefulLayer                   # LayerNormalization or RMSNormalization
     dropout: Optional[normalizations.DropOut]   # directly in front of the norm; None: inference
     forward: Callable                           # fused body, (h, residual=skip) -> body(h) + skip: the addition rides a GEMM epilogue
     backward: Optional[Callable] = None         # its mirror, (dy, optimizer_, scope, residual=) -> gradient of h (+ residual)
@@ -136,6 +161,8 @@ class _ResidualBlocks(layer.Layer):
     fused or the literal composition."""
 
     _SLACK = 0          # floats of the gradient bucket beyond the parameters' own
+    _norm = 'layer'     # which norm the blocks hold ('layer' | 'rms') and which feed-forward ('relu' | 'swiglu')
+    _ffn = 'relu'
 
     def initialize(self, x, *memory):
         self._dense2 = mlp.Linear(units=x.shape[-1])  # no activation (transformer.py:25-27)
@@ -161,6 +188,8 @@ class _ResidualBlocks(layer.Layer):
                       att._segments(), att._numel)
 
     def _feed_forward_block(self, norm, dropout) -> _Block:
+        if self._ffn == 'swiglu':
+            return self._gated_feed_forward_block(norm, dropout)
         dense1, dense2 = self._dense1, self._dense2
         lin1 = dense1._linear
 
@@ -185,6 +214,27 @@ class _ResidualBlocks(layer.Layer):
                       _linear_segments(dense2) + _linear_segments(lin1),
                       lambda: lin1._w.size + lin1._b.size + dense2._w.size + dense2._b.size, flat=True, flush=True)
 
+    def _gated_feed_forward_block(self, norm, dropout) -> _Block:
+        """``ffn='swiglu'``: dense1 is a ``mlp.GatedDense`` -- the packed gate | up projection [F, 2 U] and the gate kernel --
+        and dense2 [U, F] takes the skip in its epilogue."""
+        gated, dense2 = self._dense1, self._dense2
+        lin1 = gated._linear
+
+        def forward(h, residual):
+            h = gated(h)
+            _ensure(dense2, h)
+            return dense2._forward_impl(h, residual=residual)
+
+        def backward(dy, optimizer_, scope, residual=None):
+            dpre = gated._gate_backward(dense2._backward_impl(dy, optimizer_, scope))      # no ReLU mask: the gate has a kernel
+            scope.flush()
+            return lin1._backward_impl(dpre, optimizer_, scope, residual=residual)
+
+        return _Block(norm, dropout, forward, backward, lambda x: dense2(gated(x)),
+                      lambda dy, optimizer_, scope: gated.backward(dense2.backward(D.as_device(dy), optimizer_), optimizer_),
+                      _linear_segments(dense2) + _linear_segments(lin1),
+                      lambda: lin1._w.size + lin1._b.size + dense2._w.size + dense2._b.size, flat=True, flush=True)
+
     def _walk(self, run, x, blocks, *args):
         shape = x.shape
         for block in blocks:
@@ -193,13 +243,20 @@ class _ResidualBlocks(layer.Layer):
 
     def _fusable(self, features: int = 0) -> bool:
         """The fused composition: always without dropout; with dropout when the LayerNorm kernels can apply it (row
-        length: device.layernorm_dropout_supported)."""
-        return _dropout_folds(features, *(block.dropout for block in self._blocks())) and self._dense1._fused_relu()
+        length: device.layernorm_dropout_supported) -- the RMSNorm kernels apply none, so ``norm='rms'`` with dropout runs the
+        literal composition, the standalone DropOut in front of the norm."""
+        dropouts = [block.dropout for block in self._blocks()]
+        folds = _identity_dropout(*dropouts) if self._norm == 'rms' else _dropout_folds(features, *dropouts)
+        return folds and self._fused_feed_forward()
+
+    def _fused_feed_forward(self) -> bool:
+        """Whether the feed-forward has a fused form: the gated one, or a Dense whose activation is the ReLU."""
+        return self._ffn == 'swiglu' or self._dense1._fused_relu()
 
     def _numel(self) -> int:
         """Floats the gradients of one backward need: ONE bucket for the exchange (opened without a size, every gradient
         would be a collective of its own at N > 1)."""
-        return sum(block.numel() + 2 * block.norm._param('_gamma').size for block in self._blocks()) + self._SLACK
+        return sum(block.numel() + block.norm._grad_floats() for block in self._blocks()) + self._SLACK
 
     def _pack(self) -> None:
         """After the first forward (every sub-layer has drawn its parameters, in the reference's order): all parameters
@@ -229,7 +286,7 @@ class _ResidualBlocks(layer.Layer):
     def backward(self, dy, optimizer_):
         dy = D.as_device(dy)
         with parallel.grad_scope(self._numel(), self._arena) as scope:
-            if self._fused and self._dense1._fused_relu():           # the composition the forward ran
+            if self._fused and self._fused_feed_forward():           # the composition the forward ran
                 return self._backward_fused(dy, optimizer_, scope)
             return self._backward_unfused(dy, optimizer_, scope)
 
@@ -254,12 +311,15 @@ class TransformerEncoder(_ResidualBlocks):
     _SLACK = 64
 
     def __init__(self, num_heads: int, hidden_units: int, norm_first: bool, drop_rate: float = 0.0,
-                 *args, num_kv_heads: Optional[int] = None, rope_base: Optional[float] = None, **kwargs):
+                 *args, num_kv_heads: Optional[int] = None, rope_base: Optional[float] = None, norm: str = 'layer',
+                 ffn: str = 'relu', norm_epsilon: Optional[float] = None, **kwargs):
         super().__init__(*args, **kwargs)
+        _check_kinds('TransformerEncoder', norm, ffn)
+        self._norm, self._ffn = norm, ffn
         self._self_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads, rope_base=rope_base)
-        self._dense1 = mlp.Dense(units=hidden_units)
-        self._norm1 = normalizations.LayerNormalization()
-        self._norm2 = normalizations.LayerNormalization()
+        self._dense1 = _make_dense1(ffn, hidden_units)
+        self._norm1 = _make_norm(norm, norm_epsilon)
+        self._norm2 = _make_norm(norm, norm_epsilon)
         self._norm_first = norm_first
         self._dropout1 = normalizations.DropOut(drop_rate)
         self._dropout2 = normalizations.DropOut(drop_rate)
@@ -282,8 +342,11 @@ class TransformerDecoder(_ResidualBlocks):
 
     def __init__(self, num_heads: int, hidden_units: int, norm_first: bool, drop_rate: float = 0.0,
                  *args, num_kv_heads: Optional[int] = None, causal: bool = False, rope_base: Optional[float] = None,
-                 window: Optional[int] = None, **kwargs):
+                 window: Optional[int] = None, norm: str = 'layer', ffn: str = 'relu', norm_epsilon: Optional[float] = None,
+                 **kwargs):
         super().__init__(*args, **kwargs)
+        _check_kinds('TransformerDecoder', norm, ffn)
+        self._norm, self._ffn = norm, ffn
         if window is not None and not causal:
             raise ValueError('TransformerDecoder: window= is a rule of causal self-attention: it needs causal=True')
         self._num_heads = num_heads
@@ -295,10 +358,10 @@ class TransformerDecoder(_ResidualBlocks):
         self._self_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads, rope_base=rope_base, window=window)
         self._window = self._self_attention._window
         self._cross_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)   # never rotates: no query position
-        self._dense1 = mlp.Dense(units=hidden_units)
-        self._norm1 = normalizations.LayerNormalization()
-        self._norm2 = normalizations.LayerNormalization()
-        self._norm3 = normalizations.LayerNormalization()
+        self._dense1 = _make_dense1(ffn, hidden_units)
+        self._norm1 = _make_norm(norm, norm_epsilon)
+        self._norm2 = _make_norm(norm, norm_epsilon)
+        self._norm3 = _make_norm(norm, norm_epsilon)
         self._norm_first = norm_first
         self._dropout1 = normalizations.DropOut(drop_rate)
         self._dropout2 = normalizations.DropOut(drop_rate)
