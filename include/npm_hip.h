@@ -607,6 +607,12 @@ int npm_mha_decode_window_splits(int batch, int kv_heads, int kv_len, int new_to
 #define NPM_PREFIX_MAX_SPLITS 1024
 int npm_kv_copy_pages(void *pool, int64_t page_stride_bytes, int64_t row_bytes, const int32_t *src_pages, const int32_t *dst_pages,
                       const int32_t *rows, int32_t n);
+/* npm_kv_copy_pages_planes: npm_kv_copy_pages in `planes` pools at once.  Plane p is the pool at pool + p * plane_stride_bytes (a
+ * multiple of 16; at least one page with more than one plane) with the page stride and row bytes of the call, and the SAME n pairs
+ * are copied in every plane by one launch: the K and V pools of all layers of a layered cache, which share one block table.
+ * Everything else is npm_kv_copy_pages, which is unchanged; planes == 0 is NPM_OK and nothing is launched. */
+int npm_kv_copy_pages_planes(void *pool, int64_t page_stride_bytes, int64_t row_bytes, const int32_t *src_pages,
+                             const int32_t *dst_pages, const int32_t *rows, int32_t n, int32_t planes, int64_t plane_stride_bytes);
 int npm_mha_prefix_supported(int head_dim);
 int npm_mha_prefix_fwd(const npm_mha_decode *d, const int32_t *new_lens, const int32_t *prefix_table, int32_t page_rows,
                        int32_t prefix_rows, int32_t splits, float *part_ctx, float *part_lse, int32_t kv_f16);
@@ -632,6 +638,35 @@ int npm_attn_combine(const float *part_ctx, const float *part_lse, int32_t split
  * 16 bytes per access; everything else takes a scalar kernel with the same arithmetic and the same bits. */
 int npm_rope(float *x, int64_t pitch, int32_t batch, int32_t tokens, int32_t heads, int32_t head_dim, const float *cos,
              const float *sin, int32_t table_rows, int32_t at, const int32_t *at_lens, int32_t inverse);
+
+/* npm_rope_kv_append: npm_rope and the two appends of a self-attention step in ONE launch (a decode step is launch-bound).  qkv is
+ * the packed projection of the step, rows b * tokens + t of (heads + 2 kv_heads) * head_dim floats with row pitch `pitch`: the q
+ * heads, then the k heads, then the v heads.
+ *  1. The first heads + kv_heads heads of every row are rotated in place, exactly as
+ *       npm_rope(qkv, pitch, batch, tokens, heads + kv_heads, head_dim, cos, sin, table_rows, at, at_lens, 0)
+ *     leaves them: padded rows t >= new_lens[b] too, a row whose position is outside the table untouched.  cos == sin == NULL: no
+ *     rotation, and q is not touched at all.
+ *  2. For t < new_lens[b] (NULL: every t) the k heads, as step 1 left them, and the v heads are stored at row at_b + t of sequence b
+ *     of k_cache and v_cache, at_b = at_lens ? at_lens[b] : at.  Both caches have the row pitch cache_pitch and the stride
+ *     cache_stride, in elements of the cache: between sequences, or with block_table (device int32 [batch, table_pitch], page_rows a
+ *     power of two >= 16) between pages, as npm_kv_append_paged has it.  kv_f16 != 0: the caches hold IEEE halves, converted as
+ *     npm_kv_append_f16 converts (round to nearest even).  These are exactly the bytes npm_kv_append / _varlen / _paged / _f16 store
+ *     from that buffer; no other byte of a cache is written.
+ * Bit for bit the three launches: every product and sum of the rotation is rounded on its own.  head_dim % 8 == 0 and 16-byte
+ * aligned qkv, cos and sin move 16 bytes per access (8 per store into an fp16 cache); everything else takes a scalar instance with
+ * the same bits.  Argument errors are those of the calls it fuses: with tables npm_rope's (a NULL cos or sin alone, sizes < 1, an odd
+ * head_dim, a scalar `at` outside the table); then the appends' -- a negative size or `at`, NPM_OK and nothing launched for
+ * batch == 0 or tokens == 0, a NULL pointer, k / v parts of qkv or caches that are not 16-byte aligned, pitch % 4, kv_heads *
+ * head_dim or a cache pitch / stride that is not a multiple of 4 (8 for halves), pitch < (heads + 2 kv_heads) * head_dim,
+ * cache_pitch < kv_heads * head_dim, and with a block_table a NULL at_lens, a bad page_rows or cache_stride < page_rows *
+ * cache_pitch -- all NPM_E_BAD_ARGUMENT.  Its own: head_dim is even with or without tables (elements move in pairs).
+ * npm_last_rope_append_kernel(): "rope_kv_append_kernel D=<head_dim> vec=<0|1> rope=<0|1> varlen=<0|1> paged=<page_rows or 0>
+ * kv=<f32|f16>"; "" before the first launch. */
+int npm_rope_kv_append(float *qkv, int64_t pitch, int32_t batch, int32_t tokens, int32_t heads, int32_t kv_heads, int32_t head_dim,
+                       const float *cos, const float *sin, int32_t table_rows, int32_t at, const int32_t *at_lens,
+                       const int32_t *new_lens, void *k_cache, void *v_cache, int64_t cache_pitch, int64_t cache_stride,
+                       const int32_t *block_table, int32_t table_pitch, int32_t page_rows, int32_t kv_f16);
+const char *npm_last_rope_append_kernel(void);
 
 /* ---- skinny-M GEMM: the matrix products of a decode step (inference) ----
  * C[M, N] = epilogue(alpha * A[M, K] op(B)) for 1 <= M <= NPM_SKINNY_MAX_M rows, described by the same npm_gemm as npm_sgemm.  These

@@ -293,6 +293,11 @@ _SPECIAL = {
     'npm_rmsnorm_bwd': (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
     'npm_swiglu_fwd': (C.c_int, [_P, _I64, _I64, _I64, _P, _I64]),
     'npm_swiglu_bwd': (C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _I64]),
+    # Likewise: restated by tests/hostsim_lm.py
+    'npm_kv_copy_pages_planes': (C.c_int, [_P, _I64, _I64, _P, _P, _P, _I32, _I32, _I64]),
+    'npm_rope_kv_append': (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _I64, _P, _I32,
+                                     _I32, _I32]),
+    'npm_last_rope_append_kernel': (C.c_char_p, []),
 }
 
 COMM_SIGNATURES = {

@@ -17,7 +17,7 @@ import sys
 __version__ = '0.1.0'
 
 from np_modeling_amd import _C, device, parallel          # noqa: E402,F401
-from np_modeling_amd import optimizer, layers, loss, train, sampling, speculative, beam  # noqa: E402,F401
+from np_modeling_amd import optimizer, layers, loss, train, sampling, speculative, beam, models  # noqa: E402,F401
 from np_modeling_amd.device import DeviceArray, as_device, synchronize  # noqa: E402,F401
 from np_modeling_amd._C import set_math, get_math, last_math  # noqa: E402,F401
 from np_modeling_amd.layers.normalizations import set_dropout_rng  # noqa: E402,F401

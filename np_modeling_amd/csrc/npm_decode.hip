@@ -268,6 +268,23 @@ kv_copy_pages_kernel(u32x4v *__restrict__ pool, long page16, long row16, const i
     }
 }
 
+// npm_kv_copy_pages_planes: the copy above with a plane index on the grid.  A layered cache keeps the K and V pools of all its
+// layers in one allocation, plane16 pieces apart, with ONE block table: the same (src, dst, rows) pairs are copied in every plane.
+// blockIdx.z walks the planes, the rest is kv_copy_pages_kernel.
+__global__ void __launch_bounds__(256)
+kv_copy_pages_planes_kernel(u32x4v *__restrict__ pool, long page16, long row16, const int *__restrict__ src_pages,
+                            const int *__restrict__ dst_pages, const int *__restrict__ rows, int n, int planes, long plane16) {
+    for (int plane = blockIdx.z; plane < planes; plane += gridDim.z) {
+        u32x4v *base = pool + plane * plane16;
+        for (int pair = blockIdx.y; pair < n; pair += gridDim.y) {
+            const long pieces = (long)rows[pair] * row16;
+            const u32x4v *from = base + src_pages[pair] * page16;
+            u32x4v *to = base + dst_pages[pair] * page16;
+            for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < pieces; i += (long)gridDim.x * blockDim.x) to[i] = from[i];
+        }
+    }
+}
+
 // VL = false (npm_mha_decode_fwd): the instances that never look at the length arrays; PG: the ones that read through a block table
 template <int D, int RB, bool VL, bool PG, typename KV>
 void launch_decode(const DecodeArgs &a, const int *kv_lens, const int *new_lens, const PageArgs &pg, dim3 grid, bool nt, hipStream_t s) {
@@ -624,6 +641,26 @@ extern "C" int npm_kv_copy_pages(void *pool, int64_t page_stride_bytes, int64_t 
     const dim3 grid((unsigned)std::min<long>((page16 + 255) / 256, 64), (unsigned)std::min(n, 65535)), block(256);
     hipLaunchKernelGGL(kv_copy_pages_kernel, grid, block, 0, npm::ctx().stream, static_cast<u32x4v *>(pool), page16, (long)(row_bytes / 16),
                        src_pages, dst_pages, rows, n);
+    NPM_CHECK_LAUNCH();
+    return NPM_OK;
+}
+
+// The copy-on-write of a layered cache: npm_kv_copy_pages in `planes` pools that lie plane_stride_bytes apart behind `pool`, the
+// same pairs in each, in one launch.  planes == 0 is NPM_OK and no launch, as n == 0 and row_bytes == 0 are.
+extern "C" int npm_kv_copy_pages_planes(void *pool, int64_t page_stride_bytes, int64_t row_bytes, const int32_t *src_pages,
+                                        const int32_t *dst_pages, const int32_t *rows, int32_t n, int32_t planes,
+                                        int64_t plane_stride_bytes) {
+    NPM_REQUIRE_INIT();
+    NPM_ARG(n >= 0 && row_bytes >= 0 && page_stride_bytes >= 0 && planes >= 0 && plane_stride_bytes >= 0);
+    if (n == 0 || row_bytes == 0 || planes == 0) return NPM_OK;
+    NPM_ARG(pool != nullptr && src_pages != nullptr && dst_pages != nullptr && rows != nullptr);
+    NPM_ARG(aligned16(pool) && row_bytes % 16 == 0 && page_stride_bytes % 16 == 0 && page_stride_bytes >= row_bytes);
+    NPM_ARG(plane_stride_bytes % 16 == 0 && (planes == 1 || plane_stride_bytes >= page_stride_bytes));
+    const long page16 = page_stride_bytes / 16;
+    const dim3 grid((unsigned)std::min<long>((page16 + 255) / 256, 64), (unsigned)std::min(n, 65535), (unsigned)std::min(planes, 65535)),
+        block(256);
+    hipLaunchKernelGGL(kv_copy_pages_planes_kernel, grid, block, 0, npm::ctx().stream, static_cast<u32x4v *>(pool), page16,
+                       (long)(row_bytes / 16), src_pages, dst_pages, rows, n, planes, (long)(plane_stride_bytes / 16));
     NPM_CHECK_LAUNCH();
     return NPM_OK;
 }

@@ -1574,6 +1574,29 @@ def rope(x: Mat, batch: int, tokens: int, heads: int, head_dim: int, table: Rope
                                    at_lens, int(bool(inverse))), 'npm_rope')
 
 
+# One launch in front of the attention of a cached self-attention step instead of three (npm_rope, the K append, the V append):
+# npm_rope_kv_append on the packed projection.  Off by default: every call sequence is what it was until a layer or a model turns
+# it on (``MultiHeadAttention._fused_rope_append``; ``models.CausalLM`` does); the same bits either way (tools/lm_decode_bench.py).
+FUSED_ROPE_APPEND = os.environ.get('NPM_FUSED_ROPE_APPEND', '0') != '0'
+
+
+def rope_kv_append(qkv: Mat, k_ptr: int, v_ptr: int, layout: KVLayout, batch: int, tokens: int, heads: int, kv_heads: int,
+                   head_dim: int, table: Optional[RopeTable], at: int, lens, rows: int) -> None:
+    """``rope(qkv, batch, tokens, heads + kv_heads, head_dim, table, at, at_lens)`` and the two ``kv_append`` s of the k and the v
+    heads of the packed projection ``qkv`` (array, row pitch; rows of (heads + 2 kv_heads) * head_dim floats) into the cache tensors
+    at ``k_ptr`` / ``v_ptr`` of one ``layout``, in one launch (include/npm_hip.h npm_rope_kv_append).  ``table`` None: no rotation.
+    ``lens`` = (at_lens, new_lens) as ``kv_append`` takes them; ``rows``: the rows stored, for the timer."""
+    at_lens, new_lens = (None, None) if lens is None else lens
+    assert table is None or (table.head_dim == head_dim and (at_lens is not None or at + tokens <= table.rows)), (head_dim, at, tokens)
+    cos, sin, table_rows = (None, None, 0) if table is None else (table.cos.ptr, table.sin.ptr, table.rows)
+    row = kv_heads * head_dim
+    moved = 8.0 * batch * tokens * (heads + kv_heads) * head_dim * (table is not None) + (8.0 + 2.0 * KV_ITEMSIZE[layout.dtype]) * rows * row
+    with _timed('rope_kv_append', nbytes=moved):
+        _C.check(_entry_point('npm_rope_kv_append')(qkv.ptr, qkv.ld, batch, tokens, heads, kv_heads, head_dim, cos, sin, table_rows, int(at),
+                                                    at_lens, new_lens, k_ptr, v_ptr, layout.pitch, layout.stride, layout.table,
+                                                    layout.table_pitch, layout.page_rows, int(layout.dtype == 'f16')), 'npm_rope_kv_append')
+
+
 def take_rows(x2d: DeviceArray, idx, out: Optional[Mat] = None) -> DeviceArray:
     """``x2d[idx]`` for a 2-D ``x2d`` [R, F] and integer ``idx`` of any shape (host integers, or an ``IdBuffer`` that never
     leaves the device): [..., F].  An index outside 0 .. R - 1 gives a row of zeros and reads nothing (include/npm_hip.h
@@ -1642,7 +1665,7 @@ class KVCache:
     paged = False
 
     def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None, dtype: str = 'f32',
-                 window: Optional[int] = None):
+                 window: Optional[int] = None, layers: int = 1):
         value_dim = key_dim if value_dim is None else value_dim
         if min(batch, capacity, kv_heads, key_dim, value_dim) < 1:
             raise ValueError('KVCache: batch, capacity, kv_heads and the head sizes must be positive')
@@ -1650,8 +1673,7 @@ class KVCache:
         self.dtype = _kv_dtype(dtype, int(kv_heads), int(key_dim), int(value_dim))
         self.batch, self.capacity, self.kv_heads = int(batch), int(capacity), int(kv_heads)
         self.key_dim, self.value_dim = int(key_dim), int(value_dim)
-        self.k = self._storage([batch, capacity, kv_heads, key_dim])
-        self.v = self._storage([batch, capacity, kv_heads, value_dim])
+        self._allocate_storage([batch, capacity, kv_heads], layers)
         self.lengths = np.zeros([self.batch], dtype=np.int64)
         self._mirror = None               # (host int32 [3, B]: before, new, after; ByteBuffer) of the last ragged call
         self.frozen = False
@@ -1659,14 +1681,97 @@ class KVCache:
     def _storage(self, shape):
         return empty(shape) if self.dtype == 'f32' else HalfBuffer(shape)
 
+    # ---- one cache for a stack of layers ---------------------------------------------------------------------------------------
+    # ``layers=N`` > 1: the K and V tensors of N attention layers in ONE allocation [2, N, ...] (plane 2 * 0 + i is layer i's K,
+    # N + i its V; Dk == Dv) behind ONE set of host state -- ``lengths``, the length mirror, and for a paged cache the block table,
+    # the free list, ``refcount`` and ``dropped``.  ``fork`` / ``reorder`` / ``release`` / ``truncate`` are the single-layer host
+    # operations.  A decode step is bracketed by the model: ``begin(tokens, new_lengths)`` does, once, what ``append`` does
+    # between its checks and its launches (``room``, the window's reclaim, page allocation, copy-on-write in one launch for all
+    # planes, the mirror and table upload); every layer then appends to and attends over its own ``layer(i)``, which reads that
+    # step's numbers; ``commit()`` advances ``lengths``.  ``layers=1`` (default) is the cache as it always was.
+    def _allocate_storage(self, geometry, layers: int) -> None:
+        layers = int(layers)
+        if layers < 1:
+            raise ValueError(f'{type(self).__name__}: layers must be at least 1, got {layers}')
+        self.layers, self._step, self._serial, self._planes = layers, None, 0, None
+        if layers == 1:
+            self.k = self._storage(list(geometry) + [self.key_dim])
+            self.v = self._storage(list(geometry) + [self.value_dim])
+            return
+        if self.key_dim != self.value_dim:
+            raise ValueError(f'{type(self).__name__}: a layered cache keeps K and V of every layer as planes of one allocation: the '
+                             f'head sizes {self.key_dim} / {self.value_dim} differ')
+        shape = list(geometry) + [self.key_dim]
+        self._planes = self._storage([2, layers] + shape)
+        self._plane_elements = _prod(shape)
+        self.k, self.v = self._plane(0, shape), self._plane(layers, shape)      # layer 0's: the geometry every tensor has
+
+    def _plane(self, index: int, shape):
+        store, first = self._planes, index * self._plane_elements
+        if self.dtype == 'f32':
+            return store.flat_view(first, shape)
+        out = HalfBuffer.__new__(HalfBuffer)
+        out._buf, out.ptr, out.nbytes, out.shape = store._buf, store.ptr + 2 * first, 2 * self._plane_elements, tuple(shape)
+        return out
+
+    def _tensors(self):
+        """Every K and V tensor of the cache: two, or the 2 N planes of a layered one."""
+        if self.layers == 1:
+            return [self.k, self.v]
+        return [self._plane(i, self.k.shape) for i in range(2 * self.layers)]
+
+    def layer(self, index: int) -> 'KVLayerView':
+        """What layer ``index``'s attention sees of a layered cache: its own K and V, everything else this cache's."""
+        index = int(index)
+        if not 0 <= index < self.layers:
+            raise IndexError(f'{type(self).__name__}.layer: no layer {index} among {self.layers}')
+        if self.layers == 1:
+            return KVLayerView(self, 0, self.k, self.v)
+        return KVLayerView(self, index, self._plane(index, self.k.shape), self._plane(self.layers + index, self.k.shape))
+
+    def _single(self, what: str) -> None:
+        if self.layers != 1:
+            raise ValueError(f'{type(self).__name__}.{what}: a layered cache is appended to and attended over through layer(i), '
+                             'between begin() and commit()')
+
+    def begin(self, tokens: int, new_lengths=None) -> None:
+        """Opens a step that brings ``tokens`` (``new_lengths[b]``) rows to every layer: every check and all host work of the N
+        appends, once.  ValueError, with nothing changed, when the rows do not fit."""
+        if self._step is not None:
+            raise RuntimeError(f'{type(self).__name__}.begin: the last step was not committed')
+        self.room(tokens, new_lengths)
+        if self.frozen:
+            raise ValueError('KVCache: this cache was filled for cross-attention and is frozen; reset() it first')
+        n = self.new_lengths(tokens, new_lengths)
+        if self._scalar_call(n):
+            step = (int(tokens), np.full([self.batch], int(tokens), dtype=np.int64), int(self.lengths[0]), None)
+        else:
+            n = self._counts(tokens, n)
+            self._allocate(n)
+            step = (int(tokens), n, 0, self._device_lengths(self.lengths, n)[:2])
+            if self.paged:
+                self._device_table()
+        self._step, self._serial = step, self._serial + 1
+
+    def commit(self) -> None:
+        """Closes the step: ``lengths`` advance by what ``begin`` was told, once for all layers."""
+        if self._step is None:
+            raise RuntimeError(f'{type(self).__name__}.commit: no step is open')
+        self.lengths = self.lengths + self._step[1]
+        self._step = None
+
+    def abandon(self) -> None:
+        """Closes a step that failed half way: ``lengths`` stay (pages it took are those of rows nobody will read)."""
+        self._step = None
+
     @property
     def itemsize(self) -> int:
         return KV_ITEMSIZE[self.dtype]
 
     @property
     def nbytes(self) -> int:
-        """Bytes of K + V storage."""
-        return self.k.nbytes + self.v.nbytes
+        """Bytes of K + V storage, of all layers."""
+        return (self.k.nbytes + self.v.nbytes) * self.layers
 
     def layout(self, x) -> KVLayout:
         """Where the rows of ``x`` (``k`` or ``v``) live; pitches in elements."""
@@ -1697,6 +1802,7 @@ class KVCache:
         self.lengths = np.zeros([self.batch], dtype=np.int64)
         self._mirror = None
         self.frozen = False
+        self._step = None
 
     def new_lengths(self, tokens: int, new_lengths) -> Optional[np.ndarray]:
         """``new_lengths`` as int64 [B] with 0 <= n[b] <= tokens (ValueError otherwise); None when it is None or says what the
@@ -1745,18 +1851,33 @@ class KVCache:
     def append(self, k: Mat, v: Mat, tokens: int, new_lengths=None) -> None:
         """``tokens`` freshly projected rows per sequence ([B, T, Hkv * D] with a row pitch each) behind the valid ones; with
         ``new_lengths`` only the first n[b] of them, behind sequence b's own ``lengths[b]`` rows."""
+        n, at, lens, rows = self._append_plan(tokens, new_lengths)
+        for src, dst in ((k, self.k), (v, self.v)):
+            kv_append(src, dst.ptr, self.layout(dst), self.batch, tokens, at, lens, rows)
+        self.lengths = self.lengths + n
+
+    def _append_plan(self, tokens: int, new_lengths):
+        """What an append does in front of its launches: the checks, the pages of a ragged call, the length upload.  Returns
+        (rows every sequence brings, the scalar ``at``, (at_lens, new_lens) or None, rows stored)."""
+        self._single('append')
         self.room(tokens, new_lengths)
         if self.frozen:
             raise ValueError('KVCache: this cache was filled for cross-attention and is frozen; reset() it first')
         n = self.new_lengths(tokens, new_lengths)
         if self._scalar_call(n):
-            n, at, lens, rows = tokens, int(self.lengths[0]), None, self.batch * tokens
-        else:
-            n = self._counts(tokens, n)
-            self._allocate(n)
-            at, lens, rows = 0, self._device_lengths(self.lengths, n)[:2], int(n.sum())
-        for src, dst in ((k, self.k), (v, self.v)):
-            kv_append(src, dst.ptr, self.layout(dst), self.batch, tokens, at, lens, rows)
+            return tokens, int(self.lengths[0]), None, self.batch * tokens
+        n = self._counts(tokens, n)
+        self._allocate(n)
+        return n, 0, self._device_lengths(self.lengths, n)[:2], int(n.sum())
+
+    def append_rotated(self, qkv: Mat, heads: int, tokens: int, new_lengths=None, table: Optional['RopeTable'] = None) -> None:
+        """``append`` of the k and the v heads of the packed projection ``qkv`` ([B, T, heads + 2 Hkv, D] with a row pitch) with
+        the rotation of its q and k heads (``rope`` at the positions ``lengths[b] + t``; ``table`` None: none) in the same launch
+        (``rope_kv_append``).  Dk == Dv.  ``qkv`` is left rotated, as ``rope`` leaves it."""
+        assert self.key_dim == self.value_dim
+        n, at, lens, rows = self._append_plan(tokens, new_lengths)
+        rope_kv_append(qkv, self.k.ptr, self.v.ptr, self.layout(self.k), self.batch, tokens, heads, self.kv_heads, self.key_dim, table,
+                       at, lens, rows)
         self.lengths = self.lengths + n
 
     def _truncated(self, rows) -> np.ndarray:
@@ -1782,6 +1903,7 @@ class KVCache:
         """Sequence ``b`` is replaced: its rows 0 .. rows - 1 are the ``rows`` rows of ``k`` / ``v`` ([rows, Hkv * D] with a row
         pitch each) and ``lengths[b] = rows``; the other sequences are not touched (npm_kv_append on slot b alone).  ``k`` or ``v``
         None: that tensor is written by another call (``TransformerDecoder.admit`` projects and writes one after the other)."""
+        self._single('write_slot')
         b, rows = int(b), int(rows)
         if not 0 <= b < self.batch:
             raise IndexError(f'KVCache.write_slot: no sequence {b} in a batch of {self.batch}')
@@ -1809,7 +1931,7 @@ class KVCache:
         nothing changed for a slot outside the batch or ``src == dst``."""
         src, dst = self._fork_slots(src, dst)
         rows = int(self.lengths[src])
-        for x in (self.k, self.v):
+        for x in self._tensors():
             slot = self.itemsize * self.layout(x).stride
             if rows:
                 _C.check(_C.lib().npm_d2d(x.ptr + dst * slot, x.ptr + src * slot, self.itemsize * rows * self.layout(x).pitch), 'npm_d2d')
@@ -1836,7 +1958,7 @@ class KVCache:
         moved = [b for b in range(self.batch) if p[b] >= 0 and p[b] != b and self.lengths[p[b]] > 0]
         overwritten = set(moved)
         sources = sorted({int(p[b]) for b in moved})
-        for x in (self.k, self.v):
+        for x in self._tensors():
             layout = self.layout(x)
             slot, row = self.itemsize * layout.stride, self.itemsize * layout.pitch
             snapshot = {}
@@ -1858,6 +1980,7 @@ class KVCache:
         n[b] valid rows of sequence b (they were appended first).  ``kernel='prefill'``: ``mha_prefill``, the same contract for any
         number of rows (a uniform cache shorter than the query -- a frozen one -- takes its per-sequence call); on an fp16 cache
         only with ``PREFILL_KERNEL_F16`` on."""
+        self._single('attend')
         if kernel not in ('decode', 'prefill'):
             raise ValueError(f"KVCache.attend: kernel must be 'decode' or 'prefill', got {kernel!r}")
         windowed = self.window is not None                               # always the per-sequence call, whatever the switch says
@@ -1897,6 +2020,7 @@ class KVCache:
 
     def gather(self, rows: int):
         """(k, v) [B, rows, Hkv, D]: the valid rows of every sequence made contiguous, zeros behind them (``kv_gather_rows``)."""
+        self._single('gather')
         assert rows <= self.capacity
         if self.paged and self.dropped.any():
             raise ValueError(f'PagedKVCache.gather: the leading {self.dropped.tolist()} rows were given back (window={self.window}); '
@@ -1945,7 +2069,7 @@ class PagedKVCache(KVCache):
     paged = True
 
     def __init__(self, batch: int, capacity: int, kv_heads: int, key_dim: int, value_dim: Optional[int] = None, *, page_size: int,
-                 pages: Optional[int] = None, dtype: str = 'f32', window: Optional[int] = None):
+                 pages: Optional[int] = None, dtype: str = 'f32', window: Optional[int] = None, layers: int = 1):
         value_dim = key_dim if value_dim is None else value_dim
         if min(batch, capacity, kv_heads, key_dim, value_dim) < 1:
             raise ValueError('PagedKVCache: batch, capacity, kv_heads and the head sizes must be positive')
@@ -1961,8 +2085,7 @@ class PagedKVCache(KVCache):
         self.pages = self.batch * self.pages_per_sequence if pages is None else int(pages)
         if self.pages < 1:
             raise ValueError(f'PagedKVCache: pages must be positive, got {pages}')
-        self.k = self._storage([self.pages, page_size, kv_heads, key_dim])
-        self.v = self._storage([self.pages, page_size, kv_heads, value_dim])
+        self._allocate_storage([self.pages, page_size, kv_heads], layers)
         self.table_uploads = 0
         self.reset()
 
@@ -2090,7 +2213,13 @@ class PagedKVCache(KVCache):
             pairs = bytes_from_host(np.array([[page for _, _, page, _ in copies], [self.block_table[b, slot] for b, slot, _, _ in copies],
                                               [rows for _, _, _, rows in copies]], dtype=np.int32))
             count = len(copies)
-            for x in (self.k, self.v):
+            if self.layers > 1:                       # K and V of every layer: the planes of one allocation, one launch
+                row, planes = self.itemsize * self.kv_heads * self.key_dim, 2 * self.layers
+                with _timed('kv_copy_pages', nbytes=2.0 * planes * row * sum(rows for _, _, _, rows in copies)):
+                    _C.check(_entry_point('npm_kv_copy_pages_planes')(
+                        self._planes.ptr, self.page_size * row, row, pairs.ptr, pairs.ptr + 4 * count, pairs.ptr + 8 * count, count,
+                        planes, self.itemsize * self._plane_elements), 'npm_kv_copy_pages_planes')
+            for x in (self.k, self.v) if self.layers == 1 else ():
                 row = self.itemsize * self.kv_heads * x.shape[3]
                 with _timed('kv_copy_pages', nbytes=2.0 * row * sum(rows for _, _, _, rows in copies)):
                     _C.check(_C.lib().npm_kv_copy_pages(x.ptr, self.page_size * row, row, pairs.ptr, pairs.ptr + 4 * count,
@@ -2199,3 +2328,87 @@ class PagedKVCache(KVCache):
 
     def write_slot(self, b: int, k: Optional[Mat], v: Optional[Mat], rows: int) -> None:
         raise NotImplementedError('PagedKVCache.write_slot: a released slot is filled by the ragged append, which hands out its pages')
+
+
+class KVLayerView:
+    """Layer i of a layered cache (``KVCache(..., layers=N).layer(i)``) as ``MultiHeadAttention._forward_cached`` sees a cache: its
+    own ``k`` / ``v`` -- two planes of the parent's one allocation -- and its own ``lengths``: the parent's, plus the open step's
+    rows once this layer's ``append`` has stored them, so that the attention behind it finds its rows counted.  Everything else is
+    the parent's: geometry, type, window, the length mirror, the block table.  ``room`` is the parent's ``begin``, which ran;
+    ``append`` launches the row copies with that step's numbers and touches no host state of the parent.  It shares nothing across
+    sequences on its own: ``attend_prefix_rows`` is 0 (the one-pass prefix attention is not built for layered caches)."""
+
+    def __init__(self, parent: KVCache, index: int, k, v):
+        self._parent, self.index, self.k, self.v = parent, int(index), k, v
+        self._appended = 0                              # the serial of the step this layer has appended its rows of
+
+    def __getattr__(self, name):                        # only what this class does not define
+        if name == '_parent':
+            raise AttributeError(name)
+        return getattr(self._parent, name)
+
+    @property
+    def lengths(self) -> np.ndarray:
+        parent = self._parent
+        if parent._step is not None and self._appended == parent._serial:
+            return parent.lengths + parent._step[1]
+        return parent.lengths
+
+    ragged = KVCache.ragged
+    max_length = KVCache.max_length
+    _scalar_call = KVCache._scalar_call
+    attend = KVCache.attend
+    gather = KVCache.gather
+
+    @property
+    def length(self) -> int:
+        return KVCache.length.fget(self)
+
+    def layout(self, x) -> KVLayout:
+        return type(self._parent).layout(self, x)
+
+    def _single(self, what: str) -> None:
+        """(``attend`` and ``gather`` are the single-layer ones, run over this layer's tensors)"""
+
+    def attend_prefix_rows(self, n, causal: bool) -> int:
+        return 0
+
+    def _current_lengths(self) -> int:
+        parent = self._parent
+        if parent._mirror is None or not np.array_equal(parent._mirror[0][2], self.lengths):
+            parent._device_lengths(self.lengths, np.zeros([self.batch], dtype=np.int64))
+        return parent._mirror[1].ptr + 8 * self.batch
+
+    def _open_step(self, what: str, tokens: int, new_lengths):
+        step = self._parent._step
+        if step is None:
+            raise RuntimeError(f'KVLayerView.{what}: no step is open: the model calls begin(tokens, new_lengths) on the layered cache first')
+        n = self._counts(tokens, self.new_lengths(tokens, new_lengths))
+        if int(tokens) != step[0] or not np.array_equal(n, step[1]):
+            raise ValueError(f'KVLayerView.{what}: {n.tolist()} of {tokens} rows are not what begin() was told ({step[1].tolist()} of {step[0]})')
+        return step
+
+    def room(self, tokens: int, new_lengths=None) -> None:
+        self._open_step('room', tokens, new_lengths)
+
+    def append(self, k: Mat, v: Mat, tokens: int, new_lengths=None) -> None:
+        """This layer's rows of the open step behind its valid ones: the two row copies of ``KVCache.append`` and nothing else."""
+        _, n, at, lens = self._open_step('append', tokens, new_lengths)
+        if self._appended == self._parent._serial:
+            raise RuntimeError(f'KVLayerView.append: layer {self.index} was appended to in this step already')
+        if lens is not None:
+            lens = self._parent._device_lengths(self.lengths, n)[:2]           # the step's upload, found again
+        for src, dst in ((k, self.k), (v, self.v)):
+            kv_append(src, dst.ptr, self.layout(dst), self.batch, tokens, at, lens, int(n.sum()))
+        self._appended = self._parent._serial
+
+    def append_rotated(self, qkv: Mat, heads: int, tokens: int, new_lengths=None, table: Optional[RopeTable] = None) -> None:
+        """``KVCache.append_rotated`` for this layer's rows of the open step: one launch."""
+        _, n, at, lens = self._open_step('append', tokens, new_lengths)
+        if self._appended == self._parent._serial:
+            raise RuntimeError(f'KVLayerView.append: layer {self.index} was appended to in this step already')
+        if lens is not None:
+            lens = self._parent._device_lengths(self.lengths, n)[:2]
+        rope_kv_append(qkv, self.k.ptr, self.v.ptr, self.layout(self.k), self.batch, tokens, heads, self.kv_heads, self.key_dim, table,
+                       at, lens, int(n.sum()))
+        self._appended = self._parent._serial

@@ -108,6 +108,12 @@ the cache, the decode and prefill kernels and the fp16 rounding see rotated rows
 sizes the tables for ``capacity``.  A frozen cross-attention cache has no query position: ``fill_cache`` and a cached forward over
 one raise NotImplementedError.  ``rope_base=None`` launches nothing and allocates nothing: every call sequence is what it was.
 
+One launch in front of the cached attention (opt-in: ``device.FUSED_ROPE_APPEND``, NPM_FUSED_ROPE_APPEND=1, or the layer's own
+``_fused_rope_append``, which ``models.CausalLM`` sets; off by default).  Where the projection is packed and Dk == Dv, the rotation
+and the two appends above are ONE call, ``cache.append_rotated`` (npm_rope_kv_append, csrc/npm_rope_append.hip): the packed buffer
+is left rotated and the cache holds the same bits as after the three launches, with or without ``rope_base``.  Separate projections
+(rebound parameters, Dk != Dv) keep the three launches.
+
 Half-precision weight copies (opt-in).  ``half_weights()`` returns a ``device.HalfWeights`` snapshot of wq / wk / wv (one half
 buffer when they are adjacent, so the packed projection stays one product) and wo; ``forward(x, cache=cache, weights=hw)`` reads
 the projections of that cached forward from it: ``npm_sgemm_skinny_w16`` over the halves in place where the skinny-M GEMM
@@ -198,6 +204,7 @@ class MultiHeadAttention(layer.StatefulLayer):
         self._rope = None                                                   # device.RopeTable, made at the first use
         self._softmax = activations.Softmax()
         self._cached_forward = False    # the last forward ran with a cache: it saved nothing a backward could use
+        self._fused_rope_append = None  # None: device.FUSED_ROPE_APPEND decides; True / False: this layer's own choice (models.CausalLM)
         self._cached_path = None        # 'decode' | 'prefill' | 'fused_masked' | 'gemm' (| 'decode_shared' | 'prefill_shared'): how the last cached forward attended
 
     def initialize(self, query, key=None, value=None, *args, **kwargs) -> None:
@@ -390,7 +397,7 @@ class MultiHeadAttention(layer.StatefulLayer):
 
     # -- incremental decoding ------------------------------------------------------------------
     def make_cache(self, batch: int, capacity: int, page_size: Optional[int] = None, pages: Optional[int] = None,
-                   dtype: str = 'f32') -> D.KVCache:
+                   dtype: str = 'f32', layers: int = 1) -> D.KVCache:
         """An empty key / value cache for ``batch`` sequences of up to ``capacity`` tokens (Hkv heads: grouped-query attention
         keeps its smaller cache).  The layer must have its parameters (one forward, or a weight binder).
 
@@ -402,7 +409,10 @@ class MultiHeadAttention(layer.StatefulLayer):
 
         A layer made with ``window=W`` gives the cache that window (``device.KVCache(window=)``): cached forwards run the windowed
         decode kernel (up to its row limit, ``device.mha_decode_supported``) or the windowed prefill kernel, never a gather, a mask or a GEMM
-        composition, so it needs their head sizes too; a paged cache then gives pages back as its sequences move on."""
+        composition, so it needs their head sizes too; a paged cache then gives pages back as its sequences move on.
+
+        ``layers`` N > 1: one cache for a stack of N layers of this geometry (``device.KVCache(layers=)``); this layer's cached
+        forward then takes ``cache.layer(i)``, between the ``begin`` and ``commit`` of the model that owns the stack."""
         if not self._initialized:
             raise RuntimeError('make_cache: the layer has no parameters yet (run one forward, or bind weights, first)')
         if dtype not in D.KV_ITEMSIZE:
@@ -419,12 +429,12 @@ class MultiHeadAttention(layer.StatefulLayer):
         if page_size is None:
             if pages is not None:
                 raise ValueError('make_cache: pages= sizes the pool of a paged cache: it needs page_size=')
-            return D.KVCache(batch, capacity, self._num_kv_heads, dk, dv, dtype=dtype, window=self._window)
+            return D.KVCache(batch, capacity, self._num_kv_heads, dk, dv, dtype=dtype, window=self._window, layers=layers)
         if not (D.mha_decode_supported(dk, self._num_heads // self._num_kv_heads, dv) or D.mha_core_supported(dk, dv, any_math=True)):
             raise NotImplementedError('a paged cache needs head sizes Dk == Dv in {16, 32, 64, 128} (the decode kernel or '
                                       'the fused masked forward); the GEMM composition has no masked softmax')
         return D.PagedKVCache(batch, capacity, self._num_kv_heads, dk, dv, page_size=page_size, pages=pages, dtype=dtype,
-                              window=self._window)
+                              window=self._window, layers=layers)
 
     def fill_cache(self, cache: D.KVCache, key, value=None, lengths=None) -> D.KVCache:
         """Cross-attention: project ``key`` / ``value`` [B, Skv, F] once into ``cache`` and freeze it; ``forward(x, cache=cache)``
@@ -488,7 +498,12 @@ class MultiHeadAttention(layer.StatefulLayer):
             # ONE GEMM over M = B T rows makes q, k and v where the parameters are adjacent; K and V rows then go into the cache
             # straight out of the packed buffer (npm_kv_append reads with its row pitch)
             (q, *fresh), _, packed = self._project_in(query, query, query, weights=weights, skinny_ok=True)
-            if rope:
+            fuse = D.FUSED_ROPE_APPEND if self._fused_rope_append is None else self._fused_rope_append
+            if fuse and packed and dk == dv:
+                # the rotation and the two appends in ONE launch on the packed buffer (npm_rope_kv_append): the same bits in the
+                # buffer and in the cache as the three launches below; q is left rotated for the attention
+                cache.append_rotated(q, h, t, new_lengths, self._rope_table(cache.max_length + t) if rope else None)
+            elif rope:
                 # q and the fresh k rows at positions lengths[b] + t, BEFORE they are stored: the cache, its kernels and the
                 # fp16 rounding see rotated rows and need nothing of their own.  Per-sequence positions are the `before` row of
                 # the length mirror; the append below finds the same numbers there and uploads nothing.
@@ -502,7 +517,8 @@ class MultiHeadAttention(layer.StatefulLayer):
                 else:
                     D.rope(q, b, t, h, dk, table, at, at_lens)
                     D.rope(fresh[0], b, t, hkv, dk, table, at, at_lens)
-            cache.append(fresh[0], fresh[1], t, new_lengths)
+            if not (fuse and packed and dk == dv):
+                cache.append(fresh[0], fresh[1], t, new_lengths)
         ctx = self._attend(q, cache, t, not cross, fresh, before, new_lengths, ragged)
         out = D.empty([b, t, f])
         D.gemm(b * t, f, h * dv, Mat(ctx, h * dv), Mat(self._param('_wo'), h * dv, half=None if weights is None else weights.view(self, '_wo')),

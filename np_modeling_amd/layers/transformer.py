@@ -26,6 +26,13 @@ dropout mask, so ``norm='rms'`` with ``drop_rate > 0`` runs the literal composit
 norm.  With the defaults not one launch, upload or result differs from the reference's block.  ``decode`` and ``weights='f16'``
 use the same two layers: the packed matrix is the one ``dense1`` holds.
 
+``TransformerDecoder(cross_attention=False)`` (default True: not one launch, upload or result differs) is the decoder of a
+decoder-only language model: self-attention and feed-forward only -- the middle block, ``_cross_attention``, its norm and its dropout
+do not exist, and the layer holds ``TransformerEncoder``'s parameter set in one arena with one gradient bucket.  ``forward(q)`` takes
+no memory, ``backward`` returns ``dq`` alone, ``start_decoding(None, capacity, batch=B, ...)`` makes a state whose ``cross_cache`` is
+None, ``admit(state, b)`` takes no memory.  ``models.CausalLM`` stacks N of them over one key / value cache; ``_mask_source`` is how
+it hands every layer the one causal mask of the stack.
+
 ``TransformerDecoder(causal=True)`` gives the self-attention a lower-triangular mask (the decoder everybody means by the word;
 the reference's passes none, transformer.py:127), and ``start_decoding`` / ``decode`` run it incrementally over key / value
 caches (inference; the reference marks the gap: ``# TODO: support cache``, transformer.py:120).  With ``causal=True`` and no
@@ -343,9 +350,11 @@ class TransformerDecoder(_ResidualBlocks):
     def __init__(self, num_heads: int, hidden_units: int, norm_first: bool, drop_rate: float = 0.0,
                  *args, num_kv_heads: Optional[int] = None, causal: bool = False, rope_base: Optional[float] = None,
                  window: Optional[int] = None, norm: str = 'layer', ffn: str = 'relu', norm_epsilon: Optional[float] = None,
-                 **kwargs):
+                 cross_attention: bool = True, **kwargs):
         super().__init__(*args, **kwargs)
         _check_kinds('TransformerDecoder', norm, ffn)
+        self._cross = bool(cross_attention)
+        self._mask_source = None        # (B, Sq) -> device.AttnMask: a stack's one causal mask for all its layers (models.CausalLM)
         self._norm, self._ffn = norm, ffn
         if window is not None and not causal:
             raise ValueError('TransformerDecoder: window= is a rule of causal self-attention: it needs causal=True')
@@ -357,20 +366,26 @@ class TransformerDecoder(_ResidualBlocks):
         # in decoding; the cross-attention sees the whole memory
         self._self_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads, rope_base=rope_base, window=window)
         self._window = self._self_attention._window
-        self._cross_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)   # never rotates: no query position
         self._dense1 = _make_dense1(ffn, hidden_units)
         self._norm1 = _make_norm(norm, norm_epsilon)
         self._norm2 = _make_norm(norm, norm_epsilon)
-        self._norm3 = _make_norm(norm, norm_epsilon)
         self._norm_first = norm_first
         self._dropout1 = normalizations.DropOut(drop_rate)
         self._dropout2 = normalizations.DropOut(drop_rate)
-        self._dropout3 = normalizations.DropOut(drop_rate)
+        if self._cross:
+            self._cross_attention = attentions.MultiHeadAttention(num_heads, num_kv_heads=num_kv_heads)   # never rotates: no query position
+            self._norm3 = _make_norm(norm, norm_epsilon)
+            self._dropout3 = normalizations.DropOut(drop_rate)
+        else:
+            self._SLACK = TransformerEncoder._SLACK     # the encoder's two blocks and 16 parameters: its bucket
         self._fused = True      # which composition the last forward ran (the backward mirrors it)
 
     def _blocks(self, kv=None, kv_grad=None) -> List[_Block]:
         """Self-attention, cross-attention over ``kv``, feed-forward (transformer.py:120-157): 26 parameters.  ``kv_grad``: the
-        list a backward leaves the cross-attention's dkey + dvalue in (transformer.py:186)."""
+        list a backward leaves the cross-attention's dkey + dvalue in (transformer.py:186).  ``cross_attention=False``: the
+        encoder's two blocks, 16 parameters."""
+        if not self._cross:
+            return [self._self_attention_block(self._norm1, self._dropout1), self._feed_forward_block(self._norm2, self._dropout2)]
         ca = self._cross_attention
 
         def forward(h, residual):
@@ -396,6 +411,8 @@ class TransformerDecoder(_ResidualBlocks):
         ``tril & ~tril(-W)`` -- made once per (B, Sq): its tile summary lets the fused kernels skip the tiles outside it."""
         if not self._causal:
             return None
+        if self._mask_source is not None:
+            return self._mask_source(int(batch), int(seq))
         key = (int(batch), int(seq))
         if key not in self._causal_masks:
             band = np.tril(np.ones([seq, seq], dtype=bool))
@@ -404,9 +421,19 @@ class TransformerDecoder(_ResidualBlocks):
             self._causal_masks[key] = D.AttnMask(band, batch, self._num_heads, seq, seq)
         return self._causal_masks[key]
 
-    def forward(self, q, kv):
+    _NO_MEMORY = object()
+
+    def forward(self, q, kv=_NO_MEMORY):
         """Three residual blocks: self-attention, cross-attention over ``kv``, feed-forward (transformer.py:120-157).
-        The residual additions ride the producing GEMMs' epilogues and the dropouts the LayerNorm kernels, as in the encoder."""
+        The residual additions ride the producing GEMMs' epilogues and the dropouts the LayerNorm kernels, as in the encoder.
+        ``cross_attention=False``: ``forward(q)``, two blocks, and ``backward`` returns ``dq`` alone."""
+        if not self._cross:
+            if kv is not self._NO_MEMORY:
+                raise TypeError('TransformerDecoder(cross_attention=False).forward takes no memory: forward(q)')
+            self._decoded = False
+            return self._forward(D.as_device(q))
+        if kv is self._NO_MEMORY:
+            raise TypeError("TransformerDecoder.forward() missing 1 required positional argument: 'kv'")
         q, kv = D.as_device(q), D.as_device(kv)
         self._decoded = False
         self._kv = kv
@@ -414,7 +441,8 @@ class TransformerDecoder(_ResidualBlocks):
 
     # -- incremental decoding (inference) ------------------------------------------------------------------------------
     def start_decoding(self, kv, capacity: int, kv_lengths=None, *, page_size: Optional[int] = None, pages: Optional[int] = None,
-                       memory_capacity: Optional[int] = None, cache_dtype: str = 'f32', weights: Optional[str] = None) -> 'DecodeState':
+                       memory_capacity: Optional[int] = None, cache_dtype: str = 'f32', weights: Optional[str] = None,
+                       batch: Optional[int] = None) -> 'DecodeState':
         """Caches for ``decode``: an empty self-attention cache of ``capacity`` tokens per sequence and the cross-attention's
         keys / values, projected from ``kv`` [B, Skv, F] once.  ``kv_lengths`` [B]: ``kv`` is padded on the right and sequence b
         has only that many memory rows.  The layer must have its parameters (one forward, or bound weights).
@@ -432,13 +460,29 @@ class TransformerDecoder(_ResidualBlocks):
         (``device.HalfWeights``, kept in ``DecodeState.weights``) and ``decode`` reads those: half the weight bytes per step, the
         model whose six matrices are the rounded ones at every chunk size.  Biases and LayerNorm parameters stay fp32, and so do
         the memory projections here and in ``admit``.  The snapshot is of the weights as they are now: after they change,
-        ``state.weights.refresh()``.  None allocates and launches nothing new."""
+        ``state.weights.refresh()``.  None allocates and launches nothing new.
+
+        ``cross_attention=False``: there is no memory, so ``start_decoding(None, capacity, batch=B, ...)`` -- ``kv`` must be None,
+        ``batch`` names the slots, ``kv_lengths`` and ``memory_capacity`` are refused; ``DecodeState.cross_cache`` is None."""
         if weights not in (None, 'f16'):
             raise ValueError(f"start_decoding: weights must be None or 'f16', got {weights!r}")
         if cache_dtype not in D.KV_ITEMSIZE:
             raise ValueError(f"start_decoding: cache_dtype must be one of {sorted(D.KV_ITEMSIZE)}, got {cache_dtype!r}")
-        if not (self._initialized and self._self_attention._initialized and self._cross_attention._initialized):
+        if not (self._initialized and self._self_attention._initialized and (not self._cross or self._cross_attention._initialized)):
             raise RuntimeError('start_decoding: the decoder has no parameters yet (run one forward, or bind weights, first)')
+        if not self._cross:
+            if kv is not None or kv_lengths is not None or memory_capacity is not None:
+                raise ValueError('start_decoding: a decoder without cross-attention has no memory: kv must be None, and kv_lengths '
+                                 'and memory_capacity have nothing to describe')
+            if batch is None or int(batch) < 1:
+                raise ValueError(f'start_decoding: a decoder without cross-attention needs batch= (the number of slots), got {batch!r}')
+            paging = {} if page_size is None and pages is None else {'page_size': page_size, 'pages': pages}
+            state = DecodeState(self._self_attention.make_cache(int(batch), capacity, dtype=cache_dtype, **paging), None)
+            if weights == 'f16':
+                state.weights = self._half_weights()
+            return state
+        if batch is not None:
+            raise ValueError('start_decoding: batch= is for a decoder without cross-attention; here the memory kv [B, Skv, F] names it')
         kv = D.as_device(kv)
         batch, seq_kv, _ = kv.shape
         rows = seq_kv if memory_capacity is None else int(memory_capacity)
@@ -454,18 +498,30 @@ class TransformerDecoder(_ResidualBlocks):
         return state
 
     def _half_weights(self) -> D.HalfWeights:
-        """The six matrices of a decode step as halves, in the order the step reads them."""
-        sa, ca, lin1, lin2 = self._self_attention, self._cross_attention, self._dense1._linear, self._dense2
+        """The matrices of a decode step as halves, in the order the step reads them: eight, or six without cross-attention."""
+        sa, ca, lin1, lin2 = self._self_attention, getattr(self, '_cross_attention', None), self._dense1._linear, self._dense2
         if not (self._dense1._initialized and lin2._initialized):
             raise RuntimeError("start_decoding(weights='f16'): the feed-forward layers have no parameters yet (run one forward, or "
                                'bind weights, first)')
-        return D.HalfWeights([(sa, '_wq'), (sa, '_wk'), (sa, '_wv'), (sa, '_wo'), (ca, '_wq'), (ca, '_wo'), (lin1, '_w'), (lin2, '_w')])
+        cross = [(ca, '_wq'), (ca, '_wo')] if self._cross else []
+        return D.HalfWeights([(sa, '_wq'), (sa, '_wk'), (sa, '_wv'), (sa, '_wo')] + cross + [(lin1, '_w'), (lin2, '_w')])
 
-    def admit(self, state: 'DecodeState', b: int, kv_b, kv_length: Optional[int] = None) -> None:
+    def admit(self, state: 'DecodeState', b: int, kv_b=None, kv_length: Optional[int] = None) -> None:
         """A new sequence into slot ``b`` of a running batch (``state.release(b)`` emptied it): its memory ``kv_b`` [1, Skv, F]
         (``kv_length`` valid rows, default all) is projected with the cross-attention's K / V weights into slot b of the cross
-        cache.  The next ``decode(q_new, state, new_lengths=n)`` carries the sequence's prompt in row b of the padded chunk."""
+        cache.  The next ``decode(q_new, state, new_lengths=n)`` carries the sequence's prompt in row b of the padded chunk.
+        ``cross_attention=False``: ``admit(state, b)`` takes no memory and only checks that the slot is empty."""
         b = int(b)
+        if not self._cross:
+            if kv_b is not None or kv_length is not None:
+                raise ValueError('admit: a decoder without cross-attention takes no memory: admit(state, b)')
+            if not 0 <= b < state.self_cache.batch:
+                raise IndexError(f'admit: no slot {b} in a batch of {state.self_cache.batch}')
+            if state.self_cache.lengths[b] != 0:
+                raise ValueError(f'admit: slot {b} still holds {int(state.self_cache.lengths[b])} rows; release({b}) it first')
+            return
+        if kv_b is None:
+            raise TypeError("admit: the sequence's memory kv_b [1, Skv, F] is required")
         cross, ca = state.cross_cache, self._cross_attention
         if not 0 <= b < cross.batch:
             raise IndexError(f'admit: no slot {b} in a batch of {cross.batch}')
@@ -488,7 +544,9 @@ class TransformerDecoder(_ResidualBlocks):
 
     def reorder(self, state: 'DecodeState', parents, memory: str = 'shared') -> None:
         """Slot b of a running batch continues the sequence slot ``parents[b]`` held before the call, -1 ends it (a beam step):
-        ``DecodeState.reorder``."""
+        ``DecodeState.reorder``.  ``cross_attention=False``: there is no memory to move, ``memory`` takes its default only."""
+        if not self._cross and memory != 'shared':
+            raise ValueError(f"reorder: a decoder without cross-attention has no memory to copy: memory={memory!r}")
         state.reorder(parents, memory=memory)
 
     def decode(self, q_new, state: 'DecodeState', new_lengths=None):
@@ -504,7 +562,7 @@ class TransformerDecoder(_ResidualBlocks):
         q = D.as_device(q_new)
         state.self_cache.room(q.shape[1], new_lengths)                    # ValueError before anything is launched
         self._decoded = True
-        sa, ca, dense1, dense2 = self._self_attention, self._cross_attention, self._dense1, self._dense2
+        sa, ca, dense1, dense2 = self._self_attention, getattr(self, '_cross_attention', None), self._dense1, self._dense2
         hw = state.weights                                                # None, or the fp16 copies of the six matrices below
 
         def feed_forward(h, residual):
@@ -514,9 +572,12 @@ class TransformerDecoder(_ResidualBlocks):
             return dense2._forward_impl(dense1.forward(h, decode=True, half=half1), residual=residual, decode=True, half=half2)
 
         # the blocks of ``forward`` over the caches; no dropout, whatever drop_rate is
+        attend = _Block(self._norm1, None, lambda h, residual: sa._forward_cached(h, state.self_cache, residual=residual,
+                                                                                  new_lengths=new_lengths, weights=hw))
+        if not self._cross:                                               # two blocks: there is no memory to attend to
+            return self._walk(_fused_forward, q, (attend, _Block(self._norm2, None, feed_forward, flat=True)))
         return self._walk(_fused_forward, q, (
-            _Block(self._norm1, None, lambda h, residual: sa._forward_cached(h, state.self_cache, residual=residual,
-                                                                             new_lengths=new_lengths, weights=hw)),
+            attend,
             _Block(self._norm2, None, lambda h, residual: ca._forward_cached(h, state.cross_cache, residual=residual,
                                                                              new_lengths=new_lengths, weights=hw)),
             _Block(self._norm3, None, feed_forward, flat=True)))
@@ -546,7 +607,8 @@ class DecodeState:
         if not self.self_cache.paged:
             raise ValueError('DecodeState.release: the self-attention cache is not paged (start_decoding(..., page_size=))')
         self.self_cache.release(b)
-        self.cross_cache.lengths[np.unique(np.atleast_1d(np.asarray(b, dtype=np.int64)))] = 0
+        if self.cross_cache is not None:                                  # (None: a decoder without cross-attention)
+            self.cross_cache.lengths[np.unique(np.atleast_1d(np.asarray(b, dtype=np.int64)))] = 0
 
     def fork(self, src: int, dst: int) -> None:
         """Slot ``dst`` becomes sequence ``src``: the self-attention cache is forked (a paged one shares its pages until the
@@ -557,7 +619,8 @@ class DecodeState:
         if self.self_cache.lengths[dst] != 0:
             raise ValueError(f'fork: slot {dst} still holds {int(self.self_cache.lengths[dst])} rows; release({dst}) it first')
         self.self_cache.fork(src, dst)
-        self.cross_cache.fork(src, dst)
+        if self.cross_cache is not None:
+            self.cross_cache.fork(src, dst)
 
     def reorder(self, parents, memory: str = 'shared') -> None:
         """Slot b becomes the sequence slot ``parents[b]`` held BEFORE the call (int [B]; -1 empties the slot): the
@@ -570,6 +633,11 @@ class DecodeState:
             raise ValueError(f"reorder: memory must be 'shared' or 'copy', got {memory!r}")
         p = self.self_cache._parents(parents)
         cross = self.cross_cache
+        if cross is None:                                                 # a decoder without cross-attention: the default only
+            if memory != 'shared':
+                raise ValueError(f"reorder: there is no cross-attention cache to copy: memory={memory!r}")
+            self.self_cache.reorder(p)
+            return
         if memory == 'shared':
             live = p >= 0
             if (cross.lengths[live] != cross.lengths[p[live]]).any():
