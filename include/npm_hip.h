@@ -307,6 +307,24 @@ int npm_conv2d_bwd_w(const float *dy, const float *x, float *dw,
  * activation-sized tensors runs; results are bitwise reproducible (fixed-order slab and column reductions). */
 int npm_conv2d_bwd_w_relu(const float *dy, const float *pre, const float *x, float *g, float *dw, float *db,
                           int32_t n, int32_t h, int32_t w, int32_t c_in, int32_t c_out, int32_t ksize);
+/* What the most recent of the four calls above launched; "" before the first one.  A call that fails its argument check leaves
+ * the string as it was.  "none" for the empty calls (n == 0; no pixels: dw and db are zero-filled).  Otherwise
+ *   "<family> vec=<0|1> tall=<0|1> math=<0|1|2> korder=<0|1> buf=<0|1> splits=<s> kper=<k> wr=<0|2|3> trio=<0|1> ksync=<0|e>"
+ * family  conv_fwd (register-staged forward / grad_x kernel), conv_fwd_glds (LDS-DMA), conv_wgrad, conv_wgrad_glds,
+ *         conv_wgrad_relu (the fused filter gradient);
+ * vec     16-byte loads (the register-staged kernels' float4 instance; every LDS-DMA kernel);
+ * tall    the 256 x 64 block tile of conv_fwd_glds;
+ * math    the arithmetic that ran, as NPM_TUNE_GEMM_MATH counts it with the f16 mode folded into 2 (0 on every
+ *         register-staged kernel and on the fused one);
+ * korder  the K walk of conv_fwd_glds (NPM_TUNE_CONV_KORDER); 0 elsewhere: taps outermost;
+ * buf     the accumulators leave through buffer stores (write_tile_buf, or the fused kernel's own), not write_tile;
+ * splits  split-K blocks per output tile, kper the K range of one of them (pixels for the filter gradients, k*k*c_in for
+ *         forward / grad_x);
+ * wr      the fused kernel's tile height in 64-row units (2: 128 rows, 3: 192), trio: its twelve-wave form, ksync: the K
+ *         rendezvous interval in K tiles when it is engaged, else 0.
+ * npm_conv2d_bwd_w_relu on a shape the fused kernel does not take reports "two_pass " followed by what its
+ * npm_conv2d_bwd_w reported. */
+const char *npm_last_conv_kernel(void);
 
 /* ---- fused attention core (layers/attentions.py:103-112 forward, :146-162 backward) ----
  * ctx[b, i, h, :] = sum_j softmax_j(scale * q[b, i, h, :] . k[b, j, h, :]) v[b, j, h, :] in ONE kernel: the

@@ -298,6 +298,8 @@ _SPECIAL = {
     'npm_rope_kv_append': (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _I64, _P, _I32,
                                      _I32, _I32]),
     'npm_last_rope_append_kernel': (C.c_char_p, []),
+    # Likewise: the simulator's convolutions have no instances to report; tests/conv_cases.py restates the dispatch
+    'npm_last_conv_kernel': (C.c_char_p, []),
 }
 
 COMM_SIGNATURES = {
@@ -587,6 +589,11 @@ LOGITS_MAX_BIAS, LOGPROB_MAX_TOP = 256, 64             # include/npm_hip.h NPM_L
 def last_logits_kernel() -> str:
     """What the most recent npm_logits_process or npm_history_append launched (include/npm_hip.h npm_last_logits_kernel)."""
     return lib().npm_last_logits_kernel().decode()
+
+
+def last_conv_kernel() -> str:
+    """What the most recent npm_conv2d_* call launched (include/npm_hip.h npm_last_conv_kernel)."""
+    return lib().npm_last_conv_kernel().decode()
 
 
 def last_xent_kernel() -> str:

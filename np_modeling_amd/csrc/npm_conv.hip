@@ -13,6 +13,7 @@
 //             the N*H*W pixels with a fixed-order slab reduction (conv.py:185-194)
 // Tile machinery (LDS layouts, MFMA loop, epilogue) is shared with npm_gemm.hip.
 #include <algorithm>
+#include <cstdio>
 
 #include "npm_mfma_tile.h"
 
@@ -742,6 +743,16 @@ int g_conv_korder = 1;      // NPM_TUNE_CONV_KORDER: 1 (default) 16-channel chun
 int g_wgrad_fused = 1;           // NPM_TUNE_CONV_WGRAD_FUSED: 0 two passes (ReLU backward, then grad_w), 1 fused (tile height picked; three tile rows of 192: one block of twelve waves), 2 / 3 fused with 128- / 192-row tiles in four-wave blocks
 int g_wgrad_blocks_per_cu = 0;   // NPM_TUNE_CONV_WGRAD_BLOCKS: 0 pick_splits chooses 3 or 4 blocks per CU, 3 / 4 pins it, -1 the old ceil(3 CUs / tiles)
 
+// What the most recent conv entry point launched (npm_last_conv_kernel, include/npm_hip.h): written by the host code that
+// picks the instance, read by tests that must know which one they ran.
+char g_last_conv_kernel[192] = "";
+void note_conv(const char *family, bool vec, bool tall, int math, int korder, bool buf, int splits, int kper,
+               int wr = 0, bool trio = false, int ksync = 0) {
+    snprintf(g_last_conv_kernel, sizeof(g_last_conv_kernel), "%s vec=%d tall=%d math=%d korder=%d buf=%d splits=%d kper=%d wr=%d trio=%d ksync=%d",
+             family, (int)vec, (int)tall, math, korder, (int)buf, splits, kper, wr, (int)trio, ksync);
+}
+void note_conv_none() { snprintf(g_last_conv_kernel, sizeof(g_last_conv_kernel), "none"); }
+
 int run_conv_gemm(const float *x, const float *filt_kn, int nb, int h, int w, int c, int n_out, int ks,
                   const Epilogue &e) {
     const long m = (long)nb * h * w;
@@ -772,6 +783,7 @@ int run_conv_gemm(const float *x, const float *filt_kn, int nb, int h, int w, in
     const long grid = (long)a.tiles_m * a.tiles_n;
     NPM_ARG(grid < (1L << 31));
     npm::note_math((tall || dma) ? g_conv_math : 0);
+    note_conv(dma ? "conv_fwd_glds" : "conv_fwd", vec, tall, dma ? g_conv_math : 0, dma ? g_conv_korder : 0, dma && a.e.buf_ok, 1, a.K);
     if (tall && g_conv_math == 2) hipLaunchKernelGGL((conv_fwd_glds_kernel<true, 2>), dim3((int)grid), dim3(NTHREADS), 0, s, a);
     else if (tall && g_conv_math == 1) hipLaunchKernelGGL((conv_fwd_glds_kernel<true, 1>), dim3((int)grid), dim3(NTHREADS), 0, s, a);
     else if (tall) hipLaunchKernelGGL((conv_fwd_glds_kernel<true, 0>), dim3((int)grid), dim3(NTHREADS), 0, s, a);
@@ -800,7 +812,7 @@ int npm_conv2d_fwd(const npm_conv2d *c) {
     NPM_ARG(c != nullptr);
     NPM_ARG(c->n >= 0 && c->h >= 1 && c->w >= 1 && c->c_in >= 1 && c->c_out >= 1);
     NPM_ARG(c->ksize >= 1 && c->ksize % 2 == 1);            // conv.py:94
-    if (c->n == 0) return NPM_OK;
+    if (c->n == 0) { note_conv_none(); return NPM_OK; }
     NPM_ARG(c->x && c->filt && c->y);
     Epilogue e{};
     e.C = c->y; e.ldc = c->c_out; e.alpha = 1.f;
@@ -816,7 +828,7 @@ int npm_conv2d_bwd_x(const float *dy, const float *filt, float *dx,
                      int32_t n, int32_t h, int32_t w, int32_t c_in, int32_t c_out, int32_t ksize) {
     NPM_REQUIRE_INIT();
     NPM_ARG(n >= 0 && h >= 1 && w >= 1 && c_in >= 1 && c_out >= 1 && ksize >= 1 && ksize % 2 == 1);
-    if (n == 0) return NPM_OK;
+    if (n == 0) { note_conv_none(); return NPM_OK; }
     NPM_ARG(dy && filt && dx);
     npm::Scratch flipped;
     const size_t fsz = (size_t)ksize * ksize * c_in * c_out;
@@ -837,7 +849,10 @@ int npm_conv2d_bwd_w(const float *dy, const float *x, float *dw,
     NPM_ARG(dw != nullptr);
     const long pixels = (long)n * h * w;
     NPM_ARG(pixels < (1L << 31) - BK);
-    if (pixels == 0) return npm_fill_f32(dw, 0.f, (size_t)ksize * ksize * c_in * c_out);
+    if (pixels == 0) {
+        note_conv_none();
+        return npm_fill_f32(dw, 0.f, (size_t)ksize * ksize * c_in * c_out);
+    }
     NPM_ARG(dy && x);
     ConvArgs a{};
     a.X = x; a.F = dy;
@@ -878,6 +893,7 @@ int npm_conv2d_bwd_w(const float *dy, const float *x, float *dw,
                      ((long)a.k_per_split + 2 * halo + GK) * c_in * 4 < (1L << 30) &&
                      (long)a.k_per_split * c_out * 4 < (1L << 30);
     npm::note_math(dma ? g_conv_math : 0);
+    note_conv(dma ? "conv_wgrad_glds" : "conv_wgrad", vec, false, dma ? g_conv_math : 0, 0, dma && a.e.buf_ok, splits, a.k_per_split);
     if (dma && g_conv_math == 2) hipLaunchKernelGGL(conv_wgrad_glds_kernel<2>, dim3(grid), dim3(NTHREADS), 0, s, a);
     else if (dma && g_conv_math == 1) hipLaunchKernelGGL(conv_wgrad_glds_kernel<1>, dim3(grid), dim3(NTHREADS), 0, s, a);
     else if (dma) hipLaunchKernelGGL(conv_wgrad_glds_kernel<0>, dim3(grid), dim3(NTHREADS), 0, s, a);
@@ -906,6 +922,7 @@ int npm_conv2d_bwd_w_relu(const float *dy, const float *pre, const float *x, flo
     const long pixels = (long)n * h * w;
     NPM_ARG(pixels < (1L << 31) - BK);
     if (pixels == 0) {
+        note_conv_none();
         int rc = npm_fill_f32(dw, 0.f, (size_t)ksize * ksize * c_in * c_out);
         return rc ? rc : npm_fill_f32(db, 0.f, (size_t)c_out);
     }
@@ -962,6 +979,7 @@ int npm_conv2d_bwd_w_relu(const float *dy, const float *pre, const float *x, flo
                 a.ksync.every = npm::ksync_every();
                 a.ksync.epochs = (nkt - (splits - 1) * kt_per - 1) / a.ksync.every;
             }
+            note_conv("conv_wgrad_relu", true, false, 0, 0, true, splits, a.k_per_split, tall ? 3 : 2, trio, a.ksync.slice ? a.ksync.every : 0);
             if (trio) hipLaunchKernelGGL((conv_wgrad_relu_kernel<3, true>), dim3(grid), dim3(3 * NTHREADS), 0, s, a);
             else if (tall) hipLaunchKernelGGL(conv_wgrad_relu_kernel<3>, dim3(grid), dim3(NTHREADS), 0, s, a);
             else hipLaunchKernelGGL(conv_wgrad_relu_kernel<2>, dim3(grid), dim3(NTHREADS), 0, s, a);
@@ -979,7 +997,15 @@ int npm_conv2d_bwd_w_relu(const float *dy, const float *pre, const float *x, flo
     }
     int rc = npm_relu_bwd_colsum(pre, dy, g, db, pixels, c_out);
     if (rc) return rc;
-    return npm_conv2d_bwd_w(g, x, dw, n, h, w, c_in, c_out, ksize);
+    rc = npm_conv2d_bwd_w(g, x, dw, n, h, w, c_in, c_out, ksize);
+    if (rc == NPM_OK) {                                 // "two_pass " in front of what the filter gradient reported
+        char inner[sizeof(g_last_conv_kernel)];
+        snprintf(inner, sizeof(inner), "%s", g_last_conv_kernel);
+        snprintf(g_last_conv_kernel, sizeof(g_last_conv_kernel), "two_pass %s", inner);
+    }
+    return rc;
 }
+
+const char *npm_last_conv_kernel(void) { return g_last_conv_kernel; }
 
 }  // extern "C"

@@ -21,6 +21,12 @@ def rand(shape):
     return np.random.normal(size=shape).astype(np.float32)
 
 
+def unwritten(D, shape):
+    """An output buffer that starts as NaN: the pool reuses freed blocks, and an element the kernel never writes must not be able
+    to hold an earlier call's right answer."""
+    return D.full(shape, float('nan'))
+
+
 @pytest.mark.parametrize('name,shape,channels,k', [('conv_k3', [3, 9, 7, 8], 12, 3), ('conv_k5', [2, 8, 8, 4], 6, 5),
                                                    ('conv_k1', [2, 6, 5, 8], 4, 1)])
 def test_conv_golden(npm, name, shape, channels, k, math_mode):
@@ -55,7 +61,7 @@ def test_conv_kernels_vs_oracle(npm, n, h, w, c0, c1, k, math_mode):
     bias = rng.standard_normal(c1).astype(np.float32)
     dy = rng.standard_normal((n, h, w, c1)).astype(np.float32)
     dx_, df, db, ddy = D.from_host(x), D.from_host(filt), D.from_host(bias), D.from_host(dy)
-    y, pre = D.empty([n, h, w, c1]), D.empty([n, h, w, c1])
+    y, pre = unwritten(D, [n, h, w, c1]), unwritten(D, [n, h, w, c1])
     desc = _C.npm_conv2d(n=n, h=h, w=w, c_in=c0, c_out=c1, ksize=k, x=dx_.ptr, filt=df.ptr, bias=db.ptr,
                          y=y.ptr, pre=pre.ptr, relu=1)
     _C.check(lib.npm_conv2d_fwd(C.byref(desc)))
@@ -63,12 +69,12 @@ def test_conv_kernels_vs_oracle(npm, n, h, w, c0, c1, k, math_mode):
     assert_close(pre, want_pre, tol=3e-6)
     np.testing.assert_array_equal(y.numpy(), np.maximum(pre.numpy(), 0))
     # relu without the saved pre-activation, no bias
-    y2 = D.empty([n, h, w, c1])
+    y2 = unwritten(D, [n, h, w, c1])
     desc2 = _C.npm_conv2d(n=n, h=h, w=w, c_in=c0, c_out=c1, ksize=k, x=dx_.ptr, filt=df.ptr, bias=None,
                           y=y2.ptr, pre=None, relu=1)
     _C.check(lib.npm_conv2d_fwd(C.byref(desc2)))
     assert_close(y2, np.maximum(O.conv2d_fwd(x.astype(np.float64), filt.astype(np.float64)), 0), tol=3e-6)
-    gx, gw = D.empty([n, h, w, c0]), D.empty([k, k, c0, c1])
+    gx, gw = unwritten(D, [n, h, w, c0]), unwritten(D, [k, k, c0, c1])
     _C.check(lib.npm_conv2d_bwd_x(ddy.ptr, df.ptr, gx.ptr, n, h, w, c0, c1, k))
     _C.check(lib.npm_conv2d_bwd_w(ddy.ptr, dx_.ptr, gw.ptr, n, h, w, c0, c1, k))
     assert_close(gx, O.conv2d_grad_x(dy.astype(np.float64), filt.astype(np.float64)), tol=3e-6)
@@ -91,7 +97,7 @@ def test_conv_random_sweep(npm, math_mode):
         bias = rng.standard_normal(c1).astype(np.float32)
         dy = rng.standard_normal((n, h, w, c1)).astype(np.float32)
         dx_, df, db, ddy = D.from_host(x), D.from_host(filt), D.from_host(bias), D.from_host(dy)
-        y, pre = D.empty([n, h, w, c1]), D.empty([n, h, w, c1])
+        y, pre = unwritten(D, [n, h, w, c1]), unwritten(D, [n, h, w, c1])
         desc = _C.npm_conv2d(n=n, h=h, w=w, c_in=c0, c_out=c1, ksize=k, x=dx_.ptr, filt=df.ptr, bias=db.ptr,
                              y=y.ptr, pre=pre.ptr, relu=1)
         _C.check(lib.npm_conv2d_fwd(C.byref(desc)))
@@ -100,7 +106,7 @@ def test_conv_random_sweep(npm, math_mode):
         _, want_pre = O.conv_layer_fwd(x64, f64, bias.astype(np.float64))
         assert_close(pre, want_pre, tol=3e-6, what=what + ' fwd')
         np.testing.assert_array_equal(y.numpy(), np.maximum(pre.numpy(), 0))
-        gx, gw = D.empty([n, h, w, c0]), D.empty([k, k, c0, c1])
+        gx, gw = unwritten(D, [n, h, w, c0]), unwritten(D, [k, k, c0, c1])
         _C.check(lib.npm_conv2d_bwd_x(ddy.ptr, df.ptr, gx.ptr, n, h, w, c0, c1, k))
         _C.check(lib.npm_conv2d_bwd_w(ddy.ptr, dx_.ptr, gw.ptr, n, h, w, c0, c1, k))
         assert_close(gx, O.conv2d_grad_x(dy64, f64), tol=3e-6, what=what + ' grad_x')
@@ -155,7 +161,7 @@ def test_conv_bwd_w_relu_is_deterministic(npm):
     x, dy, pre = (D.from_host(rng.standard_normal(s).astype(np.float32)) for s in ((n, h, w, c0), (n, h, w, c1), (n, h, w, c1)))
     runs = []
     for _ in range(2):
-        g, dw, db = D.empty([n, h, w, c1]), D.empty([k, k, c0, c1]), D.empty([c1])
+        g, dw, db = unwritten(D, [n, h, w, c1]), unwritten(D, [k, k, c0, c1]), unwritten(D, [c1])
         _C.check(_C.lib().npm_conv2d_bwd_w_relu(dy.ptr, pre.ptr, x.ptr, g.ptr, dw.ptr, db.ptr, n, h, w, c0, c1, k))
         runs.append((dw.numpy(), db.numpy()))
     np.testing.assert_array_equal(runs[0][0], runs[1][0])
@@ -181,7 +187,7 @@ def test_conv_bwd_w_relu_rendezvous_changes_nothing(npm):
         for every in (0, 128, 32):
             _C.check(lib.npm_set_tuning(15, every))
             try:
-                g, dw, db = D.empty([n, h, w, c1]), D.empty([k, k, c0, c1]), D.empty([c1])
+                g, dw, db = unwritten(D, [n, h, w, c1]), unwritten(D, [k, k, c0, c1]), unwritten(D, [c1])
                 _C.check(lib.npm_conv2d_bwd_w_relu(dy.ptr, pre.ptr, x.ptr, g.ptr, dw.ptr, db.ptr, n, h, w, c0, c1, k))
                 runs[every] = (dw.numpy().copy(), db.numpy().copy(), g.numpy()[::5, ::37, ::41].copy())
             finally:
@@ -215,7 +221,7 @@ def test_conv_bwd_w_relu_twelve_wave_block_equals_three_blocks(npm, n, h, w):
     for mode in (1, 3):
         _C.check(lib.npm_set_tuning(13, mode))
         try:
-            g, dw, db = D.full([n, h, w, c1], 7.0), D.empty([k, k, c0, c1]), D.empty([c1])
+            g, dw, db = D.full([n, h, w, c1], 7.0), unwritten(D, [k, k, c0, c1]), unwritten(D, [c1])
             _C.check(lib.npm_conv2d_bwd_w_relu(dy.ptr, pre.ptr, x.ptr, g.ptr, dw.ptr, db.ptr, n, h, w, c0, c1, k))
             runs[mode] = (dw.numpy().copy(), g.numpy().copy(), db.numpy().copy())
         finally:
