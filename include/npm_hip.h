@@ -1012,6 +1012,52 @@ const char *npm_last_logits_kernel(void);
 int npm_adam_step(float *var, const float *grad, double *m, double *v, size_t n, double lr, double beta1,
                   double beta2, double eps, int step);
 int npm_fill_f64(double *dst, double value, size_t n);
+/* ---- AdamW with global-norm gradient clipping: a language-model training step with no host round trip ----
+ * Three calls: the fp64 sum of squares of the gradients, one thread that turns it into a clip factor in HBM, and an AdamW
+ * step that reads the factor from there.  All pointers are device pointers; the npm_ranges struct itself is host memory.
+ *
+ * npm_sumsq_ranges: *acc += sum over ranges[0 .. count) of (double)x * (double)x.  Every square is exact in fp64 (a product of
+ * two float32 has 48 significant bits) and every addition is an fp64 addition: no float atomics, no fp32 accumulator, no fp32
+ * square.  Range r is cut into ceil(n[r] / NPM_SUMSQ_TILE) tiles of NPM_SUMSQ_TILE elements (the last one shorter); one block
+ * of 256 threads sums one tile in a fixed order into partials[tile] (it finds its range by walking the at most
+ * NPM_SUMSQ_MAX_RANGES tile counts, which are the same for the whole block), and a second launch of ONE block adds the partials
+ * in index order with a fixed tree and adds the total to *acc.  The result is a function of the ranges (addresses and lengths),
+ * their order and NPM_SUMSQ_TILE only: not of the grid, the number of compute units or any tuning knob; a repeated call gives
+ * the same bits, and two calls accumulate in stream order.  ptr[r] is 4-byte aligned: a tile loads 16 bytes at a time over its
+ * 16-byte aligned interior and peels up to 3 elements in front and behind with 4-byte loads.  Nothing outside the ranges is
+ * read.  count == 0 or every n[r] == 0: nothing is launched.  NPM_E_BAD_ARGUMENT: ranges or acc NULL, count outside
+ * 0 .. NPM_SUMSQ_MAX_RANGES, a NULL ptr[r] with n[r] > 0, a ptr[r] that is not 4-byte aligned, more than
+ * 2^31 - 1 tiles in all. */
+#define NPM_SUMSQ_TILE 16384        /* elements per tile: 256 lanes x 64 */
+#define NPM_SUMSQ_MAX_RANGES 32
+typedef struct npm_ranges {
+    const float *ptr[32];
+    uint64_t n[32];
+    int32_t count;
+} npm_ranges;
+int npm_sumsq_ranges(const npm_ranges *ranges, double *acc);
+/* state = 4 doubles [sumsq, norm, scale, ok].  One thread: norm = sqrt(sumsq); a norm that is not finite gives scale = 0 and
+ * ok = 0; otherwise scale = (double)(float)min(1.0, max_norm / (norm + 1e-6)) -- the ratio in fp64, rounded ONCE to float32, so
+ * scale is exactly a float -- and ok = 1.  max_norm = +inf gives scale 1: the norm is reported and nothing is clipped.
+ * NPM_E_BAD_ARGUMENT: state NULL, max_norm <= 0 or NaN. */
+int npm_clip_finish(double *state, double max_norm);
+/* AdamW (Loshchilov and Hutter; what torch.optim.AdamW computes) on fp64 moments, every operation rounded on its own (no
+ * contraction).  omb1 = 1 - beta1, omb2 = 1 - beta2, c1 = 1 - beta1^step, c2 = 1 - beta2^step and lw = lr * weight_decay are
+ * computed on the host in fp64.  clip_state is NULL or the 4 doubles of npm_clip_finish.  Per element:
+ *     if clip_state and clip_state[3] == 0: nothing at all is written (var, m, v keep their bits)
+ *     g    = clip_state ? (float)clip_state[2] * grad[i] : grad[i]           one fp32 product; exact when scale == 1
+ *     G    = (double)g
+ *     m'   = beta1 * m + omb1 * G;    v' = beta2 * v + omb2 * (G * G)        fp64
+ *     d    = (double)var - lw * (double)var                                  fp64 product, fp64 difference
+ *     var' = (float)(d - lr * ((m' / c1) / (sqrt(v' / c2) + eps)))           epsilon OUTSIDE the root; ONE rounding to fp32
+ * This is deliberately NOT the arithmetic of npm_adam_step, which stays as it is: that one is the reference's Adam operation
+ * for operation (float32 gradient products, epsilon INSIDE the root, no decay), this one is the update other frameworks
+ * compute -- hyper-parameters ported from them (epsilon 1e-8, weight decay 0.01 .. 0.1) assume the outside epsilon and the
+ * decoupled decay, and an epsilon inside the root is a different regulariser by orders of magnitude (sqrt(1e-8) = 1e-4).
+ * The same grid-stride launch as npm_adam_step, a kernel of its own.  n == 0: nothing is launched.
+ * NPM_E_BAD_ARGUMENT: step < 1, weight_decay < 0 or NaN, a NULL var, grad, m or v with n > 0. */
+int npm_adamw_step(float *var, const float *grad, double *m, double *v, size_t n, double lr, double beta1, double beta2,
+                   double eps, int step, double weight_decay, const double *clip_state);
 /* MSELoss (loss.py:21-29): loss = sum((y-t)^2)/n (fp64 accumulation, returned to the host); dy = 2 (y-t) / n */
 int npm_mse_fwd(const float *y, const float *targets, size_t n, double *loss);
 int npm_mse_bwd(const float *y, const float *targets, float *dy, size_t n);

@@ -159,6 +159,13 @@ class npm_logits(C.Structure):
     ]
 
 
+SUMSQ_TILE, SUMSQ_MAX_RANGES = 16384, 32           # NPM_SUMSQ_TILE, NPM_SUMSQ_MAX_RANGES
+
+
+class npm_ranges(C.Structure):
+    _fields_ = [('ptr', C.c_void_p * SUMSQ_MAX_RANGES), ('n', C.c_uint64 * SUMSQ_MAX_RANGES), ('count', C.c_int32)]
+
+
 class npm_comm_exchange_stats(C.Structure):
     _fields_ = [('bytes', C.c_ulonglong), ('allreduce_calls', C.c_int), ('waits', C.c_int),
                 ('allreduce_ms', C.c_double), ('exposed_ms', C.c_double), ('last_allreduce_ms', C.c_double),
@@ -298,6 +305,10 @@ _SPECIAL = {
     'npm_rope_kv_append': (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _I64, _P, _I32,
                                      _I32, _I32]),
     'npm_last_rope_append_kernel': (C.c_char_p, []),
+    # Likewise: restated by tests/hostsim_adamw.py
+    'npm_sumsq_ranges': (C.c_int, [C.POINTER(npm_ranges), _P]),
+    'npm_clip_finish': (C.c_int, [_P, C.c_double]),
+    'npm_adamw_step': (C.c_int, [_P, _P, _P, _P, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _P]),
     # Likewise: the simulator's convolutions have no instances to report; tests/conv_cases.py restates the dispatch
     'npm_last_conv_kernel': (C.c_char_p, []),
 }

@@ -466,6 +466,13 @@ class UpdateQueue:
                                ((first_ptr, 8), (second_ptr, 8))))
         self._keep += [owner, grad]                 # after _enqueue: a drain in there empties _keep, and this update is still pending
 
+    def adamw(self, var: 'DeviceArray', grad: 'DeviceArray', first_ptr: int, second_ptr: int, hyper: tuple, owner) -> None:
+        """``hyper`` = (lr, beta1, beta2, epsilon, step, weight decay, address of the clip state or 0): all of it is the run key,
+        so neighbours that decay differently are separate launches.  Side arrays and adjacency as ``adam``."""
+        self._enqueue(_Pending(var.ptr, grad.ptr, var.size, ('adamw',) + tuple(hyper), var._buf, grad._buf,
+                               ((first_ptr, 8), (second_ptr, 8))))
+        self._keep += [owner, grad]
+
     def run(self) -> None:
         _C._ORDER_HOOK = None                       # the launches below are the queue itself
         lib = _C.lib(ordered=False)
@@ -479,6 +486,10 @@ class UpdateQueue:
             if run is not None and run.n:
                 if run.key[0] == 'axpy':
                     _C.check(lib.npm_axpy(run.var, run.grad, run.key[1], run.n), 'npm_axpy')
+                elif run.key[0] == 'adamw':
+                    lr, b1, b2, eps, step, decay, clip = run.key[1:]
+                    _C.check(lib.npm_adamw_step(run.var, run.grad, run.extra[0][0], run.extra[1][0], run.n, lr, b1, b2, eps,
+                                                step, decay, clip or None), 'npm_adamw_step')
                 else:
                     lr, b1, b2, eps, step = run.key[1:]
                     _C.check(lib.npm_adam_step(run.var, run.grad, run.extra[0][0], run.extra[1][0], run.n, lr, b1, b2, eps,

@@ -22,6 +22,8 @@ neighbours in the moments too; ``update`` is still called once per parameter and
 
 from __future__ import annotations
 
+from typing import Optional
+
 import numpy as np
 
 
@@ -151,3 +153,167 @@ class AdamOptimizer(Optimizer):
         variable -= self.learning_rate * (unbiased_first / np.sqrt(unbiased_second + self.epsilon))
         entry[0] = step + 1
         return variable
+
+
+def _decays_by_default(obj, attribute: str) -> bool:
+    """The matrices and the embedding table (``_w``, ``_wq``, ``_w1`` ...) decay; biases, ``_gamma`` and ``_beta`` do not."""
+    return attribute.startswith('_w')
+
+
+class AdamWOptimizer(AdamOptimizer):
+    """AdamW (decoupled weight decay, epsilon OUTSIDE the root: ``npm_adamw_step``, the update ``torch.optim.AdamW`` computes --
+    NOT ``AdamOptimizer``'s arithmetic, which is the reference's) with gradient clipping by the global norm and a learning-rate
+    schedule, for device parameters only.
+
+    ``update(obj, attribute, grad)`` does NOT step: it records the gradient.  ``apply()`` -- which ``train.Trainer`` calls at the
+    end of every backward, and a user who drives ``backward`` by hand calls themselves -- is the one point of a step where every
+    gradient exists and no parameter has moved yet: it takes the norm of all recorded gradients (``npm_sumsq_ranges`` over the
+    gradient buckets, 32 ranges a call, then ``npm_clip_finish``), and steps every parameter with a kernel that reads the clip
+    factor from HBM.  Nothing in ``apply()`` copies anything to the host; ``last_grad_norm()`` is the one call that does (32
+    bytes, and it synchronises).
+
+    * ``learning_rate``: a float, or a callable ``step -> float`` called once per ``apply()`` with the 1-based count of applies.
+    * ``decay(obj, attribute) -> bool`` says which parameters decay; by default those whose attribute starts with ``_w``.  The
+      decay is part of an update's run key (``device.UpdateQueue.adamw``): neighbours of an arena that decay alike are one
+      launch, a neighbour that decays differently starts another.  ``decay=lambda *_: True`` makes an arena one launch.
+    * A norm that is not finite (an inf or a NaN in any gradient) makes the DEVICE skip the whole step: parameters and moments
+      keep their bits.  The host cannot know that without a copy, so the per-parameter step counters (the bias correction)
+      advance all the same; ``last_grad_norm()`` reports ``ok == False`` for such a step.
+    * Data parallelism: ``parallel.GradScope._finish`` waits for the all-reduce before it calls ``update``, so every rank takes
+      the norm of the same reduced gradients and arrives at the same factor with no further collective.
+    * ``last`` = {'launches', 'updates', 'ranges'} of the most recent ``apply()``.
+    """
+
+    def __init__(self, learning_rate, beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8,
+                 weight_decay: float = 0.01, clip_norm: Optional[float] = None, decay=None):
+        super().__init__(learning_rate, beta1, beta2, epsilon)
+        if not weight_decay >= 0.0:
+            raise ValueError(f'weight_decay must be >= 0, got {weight_decay!r}')
+        if clip_norm is not None and not clip_norm > 0.0:
+            raise ValueError(f'clip_norm must be positive (or None: no clipping), got {clip_norm!r}')
+        self.weight_decay, self.clip_norm = float(weight_decay), None if clip_norm is None else float(clip_norm)
+        self.decay = _decays_by_default if decay is None else decay
+        self.last = None
+        self._pending = {}        # slot -> (obj, attribute, gradient), in update order; the gradient keeps its bucket alive
+        self._applies = 0
+        self._clip_state = None   # 4 doubles in HBM: sumsq, norm, scale, ok
+        self._clipped = False     # the most recent apply() wrote _clip_state
+
+    def update(self, obj: object, attribute: str, gradient) -> None:
+        from np_modeling_amd import device as D
+        variable = getattr(obj, attribute)
+        if isinstance(gradient, D.Scaled):
+            gradient = gradient.materialize()
+        if not isinstance(variable, D.DeviceArray) or not isinstance(gradient, D.DeviceArray):
+            raise TypeError(f'AdamWOptimizer is device-only: {type(obj).__name__}.{attribute} is a {type(variable).__name__} with a '
+                            f'{type(gradient).__name__} gradient')
+        if gradient.size != variable.size:
+            raise ValueError(f'{type(obj).__name__}.{attribute}: {variable.size} elements, gradient of {gradient.size}')
+        slot = f'{id(obj)}.{attribute}'
+        if slot in self._pending:
+            raise RuntimeError(f'{type(obj).__name__}.{attribute} already has a gradient waiting: call apply() after every backward '
+                               '(a second update would replace the first gradient, not add to it)')
+        self._pending[slot] = (obj, attribute, gradient)
+
+    def _ranges(self):
+        """The pending gradients as (address, elements): buffers in update order (a backward hands a bucket's slices over in
+        its own order, not by address), the slices of one buffer by address, joined only where one starts EXACTLY where the one
+        before ends -- the padding between slices of a bucket is uninitialised and never enters the norm.  A function of the
+        update order and the addresses alone: every rank builds the same table."""
+        buffers = {}
+        for _, _, grad in self._pending.values():
+            if grad.size:
+                buffers.setdefault(id(grad._buf), []).append((grad.ptr, grad.size))
+        out = []
+        for slices in buffers.values():
+            end = None
+            for ptr, n in sorted(slices):
+                if ptr == end:
+                    out[-1][1] += n
+                else:
+                    out.append([ptr, n])
+                end = ptr + 4 * n
+        return out
+
+    def _norm_on_device(self) -> int:
+        import ctypes as C
+        from np_modeling_amd import _C, device as D
+        if self._clip_state is None:
+            self._clip_state = D._Buffer(32)
+        state = self._clip_state.ptr
+        _C.check(_C.lib().npm_fill_f64(state, 0.0, 4), 'npm_fill_f64')
+        ranges = self._ranges()
+        for begin in range(0, len(ranges), _C.SUMSQ_MAX_RANGES):
+            table = _C.npm_ranges()
+            part = ranges[begin:begin + _C.SUMSQ_MAX_RANGES]
+            for i, (ptr, n) in enumerate(part):
+                table.ptr[i], table.n[i] = ptr, n
+            table.count = len(part)
+            _C.check(_C.lib().npm_sumsq_ranges(C.byref(table), state), 'npm_sumsq_ranges')
+        _C.check(_C.lib().npm_clip_finish(state, self.clip_norm), 'npm_clip_finish')
+        return len(ranges)
+
+    def apply(self) -> None:
+        """One step of every parameter whose gradient ``update`` recorded since the last ``apply()``."""
+        from np_modeling_amd import _C, device as D
+        if not self._pending:
+            return
+        self._applies += 1
+        lr = float(self.learning_rate(self._applies) if callable(self.learning_rate) else self.learning_rate)
+        ranges = self._norm_on_device() if self.clip_norm is not None else 0
+        self._clipped = self.clip_norm is not None
+        clip = self._clip_state.ptr if self._clipped else 0
+        direct = 0
+        with D.coalesced_updates() as queue:
+            before = queue.launches if queue is not None else 0
+            for slot, (obj, attribute, gradient) in self._pending.items():
+                variable = getattr(obj, attribute)
+                entry = self._state.get(slot)
+                if entry is None or not isinstance(entry[1], _DeviceMoments) or entry[1].count != variable.size:
+                    entry = self._state[slot] = [1, None]
+                moments = entry[1] = self._moments_for(variable, entry[1])
+                decay = self.weight_decay if self.decay(obj, attribute) else 0.0
+                hyper = (lr, float(self.beta1), float(self.beta2), float(self.epsilon), int(entry[0]), decay, clip)
+                if queue is not None:
+                    queue.adamw(variable, gradient, moments.first_ptr, moments.second_ptr, hyper, moments.owner)
+                else:
+                    _C.check(_C.lib().npm_adamw_step(variable.ptr, gradient.ptr, moments.first_ptr, moments.second_ptr, variable.size,
+                                                     *hyper[:6], clip or None), 'npm_adamw_step')
+                    direct += 1
+                entry[0] += 1
+        for obj, attribute, _ in self._pending.values():
+            setattr(obj, attribute, getattr(obj, attribute))      # the reference's contract: changed in place, stored back
+        self.last = {'launches': direct if queue is None else queue.launches - before, 'updates': len(self._pending), 'ranges': ranges}
+        self._pending = {}
+
+    def update_variable(self, identifier, variable, gradient):
+        raise TypeError('AdamWOptimizer steps in apply(): update() records the gradient')
+
+    def last_grad_norm(self):
+        """(norm, scale, ok) of the most recent clipped ``apply()``: the global gradient norm, the factor the gradients were
+        multiplied with, and whether the norm was finite (False: the device skipped that step).  Copies 32 bytes to the host
+        and waits for the device; nothing else in this class does."""
+        from np_modeling_amd import _C
+        if not self._clipped:
+            raise RuntimeError('last_grad_norm(): the most recent apply() did not clip (clip_norm is None, or no apply() yet)')
+        state = np.zeros(4)
+        _C.check(_C.lib().npm_d2h(state.ctypes.data, self._clip_state.ptr, 32), 'npm_d2h')
+        return float(state[1]), float(state[2]), bool(state[3] != 0.0)
+
+
+def warmup_cosine(peak: float, warmup_steps: int, total_steps: int, floor: float = 0.0):
+    """A learning rate for ``AdamWOptimizer``: linear from ``peak / warmup_steps`` at step 1 to ``peak`` at ``warmup_steps``, half
+    a cosine down to ``floor`` at ``total_steps``, ``floor`` from there on.  Steps count from 1."""
+    import math
+    peak, floor, warmup_steps, total_steps = float(peak), float(floor), int(warmup_steps), int(total_steps)
+    if not 0 <= warmup_steps < total_steps:
+        raise ValueError(f'need 0 <= warmup_steps < total_steps, got {warmup_steps} and {total_steps}')
+
+    def rate(step: int) -> float:
+        if step <= warmup_steps:
+            return peak * step / warmup_steps
+        if step >= total_steps:
+            return floor
+        return floor + 0.5 * (peak - floor) * (1.0 + math.cos(math.pi * (step - warmup_steps) / (total_steps - warmup_steps)))
+
+    return rate

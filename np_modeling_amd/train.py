@@ -30,6 +30,10 @@ class Trainer:
         for stage in self._layers[::-1]:
             log.debug('backward: %s', stage.name)
             grad = stage(grad, backprop=True, optimizer_=optimizer_)
+        # an optimizer that steps once per backward, with every gradient in hand (optimizer.AdamWOptimizer: the global norm)
+        apply = getattr(optimizer_, 'apply', None)
+        if apply is not None:
+            apply()
 
     def train(self, inputs, targets, steps: int, optimizer_) -> None:
         # one upload for the whole loop; a first layer or a loss that takes something else than floats (token ids) says how
