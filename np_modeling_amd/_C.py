@@ -252,7 +252,13 @@ SIGNATURES = {
     'npm_mha_prefix_fwd': [C.POINTER(npm_mha_decode), _P, _P, _I32, _I32, _I32, _P, _P, _I32],
     'npm_mha_prefix_splits': [C.c_int, C.c_int, C.c_int, C.c_int],
     'npm_attn_combine': [_P, _P, _I32, _P, _I64, _P, _I32, _I32, _I32, _I32, _P, _I32],
+    'npm_kv_copy_pages_planes': [_P, _I64, _I64, _P, _P, _P, _I32, _I32, _I64],
     'npm_rope': [_P, _I64, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _I32],
+    'npm_rope_kv_append': [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _I64, _P, _I32, _I32, _I32],
+    'npm_rmsnorm_fwd': [_P, _P, _F, _I64, _I64, _P, _P],
+    'npm_rmsnorm_bwd': [_P, _P, _P, _P, _P, _I64, _I64, _P, _P],
+    'npm_swiglu_fwd': [_P, _I64, _I64, _I64, _P, _I64],
+    'npm_swiglu_bwd': [_P, _I64, _P, _I64, _I64, _I64, _P, _I64],
     'npm_take_rows': [_P, _I64, _I64, _P, _P, _I64, _I64, _I64],
     'npm_embedding_bwd': [_P, _I64, _P, _P, _P, _I32, _P, _I64, _I64],
     'npm_sample_rows': [C.POINTER(npm_sample)],
@@ -271,10 +277,14 @@ SIGNATURES = {
     'npm_sgemm_skinny_w16_supported': [C.POINTER(npm_gemm)],
     'npm_adam_step': [_P, _P, _P, _P, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int],
     'npm_fill_f64': [_P, C.c_double, _SZ],
+    'npm_sumsq_ranges': [C.POINTER(npm_ranges), _P],
+    'npm_clip_finish': [_P, C.c_double],
+    'npm_adamw_step': [_P, _P, _P, _P, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _P],
     'npm_mse_fwd': [_P, _P, _SZ, C.POINTER(C.c_double)],
     'npm_mse_bwd': [_P, _P, _P, _SZ],
     'npm_xent_fwd': [_P, _P, _SZ, C.POINTER(C.c_double)],
     'npm_xent_bwd': [_P, _P, _P, _SZ],
+    'npm_softmax_xent_rows': [_P, _I64, _P, _I64, _I64, _F, _F, _P, _I64, _P, _P, C.POINTER(C.c_double)],
     'npm_mask_scale': [_P, _P, _P, _SZ, _F],
     'npm_dropout_philox': [_P, _P, _P, _SZ, _F, C.c_uint64, C.c_uint64],
 }
@@ -291,25 +301,9 @@ _SPECIAL = {
     'npm_last_draft_kernel': (C.c_char_p, []),
     'npm_last_beam_kernel': (C.c_char_p, []),
     'npm_last_logits_kernel': (C.c_char_p, []),
-    # Returns int like everything in SIGNATURES, but lives here: the host simulator's profiles record SIGNATURES entry by entry, and
-    # this call is restated by the tests that need it (tests/hostsim_xent.py) instead of joining the simulator.
-    'npm_softmax_xent_rows': (C.c_int, [_P, _I64, _P, _I64, _I64, _F, _F, _P, _I64, _P, _P, C.POINTER(C.c_double)]),
     'npm_last_xent_kernel': (C.c_char_p, []),
-    # Likewise: restated by tests/hostsim_llama.py
-    'npm_rmsnorm_fwd': (C.c_int, [_P, _P, _F, _I64, _I64, _P, _P]),
-    'npm_rmsnorm_bwd': (C.c_int, [_P, _P, _P, _P, _P, _I64, _I64, _P, _P]),
-    'npm_swiglu_fwd': (C.c_int, [_P, _I64, _I64, _I64, _P, _I64]),
-    'npm_swiglu_bwd': (C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _I64]),
-    # Likewise: restated by tests/hostsim_lm.py
-    'npm_kv_copy_pages_planes': (C.c_int, [_P, _I64, _I64, _P, _P, _P, _I32, _I32, _I64]),
-    'npm_rope_kv_append': (C.c_int, [_P, _I64, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P, _P, _P, _I64, _I64, _P, _I32,
-                                     _I32, _I32]),
     'npm_last_rope_append_kernel': (C.c_char_p, []),
-    # Likewise: restated by tests/hostsim_adamw.py
-    'npm_sumsq_ranges': (C.c_int, [C.POINTER(npm_ranges), _P]),
-    'npm_clip_finish': (C.c_int, [_P, C.c_double]),
-    'npm_adamw_step': (C.c_int, [_P, _P, _P, _P, _SZ, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _P]),
-    # Likewise: the simulator's convolutions have no instances to report; tests/conv_cases.py restates the dispatch
+    # not part of the tests' host simulator: its convolutions have no instances to report; tests/conv_cases.py restates the dispatch
     'npm_last_conv_kernel': (C.c_char_p, []),
 }
 

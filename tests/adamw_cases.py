@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE: the cases and checks of npm_sumsq_ranges, npm_clip_finish, npm_adamw_step (csrc/npm_clip.hip) and of
-``optimizer.AdamWOptimizer`` on a model, written once and run through whatever library ``np_modeling_amd._C`` holds: the wrapped host
-simulator (tests/hostsim_adamw.py) in tests/test_adamw_host.py, libnpm_hip.so in tests/test_gpu_adamw.py.  Models and bounds:
+``optimizer.AdamWOptimizer`` on a model, written once and run through whatever library ``np_modeling_amd._C`` holds: the host
+simulator (tests/hostsim/) in tests/test_adamw_host.py, libnpm_hip.so in tests/test_gpu_adamw.py.  Models and bounds:
 tests/adamw_reference.py.  Buffers with sentinel guards: tests/optim_cases.py ``F32`` / ``Raw``.
 
 Sizes come from the launch code: a tile of the sum is 16384 elements (sizes around one tile, and three tiles and a bit: more than

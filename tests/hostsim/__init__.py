@@ -9,16 +9,20 @@ modules of tests/.  The product never loads this: tests install it explicitly wi
 One class, ``HostSim``, assembled from parts that know nothing of each other's methods:
 
 * memory.py      views of "device" memory
-* runtime.py     memory, copies, events, knobs and everything they record
-* training.py    GEMM, elementwise and row kernels, the fused attention core, rotary embeddings, conv, Adam, losses, dropout
-* kvcache.py     the key / value cache (append, gather, page copies) and attention over it (decode, prefill, window, prefix)
+* runtime.py     memory, copies, fills, events, knobs and everything they record
+* training.py    GEMM, elementwise and row kernels (layer / RMS norm, gated SiLU), the fused attention core, rotary embeddings,
+                 conv, Adam, AdamW with its clipping, losses (the fused softmax cross-entropy among them), dropout
+* kvcache.py     the key / value cache (append, gather, page copies, each alone and fused: all planes in one call, rotation
+                 with the append) and attention over it (decode, prefill, window, prefix)
 * generation.py  take_rows, embedding_bwd, sample, verify, draft, beam, logit processors, log-probabilities
 * gemm.py        the skinny-M GEMM and the half-precision weight copies
 
 ``install()`` gives the whole ABI.  ``install(profile)`` gives the library as it was when the feature of that name had just been
 added: the same simulator with every later entry point hidden (``hasattr`` is False), because the product probes for entry
 points with ``hasattr`` and tests compare its call traces between an earlier library and a later one.  A profile hides names and
-does nothing else.  fixtures.py holds the pytest fixtures the host test modules share.
+does nothing else: a new entry point joins the part it belongs to and a new profile, and no earlier profile changes.  The features
+up to 'logits' grew on two branches ('w16' is the other one); 'xent' joins them, and from there on a profile is the whole library of
+its day, so that 'adamw', the last, is ``install()``.  fixtures.py holds the pytest fixtures the host test modules share.
 """
 
 from . import gemm, kvcache  # noqa: F401  (tests read their pure rules: gemm.auto_splits, kvcache.split_ranges, ...)
@@ -60,6 +64,10 @@ _ADDED = {
                             npm_last_prefix_kernel'''),
     'beam': (('prefix', 'rope'), 'npm_beam_step npm_last_beam_kernel'),
     'logits': (('beam',), 'npm_logits_process npm_history_append npm_logprob_rows npm_last_logits_kernel'),
+    'xent': (('logits', 'w16'), 'npm_softmax_xent_rows npm_last_xent_kernel'),
+    'llama': (('xent',), 'npm_rmsnorm_fwd npm_rmsnorm_bwd npm_swiglu_fwd npm_swiglu_bwd'),
+    'lm': (('llama',), 'npm_kv_copy_pages_planes npm_rope_kv_append npm_last_rope_append_kernel'),
+    'adamw': (('lm',), 'npm_sumsq_ranges npm_clip_finish npm_adamw_step'),
 }
 
 

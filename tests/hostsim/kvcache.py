@@ -7,7 +7,12 @@ Attention is evaluated by tests/varlen_reference.py (every sequence alone, float
 Only rows below a sequence's length, and only the table entries of their pages, are ever looked at.  What was looked at is
 recorded: ``f16_reads`` (entry point, sequence, rows) of every read of an fp16 cache, ``window_reads`` (entry point, sequence,
 first row, end) of every windowed sequence, ``prefix_calls`` dict(rows, prefix, splits, pages, f16) of every prefix pass,
-``page_copies`` (source page, destination page, rows) and ``copy_calls`` (pairs) of every npm_kv_copy_pages."""
+``page_copies`` (source page, destination page, rows) and ``copy_calls`` (pairs) of every npm_kv_copy_pages and of every plane
+of an npm_kv_copy_pages_planes, ``plane_calls`` (pairs, planes) of every npm_kv_copy_pages_planes, ``fused_calls``
+dict(batch, tokens, rope, paged, ragged, f16) of every npm_rope_kv_append.
+
+The two fused calls are what they fuse, made on the same unrecorded helpers as the entry points they replace (``_copy_pages``,
+``Training._rope``, ``_kv_append``): each adds its own one line to ``calls``."""
 
 import ctypes as C
 
@@ -125,17 +130,17 @@ def _check_row_copy(rows, rows_pitch, cache, pitch, stride, page_rows, batch, co
 class KVCache:
     def __init__(self):
         super().__init__()
-        self.last_decode = self.last_prefill = self.last_prefix = ''
+        self.last_decode = self.last_prefill = self.last_prefix = self.last_rope_append = ''
         self.f16_reads, self.window_reads = [], []
         self.page_copies, self.copy_calls, self.prefix_calls = [], [], []
+        self.plane_calls, self.fused_calls = [], []
 
     # ---- row copies -----------------------------------------------------------------------------------------------------------------
-    def _kv_append(self, entry, src, src_pitch, cache, pitch, stride, batch, tokens, row_len, at, at_lens, new_lens, ragged,
+    def _kv_append(self, src, src_pitch, cache, pitch, stride, batch, tokens, row_len, at, at_lens, new_lens, ragged,
                    paged=False, table=None, table_pitch=0, page_rows=0, f16=False):
-        """``ragged``: row at_lens[b] onwards of sequence b takes new_lens[b] rows (NULL: ``tokens``), else every sequence takes
-        ``tokens`` rows at ``at``.  ``paged``: the cache is a page pool; a NULL length array or table and a bad page size are
-        refused even when there is nothing to copy."""
-        self.calls.append(entry)
+        """The append of every layout; the caller records the call.  ``ragged``: row at_lens[b] onwards of sequence b takes
+        new_lens[b] rows (NULL: ``tokens``), else every sequence takes ``tokens`` rows at ``at``.  ``paged``: the cache is a page
+        pool; a NULL length array or table and a bad page size are refused even when there is nothing to copy."""
         if paged and not (_addr(at_lens) and _addr(table) and table_pitch >= 0 and _page_ok(page_rows)):
             return BAD
         rc = _check_row_copy(src, src_pitch, cache, pitch, stride, page_rows if paged else 0, batch, tokens, row_len, at, at_lens,
@@ -154,24 +159,26 @@ class KVCache:
         return 0
 
     def npm_kv_append(self, src, src_pitch, cache, cache_pitch, cache_stride_b, batch, tokens, row_len, at):
-        return self._kv_append('npm_kv_append', src, src_pitch, cache, cache_pitch, cache_stride_b, batch, tokens, row_len, at, None, None,
-                               ragged=False)
+        self.calls.append('npm_kv_append')
+        return self._kv_append(src, src_pitch, cache, cache_pitch, cache_stride_b, batch, tokens, row_len, at, None, None, ragged=False)
 
     def npm_kv_append_varlen(self, src, src_pitch, cache, cache_pitch, cache_stride_b, batch, tokens, row_len, at_lens, new_lens):
-        return self._kv_append('npm_kv_append_varlen', src, src_pitch, cache, cache_pitch, cache_stride_b, batch, tokens, row_len, 0,
-                               at_lens, new_lens, ragged=True)
+        self.calls.append('npm_kv_append_varlen')
+        return self._kv_append(src, src_pitch, cache, cache_pitch, cache_stride_b, batch, tokens, row_len, 0, at_lens, new_lens,
+                               ragged=True)
 
     def npm_kv_append_paged(self, src, src_pitch, pool, row_pitch, page_stride, batch, tokens, row_len, at_lens, new_lens,
                             block_table, table_pitch, page_rows):
-        return self._kv_append('npm_kv_append_paged', src, src_pitch, pool, row_pitch, page_stride, batch, tokens, row_len, 0,
-                               at_lens, new_lens, True, True, block_table, table_pitch, page_rows)
+        self.calls.append('npm_kv_append_paged')
+        return self._kv_append(src, src_pitch, pool, row_pitch, page_stride, batch, tokens, row_len, 0, at_lens, new_lens, True, True,
+                               block_table, table_pitch, page_rows)
 
     def npm_kv_append_f16(self, src, src_pitch, cache, cache_pitch, cache_stride, batch, tokens, row_len, at, at_lens, new_lens,
                           block_table, table_pitch, page_rows):
+        self.calls.append('npm_kv_append_f16')
         paged = bool(_addr(block_table))
-        return self._kv_append('npm_kv_append_f16', src, src_pitch, cache, cache_pitch, cache_stride, batch, tokens, row_len,
-                               0 if _addr(at_lens) else at, at_lens, new_lens, paged or bool(_addr(at_lens)), paged, block_table,
-                               table_pitch, page_rows, True)
+        return self._kv_append(src, src_pitch, cache, cache_pitch, cache_stride, batch, tokens, row_len, 0 if _addr(at_lens) else at,
+                               at_lens, new_lens, paged or bool(_addr(at_lens)), paged, block_table, table_pitch, page_rows, True)
 
     def _kv_gather(self, entry, cache, pitch, stride, out, batch, count, row_len, lens, paged=False, table=None, table_pitch=0,
                    page_rows=0, f16=False):
@@ -207,6 +214,10 @@ class KVCache:
 
     def npm_kv_copy_pages(self, pool, page_stride_bytes, row_bytes, src_pages, dst_pages, rows, n):
         self.calls.append('npm_kv_copy_pages')
+        return self._copy_pages(pool, page_stride_bytes, row_bytes, src_pages, dst_pages, rows, n)
+
+    def _copy_pages(self, pool, page_stride_bytes, row_bytes, src_pages, dst_pages, rows, n):
+        """The page copies of one plane; the caller records the call."""
         if n < 0 or row_bytes < 0 or page_stride_bytes < 0:
             return BAD
         if n == 0 or row_bytes == 0:
@@ -222,6 +233,65 @@ class KVCache:
             assert 0 <= r * row_bytes <= page_stride_bytes
             self.page_copies.append((s, d, r))
             C.memmove(_addr(pool) + d * page_stride_bytes, _addr(pool) + s * page_stride_bytes, r * row_bytes)
+        return 0
+
+    def npm_kv_copy_pages_planes(self, pool, page_stride_bytes, row_bytes, src_pages, dst_pages, rows, n, planes, plane_stride_bytes):
+        """The same pairs in every plane."""
+        self.calls.append('npm_kv_copy_pages_planes')
+        if min(n, row_bytes, page_stride_bytes, planes, plane_stride_bytes) < 0:
+            return BAD
+        if n == 0 or row_bytes == 0 or planes == 0:
+            return 0
+        if plane_stride_bytes % 16 or (planes > 1 and plane_stride_bytes < page_stride_bytes):
+            return BAD
+        self.plane_calls.append((int(n), int(planes)))
+        for plane in range(planes):
+            rc = self._copy_pages(_addr(pool) + plane * plane_stride_bytes if _addr(pool) else None, page_stride_bytes, row_bytes,
+                                  src_pages, dst_pages, rows, n)
+            if rc:
+                return rc
+        return 0
+
+    def npm_rope_kv_append(self, qkv, pitch, batch, tokens, heads, kv_heads, head_dim, cos, sin, table_rows, at, at_lens, new_lens,
+                           k_cache, v_cache, cache_pitch, cache_stride, block_table, table_pitch, page_rows, kv_f16):
+        """The three calls it fuses: the rotation of npm_rope (tests/rope_reference.py ``rotate``, the bitwise model) on the first
+        heads + kv_heads heads, then the append of the layout for the k and for the v heads."""
+        self.calls.append('npm_rope_kv_append')
+        rot, paged, ragged = bool(_addr(cos) or _addr(sin)), bool(_addr(block_table)), bool(_addr(at_lens))
+        self.fused_calls.append(dict(batch=batch, tokens=tokens, rope=rot, paged=paged, ragged=ragged, f16=bool(kv_f16)))
+        if paged and not (ragged and table_pitch >= 0 and _page_ok(page_rows)):
+            return BAD
+        if min(heads, kv_heads, head_dim) < 1:
+            return BAD
+        # every refusal first, as the kernel's host function has it: a refused call writes nothing
+        if rot:
+            if not (_addr(qkv) and _addr(cos) and _addr(sin)) or min(batch, tokens, table_rows) < 1 or head_dim < 2 or head_dim % 2:
+                return BAD
+            if not ragged and (at < 0 or at + tokens > table_rows):
+                return BAD
+        if min(batch, tokens) < 0 or (not ragged and at < 0):
+            return BAD
+        if batch == 0 or tokens == 0:
+            return 0
+        if head_dim % 2 or pitch < (heads + 2 * kv_heads) * head_dim or not _addr(qkv):
+            return BAD
+        row = kv_heads * head_dim
+        parts = ((_addr(qkv) + 4 * heads * head_dim, k_cache), (_addr(qkv) + 4 * (heads * head_dim + row), v_cache))
+        for src, cache in parts:
+            rc = _check_row_copy(src, pitch, cache, cache_pitch, cache_stride, page_rows if paged else 0, batch, tokens, row,
+                                 0 if ragged else at, at_lens, ragged, bool(kv_f16))
+            if rc:
+                return rc
+        if rot:
+            rc = self._rope(qkv, pitch, batch, tokens, heads + kv_heads, head_dim, cos, sin, table_rows, at, at_lens, 0)
+            assert rc == 0
+        for src, cache in parts:                    # paged implies ragged (above): one call is the append of every layout
+            rc = self._kv_append(src, pitch, cache, cache_pitch, cache_stride, batch, tokens, row, 0 if ragged else at, at_lens, new_lens,
+                                 ragged, paged, block_table, table_pitch, page_rows, bool(kv_f16))
+            assert rc == 0
+        vec = head_dim % 8 == 0 and _addr(qkv) % 16 == 0 and (not rot or (_addr(cos) % 16 == 0 and _addr(sin) % 16 == 0))
+        self.last_rope_append = 'rope_kv_append_kernel D=%d vec=%d rope=%d varlen=%d paged=%d kv=%s' % (
+            head_dim, vec, rot, ragged, page_rows if paged else 0, 'f16' if kv_f16 else 'f32')
         return 0
 
     # ---- attention over the cache ------------------------------------------------------------------------------------------------------
@@ -254,6 +324,9 @@ class KVCache:
 
     def npm_last_prefix_kernel(self):
         return self.last_prefix.encode()
+
+    def npm_last_rope_append_kernel(self):
+        return self.last_rope_append.encode()
 
     def _cached_fwd(self, entry, dref, kv_lens=None, new_lens=None, table=None, table_pitch=0, page_rows=0, window=None, kv_f16=False):
         """Every decode / prefill entry point; ``window`` None for the plain forms.  NULL kv_lens: every sequence holds kv_len rows;

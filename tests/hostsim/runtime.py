@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE ONLY -- the runtime of the simulated library: memory, copies, events, knobs, and what they record.
 
 * ``calls`` lists the compute entry points in call order; npm_h2d, npm_d2d and npm_d2h are not part of it (tests compare those
-  lists between libraries), their byte counts go to ``uploads``, ``copies`` and ``d2h``.
+  lists between libraries), their byte counts go to ``uploads``, ``copies`` and ``d2h``.  npm_fill_f64 is not part of it either:
+  ``fills64`` lists (len(calls) at the time, n) of every one, so that a test can put them back in their place.
 * ``live`` / ``peak`` count the bytes of device memory in use now / at most since a test last set ``peak = live``.
 * ``decode_splits`` / ``prefix_splits`` are NPM_TUNE_DECODE_SPLITS (knob 20) and NPM_TUNE_PREFIX_SPLITS (knob 24)."""
 
@@ -19,7 +20,7 @@ class Runtime:
         super().__init__()
         self._blocks, self._sizes = {}, {}
         self._err = b''
-        self.calls, self.uploads, self.copies, self.d2h = [], [], [], []
+        self.calls, self.uploads, self.copies, self.d2h, self.fills64 = [], [], [], [], []
         self.live = self.peak = 0
         self.decode_splits = self.prefix_splits = 0
         self.math = 0
@@ -85,6 +86,7 @@ class Runtime:
         return 0
 
     def npm_fill_f64(self, dst, value, n):
+        self.fills64.append((len(self.calls), int(n)))
         if int(n) == 0:
             return 0
         if not _addr(dst):

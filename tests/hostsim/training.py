@@ -1,20 +1,29 @@
-"""TEST INFRASTRUCTURE ONLY -- the entry points of training, restated with NumPy / the oracle: GEMM with its epilogues, elementwise
-and row kernels, the fused attention core (grouped and not), convolution, Adam, losses and dropout."""
+"""TEST INFRASTRUCTURE ONLY -- the entry points of training, restated with NumPy / the oracle / the reference modules of tests/:
+GEMM with its epilogues, elementwise and row kernels (layer and RMS normalisation, the gated SiLU), the fused attention core
+(grouped and not), rotary embeddings, convolution, Adam and AdamW with the clipping in front of it, losses and dropout."""
 
 import ctypes as C
 
 import numpy as np
 
+import adamw_reference as AR
+import llama_reference as LR
 import rope_reference as RR
+import xent_cases
+import xent_reference
 from oracle import np_oracle as O
 
-from .memory import BAD, UNSUPPORTED, _addr, _deref, _heads, _ints, _mat, _vec
+from .memory import BAD, UNSUPPORTED, _addr, _deref, _heads, _ints, _mat, _vec, _words
+
+SUMSQ_MAX_RANGES = 32                     # NPM_SUMSQ_MAX_RANGES
 
 
 class Training:
     def __init__(self):
         super().__init__()
         self.ropes = []                   # the arguments of every npm_rope
+        self.sumsq_tables = []            # [(address, n), ...] of every npm_sumsq_ranges
+        self.last_xent = b''
 
     # ---- GEMM ----------------------------------------------------------------------------
     def npm_sgemm(self, gref):
@@ -166,6 +175,67 @@ class Training:
         _mat(dx, rows, d, d)[:] = out
         return rc
 
+    def npm_rmsnorm_fwd(self, x, gamma, eps, rows, d, z, rstd):
+        self.calls.append('npm_rmsnorm_fwd')
+        rows, d = int(rows), int(d)
+        if rows < 0 or d < 1:
+            return BAD
+        if rows == 0:
+            return 0
+        if not all(_addr(p) for p in (x, gamma, z, rstd)):
+            return BAD
+        out, rs = LR.rmsnorm_fwd(_mat(x, rows, d, d), _vec(gamma, d), eps)
+        _mat(z, rows, d, d)[:] = out
+        _vec(rstd, rows)[:] = rs[:, 0]
+        return 0
+
+    def npm_rmsnorm_bwd(self, dz, x, rstd, gamma, residual, rows, d, dx, dgamma):
+        self.calls.append('npm_rmsnorm_bwd')
+        rows, d = int(rows), int(d)
+        if rows < 0 or d < 1 or not _addr(dgamma):
+            return BAD
+        if rows == 0:
+            _vec(dgamma, d)[:] = 0
+            return 0
+        if not all(_addr(p) for p in (dz, x, rstd, gamma, dx)):
+            return BAD
+        # from the saved rstd, as the kernel: xh = x rstd
+        xv, rs = _mat(x, rows, d, d).astype(np.float64), _vec(rstd, rows).astype(np.float64)[:, None]
+        dzv, gm = _mat(dz, rows, d, d).astype(np.float64), _vec(gamma, d).astype(np.float64)
+        xh, g = xv * rs, dzv * gm
+        out = rs * (g - xh * (g * xh).mean(axis=1, keepdims=True))
+        if _addr(residual):
+            out = out + _mat(residual, rows, d, d)
+        _mat(dx, rows, d, d)[:] = out
+        _vec(dgamma, d)[:] = (dzv * xh).sum(axis=0)
+        return 0
+
+    def npm_swiglu_fwd(self, pre, ld, rows, units, h, ldh):
+        self.calls.append('npm_swiglu_fwd')
+        ld, rows, units, ldh = int(ld), int(rows), int(units), int(ldh)
+        if rows < 0 or units < 1 or ld < 2 * units or ldh < units:
+            return BAD
+        if rows == 0:
+            return 0
+        if not (_addr(pre) and _addr(h)):
+            return BAD
+        with np.errstate(over='ignore', invalid='ignore'):
+            _mat(h, rows, units, ldh)[:] = LR.swiglu_fwd(_mat(pre, rows, 2 * units, ld))
+        return 0
+
+    def npm_swiglu_bwd(self, pre, ld, dh, lddh, rows, units, dpre, lddpre):
+        self.calls.append('npm_swiglu_bwd')
+        ld, lddh, rows, units, lddpre = int(ld), int(lddh), int(rows), int(units), int(lddpre)
+        if rows < 0 or units < 1 or ld < 2 * units or lddh < units or lddpre < 2 * units:
+            return BAD
+        if rows == 0:
+            return 0
+        if not (_addr(pre) and _addr(dh) and _addr(dpre)):
+            return BAD
+        with np.errstate(over='ignore', invalid='ignore'):
+            _mat(dpre, rows, 2 * units, lddpre)[:] = LR.swiglu_bwd(_mat(pre, rows, 2 * units, ld), _mat(dh, rows, units, lddh))
+        return 0
+
     # ---- fused attention core ------------------------------------------------------------------------
     def npm_mha_mask_summary(self, mask, sb, sh, sq_stride, nb, nh, seq_q, seq_kv, out):
         """byte (qt, kb) of plane (b, h): bit w = some allowed position in queries 32 qt.. x keys 128 kb + 16 w.. (include/npm_hip.h)"""
@@ -279,10 +349,14 @@ class Training:
         return rc
 
     def npm_rope(self, x, pitch, batch, tokens, heads, head_dim, cos, sin, table_rows, at, at_lens, inverse):
-        """tests/rope_reference.py ``rotate``, the bitwise model of the kernel; rows outside the table are left untouched."""
         self.calls.append('npm_rope')
         self.ropes.append(dict(x=_addr(x), pitch=int(pitch), batch=batch, tokens=tokens, heads=heads, head_dim=head_dim,
                                table_rows=table_rows, at=at, at_lens=_addr(at_lens), inverse=int(inverse)))
+        return self._rope(x, pitch, batch, tokens, heads, head_dim, cos, sin, table_rows, at, at_lens, inverse)
+
+    def _rope(self, x, pitch, batch, tokens, heads, head_dim, cos, sin, table_rows, at, at_lens, inverse):
+        """tests/rope_reference.py ``rotate``, the bitwise model of the kernel; rows outside the table are left untouched.  The
+        caller records the call."""
         if not (_addr(x) and _addr(cos) and _addr(sin)):
             return BAD
         if min(batch, tokens, heads, table_rows) < 1 or head_dim < 2 or head_dim % 2 or pitch < heads * head_dim:
@@ -355,6 +429,55 @@ class Training:
         w -= upd                                            # fp64 loop, one rounding (as NumPy's f32 -= f64)
         return 0
 
+    def npm_sumsq_ranges(self, ranges, acc):
+        self.calls.append('npm_sumsq_ranges')
+        if ranges is None or not _addr(acc):
+            return BAD
+        table = _deref(ranges)
+        if not 0 <= table.count <= SUMSQ_MAX_RANGES:
+            return BAD
+        parts = [(int(table.ptr[i] or 0), int(table.n[i])) for i in range(table.count)]
+        if any(n > 0 and (not ptr or ptr % 4) for ptr, n in parts):
+            return BAD
+        self.sumsq_tables.append(parts)
+        if not any(n for _, n in parts):
+            return 0
+        total = AR.exact_sumsq(*[_vec(ptr, n) for ptr, n in parts if n])       # the exact sum, rounded once
+        out = _words(acc, 1, C.c_double)
+        with np.errstate(all='ignore'):
+            out[0] = out[0] + total
+        return 0
+
+    def npm_clip_finish(self, state, max_norm):
+        self.calls.append('npm_clip_finish')
+        if not _addr(state) or not max_norm > 0.0:
+            return BAD
+        s = _words(state, 4, C.c_double)
+        s[1], s[2], s[3] = AR.clip_finish(s[0], max_norm)
+        return 0
+
+    def npm_adamw_step(self, var, grad, m, v, n, lr, beta1, beta2, eps, step, weight_decay, clip_state):
+        """tests/adamw_reference.py ``adamw_model``; a clip state whose step is not to be taken leaves everything as it is."""
+        self.calls.append('npm_adamw_step')
+        n = int(n)
+        if step < 1 or not weight_decay >= 0.0:
+            return BAD
+        if n == 0:
+            return 0
+        if not (_addr(var) and _addr(grad) and _addr(m) and _addr(v)):
+            return BAD
+        clip = None
+        if _addr(clip_state):
+            s = _words(clip_state, 4, C.c_double)
+            clip = (float(s[2]), float(s[3]))
+            if clip[1] == 0:
+                return 0                        # nothing at all is written
+        mm, vv = _words(m, n, C.c_double), _words(v, n, C.c_double)
+        out = AR.adamw_model(_vec(var, n), _vec(grad, n), mm, vv, int(step), (lr, beta1, beta2, eps), weight_decay, clip)
+        mm[:], vv[:] = out.m, out.v
+        _vec(var, n)[:] = out.p
+        return 0
+
     def npm_mse_fwd(self, y, t, n, out):
         if int(n) == 0 or not (_addr(y) and _addr(t)):
             return BAD
@@ -381,6 +504,48 @@ class Training:
         with np.errstate(all='ignore'):
             _vec(dy, n)[:] = -_vec(t, n) / _vec(y, n)
         return 0
+
+    def npm_softmax_xent_rows(self, logits, ld, targets, rows, vocab, smoothing, grad_scale, dlogits, ldd, row_loss, row_lse, loss_sum):
+        """tests/xent_reference.py ``reference`` over the rows that have a target."""
+        self.calls.append('npm_softmax_xent_rows')
+        rows, vocab, ld, ldd = int(rows), int(vocab), int(ld), int(ldd)
+        z_at, d_at = _addr(logits), _addr(dlogits)
+        if loss_sum is None or not 0 <= rows < 2 ** 31 or not 1 <= vocab <= 2 ** 30 or ld < vocab or not 0.0 <= smoothing < 1.0:
+            return BAD
+        if d_at and ldd < vocab:
+            return BAD
+        if rows == 0:
+            self.last_xent = b'xent_none rows=0'
+            _deref(loss_sum).value = 0.0
+            return 0
+        if not z_at or not _addr(targets) or not _addr(row_loss):
+            return BAD
+        if d_at == z_at and d_at:
+            if ldd != ld:
+                return BAD
+        elif d_at:
+            z_end, d_end = z_at + 4 * ((rows - 1) * ld + vocab), d_at + 4 * ((rows - 1) * ldd + vocab)
+            if not (z_end <= d_at or d_end <= z_at):
+                return BAD
+        t = _ints(targets, rows)
+        z = _mat(logits, rows, vocab, ld)
+        # an ignored row is not read: it may hold anything
+        seen = np.where((t >= 0)[:, None], z, 0.0).astype(np.float64)
+        ref = xent_reference.reference(seen, t, smoothing, grad_scale, need_grad=bool(d_at))
+        with np.errstate(over='ignore'):
+            if d_at:
+                _mat(dlogits, rows, vocab, ldd)[:] = ref.grad.astype(np.float32)
+            _vec(row_loss, rows)[:] = ref.row_loss.astype(np.float32)
+            if _addr(row_lse):
+                _vec(row_lse, rows)[:] = ref.lse.astype(np.float32)
+        _deref(loss_sum).value = float(_vec(row_loss, rows).astype(np.float64).sum())
+        vec = z_at % 16 == 0 and ld % 4 == 0 and (not d_at or (d_at % 16 == 0 and ldd % 4 == 0))
+        self.last_xent = ('%s V=%d grad=%d inplace=%d vec=%d nt=%d' % (xent_cases.instance_of(vocab), vocab, bool(d_at), d_at == z_at,
+                                                                       vec, 4 * rows * vocab >= 32 << 20)).encode()
+        return 0
+
+    def npm_last_xent_kernel(self):
+        return self.last_xent
 
     def npm_mask_scale(self, x, mask, y, n, keep):
         self.calls.append('npm_mask_scale')

@@ -1,6 +1,6 @@
 """RMSNorm, the gated-SiLU ("SwiGLU") gate and whole transformer blocks with either norm and either feed-forward, restated in
 float64 NumPy: the reference of tests/test_gpu_rmsnorm.py, tests/test_gpu_swiglu.py, tests/test_gpu_llama_block.py and of the host
-simulator's wrapper tests/hostsim_llama.py.  The width tables are tests/rowops_reference.py's (``RR``)."""
+simulator (tests/hostsim/training.py).  The width tables are tests/rowops_reference.py's (``RR``)."""
 
 import numpy as np
 import rowops_reference as RR  # noqa: F401  (the tests read the width grid through this module)

@@ -1,4 +1,5 @@
-"""CPU: AdamW, global-norm clipping and the learning-rate schedule without a GPU, on the wrapped simulator of tests/hostsim_adamw.py.
+"""CPU: AdamW, global-norm clipping and the learning-rate schedule without a GPU, on the host simulator (tests/hostsim/; the three
+entry points join it with the profile 'adamw').
 
 * the cases of tests/adamw_cases.py, so that every check of tests/test_gpu_adamw.py has run (and the near-tie count of every step
   case has been asserted from the model alone) before a GPU sees it;
@@ -17,25 +18,14 @@ import pytest
 
 import adamw_cases as AC
 import adamw_reference as AR
-import hostsim
-import hostsim_adamw
 import lm_cases as MC
 import optim_cases as OC
 import optim_reference as R
-from hostsim.fixtures import built  # noqa: F401
+from hostsim.fixtures import built, npm_fixture  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = hostsim_adamw.install()
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim.uninstall()
+npm = npm_fixture()
 
 
 # ---- the same cases as on the GPU -----------------------------------------------------------------------------------------------------
@@ -178,14 +168,23 @@ def test_host_operands_are_refused(npm):
         opt.last_grad_norm()                             # that apply() did not clip
 
 
+def _with_fills(sim, start, fills):
+    """``calls[start:]`` with an 'npm_fill_f64' back at every place where the runtime noted one in ``fills64[fills:]``: it keeps
+    them out of ``calls``, as (len(calls) at the time, n)."""
+    calls = sim.calls[start:]
+    for at, _ in reversed(sim.fills64[fills:]):            # from the last: an insertion moves only what follows it
+        calls.insert(at - start, 'npm_fill_f64')
+    return calls
+
+
 def test_the_calls_of_a_step_and_no_copy_to_the_host(npm):
     lm = MC.make_lm(npm)
     opt = AC.watching(npm, 1e-2, clip_norm=1.0)
     for step in range(3):
         _backward(npm, lm, opt)
-        start, d2h = len(npm.sim.calls), len(npm.sim.d2h)
+        start, d2h, fills = len(npm.sim.calls), len(npm.sim.d2h), len(npm.sim.fills64)
         opt.apply()
-        calls = npm.sim.calls[start:]
+        calls = _with_fills(npm.sim, start, fills)
         assert len(npm.sim.d2h) == d2h, 'apply() copied to the host'
         sums = math.ceil(opt.last['ranges'] / 32)
         if step:                                         # the first apply() also zeroes the moment buffers it creates
@@ -370,14 +369,16 @@ def test_the_new_kernels_spill_nothing(built):
 
 
 def test_the_entry_points_are_declared_bound_and_not_part_of_the_simulator():
+    """The name is from when the three were restated beside the simulator and therefore bound through ``_SPECIAL``; they are part
+    of it now, and bound where every call that returns a status is."""
     import ctypes
     from np_modeling_amd import _C
     P = ctypes.c_void_p
     D = ctypes.c_double
-    assert _C._SPECIAL['npm_sumsq_ranges'] == (ctypes.c_int, [ctypes.POINTER(_C.npm_ranges), P])
-    assert _C._SPECIAL['npm_clip_finish'] == (ctypes.c_int, [P, D])
-    assert _C._SPECIAL['npm_adamw_step'] == (ctypes.c_int, [P, P, P, P, ctypes.c_size_t, D, D, D, D, ctypes.c_int, D, P])
-    assert not {'npm_sumsq_ranges', 'npm_clip_finish', 'npm_adamw_step'} & set(_C.SIGNATURES)
+    assert _C.SIGNATURES['npm_sumsq_ranges'] == [ctypes.POINTER(_C.npm_ranges), P]
+    assert _C.SIGNATURES['npm_clip_finish'] == [P, D]
+    assert _C.SIGNATURES['npm_adamw_step'] == [P, P, P, P, ctypes.c_size_t, D, D, D, D, ctypes.c_int, D, P]
+    assert not {'npm_sumsq_ranges', 'npm_clip_finish', 'npm_adamw_step'} & set(_C._SPECIAL)
     header = open(os.path.join(ROOT, 'include', 'npm_hip.h')).read()
     assert '#define NPM_SUMSQ_TILE %d' % _C.SUMSQ_TILE in header and _C.SUMSQ_TILE == AR.TILE == 256 * 64
     assert '#define NPM_SUMSQ_MAX_RANGES %d' % _C.SUMSQ_MAX_RANGES in header

@@ -25,11 +25,13 @@ def _exposed(sim):
 def test_profiles_are_what_the_tower_of_simulators_was():
     """tests/golden/hostsim_profiles.json holds, per profile, ``sorted(n for n in dir(cls) if n.startswith('npm_'))`` of the
     simulator class of that name on the last commit that had one class per feature (HostSim as 'training', DecodeHostSim as
-    'decode', ... LogitsHostSim as 'logits', SkinnyHostSim, W16HostSim), one profile a line.  A profile exposes exactly those
-    names, ``hasattr`` is False for every other one, and the whole simulator exposes their union."""
+    'decode', ... LogitsHostSim as 'logits', SkinnyHostSim, W16HostSim), one profile a line.  The last four lines ('xent', 'llama',
+    'lm', 'adamw') hold the same of the chain of wrappers that stood around the one class on the last commit that had them: the
+    class's names and those of every wrapper up to the one that feature added.  A profile exposes exactly those names,
+    ``hasattr`` is False for every other one, and the whole simulator exposes their union."""
     with open(os.path.join(ROOT, 'tests', 'golden', 'hostsim_profiles.json')) as fh:
         recorded = json.load(fh)
-    assert len(recorded) == 16 and set(recorded) == set(hostsim.PROFILES)
+    assert len(recorded) == 20 and set(recorded) == set(hostsim.PROFILES)
     try:
         for profile, names in recorded.items():
             sim = hostsim.install(profile)
@@ -39,6 +41,7 @@ def test_profiles_are_what_the_tower_of_simulators_was():
     finally:
         hostsim.uninstall()
     assert len(recorded['logits']) == 99 and not (set(recorded['w16']) - set(recorded['paged'])) & set(recorded['logits'])
+    assert len(recorded['adamw']) == 119
 
 
 def test_coverage_of_the_abi_is_stated():
@@ -49,7 +52,7 @@ def test_coverage_of_the_abi_is_stated():
     assert simulated - set(_C.SIGNATURES) == {
         'npm_abi_version', 'npm_last_error', 'npm_stream', 'npm_last_attn_kernel', 'npm_last_beam_kernel', 'npm_last_decode_kernel',
         'npm_last_draft_kernel', 'npm_last_logits_kernel', 'npm_last_prefill_kernel', 'npm_last_prefix_kernel',
-        'npm_last_sample_kernel', 'npm_last_skinny_kernel'}
+        'npm_last_sample_kernel', 'npm_last_skinny_kernel', 'npm_last_xent_kernel', 'npm_last_rope_append_kernel'}
 
 
 def test_one_class_of_parts_that_do_not_override_each_other():

@@ -1,31 +1,26 @@
-"""CPU: ``norm='rms'`` / ``ffn='swiglu'`` through TransformerEncoder and TransformerDecoder on the host simulator wrapped by
-tests/hostsim_llama.py (the simulator itself does not know the four new entry points): results against tests/llama_reference.py,
+"""CPU: ``norm='rms'`` / ``ffn='swiglu'`` through TransformerEncoder and TransformerDecoder on the host simulator (tests/hostsim/;
+the four entry points join it with the profile 'llama'): results against tests/llama_reference.py,
 the entry points called, one optimizer launch and one bucket per backward, the decode route -- and the default-keyword layers
 calling what they called before the keywords existed (tests/golden/llama_default_calls.json)."""
 
 import json
 
 import hostsim
-import hostsim_llama
 import llama_cases as LC
 import numpy as np
 import pytest
 import transformer_trace_cases as TC
+from hostsim.fixtures import activate, deactivate
 
 
 @pytest.fixture
 def npm():
-    import np_modeling_amd
-    from np_modeling_amd import _C, parallel
-    parallel.set_communicator(None)
-    lib = hostsim_llama.install()
-    np_modeling_amd.sim = lib
-    recorder = TC.Recorder(lib)
-    _C._LIB = recorder
-    np_modeling_amd.recorder = recorder
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim.uninstall()
+    """The shared fixture's simulator with a recorder of every call and its arguments in front of it."""
+    from np_modeling_amd import _C
+    package = activate()
+    package.recorder = _C._LIB = TC.Recorder(package.sim)
+    yield package
+    deactivate()
 
 
 def _names(npm):
@@ -146,7 +141,7 @@ def test_a_library_without_the_entry_points_is_an_error_that_names_them():
     from np_modeling_amd import _C, parallel
     import np_modeling_amd as package
     parallel.set_communicator(None)
-    hostsim.install()                                # the plain simulator: no npm_rmsnorm_*, no npm_swiglu_*
+    hostsim.install('xent')                          # the library from just before the feature: no npm_rmsnorm_*, no npm_swiglu_*
     try:
         x = np.ones((2, 8), dtype=np.float32)
         with pytest.raises(_C.NpmError, match='npm_rmsnorm_fwd'):

@@ -1,4 +1,4 @@
-"""CPU: the decoder-only language model on the host simulator wrapped by tests/hostsim_lm.py.
+"""CPU: the decoder-only language model on the host simulator (tests/hostsim/; its two fused cache calls join it with the profile 'lm').
 
 * ``TransformerDecoder(cross_attention=False, causal=False)`` IS ``TransformerEncoder``: the same entry points in the same order and
   the same bits, for every norm x feed-forward x norm order, fused and literal; its refusals;
@@ -18,24 +18,14 @@ import re
 import numpy as np
 import pytest
 
-import hostsim
-import hostsim_lm
 import llama_cases as LC
 import llama_reference as LR
 import lm_cases as MC
+from hostsim.fixtures import npm_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-@pytest.fixture
-def npm():
-    import np_modeling_amd
-    from np_modeling_amd import parallel
-    parallel.set_communicator(None)
-    np_modeling_amd.sim = hostsim_lm.install()
-    yield np_modeling_amd
-    parallel.set_communicator(None)
-    hostsim.uninstall()
+npm = npm_fixture()
 
 
 # ---- cross_attention=False ---------------------------------------------------------------------------------------------------------
@@ -49,7 +39,7 @@ def _block_run(npm, kind, norm, ffn, norm_first, literal, **extra):
     else:
         layer = npm.layers.TransformerDecoder(cross_attention=False, causal=False, **keywords)
     x, dy = LC.inputs(8, [LC.B, LC.S, LC.F], [LC.B, LC.S, LC.F])
-    calls = npm.sim.raw.calls
+    calls = npm.sim.calls
     del calls[:]
     layer(x)
     LC.tame(layer)
@@ -110,7 +100,7 @@ def test_the_calls_of_a_decoder_without_cross_attention(npm):
     state = dec.start_decoding(None, 16, batch=2, page_size=16, weights='f16')
     assert state.cross_cache is None and len(state.weights._sources) == 6
     state = dec.start_decoding(None, 16, batch=2, page_size=16)
-    names = npm.sim.raw.calls
+    names = npm.sim.calls
     del names[:]
     rows = [np.asarray(dec.decode(x[:, :5], state)), np.asarray(dec.decode(x[:, 5:6], state))]
     assert names.count('npm_rmsnorm_fwd') == 2 * 2 and names.count('npm_swiglu_fwd') == 2          # two blocks a step
@@ -269,13 +259,13 @@ def _six_steps(npm, layers):
     rng = np.random.default_rng(5)
     state = lm.start_decoding(4, 32, page_size=16, pages=12)
     cache, sim = state.self_cache, npm.sim
-    del sim.raw.calls[:]
+    del sim.calls[:]
     log = []
 
     def step(tokens, n):
-        uploads, table, calls = len(sim.uploads), cache.table_uploads, len(sim.raw.calls)
+        uploads, table, calls = len(sim.uploads), cache.table_uploads, len(sim.calls)
         lm.decode(rng.integers(0, MC.VOCAB, [4, tokens]), state, new_lengths=np.array(n))
-        names = sim.raw.calls[calls:]
+        names = sim.calls[calls:]
         log.append(dict(uploads=sim.uploads[uploads:], table=cache.table_uploads - table, planes=names.count('npm_kv_copy_pages_planes'),
                         single=names.count('npm_kv_copy_pages'), appends=names.count('npm_kv_append_paged'),
                         fused=names.count('npm_rope_kv_append'), ropes=names.count('npm_rope')))
@@ -430,7 +420,7 @@ def test_the_fused_switch_changes_the_launches_and_not_one_bit(npm, setting):
     for on in (True, False):
         lm.fused_rope_append = on
         state = lm.start_decoding(MC.B, 8, **setting)
-        names = npm.sim.raw.calls
+        names = npm.sim.calls
         del names[:]
         out = [np.asarray(lm.decode(inputs[:, :3], state, new_lengths=np.array([3, 3, 3]))),              # uniform from empty
                np.asarray(lm.decode(inputs[:, 3:5], state, new_lengths=np.array([2, 0, 2]), rows='all')),  # ragged
@@ -458,7 +448,7 @@ def test_the_module_switch_routes_a_plain_attention_layer_and_unpacked_parameter
 
     def run():
         cache = att.make_cache(2, 8)
-        names = npm.sim.raw.calls
+        names = npm.sim.calls
         del names[:]
         outs = [np.asarray(att(x[:, :3], cache=cache)), np.asarray(att(x[:, 3:], cache=cache, new_lengths=[2, 1]))]
         return outs, [n for n in names if n.startswith(('npm_rope', 'npm_kv_append'))], cache.k.numpy(), cache.v.numpy()
@@ -521,12 +511,12 @@ def test_the_new_entry_points_are_declared_bound_and_exported():
         proto = re.search(r'int %s\((.*?)\);' % name, text, flags=re.S).group(1)
         protos[name] = [ctype[re.sub(r'\s*\w+$', '', a.strip()).strip()] for a in proto.split(',')]
     assert protos['npm_kv_copy_pages_planes'] == protos['npm_kv_copy_pages'] + [ctypes.c_int32, ctypes.c_int64]
-    assert _C._SPECIAL['npm_kv_copy_pages_planes'] == (ctypes.c_int, protos['npm_kv_copy_pages_planes'])
-    assert 'npm_kv_copy_pages_planes' not in _C.SIGNATURES               # the simulator's profiles record SIGNATURES: restated beside it
+    assert _C.SIGNATURES['npm_kv_copy_pages_planes'] == protos['npm_kv_copy_pages_planes']
+    assert 'npm_kv_copy_pages_planes' not in _C._SPECIAL                 # it returns a status: SIGNATURES, like every such call
     ctype.update({'float *': ctypes.c_void_p, 'const float *': ctypes.c_void_p})
     proto = re.search(r'int npm_rope_kv_append\((.*?)\);', text, flags=re.S).group(1)
     args = [ctype[re.sub(r'\s*\w+$', '', a.strip()).strip()] for a in proto.split(',')]
-    assert len(args) == 21 and _C._SPECIAL['npm_rope_kv_append'] == (ctypes.c_int, args) and 'npm_rope_kv_append' not in _C.SIGNATURES
+    assert len(args) == 21 and _C.SIGNATURES['npm_rope_kv_append'] == args and 'npm_rope_kv_append' not in _C._SPECIAL
     assert re.search(r'const char \*npm_last_rope_append_kernel\(void\);', text)
     assert _C._SPECIAL['npm_last_rope_append_kernel'] == (ctypes.c_char_p, [])
     makefile = open(os.path.join(ROOT, 'np_modeling_amd', 'csrc', 'Makefile')).read()

@@ -1,24 +1,16 @@
-"""CPU: the host side of ``loss.SoftmaxCrossEntropyLoss`` and of the two ``Trainer`` hooks, on the host simulator wrapped by
-tests/hostsim_xent.py (the simulator itself does not know npm_softmax_xent_rows)."""
+"""CPU: the host side of ``loss.SoftmaxCrossEntropyLoss`` and of the two ``Trainer`` hooks, on the host simulator (tests/hostsim/;
+npm_softmax_xent_rows joins it with the profile 'xent')."""
 
 import contextlib
 import io
 
 import hostsim
-import hostsim_xent
 import numpy as np
 import pytest
 import xent_reference
+from hostsim.fixtures import npm_fixture
 
-
-@pytest.fixture
-def lib():
-    from np_modeling_amd import parallel
-    parallel.set_communicator(None)
-    wrapped = hostsim_xent.install()
-    yield wrapped
-    parallel.set_communicator(None)
-    hostsim.uninstall()
+npm = npm_fixture()
 
 
 def _logits(rows=6, vocab=11, seed=0, lead=None):
@@ -29,14 +21,14 @@ def _logits(rows=6, vocab=11, seed=0, lead=None):
 
 # ---- validation ---------------------------------------------------------------------------------------------------------------
 
-def test_constructor_rejects_what_it_cannot_mean(lib):
+def test_constructor_rejects_what_it_cannot_mean(npm):
     from np_modeling_amd import loss
     for kwargs in ({'label_smoothing': 1.0}, {'label_smoothing': -0.1}, {'reduction': 'none'}, {'ignore_index': 1.5}, {'ignore_index': True}):
         with pytest.raises(ValueError):
             loss.SoftmaxCrossEntropyLoss(**kwargs)
 
 
-def test_host_targets_are_validated(lib):
+def test_host_targets_are_validated(npm):
     from np_modeling_amd import device as D, loss
     z = D.from_host(_logits())
     xent = loss.SoftmaxCrossEntropyLoss()
@@ -57,12 +49,12 @@ def test_host_targets_are_validated(lib):
         loss.SoftmaxCrossEntropyLoss(ignore_index=-100).forward(z, np.where(good == 3, -1, good))
     with pytest.raises(ValueError, match='not ignore_index'):
         loss.SoftmaxCrossEntropyLoss(ignore_index=0).forward(z, np.where(good == 3, -1, good))
-    assert lib.calls.count('npm_softmax_xent_rows') == 0            # nothing was launched on the way
+    assert npm.sim.calls.count('npm_softmax_xent_rows') == 0            # nothing was launched on the way
     with pytest.raises(ValueError, match=r'\[\.\.\., V\]'):
         xent.forward(D.empty([]), good)
 
 
-def test_an_id_buffer_takes_only_a_negative_ignore_index_and_its_own_shape(lib):
+def test_an_id_buffer_takes_only_a_negative_ignore_index_and_its_own_shape(npm):
     from np_modeling_amd import device as D, loss
     z = D.from_host(_logits())
     ids = D.ids_from_host(np.arange(6) % 11)
@@ -73,7 +65,7 @@ def test_an_id_buffer_takes_only_a_negative_ignore_index_and_its_own_shape(lib):
     assert np.isfinite(loss.SoftmaxCrossEntropyLoss(ignore_index=-100).forward(z, ids))
 
 
-def test_backward_needs_a_gradient_and_perplexity_no_smoothing(lib):
+def test_backward_needs_a_gradient_and_perplexity_no_smoothing(npm):
     from np_modeling_amd import device as D, loss
     z, t = D.from_host(_logits()), np.arange(6) % 11
     xent = loss.SoftmaxCrossEntropyLoss()
@@ -92,7 +84,7 @@ def test_backward_needs_a_gradient_and_perplexity_no_smoothing(lib):
 
 def test_a_library_without_the_entry_point_is_an_error_that_names_it():
     from np_modeling_amd import _C, device as D, loss
-    hostsim.install()                               # the simulator alone: the symbol is missing
+    hostsim.install('logits')                       # the library from just before the feature: the symbol is missing
     try:
         with pytest.raises(_C.NpmError, match='npm_softmax_xent_rows'):
             loss.SoftmaxCrossEntropyLoss().forward(D.from_host(_logits()), np.arange(6))
@@ -104,7 +96,7 @@ def test_a_library_without_the_entry_point_is_an_error_that_names_it():
 
 @pytest.mark.parametrize('reduction', ['mean', 'sum'])
 @pytest.mark.parametrize('smoothing', [0.0, 0.2])
-def test_reductions_count_and_the_per_row_results(lib, reduction, smoothing):
+def test_reductions_count_and_the_per_row_results(npm, reduction, smoothing):
     from np_modeling_amd import device as D, loss
     host = _logits(lead=(2, 4), vocab=9, seed=1)
     t = np.array([[0, 8, -1, 3], [-1, -1, 5, 2]])
@@ -126,7 +118,7 @@ def test_reductions_count_and_the_per_row_results(lib, reduction, smoothing):
         assert xent.perplexity() == pytest.approx(np.exp(row_loss32.astype(np.float64).sum() / 5), rel=1e-12)
 
 
-def test_no_valid_target_divides_by_one(lib):
+def test_no_valid_target_divides_by_one(npm):
     from np_modeling_amd import device as D, loss
     xent = loss.SoftmaxCrossEntropyLoss()
     value = xent.forward(D.from_host(_logits()), np.full(6, -1))
@@ -134,15 +126,15 @@ def test_no_valid_target_divides_by_one(lib):
     assert not xent.backward().numpy().any() and not xent.row_loss.numpy().any()
 
 
-def test_zero_rows(lib):
+def test_zero_rows(npm):
     from np_modeling_amd import device as D, loss
     xent = loss.SoftmaxCrossEntropyLoss()
     assert xent.forward(D.empty([0, 7]), np.zeros([0], dtype=np.int64)) == 0.0
     assert xent.count == 0 and xent.backward().shape == (0, 7)
-    assert lib.npm_last_xent_kernel() == b'xent_none rows=0'
+    assert npm.sim.npm_last_xent_kernel() == b'xent_none rows=0'
 
 
-def test_a_non_negative_ignore_index_becomes_minus_one_on_the_host(lib):
+def test_a_non_negative_ignore_index_becomes_minus_one_on_the_host(npm):
     from np_modeling_amd import device as D, loss
     host, t = _logits(), np.array([0, 3, 10, 3, 7, 12])        # 12: beyond the vocabulary, legal because it is the pad id
     a = loss.SoftmaxCrossEntropyLoss(ignore_index=12)
@@ -155,39 +147,39 @@ def test_a_non_negative_ignore_index_becomes_minus_one_on_the_host(lib):
     assert inside.count == 3 and not inside.backward().numpy()[[1, 3, 5]].any()
 
 
-def test_host_targets_are_read_every_forward_and_uploaded_when_they_change(lib):
+def test_host_targets_are_read_every_forward_and_uploaded_when_they_change(npm):
     from np_modeling_amd import device as D, loss
     z, t = D.from_host(_logits()), np.arange(6) % 11
     xent = loss.SoftmaxCrossEntropyLoss()
-    before = len(lib.uploads)
+    before = len(npm.sim.uploads)
     first = xent.forward(z, t)
-    assert lib.uploads[before:] == [24]                         # six int32
+    assert npm.sim.uploads[before:] == [24]                         # six int32
     assert xent.forward(z, t) == first
-    assert lib.uploads[before:] == [24]                         # same object, same contents: no second upload
+    assert npm.sim.uploads[before:] == [24]                         # same object, same contents: no second upload
     t[2] = 9                                                    # refilled in place: noticed, because the array is read again
     assert xent.forward(z, t) != first
-    assert lib.uploads[before:] == [24, 24]
+    assert npm.sim.uploads[before:] == [24, 24]
     xent.forward(z, t.copy())                                   # another object
-    assert lib.uploads[before:] == [24, 24, 24]
+    assert npm.sim.uploads[before:] == [24, 24, 24]
     t[2] = 11
     with pytest.raises(ValueError, match='outside the vocabulary'):
         xent.forward(z, t)
 
 
-def test_an_id_buffer_is_counted_once_per_object(lib):
+def test_an_id_buffer_is_counted_once_per_object(npm):
     from np_modeling_amd import device as D, loss
     z = D.from_host(_logits())
     ids = D.ids_from_host(np.array([1, -1, 4, -5, 0, 2]))
     xent = loss.SoftmaxCrossEntropyLoss()
-    before = len(lib.d2h)
+    before = len(npm.sim.d2h)
     xent.forward(z, ids)
     xent.forward(z, ids)
-    assert xent.count == 4 and lib.d2h[before:] == [24]
+    assert xent.count == 4 and npm.sim.d2h[before:] == [24]
     xent.forward(z, D.ids_from_host(np.array([1, 1, 4, 5, 0, 2])))
-    assert xent.count == 6 and lib.d2h[before:] == [24, 24]
+    assert xent.count == 6 and npm.sim.d2h[before:] == [24, 24]
 
 
-def test_inplace_returns_the_logits_buffer(lib):
+def test_inplace_returns_the_logits_buffer(npm):
     from np_modeling_amd import device as D, loss
     host, t = _logits(), np.arange(6) % 11
     z = D.from_host(host)
@@ -199,23 +191,23 @@ def test_inplace_returns_the_logits_buffer(lib):
     assert over.forward(z, t) == value
     assert over.backward() is z
     np.testing.assert_array_equal(z.numpy(), fresh.backward().numpy())
-    assert b'inplace=1' in lib.npm_last_xent_kernel()
+    assert b'inplace=1' in npm.sim.npm_last_xent_kernel()
 
 
-def test_evaluation_is_one_call_and_no_rows_by_vocab_buffer(lib):
+def test_evaluation_is_one_call_and_no_rows_by_vocab_buffer(npm):
     from np_modeling_amd import device as D, loss
     rows, vocab = 16, 4096
     z, ids = D.from_host(_logits(rows, vocab)), D.ids_from_host(np.arange(rows))
     xent = loss.SoftmaxCrossEntropyLoss()
     xent.forward(z, ids, need_grad=False)                       # the count of this buffer is known from here on
-    calls, live = len(lib.calls), lib.live
-    lib.sim.peak = lib.live
+    calls, live = len(npm.sim.calls), npm.sim.live
+    npm.sim.peak = npm.sim.live
     value = xent.forward(z, ids, need_grad=False)
-    assert lib.calls[calls:] == ['npm_softmax_xent_rows']
-    assert lib.peak - live < 4 * rows * vocab and lib.peak - live <= 2 * (8 * rows + 64)
-    assert b'grad=0' in lib.npm_last_xent_kernel()
+    assert npm.sim.calls[calls:] == ['npm_softmax_xent_rows']
+    assert npm.sim.peak - live < 4 * rows * vocab and npm.sim.peak - live <= 2 * (8 * rows + 64)
+    assert b'grad=0' in npm.sim.npm_last_xent_kernel()
     with_grad = xent.forward(z, ids)
-    assert with_grad == value and lib.peak - live >= 4 * rows * vocab
+    assert with_grad == value and npm.sim.peak - live >= 4 * rows * vocab
 
 
 def test_finite_differences_of_the_restatement():
@@ -239,14 +231,14 @@ def test_finite_differences_of_the_restatement():
                 assert ref.grad[r, j] == pytest.approx(0.5 * slope, abs=1e-8)
 
 
-def test_host_logits_take_the_numpy_path_with_the_same_rules(lib):
+def test_host_logits_take_the_numpy_path_with_the_same_rules(npm):
     from np_modeling_amd import loss
     host = _logits(7, 13, seed=2).astype(np.float64)
     host[1, 4:9] = -np.inf
     host[2, 3] = np.nan
     host[5] = -np.inf
     t = np.array([0, 12, 1, -1, 5, 2, 4])
-    calls = len(lib.calls)
+    calls = len(npm.sim.calls)
     for smoothing in (0.0, 0.1):
         xent = loss.SoftmaxCrossEntropyLoss(label_smoothing=smoothing, reduction='sum')
         value = xent.forward(host, t)
@@ -260,7 +252,7 @@ def test_host_logits_take_the_numpy_path_with_the_same_rules(lib):
     ref = xent_reference.reference(host[[0, 1, 3, 4, 6]], t[[0, 1, 3, 4, 6]], 0.0, 1 / 4)
     assert value == pytest.approx(ref.loss_sum / 4, rel=1e-13) and clean.perplexity() == pytest.approx(np.exp(ref.loss_sum / 4), rel=1e-13)
     np.testing.assert_allclose(clean.backward(), ref.grad, rtol=1e-12, atol=1e-15)
-    assert lib.calls[calls:] == []                              # nothing ran on the device
+    assert npm.sim.calls[calls:] == []                              # nothing ran on the device
 
 
 # ---- Trainer ------------------------------------------------------------------------------------------------------------------
@@ -274,7 +266,7 @@ _PARENT_TRACE = {
 
 
 @pytest.mark.parametrize('which', ['mse', 'xent'])
-def test_trainer_without_the_hooks_records_what_it_always_did(lib, which):
+def test_trainer_without_the_hooks_records_what_it_always_did(npm, which):
     from np_modeling_amd import layers, loss, optimizer, train
     np.random.seed(3)
     x = np.random.normal(size=(6, 5)).astype(np.float32)
@@ -289,10 +281,10 @@ def test_trainer_without_the_hooks_records_what_it_always_did(lib, which):
     assert not hasattr(loss_, 'resident_targets') and not hasattr(model[0], 'resident_inputs')
     with contextlib.redirect_stdout(io.StringIO()):
         train.Trainer(model, loss_).train(x, y, 3, optimizer.SGDOptimizer(0.1))
-    assert (list(lib.calls), list(lib.uploads), list(lib.d2h)) == _PARENT_TRACE[which]
+    assert (list(npm.sim.calls), list(npm.sim.uploads), list(npm.sim.d2h)) == _PARENT_TRACE[which]
 
 
-def test_trainer_keeps_token_ids_integers_and_uploads_them_once(lib):
+def test_trainer_keeps_token_ids_integers_and_uploads_them_once(npm):
     from np_modeling_amd import device as D, layers, loss, optimizer, train
     np.random.seed(4)
     vocab, batch, seq = 12, 3, 5
@@ -311,8 +303,8 @@ def test_trainer_keeps_token_ids_integers_and_uploads_them_once(lib):
         trainer.train(inputs, targets, 3, optimizer.SGDOptimizer(0.5))
     assert len(seen) == 3 and all(isinstance(ids, D.IdBuffer) for ids in seen) and seen[0] is seen[1] is seen[2]
     np.testing.assert_array_equal(seen[0].numpy(), inputs)
-    assert lib.uploads.count(4 * batch * seq) == 2              # the inputs once, the targets once: never again in three steps
-    assert lib.calls.count('npm_softmax_xent_rows') == 3
+    assert npm.sim.uploads.count(4 * batch * seq) == 2              # the inputs once, the targets once: never again in three steps
+    assert npm.sim.calls.count('npm_softmax_xent_rows') == 3
     assert xent.count == int((targets >= 0).sum())
     values = [float(line.split()[-1]) for line in out.getvalue().splitlines() if line.startswith('Loss:')]
     assert len(values) == 3 and values[2] < values[1] < values[0]
@@ -323,16 +315,16 @@ def test_trainer_keeps_token_ids_integers_and_uploads_them_once(lib):
         with contextlib.redirect_stdout(io.StringIO()):
             trainer.train(inputs, np.where(np.arange(targets.size) == 2, vocab, targets), 1, optimizer.SGDOptimizer(0.5))
     # eval: no gradient
-    calls = len(lib.calls)
+    calls = len(npm.sim.calls)
     with contextlib.redirect_stdout(io.StringIO()):
         trainer.eval(inputs, targets)
-    assert b'grad=0' in lib.npm_last_xent_kernel() and lib.calls[calls:].count('npm_softmax_xent_rows') == 1
+    assert b'grad=0' in npm.sim.npm_last_xent_kernel() and npm.sim.calls[calls:].count('npm_softmax_xent_rows') == 1
     with pytest.raises(RuntimeError):
         xent.backward()
 
 
 @pytest.mark.parametrize('pad', [0, 5, 12, 40])
-def test_trainer_with_a_non_negative_pad_id_is_the_minus_one_run(lib, pad):
+def test_trainer_with_a_non_negative_pad_id_is_the_minus_one_run(npm, pad):
     """``resident_targets`` maps the pad id to -1 once; the forward must take that buffer although ``ignore_index >= 0``.  Pad ids
     inside (0, 5) and beyond (12, 40) the vocabulary of 12; count, every loss and the last gradient equal the run with -1."""
     from np_modeling_amd import layers, loss, optimizer, train
@@ -352,9 +344,9 @@ def test_trainer_with_a_non_negative_pad_id_is_the_minus_one_run(lib, pad):
         values = [float(line.split()[-1]) for line in out.getvalue().splitlines() if line.startswith('Loss:')]
         return values, loss_.count, loss_.backward().numpy()
 
-    uploads = len(lib.uploads)
+    uploads = len(npm.sim.uploads)
     values, count, grad = run(loss.SoftmaxCrossEntropyLoss(ignore_index=pad), np.where(padded, pad, real))
-    assert lib.uploads[uploads:].count(60) == 2                 # inputs and targets once each, mapped on the host
+    assert npm.sim.uploads[uploads:].count(60) == 2                 # inputs and targets once each, mapped on the host
     want_values, want_count, want_grad = run(loss.SoftmaxCrossEntropyLoss(), np.where(padded, -1, real))
     assert count == want_count == int((~padded).sum()) and len(values) == 3 and values == want_values
     np.testing.assert_array_equal(grad, want_grad)
@@ -367,7 +359,7 @@ def test_trainer_with_a_non_negative_pad_id_is_the_minus_one_run(lib, pad):
         xent.forward(D.from_host(_logits(15, vocab)), D.ids_from_host(real))
 
 
-def test_trainer_eval_leaves_a_loss_without_need_grad_alone(lib):
+def test_trainer_eval_leaves_a_loss_without_need_grad_alone(npm):
     from np_modeling_amd import layers, loss, train
     np.random.seed(5)
     x, y = np.random.normal(size=(4, 5)).astype(np.float32), np.random.normal(size=(4, 3)).astype(np.float32)

@@ -72,7 +72,7 @@ def _encode(arg, argtype):
 
 
 class Recorder:
-    """A proxy in front of an installed simulator (composed as tests/hostsim_xent.py composes one: the simulator gains nothing).
+    """A proxy in front of an installed simulator, by composition: the simulator gains nothing.
     Every attribute is the simulator's; an entry point that is not part of the runtime is also recorded when called."""
 
     def __init__(self, sim):

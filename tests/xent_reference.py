@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY -- softmax cross-entropy from logits and token ids, restated in float64, with the rules and the error
-bound that include/npm_hip.h states for npm_softmax_xent_rows.  tests/hostsim_xent.py answers the entry point with it on the host;
+bound that include/npm_hip.h states for npm_softmax_xent_rows.  tests/hostsim/training.py answers the entry point with it on the host;
 tests/test_gpu_xent.py holds the kernel to it."""
 
 from collections import namedtuple
