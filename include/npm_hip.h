@@ -136,7 +136,7 @@ enum {
     NPM_TUNE_CONV_WGRAD_BLOCKS = 8,  /* grad_w split-K blocks per CU: 0 (default) best of 3 and 4, 3 / 4 pinned, 6 / 9 / 12 several generations of shorter K ranges (measured at C3: 14.44 -> 14.6-15.0 ms), -1 unbalanced ceil(3 CUs / tiles) */
     NPM_TUNE_GEMM_WAVE_PRIO = 9,     /* s_setprio 3 in the GEMM / conv block prologue (bit 0) and epilogue (bit 1) */
     NPM_TUNE_GEMM_MATH = 10,         /* same as npm_set_math */
-    NPM_TUNE_ATTN_STAGGER = 11,      /* attention forward: s_sleep(127) units one of the two blocks of a CU waits at its start (default 1) */
+    NPM_TUNE_ATTN_STAGGER = 11,      /* attention forward: bits 0-7 s_sleep(127) units one of the two blocks of a CU waits at its start (default 1; read by mha_fwd_kernel only: mha_fwd8_kernel, the default, does not sleep); bit 8 set: no pairing of query tiles under a tile summary */
     NPM_TUNE_CONV_WGRAD_FUSED = 13,  /* npm_conv2d_bwd_w_relu: 1 (default) ReLU backward inside the grad_w kernel, tile height picked (k*k*C0 of exactly three 192-row tiles: one block of twelve waves sharing the masked dy tile); 2 / 3 the same with 128- / 192-row tiles in four-wave blocks; 0 two passes */
     NPM_TUNE_ATTN_BWD16 = 14,        /* attention backward: 2 (default) mha_bwd8_kernel (8 waves on the 16x16x4 MFMA, one barrier per tile, every head size, both score modes, tile skipping) except head size 128 with saved scores and no tile summary, which runs mha_bwd16_kernel; 3 mha_bwd8_kernel always; 1 round 3's choice (mha_bwd16_kernel for head size 128 with saved scores, the 4-wave 32x32x2 kernel otherwise); 0 the 4-wave kernel always */
     NPM_TUNE_KSYNC = 15,             /* K tiles between the soft rendezvous of the co-resident split-K blocks of the fused Conv2D filter gradient: a power of two, default 128; 0 off */
@@ -360,7 +360,7 @@ typedef struct npm_mha_core {
      * softmax: that row of ctx and dq, and through P = NaN every dk / dv row of its (batch, head)): npm_mha_mask_summary marks
      * every tile of a mask plane that has such a row as "visit", so such planes are simply not skipped.  Positions of `scores`
      * inside skipped tiles are left unwritten (the backward never reads them).  Used for seq_q, seq_kv <= 2048; longer
-     * sequences, and calls made while npm_debug_attn_trace is active, run unskipped. */
+     * sequences run unskipped. */
     const uint8_t *tile_summary; int64_t summary_stride_b, summary_stride_h;
     int64_t summary_all_offset;   /* bytes from a tile's "some position allowed" byte to its "every position allowed" byte (the second
                                      half of what npm_mha_mask_summary writes: planes_b * planes_h * tiles bytes later); 0 = not given.
@@ -369,8 +369,8 @@ typedef struct npm_mha_core {
      * epilogue of the GEMM that produced dctx -- which exists at head_dim 128 only, but any head size is taken here), element
      * (b, h, i) at neg_delta[b * stride_b + h * stride_h + i], 16-byte aligned, strides multiples of 4; npm_mha_core_bwd then
      * does not read dctx and ctx for them.  Honoured by the eight-wave kernels (mha_bwd16_kernel, mha_bwd8_kernel) when
-     * seq_q % 4 == 0 (they fetch four row terms per load); otherwise -- and on the four-wave kernels (NPM_TUNE_ATTN_BWD16 = 0
-     * or an active npm_debug_attn_trace) -- it is ignored and the terms are recomputed from dctx and ctx: same results. */
+     * seq_q % 4 == 0 (they fetch four row terms per load); otherwise -- and on the four-wave kernel (NPM_TUNE_ATTN_BWD16 = 0
+     * or 1) -- it is ignored and the terms are recomputed from dctx and ctx: same results. */
     const float *neg_delta; int64_t neg_delta_stride_b, neg_delta_stride_h;
 } npm_mha_core;
 int npm_mha_core_supported(int head_dim);          /* 1 when npm_mha_core_fwd/bwd take this head dimension */
@@ -397,9 +397,12 @@ int npm_mha_mask_summary(const uint8_t *mask, int64_t stride_b, int64_t stride_h
  * K / V heads than query heads; "" before the first call.  Tests use it to assert that
  * a comparison exercised the kernel it names. */
 const char *npm_last_attn_kernel(void);
-/* Diagnostics: when buf != NULL every block of the backward kernel writes 16 words of s_memtime stamps of ONE of its
- * tiles (phase boundaries: tile start, after S, dP, dV, dK, the dS barrier, dQ, the dQ stores; word 8: next tile's start)
- * to buf[blockIdx * 16 ..]; NULL switches it off. */
+/* Diagnostics: when buf != NULL every block of the stamped kernel instances writes 16 words of s_memtime stamps of ONE of its
+ * tiles (backward phase boundaries: tile start, after S, dP, dV, dK, the dS barrier, dQ, the dQ stores; words 9 .. 13: the
+ * block's start and end) to buf[blockIdx * 16 ..]; NULL switches it off.  The stamped instances: mha_bwd16_kernel (a backward
+ * at head size 128 with saved scores and no tile summary runs it while buf is set, whatever NPM_TUNE_ATTN_BWD16 says) and
+ * the four-wave forward mha_fwd_kernel at head size 128 without a mask (such a forward runs it while buf is set, whatever
+ * NPM_TUNE_ATTN_FWD8 says).  Every other call runs its normal kernel and leaves buf alone. */
 int npm_debug_attn_trace(long long *buf);
 
 /* ---- incremental decoding: attention over a key / value cache (inference; the reference has none: "# TODO: support cache",

@@ -134,10 +134,6 @@ __device__ __forceinline__ void ldv(const float *p, float (&v)[4]) {
     else if (VEC == 2) { const float2 x = *reinterpret_cast<const float2 *>(p); v[0] = x.x; v[1] = x.y; }
     else v[0] = p[0];
 }
-// The saved scores (2.1 GB at C4 / C5) are read ONCE by the backward: nontemporal loads, so that they do not displace
-// the K / Q / dO tiles in L2 (backward 5.23 -> 5.19 ms).  The forward's stores keep the default policy: each lane
-// writes 16 bytes of a different row and L2 merges the four pieces of a line; nontemporal stores cost the forward 3 %.
-__device__ __forceinline__ float ld_stream(const float *p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ float xhalf(float x) { return __shfl_xor(x, 32, 64); }
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
@@ -162,21 +158,6 @@ using npm_tile::dma_group;
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
-// Instruction-order hints for one phase of `steps` steps, each `reads` LDS reads feeding `mfmas` MFMAs: the reads
-// of step i + 1 are issued before the MFMAs of step i (one step of prefetch), nothing is hoisted further.  Without
-// them hipcc clusters every LDS read of a fully unrolled phase in front of its first MFMA (hundreds of live
-// registers, spills).  Masks: 0x100 DS read, 0x008 MFMA.
-template <int STEPS, int READS, int MFMAS>
-__device__ __forceinline__ void sched_pipeline() {
-    __builtin_amdgcn_sched_group_barrier(0x100, READS, 0);
-#pragma unroll
-    for (int i = 0; i + 1 < STEPS; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x100, READS, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, MFMAS, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, MFMAS, 0);
-}
-#define PHASE_END() __builtin_amdgcn_sched_barrier(0)
 #define FENCE() __builtin_amdgcn_sched_barrier(0)
 // diagnostics: stamp `slot` of this block's trace record (wave 0, one chosen tile); costs nothing when trace == null
 #define STAMP(slot) do { if (tr) { FENCE(); tr[slot] = __builtin_amdgcn_s_memtime(); FENCE(); } } while (0)
@@ -810,7 +791,7 @@ mha_fwd8_kernel(const MhaArgs p) {
 // The row terms LSE (from the forward) and delta = rowsum(dO * O) (mha_delta_kernel, 8 B/element of [B,S,H,D]) are
 // read one tile ahead, one value per lane, and turned from "query on the lane" into "query in the registers" through LDS.
 // ---------------------------------------------------------------------------------------------------------------
-template <int D, bool MASK, bool SAVED, bool TRACE>
+template <int D, bool MASK, bool SAVED>
 __global__ void __launch_bounds__(256, 1)
 mha_bwd_kernel(const MhaArgs p) {
     using T = Tile<D>;
@@ -826,8 +807,6 @@ mha_bwd_kernel(const MhaArgs p) {
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    long long *const blk_tr = (TRACE && p.trace && tid == 0) ? p.trace + (long)blockIdx.x * 16 : nullptr;   // block-level stamps 9..13
-    if (blk_tr) blk_tr[9] = __builtin_amdgcn_s_memtime();
     const int l32 = lane & 31, half = lane >> 5;
     const int dcol = D < 32 ? (l32 & (D - 1)) : l32;
     const int bh = blockIdx.x;
@@ -928,7 +907,6 @@ mha_bwd_kernel(const MhaArgs p) {
     float dlt_n = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrcDl, l32 * 4, 0, 0));
     if (half == 0) { xs[l32] = lse_n * LOG2E; xs[32 + l32] = dlt_n; }
 
-    if (blk_tr) blk_tr[10] = __builtin_amdgcn_s_memtime();
     for (int kb = 0; kb < nkb; ++kb) {
         const int kvrow = kb * 128 + kvl;
         const bool kvok = kvrow < p.seq_kv;
@@ -950,9 +928,6 @@ mha_bwd_kernel(const MhaArgs p) {
             asm volatile("" ::: "memory");
             const bool seam = qt + 1 == nqt && kb + 1 < nkb;      // last tile of a key block that has a successor
             const int nq = qt + 1 < nqt ? qt + 1 : 0;             // the next tile to prefetch: wraps to the next block's tile 0
-            long long *tr = (TRACE && p.trace && tid == 0 && kb == (nkb > 1 ? 1 : 0) && qt == (nqt > 5 ? 5 : 0)) ? p.trace + (long)blockIdx.x * 16 : nullptr;
-            if (TRACE && p.trace && tid == 0 && kb == (nkb > 1 ? 1 : 0) && qt == (nqt > 5 ? 6 : 1)) { FENCE(); p.trace[(long)blockIdx.x * 16 + 8] = __builtin_amdgcn_s_memtime(); FENCE(); }
-            STAMP(0);
             const int cur = it & 1, nxt = cur ^ 1;
             const float *tQ = sQ + cur * QTILE, *tDO = sDO + cur * QTILE;
             const int q0 = 32 * qt;
@@ -1015,7 +990,6 @@ mha_bwd_kernel(const MhaArgs p) {
                     FENCE();
                 }
             }
-            STAMP(1);
             // ---- dP[q, kv] = dO V^T (V fragment in registers); the old dQ values are fetched along the way
             constexpr int F0 = SAVED ? 0 : (NG & 1);   // parity slot that holds dO fragment 0
             zero16(dP);
@@ -1054,7 +1028,6 @@ mha_bwd_kernel(const MhaArgs p) {
                 dS[r] = pr * (dP[r] - Dr[r]);                 // dP and delta carry the 1 / sqrt(Dk) already
                 sDS[ebs[(r >> 2) & 1][r & 3] + 8 * (r >> 2) * 128] = dS[r];
             }
-            STAMP(2);
             // ---- dV^T[d, kv] += dO^T[d, q] P[q, kv]: 16 steps (one query row each) of (1 vector read, DT MFMAs);
             //      tile t row `lane` is head dimension VEC lane + t
 #pragma unroll
@@ -1065,11 +1038,9 @@ mha_bwd_kernel(const MhaArgs p) {
                 for (int t = 0; t < DT; ++t) dV[t] = MFMA(ea[r & 1][t], P[r], dV[t]);
                 FENCE();
             }
-            STAMP(3);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                                      // dS of all four key groups is in LDS
             asm volatile("" ::: "memory");
-            STAMP(4);
 
             // ---- dQ[q, d] (+)= dS[q, kv] K[kv, d] over the 128 keys of the block; wave w takes the columns 32 w .. 32 w + 31
             if (dq_wave) {
@@ -1103,7 +1074,6 @@ mha_bwd_kernel(const MhaArgs p) {
                 issue_half(nq, nxt, 1);
                 ldv<VEC>(tQ + vb[0][0], ea[0]);
             }
-            STAMP(5);
             if (seam) {                                // every wave is done with this K block: request the next one
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
@@ -1129,11 +1099,8 @@ mha_bwd_kernel(const MhaArgs p) {
             if (half == 0) { xs[l32] = lse_n * LOG2E; xs[32 + l32] = dlt_n; }
             in_flight = 4;
             ++it;
-            STAMP(6);
-            STAMP(7);
             FENCE();
         }
-        if (blk_tr && kb == 0) blk_tr[11] = __builtin_amdgcn_s_memtime();
         if (SEAM_STORES == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         // this block's dK and dV rows: lane = key; register r of the DT tiles together is VEC adjacent head dimensions
 #pragma unroll
@@ -1154,11 +1121,6 @@ mha_bwd_kernel(const MhaArgs p) {
                 }
             }
         }
-    }
-    if (blk_tr) {
-        blk_tr[12] = __builtin_amdgcn_s_memtime();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        blk_tr[13] = __builtin_amdgcn_s_memtime();
     }
 }
 
@@ -1198,7 +1160,7 @@ mha_bwd16_kernel(const MhaArgs p) {
     const int l16 = lane & 15, kk = lane >> 4;
     const int bh = blockIdx.x;
     const int b = bh / p.heads, h = bh - b * p.heads;
-    // diagnostics (npm_debug_attn_trace, tools/attn_trace.py --bwd16): s_memtime stamps of thread 0 at the phase boundaries of one
+    // diagnostics (npm_debug_attn_trace, tools/attn_trace.py): s_memtime stamps of thread 0 at the phase boundaries of one
     // tile (key block 1, query tile 5) and at the block's start / end
     long long *const blk_tr = (TRACE && p.trace && tid == 0) ? p.trace + (long)blockIdx.x * 16 : nullptr;
     if (blk_tr) blk_tr[9] = __builtin_amdgcn_s_memtime();
@@ -1308,7 +1270,7 @@ mha_bwd16_kernel(const MhaArgs p) {
 #pragma unroll
             for (int t = 0; t < 2; ++t) { Lr[t] = Lr_n[t]; Dr[t] = Dr_n[t]; }
             load_rows(32 * nq);
-            // raw scores of this tile (nontemporal: read once) and the old dQ values (the dQ accumulators start from them)
+            // raw scores of this tile (nontemporal: read once, they must not displace the K / Q / dO tiles in L2) and the old dQ values (the dQ accumulators start from them)
             // (requesting the scores a whole tile ahead, like the row terms, was measured in round 4: 4.56 -> 4.58-4.62 ms --
             //  their trip from HBM is covered by the dP product)
             f32x4 S[2], acc[2];
@@ -2237,8 +2199,9 @@ mha_mask_nokey_rows_kernel(const unsigned char *__restrict__ mask, long sb, long
         for (int i = threadIdx.x; i < tiles_per_plane; i += 256) out[plane * tiles_per_plane + i] = 0xFF;
 }
 
-// The s_memtime stamps of npm_debug_attn_trace live in instances of their own (D = 128, no mask): the product
-// instances carry no trace code at all (each stamp is an exec-masked branch in a loop where every instruction counts).
+// The s_memtime stamps of npm_debug_attn_trace live in instances of their own (mha_fwd_kernel at D = 128 without a mask, and
+// mha_bwd16_kernel<true>): the product instances carry no trace code at all (each stamp is an exec-masked branch in a loop
+// where every instruction counts).
 template <int D, bool MASK, bool SAVE>
 void launch_fwd_instance(const MhaArgs &a, int grid, hipStream_t s) {
     if (D == 128 && !MASK && a.trace) hipLaunchKernelGGL((mha_fwd_kernel<D, MASK, SAVE, D == 128 && !MASK>), dim3(grid), dim3(256), 0, s, a);
@@ -2249,7 +2212,8 @@ template <int D>
 int launch_fwd(const MhaArgs &a, hipStream_t s) {
     const int grid = a.batch * a.heads * (a.q_pair ? (a.q_tiles + 1) / 2 : a.q_tiles);
     const bool mask = a.mask != nullptr, save = a.scores != nullptr;
-    if ((g_attn_fwd8 == 2 || (g_attn_fwd8 == 1 && D < 128)) && !a.trace) {
+    const bool stamped = a.trace && D == 128 && !mask;      // the one forward instance that stamps: a trace reroutes nothing else
+    if ((g_attn_fwd8 == 2 || (g_attn_fwd8 == 1 && D < 128)) && !stamped) {
         if (mask && save) hipLaunchKernelGGL((mha_fwd8_kernel<D, true, true>), dim3(grid), dim3(512), 0, s, a);
         else if (mask) hipLaunchKernelGGL((mha_fwd8_kernel<D, true, false>), dim3(grid), dim3(512), 0, s, a);
         else if (save) hipLaunchKernelGGL((mha_fwd8_kernel<D, false, true>), dim3(grid), dim3(512), 0, s, a);
@@ -2265,12 +2229,6 @@ int launch_fwd(const MhaArgs &a, hipStream_t s) {
     note_kernel("mha_fwd_kernel", D, mask, save);
     NPM_CHECK_LAUNCH();
     return NPM_OK;
-}
-
-template <int D, bool MASK, bool SAVED>
-void launch_bwd_instance(const MhaArgs &a, int grid, hipStream_t s) {
-    if (D == 128 && !MASK && a.trace) hipLaunchKernelGGL((mha_bwd_kernel<D, MASK, SAVED, D == 128 && !MASK>), dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((mha_bwd_kernel<D, MASK, SAVED, false>), dim3(grid), dim3(256), 0, s, a);
 }
 
 template <int D>
@@ -2293,9 +2251,9 @@ int launch_bwd(const MhaArgs &a, hipStream_t s) {
     // there): the backward needs the mask bytes only when it recomputes q.k.  One instance less per head size -- the
     // one whose 16 extra byte loads per tile did not fit the register file at D = 128.
     // (mha_bwd16_kernel and mha_bwd8_kernel are launched by npm_mha_core_bwd itself: they take the padded row terms)
-    if (saved) launch_bwd_instance<D, false, true>(a, grid, s);
-    else if (mask) launch_bwd_instance<D, true, false>(a, grid, s);
-    else launch_bwd_instance<D, false, false>(a, grid, s);
+    if (saved) hipLaunchKernelGGL((mha_bwd_kernel<D, false, true>), dim3(grid), dim3(256), 0, s, a);
+    else if (mask) hipLaunchKernelGGL((mha_bwd_kernel<D, true, false>), dim3(grid), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((mha_bwd_kernel<D, false, false>), dim3(grid), dim3(256), 0, s, a);
     note_kernel("mha_bwd_kernel", D, mask && !saved, saved);
     NPM_CHECK_LAUNCH();
     return NPM_OK;
@@ -2329,9 +2287,7 @@ int fill_args(const npm_mha_core *c, bool backward, int kv_heads, MhaArgs &a) {
     a.scores = c->scores;
     // tile summary: the kernels keep one bit per tile in a 64-bit scalar, so sequences beyond 2048 just do not skip
     // (and the older backward kernels know nothing of it: with them selected the forward must write every score)
-    // (nor do the diagnostic instances of npm_debug_attn_trace: with a trace buffer set the backward falls through to the 4-wave
-    //  kernel, which reads every saved score -- the forward must then have written every one)
-    if (c->mask && c->tile_summary && c->seq_q <= 2048 && c->seq_kv <= 2048 && g_attn_bwd16 >= 2 && !g_attn_trace) {
+    if (c->mask && c->tile_summary && c->seq_q <= 2048 && c->seq_kv <= 2048 && g_attn_bwd16 >= 2) {
         NPM_ARG(c->summary_stride_b >= 0 && c->summary_stride_h >= 0);
         a.skip = c->tile_summary;
         a.skip_sb = c->summary_stride_b;
@@ -2426,8 +2382,10 @@ int run_bwd(MhaArgs &a, const npm_mha_core *c, hipStream_t s) {
     int rc;
     npm::Scratch ws;                                  // stream-ordered pool: safe to release when this call returns
     const bool wide128 = c->head_dim == 128 && a.scores != nullptr && a.skip == nullptr;      // the case mha_bwd16_kernel was built for
-    const bool use8 = (g_attn_bwd16 == 3 || (g_attn_bwd16 == 2 && !wide128)) && !a.trace;
-    const bool use16 = !use8 && wide128 && (g_attn_bwd16 == 1 || g_attn_bwd16 == 2) && (!a.trace || g_attn_bwd16 == 1);   // traced: knob 1
+    // mha_bwd16_kernel<true> is the only stamped backward instance: with a trace buffer set the call it was built for runs it
+    // whatever the knob says; every other backward runs its normal kernel and leaves the buffer alone
+    const bool use16 = wide128 && (g_attn_bwd16 == 1 || g_attn_bwd16 == 2 || a.trace);
+    const bool use8 = !use16 && g_attn_bwd16 >= 2;
     if (use8 || use16) {
         // mha_bwd8_kernel: row terms padded to whole query tiles ([B, H, sq_pad] each: delta, then log2(e) LSE)
         a.sq_pad = (a.seq_q + 31) / 32 * 32;

@@ -462,6 +462,47 @@ def test_core_rejects_unsupported_head_dim(npm):
     assert b'head_dim' in _C.lib().npm_last_error()
 
 
+def test_core_trace_stamps_only_the_wide_backward(npm, bwd_kernel, fwd_kernel):
+    """npm_debug_attn_trace: the stamped instances are mha_fwd_kernel at head size 128 without a mask and mha_bwd16_kernel<true>.
+    With a buffer set, the calls they can take run them whatever the knobs say; any other call runs its normal kernel and
+    leaves the buffer alone.  One block and one key tile here, 16 eight-byte words: the forward writes words 0 .. 3 and 9 .. 13 (word 4 is the
+    start of a second key tile), the backward 0 .. 7 and 9 .. 13, so words 4 .. 7 are the backward's alone."""
+    from np_modeling_amd import _C, device as D
+    lib = _C.lib()
+    rng = np.random.default_rng(15)
+    fwd_name = 'mha_fwd8_kernel' if fwd_kernel == 2 else 'mha_fwd_kernel'
+    untouched = np.full([32], 777.0, dtype=np.float32).view(np.int64)
+
+    def traced(*args, **kw):
+        buf = D.full([32], 777.0)
+        _C.check(lib.npm_debug_attn_trace(buf.ptr), 'npm_debug_attn_trace')
+        try:
+            got = _run_core(npm, *args, **kw)
+        finally:
+            _C.check(lib.npm_debug_attn_trace(None), 'npm_debug_attn_trace')
+        return got, _C.last_attn_kernel(), buf.numpy().view(np.int64)
+
+    q, k, v, dctx = (rng.standard_normal([1, 32, 1, 16]).astype(np.float32) for _ in range(4))
+    _, last, words = traced(q, k, v, 0.25)                                       # forward alone, small head
+    assert last.startswith(fwd_name + ' D=16')
+    np.testing.assert_array_equal(words, untouched)
+    _, last, words = traced(q, k, v, 0.25, dctx=dctx)
+    assert last.startswith(('mha_bwd8_kernel' if bwd_kernel >= 2 else 'mha_bwd_kernel') + ' D=16')
+    np.testing.assert_array_equal(words, untouched)
+    q, k, v, dctx = (rng.standard_normal([1, 32, 1, 128]).astype(np.float32) for _ in range(4))
+    causal = np.tril(np.ones([32, 32], dtype=bool))[None, None]
+    _, last, words = traced(q, k, v, 0.09, mask=causal, save=True)               # head size 128 with a mask and its summary
+    assert last.startswith(fwd_name + ' D=128 mask=1')
+    np.testing.assert_array_equal(words, untouched)
+    _, last, words = traced(q, k, v, 0.09, save=True)                            # the stamped forward
+    assert last.startswith('mha_fwd_kernel D=128 mask=0')
+    assert (words[:4] != untouched[:4]).all() and (words[4:8] == untouched[4:8]).all()
+    got, last, words = traced(q, k, v, 0.09, dctx=dctx, save=True)               # ... and the stamped backward behind it
+    assert last.startswith('mha_bwd16_kernel D=128')
+    assert (words[:8] != untouched[:8]).all() and (np.diff(words[:8]) >= 0).all() and words[7] > words[0]
+    assert all(np.isfinite(got[name]).all() for name in ('dq', 'dk', 'dv'))
+
+
 def test_core_is_deterministic(npm):
     """dQ is summed over key blocks by one wave in program order: two runs give the same bits."""
     rng = np.random.default_rng(9)
