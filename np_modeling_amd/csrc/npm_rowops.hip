@@ -6,8 +6,10 @@
 // the write, so the HBM traffic is the algorithmic minimum (DESIGN.md "Row kernels").
 // Reductions across the 64-lane wavefront use DPP/shuffle butterflies, not LDS.
 #include <algorithm>
+#include <type_traits>
 
 #include "npm_internal.h"
+#include "npm_row_plan.h"
 
 namespace {
 
@@ -25,7 +27,7 @@ constexpr int COLSUM_BLOCKS_PER_CU = 8;     // whole-line column sums: grid = th
 // do not displace what the GEMMs around them keep in L2 and the Infinity Cache, and from cold caches the kernels
 // themselves run faster (LayerNorm backward 131072 x 1024: 0.439 -> 0.381 ms, profiles/r02_stream_nt.log).  Small
 // tensors (parameters, partial sums) keep the default policy.
-inline bool stream_nt(size_t bytes) { return g_stream_nt && bytes >= ((size_t)32 << 20); }
+inline bool stream_nt(size_t bytes) { return g_stream_nt && bytes >= npm::STREAM_NT_BYTES; }
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 template <bool NT>
@@ -45,7 +47,7 @@ __device__ __forceinline__ void stg4(float *p, const float4 &v) {
 #define NPM_NT_LAUNCH(nt, LAUNCH) do { if (nt) { constexpr bool NT = true; LAUNCH; } else { constexpr bool NT = false; LAUNCH; } } while (0)
 
 constexpr int WAVE = 64;
-constexpr int ROWS_PER_BLOCK = 4;          // 256 threads = 4 waves, one row per wave
+using npm::ROWS_PER_BLOCK;
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -946,6 +948,76 @@ embedding_bwd_kernel(const float *__restrict__ dy, long dy_pitch, const int *__r
     dw[(long)tokens[s] * dw_pitch + c] = acc;
 }
 
+// ---------------------------------------------------------------------------------
+// host side of the row-in-registers kernels: npm_row_plan.h decides width, hint and grid, these launch what it names
+// ---------------------------------------------------------------------------------
+using npm::RowHint;
+using npm::RowKind;
+using npm::RowPlan;
+
+RowPlan plan_for(RowKind kind, int64_t rows, int64_t d, bool aligned) {
+    return npm::row_plan(kind, rows, d, aligned, g_ln_nt_split, g_stream_nt != 0, g_ln_bwd_blocks_per_cu, npm::ctx().num_cus);
+}
+#define NPM_PLAN_FITS(p)                                                                                                \
+    do {                                                                                                                \
+        if (!(p).fits) return npm::fail(NPM_E_BAD_ARGUMENT, "%s: bad argument: %s", __func__, "(rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK < (1L << 31)"); \
+    } while (0)
+
+// launch(VPL, hint on the loads, hint on the stores), each an integral constant, for the ONE instance a fast plan names.  Only these
+// exist in the code object: PLAIN and BOTH at every width, LOADS and -- where STORES_SPLIT (not the dropout forms) -- STORES at VPL 4.
+template <int VPL, bool STORES_SPLIT, typename L>
+void row_launch_width(RowHint hint, L &launch) {
+    constexpr std::integral_constant<int, VPL> vpl{};
+    constexpr std::true_type on{};
+    constexpr std::false_type off{};
+    if constexpr (VPL == 4) {
+        if (hint == RowHint::LOADS) return launch(vpl, on, off);
+        if constexpr (STORES_SPLIT)
+            if (hint == RowHint::STORES) return launch(vpl, off, on);
+    }
+    if (hint == RowHint::PLAIN) launch(vpl, off, off);
+    else launch(vpl, on, on);
+}
+template <bool STORES_SPLIT = true, typename L>
+void row_launch(const RowPlan &p, L launch) {
+    switch (p.vpl) {
+    case 1: return row_launch_width<1, STORES_SPLIT>(p.hint, launch);
+    case 2: return row_launch_width<2, STORES_SPLIT>(p.hint, launch);
+    case 4: return row_launch_width<4, STORES_SPLIT>(p.hint, launch);
+    case 8: return row_launch_width<8, STORES_SPLIT>(p.hint, launch);
+    default: return row_launch_width<16, STORES_SPLIT>(p.hint, launch);
+    }
+}
+
+// The fast backwards: launch(VPL, hints, partials) leaves [grid][k d] block partials (k = 2 LayerNorm: dgamma | dbeta; k = 1 RMSNorm,
+// dbeta null), summed over the blocks in a fixed order.
+template <bool STORES_SPLIT = true, typename L>
+int row_bwd_fast(const RowPlan &p, int64_t d, float *dgamma, float *dbeta, L launch) {
+    const int k = dbeta ? 2 : 1;
+    npm::Scratch part;
+    int rc = part.alloc(sizeof(float) * k * (size_t)p.grid * d);
+    if (rc) return rc;
+    float *pp = (float *)part.ptr;
+    row_launch<STORES_SPLIT>(p, [&](auto vpl, auto nt, auto nts) { launch(vpl, nt, nts, pp); });
+    NPM_CHECK_LAUNCH();
+    if (k == 1 || dbeta == dgamma + d) return colsum_impl(pp, dgamma, p.grid, k * d, k * d);   // adjacent outputs (the gradient bucket): one pass
+    rc = colsum_impl(pp, dgamma, p.grid, d, 2 * d);
+    if (rc) return rc;
+    return colsum_impl(pp + d, dbeta, p.grid, d, 2 * d);
+}
+
+// The generic backwards: launch(tmp) writes dx and the rows x d products whose column sum is dgamma; dbeta (LayerNorm) is dz's.
+template <typename L>
+int row_bwd_generic(int64_t rows, int64_t d, const float *dz, float *dgamma, float *dbeta, L launch) {
+    npm::Scratch tmp;
+    int rc = tmp.alloc(sizeof(float) * (size_t)rows * d);
+    if (rc) return rc;
+    launch((float *)tmp.ptr);
+    NPM_CHECK_LAUNCH();
+    rc = colsum_impl((const float *)tmp.ptr, dgamma, rows, d, d);
+    return rc || !dbeta ? rc : colsum_impl(dz, dbeta, rows, d, d);
+}
+
 }  // namespace
 
 namespace npm {
@@ -1063,22 +1135,6 @@ int npm_relu_bwd_colsum(const float *x_pre, const float *dy, float *dx, float *c
     return colsum_run<true>(x_pre, colsum, rows, cols, cols, dy, dx);
 }
 
-#define NPM_ROW_DISPATCH_NT(KERNEL, NT, n, ...)                                                          \
-    do {                                                                                                 \
-        if (n <= 256) hipLaunchKernelGGL((KERNEL<1, NT>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);       \
-        else if (n <= 512) hipLaunchKernelGGL((KERNEL<2, NT>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);  \
-        else if (n <= 1024) hipLaunchKernelGGL((KERNEL<4, NT>), dim3(grid), dim3(256), 0, s, __VA_ARGS__); \
-        else if (n <= 2048) hipLaunchKernelGGL((KERNEL<8, NT>), dim3(grid), dim3(256), 0, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<16, NT>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);               \
-    } while (0)
-// one wave per row; rows x n floats stream through once: nontemporal when that is far more than the caches hold
-#define NPM_ROW_DISPATCH(KERNEL, n, ...)                                                       \
-    do {                                                                                       \
-        const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);                  \
-        if (stream_nt(sizeof(float) * (size_t)rows * (size_t)(n))) NPM_ROW_DISPATCH_NT(KERNEL, true, n, __VA_ARGS__); \
-        else NPM_ROW_DISPATCH_NT(KERNEL, false, n, __VA_ARGS__);                               \
-    } while (0)
-
 int npm_attn_rowdot(const float *a, const float *b, float *out, int64_t batch, int64_t seq, int64_t heads, int64_t dim) {
     NPM_REQUIRE_INIT();
     NPM_ARG(batch >= 0 && seq >= 0 && heads >= 1 && dim >= 1);
@@ -1099,15 +1155,13 @@ int npm_softmax_fwd(const float *x, float *y, int64_t rows, int64_t n, float sca
     NPM_ARG(rows >= 0 && n >= 0);
     if (rows == 0 || n == 0) return NPM_OK;
     NPM_ARG(x != nullptr && y != nullptr);
-    NPM_ARG((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK < (1L << 31));
+    const RowPlan p = plan_for(RowKind::SOFTMAX, rows, n, aligned16(x) && aligned16(y));
+    NPM_PLAN_FITS(p);
     hipStream_t s = npm::ctx().stream;
-    const bool fast = n % 4 == 0 && n <= 4096 && aligned16(x) && aligned16(y);
-    if (fast) {
-        NPM_ROW_DISPATCH(softmax_fwd_kernel, n, x, y, (long)rows, (int)n, scale);
-    } else {
-        const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-        hipLaunchKernelGGL(softmax_fwd_generic, dim3(grid), dim3(256), 0, s, x, y, (long)rows, (long)n, scale);
-    }
+    if (p.vpl == 0) hipLaunchKernelGGL(softmax_fwd_generic, dim3(p.grid), dim3(256), 0, s, x, y, (long)rows, (long)n, scale);
+    else row_launch(p, [&](auto vpl, auto nt, auto) {
+        hipLaunchKernelGGL((softmax_fwd_kernel<vpl(), nt()>), dim3(p.grid), dim3(256), 0, s, x, y, (long)rows, (int)n, scale);
+    });
     NPM_CHECK_LAUNCH();
     return NPM_OK;
 }
@@ -1117,31 +1171,19 @@ int npm_softmax_bwd(const float *y, const float *dy, float *dx, int64_t rows, in
     NPM_ARG(rows >= 0 && n >= 0);
     if (rows == 0 || n == 0) return NPM_OK;
     NPM_ARG(y != nullptr && dy != nullptr && dx != nullptr);
-    NPM_ARG((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK < (1L << 31));
+    const RowPlan p = plan_for(RowKind::SOFTMAX, rows, n, aligned16(y) && aligned16(dy) && aligned16(dx));
+    NPM_PLAN_FITS(p);
     hipStream_t s = npm::ctx().stream;
-    const bool fast = n % 4 == 0 && n <= 4096 && aligned16(y) && aligned16(dy) && aligned16(dx);
-    if (fast) {
-        NPM_ROW_DISPATCH(softmax_bwd_kernel, n, y, dy, dx, (long)rows, (int)n, scale);
-    } else {
-        const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-        hipLaunchKernelGGL(softmax_bwd_generic, dim3(grid), dim3(256), 0, s, y, dy, dx, (long)rows, (long)n, scale);
-    }
+    if (p.vpl == 0) hipLaunchKernelGGL(softmax_bwd_generic, dim3(p.grid), dim3(256), 0, s, y, dy, dx, (long)rows, (long)n, scale);
+    else row_launch(p, [&](auto vpl, auto nt, auto) {
+        hipLaunchKernelGGL((softmax_bwd_kernel<vpl(), nt()>), dim3(p.grid), dim3(256), 0, s, y, dy, dx, (long)rows, (int)n, scale);
+    });
     NPM_CHECK_LAUNCH();
     return NPM_OK;
 }
 
-#define NPM_ROW_DISPATCH_DROP(KERNEL, NT, n, ...)                                                                    \
-    do {                                                                                                            \
-        if (n <= 256) hipLaunchKernelGGL((KERNEL<1, NT, NT, true>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);       \
-        else if (n <= 512) hipLaunchKernelGGL((KERNEL<2, NT, NT, true>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);  \
-        else if (n <= 1024) hipLaunchKernelGGL((KERNEL<4, NT, NT, true>), dim3(grid), dim3(256), 0, s, __VA_ARGS__); \
-        else if (n <= 2048) hipLaunchKernelGGL((KERNEL<8, NT, NT, true>), dim3(grid), dim3(256), 0, s, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<16, NT, NT, true>), dim3(grid), dim3(256), 0, s, __VA_ARGS__);               \
-    } while (0)
-
-// The row-in-registers kernels with a dropout mask in front (npm_layernorm_dropout_fwd / _bwd): same hint placement as the
-// plain kernels at d in (512, 1024] (NPM_TUNE_LN_NT_SPLIT mode 1: loads only), the default elsewhere.
-static bool ln_dropout_ok(int64_t d, const void *mask) { return d % 4 == 0 && d <= 4096 && ((uintptr_t)mask & 3) == 0; }
+// The row-in-registers kernels with a dropout mask in front (npm_layernorm_dropout_fwd / _bwd): no generic kernel behind them.
+static bool aligned4(const void *p) { return ((uintptr_t)p & 3) == 0; }
 
 int npm_layernorm_dropout_fwd(const float *x, const unsigned char *mask, float keep_prob, const float *gamma, const float *beta,
                               float eps, int64_t rows, int64_t d, float *z, float *mean, float *rstd) {
@@ -1149,16 +1191,14 @@ int npm_layernorm_dropout_fwd(const float *x, const unsigned char *mask, float k
     NPM_ARG(rows >= 0 && d >= 1 && keep_prob > 0.f);
     if (rows == 0) return NPM_OK;
     NPM_ARG(x && mask && gamma && beta && z && mean && rstd);
-    NPM_ARG((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK < (1L << 31));
-    if (!(ln_dropout_ok(d, mask) && aligned16(x) && aligned16(z) && aligned16(gamma) && aligned16(beta)))
+    const RowPlan p = plan_for(RowKind::DROPOUT_FWD, rows, d, aligned4(mask) && aligned16(x) && aligned16(z) && aligned16(gamma) && aligned16(beta));
+    NPM_PLAN_FITS(p);
+    if (p.vpl == 0)
         return npm::fail(NPM_E_UNSUPPORTED, "npm_layernorm_dropout_fwd: d %% 4 == 0, d <= 4096 and 16-byte aligned rows (npm_mask_scale + npm_layernorm_fwd otherwise)");
     hipStream_t s = npm::ctx().stream;
-    const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-    const bool nt = stream_nt(sizeof(float) * (size_t)rows * (size_t)d);
-    if (nt && (g_ln_nt_split >> 2) == 1 && d > 512 && d <= 1024)
-        hipLaunchKernelGGL((layernorm_fwd_kernel<4, true, false, true>), dim3(grid), dim3(256), 0, s, x, gamma, beta, eps, (long)rows, (int)d, z, mean, rstd, mask, keep_prob);
-    else if (nt) NPM_ROW_DISPATCH_DROP(layernorm_fwd_kernel, true, d, x, gamma, beta, eps, (long)rows, (int)d, z, mean, rstd, mask, keep_prob);
-    else NPM_ROW_DISPATCH_DROP(layernorm_fwd_kernel, false, d, x, gamma, beta, eps, (long)rows, (int)d, z, mean, rstd, mask, keep_prob);
+    row_launch<false>(p, [&](auto vpl, auto nt, auto nts) {
+        hipLaunchKernelGGL((layernorm_fwd_kernel<vpl(), nt(), nts(), true>), dim3(p.grid), dim3(256), 0, s, x, gamma, beta, eps, (long)rows, (int)d, z, mean, rstd, mask, keep_prob);
+    });
     NPM_CHECK_LAUNCH();
     return NPM_OK;
 }
@@ -1174,25 +1214,13 @@ int npm_layernorm_dropout_bwd(const float *dz, const float *x, const unsigned ch
         return rc ? rc : npm_fill_f32(dbeta, 0.f, (size_t)d);
     }
     NPM_ARG(dz && x && mask && mean && rstd && gamma && dx);
-    if (!(ln_dropout_ok(d, mask) && aligned16(dz) && aligned16(x) && aligned16(dx) && aligned16(gamma) && (residual == nullptr || aligned16(residual))))
-        return npm::fail(NPM_E_UNSUPPORTED, "npm_layernorm_dropout_bwd: d %% 4 == 0, d <= 4096 and 16-byte aligned rows");
+    const RowPlan p = plan_for(RowKind::DROPOUT_BWD, rows, d, aligned4(mask) && aligned16(dz) && aligned16(x) && aligned16(dx) &&
+                                                                  aligned16(gamma) && (residual == nullptr || aligned16(residual)));
+    if (p.vpl == 0) return npm::fail(NPM_E_UNSUPPORTED, "npm_layernorm_dropout_bwd: d %% 4 == 0, d <= 4096 and 16-byte aligned rows");
     hipStream_t s = npm::ctx().stream;
-    const bool nt = stream_nt(sizeof(float) * (size_t)rows * (size_t)d);
-    const long row_blocks = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-    const int grid = (int)std::min<long>(row_blocks, (long)g_ln_bwd_blocks_per_cu * npm::ctx().num_cus);
-    npm::Scratch part;
-    int rc = part.alloc(sizeof(float) * 2 * (size_t)grid * d);
-    if (rc) return rc;
-    float *pp = (float *)part.ptr;
-    if (nt && (g_ln_nt_split & 3) == 1 && d > 512 && d <= 1024)
-        hipLaunchKernelGGL((layernorm_bwd_kernel<4, true, false, true>), dim3(grid), dim3(256), 0, s, dz, x, mean, rstd, gamma, residual, (long)rows, (int)d, dx, pp, mask, keep_prob);
-    else if (nt) NPM_ROW_DISPATCH_DROP(layernorm_bwd_kernel, true, d, dz, x, mean, rstd, gamma, residual, (long)rows, (int)d, dx, pp, mask, keep_prob);
-    else NPM_ROW_DISPATCH_DROP(layernorm_bwd_kernel, false, d, dz, x, mean, rstd, gamma, residual, (long)rows, (int)d, dx, pp, mask, keep_prob);
-    NPM_CHECK_LAUNCH();
-    if (dbeta == dgamma + d) return colsum_impl(pp, dgamma, grid, 2 * d, 2 * d);
-    rc = colsum_impl(pp, dgamma, grid, d, 2 * d);
-    if (rc) return rc;
-    return colsum_impl(pp + d, dbeta, grid, d, 2 * d);
+    return row_bwd_fast<false>(p, d, dgamma, dbeta, [&](auto vpl, auto nt, auto nts, float *pp) {
+        hipLaunchKernelGGL((layernorm_bwd_kernel<vpl(), nt(), nts(), true>), dim3(p.grid), dim3(256), 0, s, dz, x, mean, rstd, gamma, residual, (long)rows, (int)d, dx, pp, mask, keep_prob);
+    });
 }
 
 int npm_layernorm_fwd(const float *x, const float *gamma, const float *beta, float eps,
@@ -1201,20 +1229,13 @@ int npm_layernorm_fwd(const float *x, const float *gamma, const float *beta, flo
     NPM_ARG(rows >= 0 && d >= 1);
     if (rows == 0) return NPM_OK;
     NPM_ARG(x && gamma && beta && z && mean && rstd);
-    NPM_ARG((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK < (1L << 31));
+    const RowPlan p = plan_for(RowKind::NORM_FWD, rows, d, aligned16(x) && aligned16(z) && aligned16(gamma) && aligned16(beta));
+    NPM_PLAN_FITS(p);
     hipStream_t s = npm::ctx().stream;
-    const bool fast = d % 4 == 0 && d <= 4096 && aligned16(x) && aligned16(z) && aligned16(gamma) && aligned16(beta);
-    const int fwd_mode = g_ln_nt_split >> 2;
-    if (fast && fwd_mode && d > 512 && d <= 1024 && stream_nt(sizeof(float) * (size_t)rows * (size_t)d)) {
-        const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-        if (fwd_mode == 1) hipLaunchKernelGGL((layernorm_fwd_kernel<4, true, false>), dim3(grid), dim3(256), 0, s, x, gamma, beta, eps, (long)rows, (int)d, z, mean, rstd);
-        else hipLaunchKernelGGL((layernorm_fwd_kernel<4, false, true>), dim3(grid), dim3(256), 0, s, x, gamma, beta, eps, (long)rows, (int)d, z, mean, rstd);
-    } else if (fast) {
-        NPM_ROW_DISPATCH(layernorm_fwd_kernel, d, x, gamma, beta, eps, (long)rows, (int)d, z, mean, rstd);
-    } else {
-        const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-        hipLaunchKernelGGL(layernorm_fwd_generic, dim3(grid), dim3(256), 0, s, x, gamma, beta, eps, (long)rows, (long)d, z, mean, rstd);
-    }
+    if (p.vpl == 0) hipLaunchKernelGGL(layernorm_fwd_generic, dim3(p.grid), dim3(256), 0, s, x, gamma, beta, eps, (long)rows, (long)d, z, mean, rstd);
+    else row_launch(p, [&](auto vpl, auto nt, auto nts) {
+        hipLaunchKernelGGL((layernorm_fwd_kernel<vpl(), nt(), nts()>), dim3(p.grid), dim3(256), 0, s, x, gamma, beta, eps, (long)rows, (int)d, z, mean, rstd);
+    });
     NPM_CHECK_LAUNCH();
     return NPM_OK;
 }
@@ -1230,64 +1251,31 @@ int npm_layernorm_bwd(const float *dz, const float *x, const float *mean, const 
         return rc ? rc : npm_fill_f32(dbeta, 0.f, (size_t)d);
     }
     NPM_ARG(dz && x && mean && rstd && gamma && dx);
+    const RowPlan p = plan_for(RowKind::NORM_BWD, rows, d, aligned16(dz) && aligned16(x) && aligned16(dx) && aligned16(gamma) &&
+                                                               (residual == nullptr || aligned16(residual)));
+    NPM_PLAN_FITS(p);
     hipStream_t s = npm::ctx().stream;
-    const bool fast = d % 4 == 0 && d <= 4096 && aligned16(dz) && aligned16(x) && aligned16(dx) &&
-                      aligned16(gamma) && (residual == nullptr || aligned16(residual));
-    if (fast) {
-        const bool nt_rows = stream_nt(sizeof(float) * (size_t)rows * (size_t)d);
-        const long row_blocks = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-        const int grid = (int)std::min<long>(row_blocks, (long)g_ln_bwd_blocks_per_cu * npm::ctx().num_cus);
-        npm::Scratch part;
-        int rc = part.alloc(sizeof(float) * 2 * (size_t)grid * d);
-        if (rc) return rc;
-        float *pp = (float *)part.ptr;                     // [grid][2 d]: dgamma partials | dbeta partials
-        if (nt_rows && (g_ln_nt_split & 3) == 1 && d > 512 && d <= 1024)
-            hipLaunchKernelGGL((layernorm_bwd_kernel<4, true, false>), dim3(grid), dim3(256), 0, s, dz, x, mean, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
-        else if (stream_nt(sizeof(float) * (size_t)rows * (size_t)d) && (g_ln_nt_split & 3) == 2 && d > 512 && d <= 1024)
-            hipLaunchKernelGGL((layernorm_bwd_kernel<4, false, true>), dim3(grid), dim3(256), 0, s, dz, x, mean, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
-        else if (stream_nt(sizeof(float) * (size_t)rows * (size_t)d))
-            NPM_ROW_DISPATCH_NT(layernorm_bwd_kernel, true, d, dz, x, mean, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
-        else
-            NPM_ROW_DISPATCH_NT(layernorm_bwd_kernel, false, d, dz, x, mean, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
-        NPM_CHECK_LAUNCH();
-        if (dbeta == dgamma + d) return colsum_impl(pp, dgamma, grid, 2 * d, 2 * d);      // adjacent outputs (the gradient bucket): one pass
-        rc = colsum_impl(pp, dgamma, grid, d, 2 * d);
-        if (rc) return rc;
-        return colsum_impl(pp + d, dbeta, grid, d, 2 * d);
-    }
-    NPM_ARG((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK < (1L << 31));
-    npm::Scratch tmp;
-    int rc = tmp.alloc(sizeof(float) * (size_t)rows * d);
-    if (rc) return rc;
-    const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-    hipLaunchKernelGGL(layernorm_bwd_dx_generic, dim3(grid), dim3(256), 0, s, dz, x, mean, rstd, gamma, residual,
-                       (long)rows, (long)d, dx, (float *)tmp.ptr);
-    NPM_CHECK_LAUNCH();
-    rc = colsum_impl((const float *)tmp.ptr, dgamma, rows, d, d);
-    if (rc) return rc;
-    return colsum_impl(dz, dbeta, rows, d, d);
+    if (p.vpl == 0) return row_bwd_generic(rows, d, dz, dgamma, dbeta, [&](float *tmp) {
+        hipLaunchKernelGGL(layernorm_bwd_dx_generic, dim3(p.grid), dim3(256), 0, s, dz, x, mean, rstd, gamma, residual, (long)rows, (long)d, dx, tmp);
+    });
+    return row_bwd_fast(p, d, dgamma, dbeta, [&](auto vpl, auto nt, auto nts, float *pp) {
+        hipLaunchKernelGGL((layernorm_bwd_kernel<vpl(), nt(), nts()>), dim3(p.grid), dim3(256), 0, s, dz, x, mean, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
+    });
 }
 
-// RMSNorm: the LayerNorm width grid and, at d in (512, 1024], its hint placement (NPM_TUNE_LN_NT_SPLIT, default: loads only).
+// RMSNorm: the LayerNorm plan (width grid and, at d in (512, 1024], hint placement; NPM_TUNE_LN_NT_SPLIT default: loads only).
 int npm_rmsnorm_fwd(const float *x, const float *gamma, float eps, int64_t rows, int64_t d, float *z, float *rstd) {
     NPM_REQUIRE_INIT();
     NPM_ARG(rows >= 0 && d >= 1);
     if (rows == 0) return NPM_OK;
     NPM_ARG(x && gamma && z && rstd);
-    NPM_ARG((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK < (1L << 31));
+    const RowPlan p = plan_for(RowKind::NORM_FWD, rows, d, aligned16(x) && aligned16(z) && aligned16(gamma));
+    NPM_PLAN_FITS(p);
     hipStream_t s = npm::ctx().stream;
-    const bool fast = d % 4 == 0 && d <= 4096 && aligned16(x) && aligned16(z) && aligned16(gamma);
-    const int fwd_mode = g_ln_nt_split >> 2;
-    if (fast && fwd_mode && d > 512 && d <= 1024 && stream_nt(sizeof(float) * (size_t)rows * (size_t)d)) {
-        const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-        if (fwd_mode == 1) hipLaunchKernelGGL((rmsnorm_fwd_kernel<4, true, false>), dim3(grid), dim3(256), 0, s, x, gamma, eps, (long)rows, (int)d, z, rstd);
-        else hipLaunchKernelGGL((rmsnorm_fwd_kernel<4, false, true>), dim3(grid), dim3(256), 0, s, x, gamma, eps, (long)rows, (int)d, z, rstd);
-    } else if (fast) {
-        NPM_ROW_DISPATCH(rmsnorm_fwd_kernel, d, x, gamma, eps, (long)rows, (int)d, z, rstd);
-    } else {
-        const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-        hipLaunchKernelGGL(rmsnorm_fwd_generic, dim3(grid), dim3(256), 0, s, x, gamma, eps, (long)rows, (long)d, z, rstd);
-    }
+    if (p.vpl == 0) hipLaunchKernelGGL(rmsnorm_fwd_generic, dim3(p.grid), dim3(256), 0, s, x, gamma, eps, (long)rows, (long)d, z, rstd);
+    else row_launch(p, [&](auto vpl, auto nt, auto nts) {
+        hipLaunchKernelGGL((rmsnorm_fwd_kernel<vpl(), nt(), nts()>), dim3(p.grid), dim3(256), 0, s, x, gamma, eps, (long)rows, (int)d, z, rstd);
+    });
     NPM_CHECK_LAUNCH();
     return NPM_OK;
 }
@@ -1299,38 +1287,16 @@ int npm_rmsnorm_bwd(const float *dz, const float *x, const float *rstd, const fl
     NPM_ARG(dgamma != nullptr);
     if (rows == 0) return npm_fill_f32(dgamma, 0.f, (size_t)d);
     NPM_ARG(dz && x && rstd && gamma && dx);
+    const RowPlan p = plan_for(RowKind::NORM_BWD, rows, d, aligned16(dz) && aligned16(x) && aligned16(dx) && aligned16(gamma) &&
+                                                               (residual == nullptr || aligned16(residual)));
+    NPM_PLAN_FITS(p);
     hipStream_t s = npm::ctx().stream;
-    const bool fast = d % 4 == 0 && d <= 4096 && aligned16(dz) && aligned16(x) && aligned16(dx) &&
-                      aligned16(gamma) && (residual == nullptr || aligned16(residual));
-    if (fast) {
-        const bool nt_rows = stream_nt(sizeof(float) * (size_t)rows * (size_t)d);
-        const long row_blocks = (rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-        const int grid = (int)std::min<long>(row_blocks, (long)g_ln_bwd_blocks_per_cu * npm::ctx().num_cus);
-        npm::Scratch part;
-        int rc = part.alloc(sizeof(float) * (size_t)grid * d);
-        if (rc) return rc;
-        float *pp = (float *)part.ptr;                     // [grid][d]: dgamma partials
-        const int bwd_mode = g_ln_nt_split & 3;
-        if (nt_rows && bwd_mode == 1 && d > 512 && d <= 1024)
-            hipLaunchKernelGGL((rmsnorm_bwd_kernel<4, true, false>), dim3(grid), dim3(256), 0, s, dz, x, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
-        else if (nt_rows && bwd_mode == 2 && d > 512 && d <= 1024)
-            hipLaunchKernelGGL((rmsnorm_bwd_kernel<4, false, true>), dim3(grid), dim3(256), 0, s, dz, x, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
-        else if (nt_rows)
-            NPM_ROW_DISPATCH_NT(rmsnorm_bwd_kernel, true, d, dz, x, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
-        else
-            NPM_ROW_DISPATCH_NT(rmsnorm_bwd_kernel, false, d, dz, x, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
-        NPM_CHECK_LAUNCH();
-        return colsum_impl(pp, dgamma, grid, d, d);
-    }
-    NPM_ARG((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK < (1L << 31));
-    npm::Scratch tmp;
-    int rc = tmp.alloc(sizeof(float) * (size_t)rows * d);
-    if (rc) return rc;
-    const int grid = (int)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
-    hipLaunchKernelGGL(rmsnorm_bwd_dx_generic, dim3(grid), dim3(256), 0, s, dz, x, rstd, gamma, residual,
-                       (long)rows, (long)d, dx, (float *)tmp.ptr);
-    NPM_CHECK_LAUNCH();
-    return colsum_impl((const float *)tmp.ptr, dgamma, rows, d, d);
+    if (p.vpl == 0) return row_bwd_generic(rows, d, dz, dgamma, nullptr, [&](float *tmp) {
+        hipLaunchKernelGGL(rmsnorm_bwd_dx_generic, dim3(p.grid), dim3(256), 0, s, dz, x, rstd, gamma, residual, (long)rows, (long)d, dx, tmp);
+    });
+    return row_bwd_fast(p, d, dgamma, nullptr, [&](auto vpl, auto nt, auto nts, float *pp) {
+        hipLaunchKernelGGL((rmsnorm_bwd_kernel<vpl(), nt(), nts()>), dim3(p.grid), dim3(256), 0, s, dz, x, rstd, gamma, residual, (long)rows, (int)d, dx, pp);
+    });
 }
 
 }  // extern "C"

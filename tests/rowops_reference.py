@@ -1,6 +1,6 @@
 """The row kernels of csrc/npm_rowops.hip, restated: shared by tests/test_rowops_host.py (CPU) and tests/test_gpu_rowops_paths.py.
 
-* ``WIDTHS`` / ``GENERIC_WIDTHS`` / ``ROW_COUNTS``: the width grid.  NPM_ROW_DISPATCH keeps a row in VPL float4 per lane, VPL =
+* ``WIDTHS`` / ``GENERIC_WIDTHS`` / ``ROW_COUNTS``: the width grid.  The launch plan (csrc/npm_row_plan.h) keeps a row in VPL float4 per lane, VPL =
   1 / 2 / 4 / 8 / 16 for rows of <= 256 / 512 / 1024 / 2048 / 4096 floats (``vpl_of``); per class the smallest width (4 floats past
   the class below), a width whose last 64-chunk group is partly filled (where the ``lane + 64 j < nvec`` guards decide) and the
   largest.  Widths that are no multiple of 4 or exceed 4096 take the generic kernels.  Row counts 1 / 5 / 7 / 9: a single row; a
