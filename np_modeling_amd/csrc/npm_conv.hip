@@ -746,52 +746,47 @@ int g_wgrad_blocks_per_cu = 0;   // NPM_TUNE_CONV_WGRAD_BLOCKS: 0 pick_splits ch
 // What the most recent conv entry point launched (npm_last_conv_kernel, include/npm_hip.h): written by the host code that
 // picks the instance, read by tests that must know which one they ran.
 char g_last_conv_kernel[192] = "";
-void note_conv(const char *family, bool vec, bool tall, int math, int korder, bool buf, int splits, int kper,
-               int wr = 0, bool trio = false, int ksync = 0) {
-    snprintf(g_last_conv_kernel, sizeof(g_last_conv_kernel), "%s vec=%d tall=%d math=%d korder=%d buf=%d splits=%d kper=%d wr=%d trio=%d ksync=%d",
-             family, (int)vec, (int)tall, math, korder, (int)buf, splits, kper, wr, (int)trio, ksync);
-}
+void note_conv(const npm::ConvReport &r) { npm::format_conv_report(g_last_conv_kernel, sizeof(g_last_conv_kernel), r); }
 void note_conv_none() { snprintf(g_last_conv_kernel, sizeof(g_last_conv_kernel), "none"); }
+
+using npm::ConvKernel;
+
+npm::ConvKnobs conv_knobs() {
+    npm::ConvKnobs kn;
+    kn.dma = g_conv_dma; kn.korder = g_conv_korder; kn.math = g_conv_math;
+    kn.wgrad_blocks = g_wgrad_blocks_per_cu; kn.wgrad_fused = g_wgrad_fused; kn.ksync_every = npm::ksync_every();
+    return kn;
+}
 
 int run_conv_gemm(const float *x, const float *filt_kn, int nb, int h, int w, int c, int n_out, int ks,
                   const Epilogue &e) {
     const long m = (long)nb * h * w;
     NPM_ARG(m < (1L << 31) - BM);
+    const npm::ConvGemmPlan p = npm::conv_gemm_plan(m, w, c, n_out, ks, aligned16(x) && aligned16(filt_kn), conv_knobs());
+    const long grid = p.grid;
+    NPM_ARG(grid < (1L << 31));
     ConvArgs a{};
     a.X = x; a.F = filt_kn;
     a.H = h; a.W = w; a.C = c; a.ks = ks; a.pad = ks / 2;
-    a.M = (int)m; a.N = n_out; a.K = ks * ks * c;
-    a.tiles_m = (a.M + BM - 1) / BM;
-    a.tiles_n = (a.N + BN - 1) / BN;
+    a.M = (int)m; a.N = n_out; a.K = p.k;
+    a.tiles_m = p.tiles_m;
+    a.tiles_n = p.tiles_n;
     a.splits = 1; a.k_per_split = a.K; a.group_m = 8;
     a.korder = g_conv_korder;
     fast_div_setup((unsigned)w, a.w_mul, a.w_shift);
     fast_div_setup((unsigned)h, a.h_mul, a.h_shift);
     a.e = e;
-    const bool vec = c % 4 == 0 && n_out % 4 == 0 && aligned16(x) && aligned16(filt_kn);
-    hipStream_t s = npm::ctx().stream;
-    const long halo = (long)a.pad * w + a.pad;
-    a.e.buf_ok = g_conv_dma && (256L * n_out + n_out) * 4 < (1L << 31);
+    a.e.buf_ok = p.buf_ok;
     a.e.prio = g_conv_wave_prio;
-    const bool dma = g_conv_dma && vec && c % GK == 0 && (256 + 2 * halo) * c * 4 < (1L << 30) &&
-                     (long)a.K * n_out * 4 < (1L << 31);
-    const bool tall = dma && n_out <= 64 && n_out % 16 == 0 && g_conv_dma != 2;
-    if (tall) {
-        a.tiles_m = (a.M + 255) / 256;
-        a.tiles_n = (a.N + 63) / 64;
+    npm::note_math(p.math);
+    note_conv(p.report);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3((int)grid), dim3(NTHREADS), 0, npm::ctx().stream, a); };
+    switch (p.kernel) {
+        case ConvKernel::TALL: p.math == 2 ? go(conv_fwd_glds_kernel<true, 2>) : p.math == 1 ? go(conv_fwd_glds_kernel<true, 1>) : go(conv_fwd_glds_kernel<true, 0>); break;
+        case ConvKernel::DMA: p.math == 2 ? go(conv_fwd_glds_kernel<false, 2>) : p.math == 1 ? go(conv_fwd_glds_kernel<false, 1>) : go(conv_fwd_glds_kernel<false, 0>); break;
+        case ConvKernel::VEC: go(conv_fwd_kernel<true>); break;
+        case ConvKernel::SCALAR: go(conv_fwd_kernel<false>); break;
     }
-    const long grid = (long)a.tiles_m * a.tiles_n;
-    NPM_ARG(grid < (1L << 31));
-    npm::note_math((tall || dma) ? g_conv_math : 0);
-    note_conv(dma ? "conv_fwd_glds" : "conv_fwd", vec, tall, dma ? g_conv_math : 0, dma ? g_conv_korder : 0, dma && a.e.buf_ok, 1, a.K);
-    if (tall && g_conv_math == 2) hipLaunchKernelGGL((conv_fwd_glds_kernel<true, 2>), dim3((int)grid), dim3(NTHREADS), 0, s, a);
-    else if (tall && g_conv_math == 1) hipLaunchKernelGGL((conv_fwd_glds_kernel<true, 1>), dim3((int)grid), dim3(NTHREADS), 0, s, a);
-    else if (tall) hipLaunchKernelGGL((conv_fwd_glds_kernel<true, 0>), dim3((int)grid), dim3(NTHREADS), 0, s, a);
-    else if (dma && g_conv_math == 2) hipLaunchKernelGGL((conv_fwd_glds_kernel<false, 2>), dim3((int)grid), dim3(NTHREADS), 0, s, a);
-    else if (dma && g_conv_math == 1) hipLaunchKernelGGL((conv_fwd_glds_kernel<false, 1>), dim3((int)grid), dim3(NTHREADS), 0, s, a);
-    else if (dma) hipLaunchKernelGGL((conv_fwd_glds_kernel<false, 0>), dim3((int)grid), dim3(NTHREADS), 0, s, a);
-    else if (vec) hipLaunchKernelGGL(conv_fwd_kernel<true>, dim3((int)grid), dim3(NTHREADS), 0, s, a);
-    else hipLaunchKernelGGL(conv_fwd_kernel<false>, dim3((int)grid), dim3(NTHREADS), 0, s, a);
     NPM_CHECK_LAUNCH();
     return NPM_OK;
 }
@@ -854,55 +849,40 @@ int npm_conv2d_bwd_w(const float *dy, const float *x, float *dw,
         return npm_fill_f32(dw, 0.f, (size_t)ksize * ksize * c_in * c_out);
     }
     NPM_ARG(dy && x);
+    const npm::ConvWgradPlan p = npm::conv_wgrad_plan(pixels, w, c_in, c_out, ksize, aligned16(x) && aligned16(dy), conv_knobs(), npm::ctx().num_cus);
     ConvArgs a{};
     a.X = x; a.F = dy;
     a.H = h; a.W = w; a.C = c_in; a.ks = ksize; a.pad = ksize / 2;
-    a.M = ksize * ksize * c_in; a.N = c_out; a.K = (int)pixels;
-    a.tiles_m = (a.M + BM - 1) / BM;
-    a.tiles_n = (a.N + BN - 1) / BN;
+    a.M = p.m; a.N = c_out; a.K = (int)pixels;
+    a.tiles_m = p.tiles_m;
+    a.tiles_n = p.tiles_n;
     a.group_m = 8;
-    const long tiles = (long)a.tiles_m * a.tiles_n;
-    const int nkt = (a.K + BK - 1) / BK;
-    int splits = 1;
-    // 5 tiles x 154 splits = 770 blocks left a quarter of the CUs with 4 blocks and the rest with 3 (19.9 ms at C3);
-    // pick_splits keeps every CU equally full.
-    if (tiles < 2L * npm::ctx().num_cus && nkt >= 16) {
-        if (g_wgrad_blocks_per_cu < 0) splits = (int)std::min<long>((3L * npm::ctx().num_cus + tiles - 1) / tiles, nkt / 8);
-        else splits = pick_splits(tiles, nkt, npm::ctx().num_cus, g_wgrad_blocks_per_cu, g_conv_math == 2 ? 2 : g_conv_math == 1 ? 3 : 4);
-    }
-    splits = std::max(1, splits);
-    const int kt_per = (nkt + splits - 1) / splits;
-    splits = (nkt + kt_per - 1) / kt_per;
-    a.splits = splits;
-    a.k_per_split = kt_per * BK;
+    a.splits = p.splits;
+    a.k_per_split = p.k_per_split;
     a.e.C = dw; a.e.ldc = c_out; a.e.alpha = 1.f;
     npm::Scratch ws;
-    if (splits > 1) {
+    if (p.splits > 1) {
         a.slab = (long)a.M * a.N;
-        int rc = ws.alloc(sizeof(float) * (size_t)a.slab * splits);
+        int rc = ws.alloc(sizeof(float) * (size_t)a.slab * p.splits);
         if (rc) return rc;
         a.e.ws = (float *)ws.ptr;
     }
-    const bool vec = c_in % 4 == 0 && c_out % 4 == 0 && aligned16(x) && aligned16(dy);
     hipStream_t s = npm::ctx().stream;
-    const int grid = (int)(tiles * splits);
-    const long halo = (long)a.pad * w + a.pad;
-    a.e.buf_ok = g_conv_dma && (256L * a.N + a.N) * 4 < (1L << 31);
+    a.e.buf_ok = p.buf_ok;
     a.e.prio = g_conv_wave_prio;
-    const bool dma = g_conv_dma && vec && pixels % GK == 0 && a.k_per_split % GK == 0 &&
-                     ((long)a.k_per_split + 2 * halo + GK) * c_in * 4 < (1L << 30) &&
-                     (long)a.k_per_split * c_out * 4 < (1L << 30);
-    npm::note_math(dma ? g_conv_math : 0);
-    note_conv(dma ? "conv_wgrad_glds" : "conv_wgrad", vec, false, dma ? g_conv_math : 0, 0, dma && a.e.buf_ok, splits, a.k_per_split);
-    if (dma && g_conv_math == 2) hipLaunchKernelGGL(conv_wgrad_glds_kernel<2>, dim3(grid), dim3(NTHREADS), 0, s, a);
-    else if (dma && g_conv_math == 1) hipLaunchKernelGGL(conv_wgrad_glds_kernel<1>, dim3(grid), dim3(NTHREADS), 0, s, a);
-    else if (dma) hipLaunchKernelGGL(conv_wgrad_glds_kernel<0>, dim3(grid), dim3(NTHREADS), 0, s, a);
-    else if (vec) hipLaunchKernelGGL(conv_wgrad_kernel<true>, dim3(grid), dim3(NTHREADS), 0, s, a);
-    else hipLaunchKernelGGL(conv_wgrad_kernel<false>, dim3(grid), dim3(NTHREADS), 0, s, a);
+    npm::note_math(p.math);
+    note_conv(p.report);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(NTHREADS), 0, s, a); };
+    switch (p.kernel) {
+        case ConvKernel::TALL:                 // the filter gradient has no tall tile: conv_wgrad_plan never names it
+        case ConvKernel::DMA: p.math == 2 ? go(conv_wgrad_glds_kernel<2>) : p.math == 1 ? go(conv_wgrad_glds_kernel<1>) : go(conv_wgrad_glds_kernel<0>); break;
+        case ConvKernel::VEC: go(conv_wgrad_kernel<true>); break;
+        case ConvKernel::SCALAR: go(conv_wgrad_kernel<false>); break;
+    }
     NPM_CHECK_LAUNCH();
-    if (splits > 1) {
+    if (p.splits > 1) {
         ReduceArgs r{};
-        r.ws = a.e.ws; r.slab = a.slab; r.splits = splits;
+        r.ws = a.e.ws; r.slab = a.slab; r.splits = p.splits;
         r.M = a.M; r.N = a.N; r.batch1 = 1;
         r.e = a.e;
         return launch_splitk_reduce(r, s);
@@ -927,73 +907,54 @@ int npm_conv2d_bwd_w_relu(const float *dy, const float *pre, const float *x, flo
         return rc ? rc : npm_fill_f32(db, 0.f, (size_t)c_out);
     }
     NPM_ARG(dy && pre && x && g);
-    const int m = ksize * ksize * c_in;
-    const long halo = (long)(ksize / 2) * w + ksize / 2;
-    const bool fused = g_conv_dma && g_conv_math == 0 && g_wgrad_fused && c_in % 4 == 0 && c_out % 4 == 0 && pixels % GK == 0 && w >= GK &&
-                       aligned16(x) && aligned16(dy) && aligned16(pre) && aligned16(g) && (long)m * c_out * 4 < (1L << 31);
-    if (fused) {
+    const npm::ConvWgradFusedPlan p = npm::conv_wgrad_fused_plan(pixels, w, c_in, c_out, ksize, aligned16(x) && aligned16(dy) && aligned16(pre) && aligned16(g),
+                                                                 conv_knobs(), npm::ctx().num_cus);
+    if (p.fused) {
         WgradArgs a{};
         a.X = x; a.DY = dy; a.PRE = pre; a.G = g;
         a.H = h; a.W = w; a.C = c_in; a.ks = ksize; a.pad = ksize / 2;
-        a.M = m; a.N = c_out; a.K = (int)pixels;
-        // tile height: the one that pads k*k*C0 least (192-row tiles: 3 blocks per CU, 128-row tiles: 4)
-        const long pad128 = (long)((m + 127) / 128) * 128, pad192 = (long)((m + 191) / 192) * 192;
-        const bool tall = g_wgrad_fused == 3 || (g_wgrad_fused != 2 && pad192 < pad128);
-        const int tm_rows = tall ? 192 : 128, resident = tall ? 3 : 4;
-        a.tiles_m = (m + tm_rows - 1) / tm_rows;
-        a.tiles_n = (c_out + BN - 1) / BN;
-        const long tiles = (long)a.tiles_m * a.tiles_n;
-        const int nkt = (int)(pixels / GK);
-        int splits = 1;
-        if (tiles < 2L * npm::ctx().num_cus && nkt >= 16)
-            splits = pick_splits(tiles, nkt, npm::ctx().num_cus, g_wgrad_blocks_per_cu > 0 ? g_wgrad_blocks_per_cu : 0, resident);
-        splits = std::max(1, splits);
-        const int kt_per = (nkt + splits - 1) / splits;
-        splits = (nkt + kt_per - 1) / kt_per;
-        a.splits = splits;
-        a.k_per_split = kt_per * GK;
-        const bool fits = ((long)a.k_per_split + 2 * halo + GK) * c_in * 4 < (1L << 30) && (long)a.k_per_split * c_out * 4 < (1L << 30) &&
-                          tiles * splits < (1L << 31);
-        if (fits) {
-            // TRIO: the three tile rows of a split in one block of twelve waves (NPM_TUNE_CONV_WGRAD_FUSED = 3 keeps the four-wave blocks)
-            const bool trio = tall && a.tiles_m == 3 && splits > 1 && g_wgrad_fused != 3;
-            a.parts_m = trio ? 1 : a.tiles_m;
-            npm::Scratch ws, parts;
-            int rc = parts.alloc(sizeof(float) * (size_t)splits * a.parts_m * c_out);
+        a.M = p.m; a.N = c_out; a.K = (int)pixels;
+        a.tiles_m = p.tiles_m;
+        a.tiles_n = p.tiles_n;
+        a.splits = p.splits;
+        a.k_per_split = p.k_per_split;
+        a.parts_m = p.parts_m;
+        npm::Scratch ws, parts;
+        int rc = parts.alloc(sizeof(float) * (size_t)p.splits * a.parts_m * c_out);
+        if (rc) return rc;
+        a.colpart = (float *)parts.ptr;
+        a.slab = (long)p.m * c_out;
+        if (p.splits > 1) {
+            rc = ws.alloc(sizeof(float) * (size_t)a.slab * p.splits);
             if (rc) return rc;
-            a.colpart = (float *)parts.ptr;
-            a.slab = (long)m * c_out;
-            if (splits > 1) {
-                rc = ws.alloc(sizeof(float) * (size_t)a.slab * splits);
-                if (rc) return rc;
-                a.out = (float *)ws.ptr;
-            } else {
-                a.out = dw;
-            }
-            hipStream_t s = npm::ctx().stream;
-            npm::note_math(0);
-            const int grid = (int)((trio ? a.tiles_n : tiles) * splits);
-            // K rendezvous: all blocks resident at once (3 or 4 per CU), every split long enough
-            if (!trio && splits > 1 && grid <= (long)resident * npm::ctx().num_cus && npm::ksync_every() > 0 && kt_per >= 2 * npm::ksync_every()) {
-                a.ksync.slice = npm::ksync_slice();
-                a.ksync.every = npm::ksync_every();
-                a.ksync.epochs = (nkt - (splits - 1) * kt_per - 1) / a.ksync.every;
-            }
-            note_conv("conv_wgrad_relu", true, false, 0, 0, true, splits, a.k_per_split, tall ? 3 : 2, trio, a.ksync.slice ? a.ksync.every : 0);
-            if (trio) hipLaunchKernelGGL((conv_wgrad_relu_kernel<3, true>), dim3(grid), dim3(3 * NTHREADS), 0, s, a);
-            else if (tall) hipLaunchKernelGGL(conv_wgrad_relu_kernel<3>, dim3(grid), dim3(NTHREADS), 0, s, a);
-            else hipLaunchKernelGGL(conv_wgrad_relu_kernel<2>, dim3(grid), dim3(NTHREADS), 0, s, a);
-            NPM_CHECK_LAUNCH();
-            if (splits > 1) {
-                ReduceArgs r{};
-                r.ws = a.out; r.slab = a.slab; r.splits = splits;
-                r.M = m; r.N = c_out; r.batch1 = 1;
-                r.e.C = dw; r.e.ldc = c_out; r.e.alpha = 1.f;
-                rc = launch_splitk_reduce(r, s);
-                if (rc) return rc;
-            }
-            return npm_colsum(a.colpart, db, (int64_t)splits * a.parts_m, c_out, c_out);       // fixed order over the partial rows
+            a.out = (float *)ws.ptr;
+        } else {
+            a.out = dw;
         }
+        hipStream_t s = npm::ctx().stream;
+        npm::note_math(0);
+        if (p.ksync_every) {                    // the counters of this launch, or null when the runtime has none to give
+            a.ksync.slice = npm::ksync_slice();
+            a.ksync.every = p.ksync_every;
+            a.ksync.epochs = p.ksync_epochs;
+        }
+        npm::ConvReport report = p.report;
+        report.ksync = a.ksync.slice ? p.ksync_every : 0;
+        note_conv(report);
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), 0, s, a); };
+        if (p.trio) go(conv_wgrad_relu_kernel<3, true>);
+        else if (p.rows == 192) go(conv_wgrad_relu_kernel<3>);
+        else go(conv_wgrad_relu_kernel<2>);
+        NPM_CHECK_LAUNCH();
+        if (p.splits > 1) {
+            ReduceArgs r{};
+            r.ws = a.out; r.slab = a.slab; r.splits = p.splits;
+            r.M = p.m; r.N = c_out; r.batch1 = 1;
+            r.e.C = dw; r.e.ldc = c_out; r.e.alpha = 1.f;
+            rc = launch_splitk_reduce(r, s);
+            if (rc) return rc;
+        }
+        return npm_colsum(a.colpart, db, (int64_t)p.splits * a.parts_m, c_out, c_out);       // fixed order over the partial rows
     }
     int rc = npm_relu_bwd_colsum(pre, dy, g, db, pixels, c_out);
     if (rc) return rc;

@@ -362,45 +362,39 @@ sgemm_glds_kernel(const GemmArgs p) {
 
 inline bool aligned16(const void *ptr) { return ((uintptr_t)ptr & 15) == 0; }
 
+using npm::GemmKernel;
+
+// The one launch of the instance the plan names (npm_gemm_plan.h has the table).  The fused k-sums exist for the TN layout only and
+// the row-dot epilogue for NN only; gemm_plan names them for no other layout, and a plan this layout has no kernel for is an error.
 template <bool A_KMAJ, bool B_KMAJ>
-void launch(const GemmArgs &a, bool vec, bool dma, int grid, hipStream_t stream) {
-    // The split-bf16 modes exist on the LDS-DMA pipeline with the 128 x 128 tile (with or without the fused k-sums);
-    // the wide tile, the epilogue column sums and the register-staged fallback (unaligned operands, K % 16 != 0) run
-    // the exact-f32 MFMA whatever was requested: npm_last_math() tells which it was.
-    const bool math_honoured = dma && (a.ksum || (!a.wide && !a.e.cs));
-    npm::note_math(math_honoured ? a.math : 0);
-    if (dma && a.ksum) {
-        if constexpr (!A_KMAJ && !B_KMAJ) {
-            if (a.math == 1) {
-                if (a.ksum_op == 1) hipLaunchKernelGGL((sgemm_glds_kernel<false, false, false, 2, 2, 1, 1>), dim3(grid), dim3(NTHREADS), 0, stream, a);
-                else hipLaunchKernelGGL((sgemm_glds_kernel<false, false, false, 2, 2, 2, 1>), dim3(grid), dim3(NTHREADS), 0, stream, a);
-            } else if (a.math == 2) {
-                if (a.ksum_op == 1) hipLaunchKernelGGL((sgemm_glds_kernel<false, false, false, 2, 2, 1, 2>), dim3(grid), dim3(NTHREADS), 0, stream, a);
-                else hipLaunchKernelGGL((sgemm_glds_kernel<false, false, false, 2, 2, 2, 2>), dim3(grid), dim3(NTHREADS), 0, stream, a);
-            } else {
-                if (a.ksum_op == 1) hipLaunchKernelGGL((sgemm_glds_kernel<false, false, false, 2, 2, 1>), dim3(grid), dim3(NTHREADS), 0, stream, a);
-                else hipLaunchKernelGGL((sgemm_glds_kernel<false, false, false, 2, 2, 2>), dim3(grid), dim3(NTHREADS), 0, stream, a);
+int launch(const GemmArgs &a, const npm::GemmPlan &p, hipStream_t stream) {
+    auto go = [&](auto kernel) {                   // npm_sgemm asks for the launch's error, under its own name
+        hipLaunchKernelGGL(kernel, dim3((int)p.grid), dim3(p.block), 0, stream, a);
+        return (int)NPM_OK;
+    };
+    switch (p.kernel) {
+        case GemmKernel::DMA_KSUM:
+            if constexpr (!A_KMAJ && !B_KMAJ) {
+                if (p.math == 1) return p.ksum_op == 1 ? go(sgemm_glds_kernel<false, false, false, 2, 2, 1, 1>) : go(sgemm_glds_kernel<false, false, false, 2, 2, 2, 1>);
+                if (p.math == 2) return p.ksum_op == 1 ? go(sgemm_glds_kernel<false, false, false, 2, 2, 1, 2>) : go(sgemm_glds_kernel<false, false, false, 2, 2, 2, 2>);
+                return p.ksum_op == 1 ? go(sgemm_glds_kernel<false, false, false, 2, 2, 1>) : go(sgemm_glds_kernel<false, false, false, 2, 2, 2>);
             }
-        }
-    } else if (dma && a.math == 1 && !a.wide && !a.e.cs)
-        hipLaunchKernelGGL((sgemm_glds_kernel<A_KMAJ, B_KMAJ, false, 2, 2, 0, 1>), dim3(grid), dim3(NTHREADS), 0, stream, a);
-    else if (dma && a.math == 2 && !a.wide && !a.e.cs)
-        hipLaunchKernelGGL((sgemm_glds_kernel<A_KMAJ, B_KMAJ, false, 2, 2, 0, 2>), dim3(grid), dim3(NTHREADS), 0, stream, a);
-    else if (dma && a.wide)
-        hipLaunchKernelGGL((sgemm_glds_kernel<A_KMAJ, B_KMAJ, false, 2, 4>), dim3(grid), dim3(512), 0, stream, a);
-    else if (dma && a.e.cs)
-        hipLaunchKernelGGL((sgemm_glds_kernel<A_KMAJ, B_KMAJ, true>), dim3(grid), dim3(NTHREADS), 0, stream, a);
-    else if (dma && a.e.rowdot) {
-        if constexpr (A_KMAJ && !B_KMAJ)       // dctx = dy wo (attentions.py:136): the one product that takes it
-            hipLaunchKernelGGL((sgemm_glds_kernel<true, false, false, 2, 2, 0, 0, true>), dim3(grid), dim3(NTHREADS), 0, stream, a);
-    } else if (dma)
-        hipLaunchKernelGGL((sgemm_glds_kernel<A_KMAJ, B_KMAJ, false>), dim3(grid), dim3(NTHREADS), 0, stream, a);
-    else if (!vec)
-        hipLaunchKernelGGL((sgemm_mfma_kernel<A_KMAJ, B_KMAJ, false, 0>), dim3(grid), dim3(NTHREADS), 0, stream, a);
-    else if (g_pipe == 1)
-        hipLaunchKernelGGL((sgemm_mfma_kernel<A_KMAJ, B_KMAJ, true, 1>), dim3(grid), dim3(NTHREADS), 0, stream, a);
-    else
-        hipLaunchKernelGGL((sgemm_mfma_kernel<A_KMAJ, B_KMAJ, true, 0>), dim3(grid), dim3(NTHREADS), 0, stream, a);
+            break;
+        case GemmKernel::DMA_MATH1: return go(sgemm_glds_kernel<A_KMAJ, B_KMAJ, false, 2, 2, 0, 1>);
+        case GemmKernel::DMA_MATH2: return go(sgemm_glds_kernel<A_KMAJ, B_KMAJ, false, 2, 2, 0, 2>);
+        case GemmKernel::DMA_WIDE: return go(sgemm_glds_kernel<A_KMAJ, B_KMAJ, false, 2, 4>);
+        case GemmKernel::DMA_COLSUM: return go(sgemm_glds_kernel<A_KMAJ, B_KMAJ, true>);
+        case GemmKernel::DMA_ROWDOT:
+            if constexpr (A_KMAJ && !B_KMAJ)       // dctx = dy wo (attentions.py:136): the one product that takes it
+                return go(sgemm_glds_kernel<true, false, false, 2, 2, 0, 0, true>);
+            break;
+        case GemmKernel::DMA: return go(sgemm_glds_kernel<A_KMAJ, B_KMAJ, false>);
+        case GemmKernel::STAGED_SCALAR: return go(sgemm_mfma_kernel<A_KMAJ, B_KMAJ, false, 0>);
+        case GemmKernel::STAGED_VEC_2BUF: return go(sgemm_mfma_kernel<A_KMAJ, B_KMAJ, true, 1>);
+        case GemmKernel::STAGED_VEC: return go(sgemm_mfma_kernel<A_KMAJ, B_KMAJ, true, 0>);
+        case GemmKernel::F16X2: break;             // npm_gemm_f16x2.hip: launched by npm_sgemm itself
+    }
+    return npm::fail(NPM_E_UNSUPPORTED, "npm_sgemm: the launch plan names a kernel this layout does not have");
 }
 
 }  // namespace
@@ -434,21 +428,6 @@ int launch_splitk_reduce(const ReduceArgs &r, hipStream_t stream) {
 }
 
 }  // namespace npm_tile
-
-extern "C" int npm_conv_set_dma(int on);
-extern "C" int npm_conv_set_wgrad_blocks(int per_cu);
-extern "C" int npm_conv_set_wave_prio(int bits);
-extern "C" int npm_conv_set_korder(int order);
-extern "C" int npm_conv_set_math(int mode);
-extern "C" int npm_conv_set_wgrad_fused(int mode);
-extern "C" int npm_attn_set_bwd16(int on);
-extern "C" int npm_attn_set_fwd8(int mode);
-extern "C" int npm_attn_set_stagger(int units);
-extern "C" int npm_decode_set_splits(int value);
-extern "C" int npm_decode_set_nt(int value);
-extern "C" int npm_skinny_set_splits(int value);
-extern "C" int npm_skinny_set_nt(int value);
-extern "C" int npm_prefix_set_splits(int value);
 
 extern "C" int npm_set_math(int mode) { return npm_set_tuning(NPM_TUNE_GEMM_MATH, mode); }
 extern "C" int npm_get_math(void) { return g_math; }
@@ -507,6 +486,44 @@ extern "C" int npm_sgemm(const npm_gemm *g) {
     const bool a_kmaj = g->trans_a == 0;   // A[M,K]: K contiguous
     const bool b_kmaj = g->trans_b != 0;   // B stored [N,K]: K contiguous
     if (!a_kmaj && b_kmaj) return npm::fail(NPM_E_UNSUPPORTED, "npm_sgemm: trans_a && trans_b is not used by the hot path");
+    const bool want_colsum = g->colsum != nullptr;
+    const bool want_bsum = g->bsum != nullptr, want_asum = g->asum != nullptr;
+    NPM_ARG(!want_bsum || (!b_kmaj && g->batch0 == 1 && g->batch1 == 1 && !want_colsum));   // B stored [K, N]
+    NPM_ARG(!want_asum || (!a_kmaj && g->batch0 == 1 && g->batch1 == 1 && !want_colsum && !want_bsum));   // A stored [K, M]
+
+    npm::GemmShape s{};
+    s.m = g->m; s.n = g->n; s.k = g->k; s.batch0 = g->batch0; s.batch1 = g->batch1;
+    s.lda = g->lda; s.ldb = g->ldb; s.ldc = g->ldc; s.ldr = g->ldr; s.ldaux = g->ldaux;
+    s.stride_a0 = g->stride_a0; s.stride_a1 = g->stride_a1; s.stride_b0 = g->stride_b0; s.stride_b1 = g->stride_b1;
+    s.trans_a = !a_kmaj; s.trans_b = b_kmaj;
+    s.epilogue = epi;
+    s.a_aligned = aligned16(g->a); s.b_aligned = aligned16(g->b);
+    s.split_k = g->split_k;
+    s.colsum = want_colsum; s.bsum = want_bsum; s.asum = want_asum;
+    s.diagnostics = g_ablate != 0 || g_trace != nullptr;
+    npm::GemmKnobs knobs;
+    knobs.pipe = g_pipe; knobs.wide_tile = g_wide_tile; knobs.buf_epilogue = g_buf_epilogue; knobs.math = g_math; knobs.split_gens = g_split_gens;
+    const npm::GemmPlan p = npm::gemm_plan(s, knobs, npm::ctx().num_cus);
+    const long grid = p.grid;
+    NPM_ARG(grid < (1L << 31));
+    if (p.refusal == npm::GemmRefusal::WIDE_SPANS)
+        return npm::fail(NPM_E_UNSUPPORTED, "npm_sgemm: operand spans too large for the 128x256 tile (disable NPM_TUNE_GEMM_WIDE_TILE)");
+    if (p.refusal == npm::GemmRefusal::ROWDOT)
+        return npm::fail(NPM_E_UNSUPPORTED, "npm_sgemm: NPM_EPI_ROWDOT needs the 128 x 128 LDS-DMA kernel in exact fp32 (A [M, K], B [K, N], "
+                                            "aligned operands, k %% 16 == 0, n %% 128 == 0, no batch, no split-K)");
+
+    // Scratch by the plan: split-K slabs, the partial rows of the fused k-sums and of the epilogue column sums, the f16x2 scales.
+    const bool f16x2 = p.kernel == GemmKernel::F16X2;
+    const int ksum_len = want_bsum ? g->n : g->m;
+    const long slab = (long)g->batch0 * g->batch1 * g->m * g->n;
+    const long cs_rows = (long)g->batch0 * p.tiles_m * 2, cs_cols = (long)g->batch1 * g->n;
+    npm::Scratch ws, ks_part, cs_part, scales;
+    int rc = NPM_OK;
+    if (p.splits > 1) rc = ws.alloc(sizeof(float) * (size_t)slab * p.splits);
+    if (!rc && p.ksum_op) rc = ks_part.alloc(sizeof(float) * (size_t)p.ksum_rows * ksum_len);
+    if (!rc && p.colsum_fused) rc = cs_part.alloc(sizeof(float) * (size_t)cs_rows * cs_cols);
+    if (!rc && f16x2) rc = scales.alloc(3 * sizeof(float) * ((size_t)g->m + (size_t)g->n));
+    if (rc) return rc;
 
     GemmArgs a{};
     a.A = g->a; a.B = g->b; a.e.C = g->c;
@@ -516,25 +533,15 @@ extern "C" int npm_sgemm(const npm_gemm *g) {
     a.sC0 = g->stride_c0; a.sC1 = g->stride_c1;
     a.M = g->m; a.N = g->n; a.K = g->k;
     a.batch1 = g->batch1;
-    // float4 / DMA staging needs 16-B aligned rows in both operands.
-    auto strides_ok = [](long s0, long s1) { return (s0 % 4 == 0) && (s1 % 4 == 0); };
-    bool vec = aligned16(g->a) && aligned16(g->b) && g->lda % 4 == 0 && g->ldb % 4 == 0 &&
-               strides_ok(g->stride_a0, g->stride_a1) && strides_ok(g->stride_b0, g->stride_b1);
-    vec = vec && (a_kmaj ? g->k % 4 == 0 : g->m % 4 == 0);
-    vec = vec && (b_kmaj ? g->k % 4 == 0 : g->n % 4 == 0);
-    const bool want_colsum = g->colsum != nullptr;
-    const bool want_bsum = g->bsum != nullptr, want_asum = g->asum != nullptr;
-    NPM_ARG(!want_bsum || (!b_kmaj && g->batch0 == 1 && g->batch1 == 1 && !want_colsum));   // B stored [K, N]
-    NPM_ARG(!want_asum || (!a_kmaj && g->batch0 == 1 && g->batch1 == 1 && !want_colsum && !want_bsum));   // A stored [K, M]
-    const bool want_ksum = want_bsum || want_asum;
-    const int ksum_len = want_bsum ? g->n : g->m;
-    float *ksum_out = want_bsum ? g->bsum : g->asum;
-    // 128 x 256 tile: only where it divides N and the LDS-DMA kernel will run (spans re-checked below)
-    const int tile_n = ((g_wide_tile == 1 || (g_wide_tile == 2 && a_kmaj) || (g_wide_tile == 3 && a_kmaj && b_kmaj)) && g_pipe == 2 && vec && g->k % GK == 0 && g->n % 256 == 0 && !want_colsum && !want_ksum &&
-                        (long)256 * g->ldb * 4 < (1L << 30)) ? 256 : BN;
-    a.wide = tile_n == 256;
-    a.tiles_m = (g->m + BM - 1) / BM;
-    a.tiles_n = (g->n + tile_n - 1) / tile_n;
+    a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n;
+    a.splits = p.splits; a.k_per_split = p.k_per_split;
+    a.group_m = g_group_m;
+    a.ksum = (float *)ks_part.ptr; a.ksum_op = p.ksum_op;
+    a.math = p.math;
+    a.trace = g_trace;
+    a.wide = p.wide;
+    a.ablate = g_ablate;
+    a.slab = p.splits > 1 ? slab : 0;
     a.e.alpha = g->alpha;
     a.e.flags = epi;
     a.e.bias = g->bias;
@@ -546,91 +553,14 @@ extern "C" int npm_sgemm(const npm_gemm *g) {
     a.e.rowdot_m = g->m;
     a.e.rowvec = (epi & NPM_EPI_SOFTMAX_BWD) ? g->rowvec : nullptr;
     a.e.ldaux = g->ldaux;
-    {
-        // the buffer epilogue addresses one block (<= 256 rows) at a time: its row pitches must keep that below 2^31
-        auto fits = [&](long ld) { return (256L * ld + g->n) * 4 < (1L << 31); };
-        a.e.buf_ok = g_buf_epilogue && fits(g->ldc) && (!(epi & NPM_EPI_RESIDUAL) || fits(g->ldr)) &&
-                     (!(epi & (NPM_EPI_RELU_SAVE | NPM_EPI_RELU_MASK | NPM_EPI_SOFTMAX_BWD | NPM_EPI_ROWDOT)) || fits(g->ldaux)) && fits(g->n);
-    }
-    a.group_m = g_group_m;
-    a.ablate = g_ablate;
+    a.e.buf_ok = p.buf_ok;
     a.e.prio = g_wave_prio;
-    a.math = g_math == 3 ? 2 : g_math;          // NPM_MATH_F16X2 where its kernel does not apply: the bf16 split
-    a.trace = g_trace;
+    a.e.ws = (float *)ws.ptr;
+    a.e.cs = (float *)cs_part.ptr;
 
-    const long batch = (long)g->batch0 * g->batch1;
-    const long tiles = (long)a.tiles_m * a.tiles_n * batch;
-
-    // Split-K: only for the linear epilogues, when the grid cannot fill 256 CUs x 2-3 blocks.
-    int splits = 1;
-    const int nkt = (g->k + BK - 1) / BK;
-    const bool linear_epi = !(epi & (NPM_EPI_RELU_SAVE | NPM_EPI_RELU_MASK | NPM_EPI_RELU | NPM_EPI_SOFTMAX_BWD | NPM_EPI_ROWDOT));
-    if (g->split_k > 1) {
-        splits = g->split_k;
-    } else if (g->split_k == 0 && linear_epi && tiles < 2L * npm::ctx().num_cus && nkt >= 16) {
-        // (several generations of shorter K ranges: measured to pay for the A-heavy products that also sum A's columns -- the packed
-        //  q/k/v weight gradient [3F, F] -- and to cost 0.3 ms per step on the FFN weight gradients, which sum B's: profiles/r04_splitk_sweep.log)
-        const bool more_generations = g_math == 0 && g_split_gens && want_asum && a.tiles_m > a.tiles_n;
-        splits = pick_splits(tiles, nkt, npm::ctx().num_cus, 0, g_math >= 2 ? 2 : g_math == 1 ? 3 : 4, more_generations ? 1 : 0);
-    }
-    if (!linear_epi) splits = 1;
-    if (splits > nkt) splits = nkt > 0 ? nkt : 1;
-    if (splits < 1) splits = 1;
-    int kt_per_split = (nkt + splits - 1) / splits;
-    if (kt_per_split < 1) kt_per_split = 1;
-    splits = nkt > 0 ? (nkt + kt_per_split - 1) / kt_per_split : 1;
-    a.splits = splits;
-    a.k_per_split = splits > 1 ? kt_per_split * BK : (g->k > 0 ? nkt * BK : BK);
-
-    if (want_colsum) splits = a.splits = 1, a.k_per_split = g->k > 0 ? nkt * BK : BK;
-    npm::Scratch ws;
-    if (splits > 1) {
-        a.slab = batch * (long)g->m * g->n;
-        int rc = ws.alloc(sizeof(float) * (size_t)a.slab * splits);
-        if (rc) return rc;
-        a.e.ws = (float *)ws.ptr;
-    }
-
-    const long grid = tiles * splits;
-    NPM_ARG(grid < (1L << 31));
     hipStream_t stream = npm::ctx().stream;
-    // Column sums of the stored C: taken in the epilogue of the LDS-DMA kernel when it is eligible,
-    // otherwise by a separate pass over C (small / unaligned shapes).
-    const long a_span = (a_kmaj ? (long)BM * g->lda + g->k : (long)a.k_per_split * g->lda + BM) * 4;
-    const long b_span = (b_kmaj ? (long)tile_n * g->ldb + g->k : (long)a.k_per_split * g->ldb + tile_n) * 4;
-    const bool dma = g_pipe == 2 && vec && g->k % GK == 0 && a.k_per_split % GK == 0 &&
-                     a_span < (1L << 31) && b_span < (1L << 31);
-    if (a.wide && !(dma && a.e.buf_ok))
-        return npm::fail(NPM_E_UNSUPPORTED, "npm_sgemm: operand spans too large for the 128x256 tile (disable NPM_TUNE_GEMM_WIDE_TILE)");
-    const bool dma_path = dma && a.e.buf_ok;
-    if (rowdot && !(dma_path && a_kmaj && !b_kmaj && !a.wide && batch == 1 && splits == 1 && g->n % 128 == 0 && g_math == 0 && !a.ablate && !a.trace))
-        return npm::fail(NPM_E_UNSUPPORTED, "npm_sgemm: NPM_EPI_ROWDOT needs the 128 x 128 LDS-DMA kernel in exact fp32 (A [M, K], B [K, N], "
-                                            "aligned operands, k %% 16 == 0, n %% 128 == 0, no batch, no split-K)");
-    // Column sums of B beside a TN product: in the kernel when the LDS-DMA path runs, else a pass over B.
-    npm::Scratch bs_part;
-    // NPM_MATH_F16X2: one product (no batch), the LDS-DMA path's alignment rules, no epilogue column sums
-    const bool f16x2 = g_math == 3 && dma_path && batch == 1 && !a.wide && !want_colsum && g->k > 0 && !a.ablate && !a.trace;
-    const bool ksum_fused = want_ksum && dma_path && !a_kmaj && !b_kmaj && g->k > 0 && !f16x2;
-    const long ksum_rows = (long)splits * std::min(want_bsum ? a.tiles_m : a.tiles_n, GK);
-    if (ksum_fused) {
-        a.ksum_op = want_bsum ? 1 : 2;
-        int rc = bs_part.alloc(sizeof(float) * (size_t)ksum_rows * ksum_len);
-        if (rc) return rc;
-        a.ksum = (float *)bs_part.ptr;
-    }
-    npm::Scratch cs_part;
-    const long cs_rows = (long)g->batch0 * a.tiles_m * 2, cs_cols = (long)g->batch1 * g->n;
-    if (want_colsum && dma_path) {
-        int rc = cs_part.alloc(sizeof(float) * (size_t)cs_rows * cs_cols);
-        if (rc) return rc;
-        a.e.cs = (float *)cs_part.ptr;
-    }
-    npm::Scratch scales;
     if (f16x2) {
         // maxima along K of both operands -> power-of-two scales (one pass over each), then the product
-        const size_t mn = (size_t)g->m + (size_t)g->n;
-        int rc = scales.alloc(3 * sizeof(float) * mn);
-        if (rc) return rc;
         float *sa = (float *)scales.ptr, *sb = sa + g->m, *ia = sb + g->n, *ib = ia + g->m;
         unsigned *ua = (unsigned *)(ib + g->n), *ub = ua + g->m;
         // the bias gradient beside a weight gradient (asum / bsum: column sums of an MN-major operand) rides the same pass
@@ -646,37 +576,40 @@ extern "C" int npm_sgemm(const npm_gemm *g) {
         f.splits = a.splits; f.k_per_split = a.k_per_split; f.slab = a.slab;
         f.sa = sa; f.sb = sb; f.inv_sa = ia; f.inv_sb = ib;
         f.e = a.e;
-        npm::note_math(3);
+        npm::note_math(p.math);
         rc = npm_tile::launch_f16x2(f, stream);
         if (rc) return rc;
     } else {
-        if (a_kmaj && b_kmaj) launch<true, true>(a, vec, dma, (int)grid, stream);
-        else if (a_kmaj && !b_kmaj) launch<true, false>(a, vec, dma, (int)grid, stream);
-        else launch<false, false>(a, vec, dma, (int)grid, stream);
+        npm::note_math(p.math);
+        rc = a_kmaj && b_kmaj ? launch<true, true>(a, p, stream) : a_kmaj ? launch<true, false>(a, p, stream) : launch<false, false>(a, p, stream);
+        if (rc) return rc;
         NPM_CHECK_LAUNCH();
     }
 
-    if (want_ksum && !f16x2) {
-        int rc = NPM_OK;
-        if (!ksum_fused) rc = want_bsum ? npm::colsum_launch(g->b, g->bsum, g->k, g->n, g->ldb)
-                                        : npm::colsum_launch(g->a, g->asum, g->k, g->m, g->lda);
-        else rc = npm::colsum_launch(a.ksum, ksum_out, ksum_rows, ksum_len, ksum_len);
+    // Finishing passes.  Column sums of an operand beside a TN product: the partial rows of the kernel where it took them, else a
+    // pass over the operand (the f16x2 scale passes have taken them already).
+    if ((want_bsum || want_asum) && !f16x2) {
+        if (p.ksum_op) rc = npm::colsum_launch(a.ksum, want_bsum ? g->bsum : g->asum, p.ksum_rows, ksum_len, ksum_len);
+        else rc = want_bsum ? npm::colsum_launch(g->b, g->bsum, g->k, g->n, g->ldb)
+                            : npm::colsum_launch(g->a, g->asum, g->k, g->m, g->lda);
         if (rc) return rc;
     }
+    // Column sums of the stored C: the partial rows of the epilogue where the LDS-DMA kernel took them, otherwise a separate pass
+    // over C (small / unaligned shapes).
     if (want_colsum) {
-        if (a.e.cs) return npm::colsum_launch(a.e.cs, g->colsum, cs_rows, cs_cols, cs_cols);
+        if (p.colsum_fused) return npm::colsum_launch(a.e.cs, g->colsum, cs_rows, cs_cols, cs_cols);
         // fallback: one strided pass per z1 over the stored C (batches must be row-contiguous)
         NPM_ARG(g->batch0 == 1 || g->stride_c0 == (int64_t)g->m * g->ldc);
         for (int z1 = 0; z1 < g->batch1; ++z1) {
-            int rc = npm::colsum_launch(g->c + z1 * g->stride_c1, g->colsum + (long)z1 * g->n,
-                                        (long)g->m * g->batch0, g->n, g->ldc);
+            rc = npm::colsum_launch(g->c + z1 * g->stride_c1, g->colsum + (long)z1 * g->n,
+                                    (long)g->m * g->batch0, g->n, g->ldc);
             if (rc) return rc;
         }
         return NPM_OK;
     }
-    if (splits > 1) {
+    if (p.splits > 1) {
         ReduceArgs r{};
-        r.ws = a.e.ws; r.slab = a.slab; r.splits = splits;
+        r.ws = a.e.ws; r.slab = a.slab; r.splits = p.splits;
         r.M = a.M; r.N = a.N; r.batch1 = a.batch1; r.sC0 = a.sC0; r.sC1 = a.sC1;
         r.e = a.e;
         return launch_splitk_reduce(r, stream);

@@ -50,7 +50,23 @@ struct Scratch {
 
 }  // namespace npm
 
-#define NPM_REQUIRE_INIT()                                                         \
+// The knob setters of the other translation units, behind npm_set_tuning (npm_gemm.hip).
+extern "C" int npm_conv_set_dma(int on);
+extern "C" int npm_conv_set_wgrad_blocks(int per_cu);
+extern "C" int npm_conv_set_wave_prio(int bits);
+extern "C" int npm_conv_set_korder(int order);
+extern "C" int npm_conv_set_math(int mode);
+extern "C" int npm_conv_set_wgrad_fused(int mode);
+extern "C" int npm_attn_set_bwd16(int on);
+extern "C" int npm_attn_set_fwd8(int mode);
+extern "C" int npm_attn_set_stagger(int units);
+extern "C" int npm_decode_set_splits(int value);
+extern "C" int npm_decode_set_nt(int value);
+extern "C" int npm_skinny_set_splits(int value);
+extern "C" int npm_skinny_set_nt(int value);
+extern "C" int npm_prefix_set_splits(int value);
+
+#define NPM_REQUIRE_INIT()                                                        \
     do {                                                                           \
         if (!npm::ctx().ready)                                                     \
             return npm::fail(NPM_E_NOT_INITIALIZED, "%s: npm_init() has not been called", __func__); \

@@ -3,15 +3,15 @@
 // See npm_gemm.hip for the design notes.
 #pragma once
 
+#include "npm_gemm_plan.h"
 #include "npm_internal.h"
 
 namespace npm_tile {
 
+using npm::BM, npm::BN, npm::BK, npm::GK;      // block tile 128 x 128, K step 32 (register-staged) / 16 (LDS-DMA): npm_gemm_plan.h
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int BM = 128;
-constexpr int BN = 128;
-constexpr int BK = 32;
 constexpr int KPITCH = 36;                  // floats; K-major LDS row pitch (conflict-free ds_read_b128)
 constexpr int NTHREADS = 256;
 constexpr int TILE_FLOATS = BM * KPITCH;    // >= BK * BM: one operand tile in either layout
@@ -461,7 +461,6 @@ __device__ __forceinline__ void load_tile(const float *__restrict__ base, long l
 }
 
 // ---- LDS-DMA pipeline pieces (K step 16, lane-linear LDS images) ------------------------------
-constexpr int GK = 16;                         // K step of the DMA pipeline
 constexpr int G_TILE = BM * GK;                // floats per operand tile (8 KB)
 constexpr int G_STAGE = 2 * G_TILE;            // A + B
 
@@ -745,49 +744,6 @@ __device__ __attribute__((noinline)) void ksync_rendezvous(unsigned *slice, unsi
 __device__ __forceinline__ void ksync_wait(const KSync &k, int kt) {
     if (k.slice != nullptr && kt > 0 && (kt & (k.every - 1)) == 0 && kt / k.every <= k.epochs)
         ksync_rendezvous(k.slice, (unsigned)(kt / k.every));
-}
-
-// Split-K factor for a grid of `tiles` output tiles over `nkt` K tiles.  All blocks of such a launch are
-// resident at once (`resident` fit a CU: 4 with the f32 MFMA, 3 / 2 with the split-bf16 modes) and run equally
-// long, so the launch lasts as long as the fullest CU: cost(s) = ceil(tiles * s / CUs) / s.  Candidates leave the
-// fullest CU with `resident` or `resident - 1` blocks (fewer cannot keep the matrix pipe busy, more would queue a
-// second generation).  `force_per_cu` > 0 pins the blocks-per-CU target.
-inline int pick_splits(long tiles, int nkt, long cus, int force_per_cu = 0, int resident = 4, int generations = 0) {
-    const long max_s = nkt / 8;
-    if (force_per_cu > resident) {                       // several generations of `resident` blocks, pinned (experiments)
-        const long s = (long)force_per_cu * cus / tiles;
-        return (int)(s < 1 ? 1 : s > max_s ? max_s : s);
-    }
-    int best = 1;
-    double best_cost = 1e30;
-    // candidates in order of preference: 3 blocks per CU where that many fit (measured on the FFN weight gradients,
-    // f32 math: 768 blocks 7.57 ms, 1024 blocks 8.15 ms), then the other neighbour of `resident`
-    const int first = resident < 3 ? resident : 3;
-    const int second = first == resident ? resident - 1 : resident;
-    const int order[2] = {first, second < 2 ? first : second};
-    for (int c = 0; c < 2; ++c) {
-        const int per_cu = order[c];
-        if (force_per_cu > 0 && force_per_cu <= resident && per_cu != force_per_cu) continue;
-        long s = per_cu * cus / tiles;
-        if (s > max_s) s = max_s;
-        if (s < 1) s = 1;
-        const double cost = (double)((tiles * s + cus - 1) / cus) / (double)s;
-        if (cost < best_cost * (1.0 - 1e-6)) { best_cost = cost; best = (int)s; }
-    }
-    // Long K ranges (round 4, `generations` > 0): the blocks of one generation stream the same operand panels through their XCD's
-    // L2 and drift apart over a thousand K tiles (the packed q/k/v weight gradient, 192 tiles x 4 splits of 1024 K tiles of 32:
-    // 6.00 ms; x 16 splits of 256: 5.71 ms).  When the chosen range is longer than 768 K tiles and an exact number of FULL
-    // generations (`resident` blocks on every CU, 3 then 2 of them) exists with at least 128 K tiles per block, take that.
-    if (generations > 0 && force_per_cu == 0 && nkt / best > 768) {
-        for (int gens = 3; gens >= 2; --gens) {
-            const long blocks = (long)resident * gens * cus;
-            if (blocks % tiles) continue;
-            const long s = blocks / tiles;
-            if (s <= best || s > max_s || nkt / s < 128) continue;
-            return (int)s;
-        }
-    }
-    return best;
 }
 
 // Sum split-K slabs in split order and apply the linear part of the epilogue.

@@ -1,4 +1,5 @@
-"""TEST INFRASTRUCTURE ONLY -- the Conv2D path tests: the dispatch of np_modeling_amd/csrc/npm_conv.hip restated (``route``), the
+"""TEST INFRASTRUCTURE ONLY -- the Conv2D path tests: the dispatch of np_modeling_amd/csrc/npm_conv.hip (the conv plans of
+csrc/npm_gemm_plan.h) restated (``route``), the
 fixed case lists with the cell each case exists for, the geometry properties those cells claim (computed, so that
 tests/test_conv_host.py can prove them on the CPU) and the harness that runs a case on the device (``ConvCall``).
 tests/test_gpu_conv_paths.py runs the same lists on the GPU and asserts that ``npm_last_conv_kernel`` reports what ``route`` says.
@@ -46,7 +47,7 @@ def _cdiv(a, b):
 
 
 def pick_splits(tiles, nkt, cus, force_per_cu=0, resident=4):
-    """csrc/npm_mfma_tile.h pick_splits with generations = 0 (the conv entry points never pass it)."""
+    """csrc/npm_gemm_plan.h pick_splits with generations = 0 (the conv entry points never pass it)."""
     max_s = nkt // 8
     if force_per_cu > resident:
         s = force_per_cu * cus // tiles
@@ -70,7 +71,7 @@ def _fmt(family, vec, tall, math, korder, buf, splits, kper, wr=0, trio=False, k
 
 
 def _route_gemm(n, h, w, c, n_out, k, kn, aligned):
-    """run_conv_gemm: forward (c = c_in, n_out = c_out) and grad_x (c = c_out, n_out = c_in)."""
+    """conv_gemm_plan: forward (c = c_in, n_out = c_out) and grad_x (c = c_out, n_out = c_in)."""
     if n == 0:
         return 'none'
     math = CONV_MATH[kn.math][0]
@@ -85,12 +86,14 @@ def _route_gemm(n, h, w, c, n_out, k, kn, aligned):
 
 
 def _renormalise(nkt, splits):
+    """csrc/npm_gemm_plan.h split_ranges, as the conv entry points see it (nkt >= 1)."""
     splits = max(1, splits)
     kt_per = _cdiv(nkt, splits)
     return _cdiv(nkt, kt_per), kt_per
 
 
 def _route_bwd_w(n, h, w, c0, c1, k, kn, cus, aligned):
+    """conv_wgrad_plan: the filter gradient."""
     pixels = n * h * w
     if pixels == 0:
         return 'none'
@@ -119,7 +122,7 @@ def ksync_every(value):
 
 
 def fused_plan(n, h, w, c0, c1, k, kn, cus, aligned=True):
-    """npm_conv2d_bwd_w_relu's choices as a dict, or None where it takes the two-pass form."""
+    """conv_wgrad_fused_plan (npm_conv2d_bwd_w_relu's choices) as a dict, or None where it takes the two-pass form."""
     pixels, m = n * h * w, k * k * c0
     halo = (k // 2) * w + k // 2
     fused = (bool(kn.dma) and CONV_MATH[kn.math][0] == 0 and bool(kn.fused) and c0 % 4 == 0 and c1 % 4 == 0 and pixels % GK == 0

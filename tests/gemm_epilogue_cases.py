@@ -78,7 +78,7 @@ COLSUM_LAYOUTS = LAYOUTS
 
 def instance_of(flags: int, alpha: float, colsum: bool) -> tuple:
     """Which code ``write_tile_buf<WITH_COLSUM>`` runs (csrc/npm_mfma_tile.h:354-411), restated.  ``colsum``: the launch asked
-    for column sums, i.e. the WITH_COLSUM instantiation of the kernel with e.cs set (csrc/npm_gemm.hip:348-353, 391-392)."""
+    for column sums, i.e. the WITH_COLSUM instantiation of the kernel with e.cs set (csrc/npm_gemm_plan.h gemm_plan: DMA_COLSUM)."""
     has_bias, relu = bool(flags & BIAS), bool(flags & RELU)
     if not flags & (RESIDUAL | RELU_SAVE | RELU_MASK | SOFTMAX_BWD):                   # :354
         simple = not relu and not colsum                                               # :358
@@ -211,7 +211,7 @@ def describe(case: Case) -> Desc:
     if (b0, b1) == (1, 1):
         ldr, ldaux = n + 1, n + 3
     else:
-        # the residual and aux are addressed with C's batch strides (csrc/npm_gemm.hip:343-346): a pitch in [ldc - 4, ldc) keeps the
+        # the residual and aux are addressed with C's batch strides (csrc/npm_gemm.hip sgemm_glds_kernel): a pitch in [ldc - 4, ldc) keeps the
         # rows of all heads and batches apart
         ldr, ldaux = ldc - 1, ldc - 3
     if fam.alias:
@@ -222,39 +222,39 @@ def describe(case: Case) -> Desc:
 
 def takes_dma_kernel(case: Case, pipeline: int = 2, buf_epilogue: int = 1) -> bool:
     """The predicate under which ``npm_sgemm`` launches sgemm_glds_kernel (or the f16x2 kernel, which has the same one) with the
-    buffer epilogue: csrc/npm_gemm.hip:521-524 (vec), :551-553 (buf_ok), :577-583 (k_per_split), :599-605 (dma, dma_path).
+    buffer epilogue: csrc/npm_gemm_plan.h gemm_plan (vec, buf_ok, dma, dma_path) and split_ranges (k_per_split).
     Allocations of the harness are 16-byte aligned (the pool hands out 256-byte aligned blocks, operands start at offset 0)."""
     d, (m, n, k) = describe(case), (case.m, case.n, case.k)
     a_kmaj, b_kmaj = case.layout != 'TN', case.layout == 'NT'
-    vec = d.lda % 4 == 0 and d.ldb % 4 == 0 and all(s % 4 == 0 for s in d.sa + d.sb)                       # :521-522
-    vec = vec and (k % 4 == 0 if a_kmaj else m % 4 == 0) and (k % 4 == 0 if b_kmaj else n % 4 == 0)        # :523-524
+    vec = d.lda % 4 == 0 and d.ldb % 4 == 0 and all(s % 4 == 0 for s in d.sa + d.sb)                       # vec
+    vec = vec and (k % 4 == 0 if a_kmaj else m % 4 == 0) and (k % 4 == 0 if b_kmaj else n % 4 == 0)
     fam = FAMILY[case.family]
     fits = lambda ld: (256 * ld + n) * 4 < 2 ** 31
     uses_aux = fam.flags & (RELU_SAVE | RELU_MASK | SOFTMAX_BWD)
     buf_ok = bool(buf_epilogue) and fits(d.ldc) and (not fam.flags & RESIDUAL or fits(d.ldr)) and (not uses_aux or fits(d.ldaux)) and fits(n)
-    nkt = (k + 31) // 32                                                                                  # :566 (BK = 32)
-    splits = case.split_k if case.split_k > 1 else 1                                                      # :568 (split_k = 1 here)
+    nkt = (k + 31) // 32                                                                                  # BK = 32
+    splits = case.split_k if case.split_k > 1 else 1                                                      # split_k = 1 here
     linear = not fam.flags & (RELU_SAVE | RELU_MASK | RELU | SOFTMAX_BWD)
     if not linear or fam.colsum:
-        splits = 1                                                                                        # :576, :585
+        splits = 1                                                                                        # not linear, or colsum
     splits = max(1, min(splits, nkt))
     per = max(1, -(-nkt // splits))
-    k_per_split = per * 32 if splits > 1 else (nkt * 32 if k > 0 else 32)                                 # :583
+    k_per_split = per * 32 if splits > 1 else (nkt * 32 if k > 0 else 32)                                 # split_ranges
     tile_n = BN
-    a_span = (BM * d.lda + k if a_kmaj else k_per_split * d.lda + BM) * 4                                 # :599-600
+    a_span = (BM * d.lda + k if a_kmaj else k_per_split * d.lda + BM) * 4                                 # the operand panels
     b_span = (tile_n * d.ldb + k if b_kmaj else k_per_split * d.ldb + tile_n) * 4
-    dma = pipeline == 2 and vec and k % GK == 0 and k_per_split % GK == 0 and a_span < 2 ** 31 and b_span < 2 ** 31      # :601-602
-    return dma and buf_ok                                                                                 # :605
+    dma = pipeline == 2 and vec and k % GK == 0 and k_per_split % GK == 0 and a_span < 2 ** 31 and b_span < 2 ** 31      # dma
+    return dma and buf_ok                                                                                 # dma_path
 
 
 def takes_wide_tile(case: Case) -> bool:
-    """csrc/npm_gemm.hip:533-535 with NPM_TUNE_GEMM_WIDE_TILE = 1, on top of ``takes_dma_kernel``."""
+    """``wide`` of csrc/npm_gemm_plan.h gemm_plan with NPM_TUNE_GEMM_WIDE_TILE = 1, on top of ``takes_dma_kernel``."""
     d = describe(case)
     return takes_dma_kernel(case) and case.n % 256 == 0 and not FAMILY[case.family].colsum and 256 * d.ldb * 4 < 2 ** 30
 
 
 def expected_math(case: Case, mode: str, wide: bool = False, dma: bool = True) -> str:
-    """What ``npm_last_math`` reports after the launch (csrc/npm_gemm.hip:370-371, :612, :649)."""
+    """What ``npm_last_math`` reports after the launch (``math`` of csrc/npm_gemm_plan.h gemm_plan: the table's last column)."""
     if not dma or wide or FAMILY[case.family].colsum:
         return 'f32'
     if mode == 'f16x2' and (case.batch != (1, 1) or case.k == 0):
@@ -263,7 +263,7 @@ def expected_math(case: Case, mode: str, wide: bool = False, dma: bool = True) -
 
 
 def grid_blocks(case: Case) -> int:
-    """Blocks of the launch (csrc/npm_gemm.hip:536-537, :562, :594)."""
+    """Blocks of the launch (``grid`` of csrc/npm_gemm_plan.h gemm_plan)."""
     splits = min(case.split_k, (case.k + 31) // 32) if case.split_k > 1 else 1
     return -(-case.m // BM) * -(-case.n // BN) * case.batch[0] * case.batch[1] * splits
 

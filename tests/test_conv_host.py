@@ -162,7 +162,7 @@ def test_rendezvous_case_engages(cus):
 
 
 def test_pick_splits_restatement():
-    """Hand-evaluated values of csrc/npm_mfma_tile.h pick_splits."""
+    """Hand-evaluated values of csrc/npm_gemm_plan.h pick_splits."""
     assert CC.pick_splits(2, 16, 256) == 2                       # capped by nkt / 8
     assert CC.pick_splits(25, 512, 256) == 30                    # 3 per CU: cost 3 / 30; 4 per CU: 40 splits, cost 4 / 40: no better
     assert CC.pick_splits(25, 512, 256, 4) == 40

@@ -1,6 +1,6 @@
 """CPU: the case lists, the harness and the references of the GEMM epilogue tests (tests/gemm_epilogue_cases.py), without a GPU.
 
-* No case can silently miss its target: the dispatch of ``npm_sgemm`` (csrc/npm_gemm.hip:521-605) and the instance choice of
+* No case can silently miss its target: the dispatch of ``npm_sgemm`` (csrc/npm_gemm_plan.h gemm_plan) and the instance choice of
   ``write_tile_buf`` (csrc/npm_mfma_tile.h:354-411) are restated in Python in the cases module (each line cited there); every case
   of every list must meet the LDS-DMA predicate -- the share left out is zero, as a condition --, every family must reach the
   instance it is named after, and every (family, layout) list must cover all M, N and K classes.

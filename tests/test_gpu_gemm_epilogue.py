@@ -25,7 +25,7 @@ from conftest import assert_close
 
 pytestmark = pytest.mark.gpu
 
-DEFAULTS = {GC.TUNE_PIPELINE: 2, GC.TUNE_GROUP_M: 8, GC.TUNE_BUF_EPILOGUE: 1, GC.TUNE_WIDE_TILE: 0}      # csrc/npm_gemm.hip:51-59
+DEFAULTS = {GC.TUNE_PIPELINE: 2, GC.TUNE_GROUP_M: 8, GC.TUNE_BUF_EPILOGUE: 1, GC.TUNE_WIDE_TILE: 0}      # csrc/npm_gemm.hip: the knobs' initial values
 
 
 @pytest.fixture(scope='module')
