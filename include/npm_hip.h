@@ -1061,6 +1061,33 @@ int npm_clip_finish(double *state, double max_norm);
  * NPM_E_BAD_ARGUMENT: step < 1, weight_decay < 0 or NaN, a NULL var, grad, m or v with n > 0. */
 int npm_adamw_step(float *var, const float *grad, double *m, double *v, size_t n, double lr, double beta1, double beta2,
                    double eps, int step, double weight_decay, const double *clip_state);
+/* ---- gradient accumulation over micro-batches (csrc/npm_accum.hip) ----
+ * npm_accumulate_ranges: dst[r][i] = dst[r][i] + src[r][i] for every range r and element i -- ONE float32 addition and nothing else;
+ * an inf or a NaN stays in its own element.  src is not written.  The two tables are host memory, their pointers device pointers.
+ * The grid is the tiling of npm_sumsq_ranges laid over the dst ranges: range r is ceil(n[r] / NPM_SUMSQ_TILE) tiles, one block of
+ * 256 threads a tile, found by the same scalar walk of the tile counts.  Inside a tile the elements follow dst's alignment as they
+ * do there: up to 3 head elements on lanes 0 .. 2, aligned groups of four with group q on lane q % 256 in ascending order, up to
+ * 3 tail elements.  dst is read and written 16 bytes at a time over its aligned interior; src is read 16 bytes at a time where it
+ * has dst's 16-byte phase and with four 4-byte loads where it has not -- the same bits either way.
+ * sumsq_acc == NULL: one launch, no reduction.  sumsq_acc != NULL: the same launch also squares every NEW dst value exactly in
+ * fp64, adds the squares per lane in the order above, reduces with the fixed 256-lane tree into one partial per tile; a second
+ * launch of one block adds the partials in index order with the same tree, and *sumsq_acc = *sumsq_acc + total.
+ * CONTRACT: after the call *sumsq_acc holds the bits that npm_sumsq_ranges(dst, sumsq_acc) would have produced on the updated
+ * buffers from the same starting value -- the pass over the gradients that the norm costs disappears into the last fold.
+ * count == 0 or every n[r] == 0: nothing is launched.  NPM_E_BAD_ARGUMENT, with nothing written: dst or src NULL, count outside
+ * 0 .. NPM_SUMSQ_MAX_RANGES, dst->count != src->count, dst->n[r] != src->n[r], a NULL pointer with n[r] > 0, a pointer that is not
+ * 4-byte aligned, a dst range that overlaps another dst range or any src range, more than 2^31 - 1 tiles in all. */
+int npm_accumulate_ranges(const npm_ranges *dst, const npm_ranges *src, double *sumsq_acc);
+/* npm_clip_finish for gradients that are still to be multiplied by grad_scale (1 / micro-batches, 1 / counted tokens): the norm
+ * reported and clipped is the norm of the SCALED gradient, and the factor npm_adamw_step multiplies with carries the scale.
+ * state = 4 doubles [sumsq, norm, scale, ok], sumsq over the unscaled gradients.  One thread, every operation rounded on its own:
+ *     norm = grad_scale * sqrt(sumsq);  state[1] = norm
+ *     norm not finite:  state[2] = state[3] = 0
+ *     otherwise:        ratio = max_norm / (norm + 1e-6);  c = ratio < 1 ? ratio : 1
+ *                       state[2] = (double)(float)(grad_scale * c);  state[3] = 1
+ * max_norm = +inf: no clipping, the factor is (float)grad_scale.  grad_scale == 1.0: the four doubles of npm_clip_finish, bit
+ * for bit.  NPM_E_BAD_ARGUMENT: state NULL, max_norm <= 0 or NaN, grad_scale <= 0, NaN or inf. */
+int npm_clip_finish_scaled(double *state, double max_norm, double grad_scale);
 /* MSELoss (loss.py:21-29): loss = sum((y-t)^2)/n (fp64 accumulation, returned to the host); dy = 2 (y-t) / n */
 int npm_mse_fwd(const float *y, const float *targets, size_t n, double *loss);
 int npm_mse_bwd(const float *y, const float *targets, float *dy, size_t n);

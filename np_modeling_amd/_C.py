@@ -305,6 +305,9 @@ _SPECIAL = {
     'npm_last_rope_append_kernel': (C.c_char_p, []),
     # not part of the tests' host simulator: its convolutions have no instances to report; tests/conv_cases.py restates the dispatch
     'npm_last_conv_kernel': (C.c_char_p, []),
+    # gradient accumulation (csrc/npm_accum.hip): not part of the simulator either; tests/accum_sim.py restates the two
+    'npm_accumulate_ranges': (C.c_int, [C.POINTER(npm_ranges), C.POINTER(npm_ranges), _P]),
+    'npm_clip_finish_scaled': (C.c_int, [_P, C.c_double, C.c_double]),
 }
 
 COMM_SIGNATURES = {

@@ -323,6 +323,15 @@ COALESCE_UPDATES = os.environ.get('NPM_COALESCE_UPDATES', '1') != '0'   # A/B sw
 _ALIGN = 4                                                              # floats: 16-byte aligned slices (GEMM / DMA operands)
 
 
+# Gradient accumulation (optimizer.AdamWOptimizer(accumulate=True)), A/B switches.  ACCUM_RANGES: True / NPM_ACCUM_RANGES=1 folds with
+# npm_accumulate_ranges whatever the shape, False / 0 with one npm_axpy per joined pair (the yardstick); None (unset) takes the ranges
+# except for a single pair without the sum, which tools/accum_bench.py measured slower than npm_axpy.  ACCUM_FUSED_NORM: the last fold
+# of a step also produces the sum of squares of the norm -- the same bits either way; on, because the fused call measured 0.73 - 0.83
+# of fold + npm_sumsq_ranges at 12.6 M and 200 M elements (profiles/r28_accum_bench.log).
+ACCUM_RANGES = {'0': False, '1': True}.get(os.environ.get('NPM_ACCUM_RANGES', ''))
+ACCUM_FUSED_NORM = os.environ.get('NPM_ACCUM_FUSED_NORM', '1') != '0'
+
+
 class _LayerRef:
     """Weak reference to a layer that survives ``copy.deepcopy`` of the structure holding it by pointing at the COPY of
     the layer (through the deepcopy memo).  A ParamArena is an attribute of the layer whose parameters it lists: strong

@@ -158,10 +158,15 @@ class SoftmaxCrossEntropyLoss(Loss):
         self._reduction, self._inplace = reduction, bool(inplace)
         self._uploaded = None           # (host array object, its int32 contents, IdBuffer): the last upload of host targets
         self._known = None              # (IdBuffer, count, largest id or None): what the host knows about a resident buffer
+        self._known_before = []         # the same of the buffers used before it (micro-batch views take turns): the last 16
         self._grad = None
         self.row_loss = self.lse = None
         self.count = 0
         self._sum = 0.0
+
+    @property
+    def reduction(self) -> str:
+        return self._reduction
 
     # ---- targets ----------------------------------------------------------------------------------------------------------
     def _checked(self, targets) -> np.ndarray:
@@ -189,6 +194,9 @@ class SoftmaxCrossEntropyLoss(Loss):
     def _device_ids(self, targets, shape, vocab):
         """(IdBuffer, count) of one forward."""
         if isinstance(targets, D.IdBuffer):
+            if self._known is not None and self._known[0] is not targets:       # one of several resident buffers taking turns
+                self._known_before = ([self._known] + [k for k in self._known_before if k[0] is not self._known[0]])[:16]
+                self._known = next((k for k in self._known_before if k[0] is targets), None)
             # the buffer resident_targets made from host targets holds -1 where ignore_index was: nothing left to map
             mapped = self._known is not None and self._known[0] is targets and self._known[2] is not None
             if self._ignore >= 0 and not mapped:

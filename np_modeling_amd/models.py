@@ -24,6 +24,8 @@ states (the layers plus the final norm), so ``speculative.decode_step(lm.stack, 
 ``beam.decode_step(lm.stack, state, lm.embedding, lm.head, search)`` run a multi-layer model.  ``lm.generate`` is the plain
 prefill-then-one-token loop.
 
+Batches larger than one forward holds: ``Trainer.train(..., micro_batches=k)`` with ``AdamWOptimizer(accumulate=True)`` (optimizer.py).
+
 Not built: a bias-free ``Linear``, a tied embedding / head, GELU, an in-kernel causal rule for the training kernels (the mask's tile
 summary skips tiles up to S 2048), a HIP graph of the step, activation checkpointing, and the one-pass shared-prefix attention
 (``device.SHARED_PREFIX``) over a layered cache."""

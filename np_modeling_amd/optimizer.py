@@ -181,11 +181,21 @@ class AdamWOptimizer(AdamOptimizer):
       advance all the same; ``last_grad_norm()`` reports ``ok == False`` for such a step.
     * Data parallelism: ``parallel.GradScope._finish`` waits for the all-reduce before it calls ``update``, so every rank takes
       the norm of the same reduced gradients and arrives at the same factor with no further collective.
-    * ``last`` = {'launches', 'updates', 'ranges'} of the most recent ``apply()``.
+    * ``last`` = {'launches', 'updates', 'ranges', 'folds', 'fold_launches', 'fused_norm'} of the most recent ``apply()``.
+    * ``accumulate=True``: gradient accumulation over several backwards (micro-batches).  The FIRST gradient a slot receives after
+      an ``apply()`` is adopted as that slot's accumulator -- the bucket slice itself, kept alive as a pending gradient is;
+      nothing is launched and nothing is zeroed.  A later ``update`` of the slot records the gradient as incoming, and ``fold()``
+      adds every incoming gradient into its accumulator (``npm_accumulate_ranges``: one float32 addition per element, 32 joined
+      pairs a call) and drops the incoming buffers.  ``apply(grad_scale)`` folds what is left, takes the norm of the SCALED sum
+      and steps with ``grad_scale`` inside the clip factor, so the gradients themselves are never rescaled.  Where the last fold
+      covers exactly the ranges of the norm, it produces the sum of squares in the same pass (``device.ACCUM_FUSED_NORM``): the
+      bits of ``npm_sumsq_ranges`` afterwards, without that pass.  Memory: during micro-batches 2 .. k a SECOND set of gradients
+      exists beside the accumulators, from its backward until the fold.  With one backward per ``apply()`` the calls and the bits
+      are those of ``accumulate=False``, where a second gradient for a pending slot raises as it always did.
     """
 
     def __init__(self, learning_rate, beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-8,
-                 weight_decay: float = 0.01, clip_norm: Optional[float] = None, decay=None):
+                 weight_decay: float = 0.01, clip_norm: Optional[float] = None, decay=None, accumulate: bool = False):
         super().__init__(learning_rate, beta1, beta2, epsilon)
         if not weight_decay >= 0.0:
             raise ValueError(f'weight_decay must be >= 0, got {weight_decay!r}')
@@ -194,7 +204,11 @@ class AdamWOptimizer(AdamOptimizer):
         self.weight_decay, self.clip_norm = float(weight_decay), None if clip_norm is None else float(clip_norm)
         self.decay = _decays_by_default if decay is None else decay
         self.last = None
+        self.accumulate = bool(accumulate)
         self._pending = {}        # slot -> (obj, attribute, gradient), in update order; the gradient keeps its bucket alive
+        self._incoming = {}       # accumulate: slot -> a later gradient, not yet folded into the pending one (its accumulator)
+        self._folds = self._fold_launches = 0     # since the last apply()
+        self._fused = False       # the most recent apply() took its sum of squares out of the last fold
         self._applies = 0
         self._clip_state = None   # 4 doubles in HBM: sumsq, norm, scale, ok
         self._clipped = False     # the most recent apply() wrote _clip_state
@@ -211,8 +225,13 @@ class AdamWOptimizer(AdamOptimizer):
             raise ValueError(f'{type(obj).__name__}.{attribute}: {variable.size} elements, gradient of {gradient.size}')
         slot = f'{id(obj)}.{attribute}'
         if slot in self._pending:
-            raise RuntimeError(f'{type(obj).__name__}.{attribute} already has a gradient waiting: call apply() after every backward '
-                               '(a second update would replace the first gradient, not add to it)')
+            if not self.accumulate:
+                raise RuntimeError(f'{type(obj).__name__}.{attribute} already has a gradient waiting: call apply() after every backward '
+                                   '(a second update would replace the first gradient, not add to it)')
+            if slot in self._incoming:
+                self.fold()
+            self._incoming[slot] = gradient
+            return
         self._pending[slot] = (obj, attribute, gradient)
 
     def _ranges(self):
@@ -235,6 +254,61 @@ class AdamWOptimizer(AdamOptimizer):
                 end = ptr + 4 * n
         return out
 
+    def _fold_pairs(self):
+        """The incoming gradients as [accumulator address, gradient address, elements], ordered as ``_ranges()`` orders the
+        accumulators and joined only where BOTH sides continue exactly: bucket padding never enters."""
+        buffers = {}
+        for slot, (_, _, acc) in self._pending.items():
+            grad = self._incoming.get(slot)
+            if grad is not None and acc.size:
+                buffers.setdefault(id(acc._buf), []).append((acc.ptr, grad.ptr, acc.size))
+        out = []
+        for slices in buffers.values():
+            ends = None
+            for dst, src, n in sorted(slices):
+                if (dst, src) == ends:
+                    out[-1][2] += n
+                else:
+                    out.append([dst, src, n])
+                ends = (dst + 4 * n, src + 4 * n)
+        return out
+
+    @staticmethod
+    def _ranges_route(lib, pairs, with_sum: bool) -> bool:
+        """npm_accumulate_ranges (True) or one npm_axpy per pair (False): ``device.ACCUM_RANGES`` where it is set; otherwise the
+        ranges, except for a single pair without the sum -- the one shape measured slower than its yardstick (README)."""
+        from np_modeling_amd import device as D
+        if not hasattr(lib, 'npm_accumulate_ranges') or D.ACCUM_RANGES is False:
+            return False
+        return D.ACCUM_RANGES is True or with_sum or len(pairs) != 1
+
+    def _fold(self, pairs, sumsq_state: int = 0) -> None:
+        import ctypes as C
+        from np_modeling_amd import _C, device as D
+        lib = _C.lib()                          # a queued update drains first
+        if self._ranges_route(lib, pairs, bool(sumsq_state)):
+            for begin in range(0, len(pairs), _C.SUMSQ_MAX_RANGES):
+                dst, src = _C.npm_ranges(), _C.npm_ranges()
+                part = pairs[begin:begin + _C.SUMSQ_MAX_RANGES]
+                for i, (d, g, n) in enumerate(part):
+                    dst.ptr[i], src.ptr[i], dst.n[i], src.n[i] = d, g, n, n
+                dst.count = src.count = len(part)
+                _C.check(lib.npm_accumulate_ranges(C.byref(dst), C.byref(src), sumsq_state or None), 'npm_accumulate_ranges')
+                self._fold_launches += 1
+        else:                                   # the yardstick: 1 * g is exact, the same bits
+            assert not sumsq_state
+            for d, g, n in pairs:
+                _C.check(lib.npm_axpy(d, g, 1.0, n), 'npm_axpy')
+                self._fold_launches += 1
+        self._folds += 1
+        self._incoming = {}
+
+    def fold(self) -> None:
+        """Add every incoming gradient into its accumulator and drop the incoming buffers (``accumulate=True``; nothing to
+        fold: nothing happens)."""
+        if self._incoming:
+            self._fold(self._fold_pairs())
+
     def _norm_on_device(self) -> int:
         import ctypes as C
         from np_modeling_amd import _C, device as D
@@ -243,6 +317,14 @@ class AdamWOptimizer(AdamOptimizer):
         state = self._clip_state.ptr
         _C.check(_C.lib().npm_fill_f64(state, 0.0, 4), 'npm_fill_f64')
         ranges = self._ranges()
+        pairs = self._fold_pairs() if self._incoming else []
+        self._fused = bool(pairs) and D.ACCUM_FUSED_NORM and self._ranges_route(_C.lib(), pairs, True) \
+            and [[d, n] for d, _, n in pairs] == ranges
+        if self._fused:                         # the last fold touches every element the norm is over: the sum comes out of it
+            self._fold(pairs, state)
+            return len(ranges)
+        if pairs:
+            self._fold(pairs)
         for begin in range(0, len(ranges), _C.SUMSQ_MAX_RANGES):
             table = _C.npm_ranges()
             part = ranges[begin:begin + _C.SUMSQ_MAX_RANGES]
@@ -250,19 +332,45 @@ class AdamWOptimizer(AdamOptimizer):
                 table.ptr[i], table.n[i] = ptr, n
             table.count = len(part)
             _C.check(_C.lib().npm_sumsq_ranges(C.byref(table), state), 'npm_sumsq_ranges')
-        _C.check(_C.lib().npm_clip_finish(state, self.clip_norm), 'npm_clip_finish')
         return len(ranges)
 
-    def apply(self) -> None:
-        """One step of every parameter whose gradient ``update`` recorded since the last ``apply()``."""
+    def _finish_scaled(self, max_norm: float, grad_scale: float) -> None:
+        from np_modeling_amd import _C
+        lib = _C.lib()
+        if not hasattr(lib, 'npm_clip_finish_scaled'):
+            raise _C.NpmError('AdamWOptimizer.apply(grad_scale != 1) needs npm_clip_finish_scaled, which the loaded library does not have')
+        _C.check(lib.npm_clip_finish_scaled(self._clip_state.ptr, max_norm, grad_scale), 'npm_clip_finish_scaled')
+
+    def apply(self, grad_scale: float = 1.0) -> None:
+        """One step of every parameter whose gradient ``update`` recorded since the last ``apply()``.  ``grad_scale``: the factor
+        the (accumulated) gradients are still to be multiplied with -- 1 / micro-batches for a mean loss, 1 / counted tokens for a
+        summed one.  It travels inside the clip factor (``npm_clip_finish_scaled``); the norm reported and clipped is that of the
+        scaled gradients.  1.0: exactly the calls of an optimizer without it."""
         from np_modeling_amd import _C, device as D
         if not self._pending:
             return
+        grad_scale = float(grad_scale)
+        if not 0.0 < grad_scale < float('inf'):
+            raise ValueError(f'grad_scale must be positive and finite, got {grad_scale!r}')
         self._applies += 1
         lr = float(self.learning_rate(self._applies) if callable(self.learning_rate) else self.learning_rate)
-        ranges = self._norm_on_device() if self.clip_norm is not None else 0
+        self._fused = False
         self._clipped = self.clip_norm is not None
-        clip = self._clip_state.ptr if self._clipped else 0
+        if self._clipped:
+            ranges = self._norm_on_device()
+            if grad_scale == 1.0:
+                _C.check(_C.lib().npm_clip_finish(self._clip_state.ptr, self.clip_norm), 'npm_clip_finish')
+            else:
+                self._finish_scaled(self.clip_norm, grad_scale)
+        else:
+            ranges = 0
+            self.fold()
+            if grad_scale != 1.0:               # no norm: a zeroed state whose factor is float(grad_scale)
+                if self._clip_state is None:
+                    self._clip_state = D._Buffer(32)
+                _C.check(_C.lib().npm_fill_f64(self._clip_state.ptr, 0.0, 4), 'npm_fill_f64')
+                self._finish_scaled(float('inf'), grad_scale)
+        clip = self._clip_state.ptr if self._clipped or grad_scale != 1.0 else 0
         direct = 0
         with D.coalesced_updates() as queue:
             before = queue.launches if queue is not None else 0
@@ -283,8 +391,10 @@ class AdamWOptimizer(AdamOptimizer):
                 entry[0] += 1
         for obj, attribute, _ in self._pending.values():
             setattr(obj, attribute, getattr(obj, attribute))      # the reference's contract: changed in place, stored back
-        self.last = {'launches': direct if queue is None else queue.launches - before, 'updates': len(self._pending), 'ranges': ranges}
+        self.last = {'launches': direct if queue is None else queue.launches - before, 'updates': len(self._pending), 'ranges': ranges,
+                     'folds': self._folds, 'fold_launches': self._fold_launches, 'fused_norm': self._fused}
         self._pending = {}
+        self._folds = self._fold_launches = 0
 
     def update_variable(self, identifier, variable, gradient):
         raise TypeError('AdamWOptimizer steps in apply(): update() records the gradient')
